@@ -4,7 +4,7 @@
 batch: wm = G(x, msg) + x, then the detector's time-averaged bit probabilities on wm and the
 >= 0.5 decision.  Inputs are already in HBM when the timed region starts.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -47,6 +47,8 @@ PEAK_HBM_GBS = 8000.0             # MI355X_MICROARCH.md: HBM3E spec peak
 PEAK_F16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense f16 / bf16 (v_mfma_f32_32x32x16_f16, 32 cycles per SIMD)
 PMC_FILE = os.path.join(ROOT, "profiles", "r04_pmc_traffic.json")
 PMC_FILE_F16 = os.path.join(ROOT, "profiles", "r04_pmc_traffic_f16.json")   # the same passes over the f16 mode's command (tools/profile_f16.sh)
+DUMP_BUDGET_BYTES = 64_000_000    # --dump-outputs: all .npy files of one run together
+DUMP_SEED = 0                     # --dump-outputs: the fixed sample of an output larger than its share of that budget
 
 
 def parse():
@@ -68,7 +70,45 @@ def parse():
     ap.add_argument("--precision", default="f32", choices=["f32", "f16"],
                     help="f16 = the f16-operand / f32-accumulate mode of the nets (csrc/wv_h16.hip) for embed_detect / longform / detector_stress: "
                          "its own line (dtype f16) with its own parity block and roofs; the headline `value` is always exact f32")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / "
+                         "float64, %d MB at most in all: larger outputs as a fixed seeded sample); inputs and weights are seeded, so two "
+                         "builds can be compared output for output" % (DUMP_BUDGET_BYTES // 1_000_000))
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.workload in ("grad_allreduce", "rendezvous"):
+        ap.error(f"--dump-outputs: the {a.workload} workload computes no outputs to dump")
+    return a
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: rank 0 writes each array as d/<name>.npy (float64 stays float64, everything else becomes float32), all files
+    together under DUMP_BUDGET_BYTES.  The smaller arrays are written whole; an array larger than its even share of what is left is
+    written as the sample flat[idx] of its flattened elements, idx = sorted(default_rng(DUMP_SEED).choice(size, n, replace=False)),
+    the same elements on every run for the same shape.  Returns the manifest that goes into the JSON line."""
+    os.makedirs(d, exist_ok=True)
+    host = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+        host[k] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    budget = DUMP_BUDGET_BYTES - 4096 * len(host)         # headroom for the .npy headers
+    order = sorted(host, key=lambda k: host[k].nbytes)
+    manifest = {}
+    for i, k in enumerate(order):
+        v = host[k]
+        share = budget // (len(order) - i)
+        entry = dict(shape=list(v.shape), dtype=str(v.dtype))
+        if v.nbytes > share:
+            n = share // v.itemsize
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(v.size, n, replace=False))
+            v = v.reshape(-1)[idx]
+            entry["sample"] = dict(elements=int(n), of=int(host[k].size), seed=DUMP_SEED,
+                                   index="sorted(numpy.random.default_rng(seed).choice(of, elements, replace=False)) into the flattened array")
+        np.save(os.path.join(d, f"{k}.npy"), v)
+        budget -= v.nbytes
+        manifest[k] = entry
+    return dict(dir=d, arrays=manifest)
 
 
 def cpu_baseline(cfgG, cfgD, sdG, sdD, x, msg, n):
@@ -184,6 +224,7 @@ def train_step(a, dev, dist, world, rank):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    last_timed = outs[-1]
     # anatomy: a second pass of the same K steps with a hipEvent pair around every instrumented launch (the K1 GEMMs of forward and
     # backward, the dW GEMM); the stencil / reduction / optimizer kernels of the training library carry no events and make up the rest
     profile.reset()
@@ -201,6 +242,8 @@ def train_step(a, dev, dist, world, rank):
         for f in ("ms", "launches", "flops", "bytes"):
             k[f] += e[f]
     if rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {k.replace("/", "_"): v for k, v in last_timed.items() if torch.is_tensor(v)}) \
+            if a.dump_outputs else None
         ms = elapsed / a.steps * 1e3
         kernels = sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3), "launches_per_step": v["launches"] // a.steps,
                            "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] else 0.0,
@@ -237,7 +280,7 @@ def train_step(a, dev, dist, world, rank):
                                key=lambda d: -d["ms_per_step"]),
                 note="the depth-wise stencils' transposes (dh and the tap / bias sums; the second half's also the res_scale dot): algorithmic bytes "
                      "= read dy, read h (and v), write dh, over their own event time") if stencil else None,
-            kernels=kernels[:12], profiled_ms_per_step=round(elapsed_prof / a.steps * 1e3, 3),
+            kernels=kernels[:12], profiled_ms_per_step=round(elapsed_prof / a.steps * 1e3, 3), dumped_outputs=dumped,
             note="backward on saved activations (the blocks' 1x1 outputs kept from forward), activation derivative / residual / scale "
                  "epilogues fused into the K1 GEMMs, parameter gradients written in place into one flat arena per net")), flush=True)
 
@@ -353,6 +396,7 @@ def main():
         Lnet = HipNet(cfgL, random_state_dict(cfgL, 0), dev)
     x_np, msg_np = synthetic_clips(B, T, seed=1234 + rank)         # each rank owns its shard
     x, msg = torch.from_numpy(x_np).to(dev), torch.from_numpy(msg_np).to(dev)
+    loc_out = {}                                  # the locator logits of the latest longform step (--dump-outputs)
 
     def step(precision=a.precision):
         if a.workload == "detector_stress":
@@ -360,7 +404,7 @@ def main():
             return x, mp, mp >= 0.5
         wm = G.generator(x, msg, add_input=True, precision=precision)
         if Lnet is not None:
-            Lnet.locator(wm, precision=precision)
+            loc_out["loc"] = Lnet.locator(wm, precision=precision)
         mp = D.detector_mean_prob(wm, precision=precision)
         return wm, mp, mp >= 0.5
 
@@ -389,6 +433,11 @@ def main():
     for _ in range(a.warmup):
         step()
     elapsed, (wm, mp, bits) = timed(False)        # the number: clean pass, events off
+    dump = dict(mean_prob=mp, bits=bits)          # what the timed path returned in its last timed step
+    if a.workload != "detector_stress":           # (detector_stress: its first output is the input itself)
+        dump["wm"] = wm
+    if "loc" in loc_out:
+        dump["loc_logits"] = loc_out["loc"]
     elapsed_prof, _ = timed(True)                 # the anatomy: same K steps with per-launch events
     prof = profile.collect()
     with_locator = None
@@ -573,6 +622,8 @@ def main():
                                  bits_decidable_at_4x_err=int((mg > 4 * err).sum()), bits=int(mg.size),
                                  note="torch-CPU port of the reference detector on the first clips of the batch; the golden-fixture checks "
                                       "(reference outputs, incl. the narrow-margin detector) are tests/test_gpu_h16.py")
+    if a.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(a.dump_outputs, dump)
     print(json.dumps(out), flush=True)
     if dist:
         dist.destroy_process_group()
