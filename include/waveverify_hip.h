@@ -12,6 +12,8 @@
  *                         (+ sigmoid/mean-over-time of waveverify/core.py:577-580 when
  *                          mean_prob != NULL, so the [B,nbits,T] logits need not be stored)
  *   wv_locator_forward    Locator.forward              model/locator.py:268-299
+ *   wv_window_* / wv_session_advance / wv_detector_forward_windowed
+ *                         not in the reference: windowed long-form and live-session execution
  *   wv_model_set_param*   nn.Module.load_state_dict on the stripped / parametrized key layouts
  *                         waveverify/core.py:324-426, scripts/train.py:1589-1676
  *   wv_op_*               the fused units of modules/seanet.py + modules/conv.py, exported one by
@@ -127,6 +129,34 @@ int wv_locator_forward(wv_model* m, const float* x, float* logits, int B, int T,
  * msg may be NULL (no FiLM), as for the detector / locator. */
 int wv_encoder_forward(wv_model* m, const float* x, const float* msg, int msg_rows, float* latent,
                        int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- windowed long-form and live sessions (waveverify_amd/window.py, session.py) -----------
+ * A clip or a stream runs as a batch of WINDOWS of L samples: a run of frames plus a left halo no shorter than the net's
+ * receptive field (window.halo), window starts and keep edges on hop multiples counted from the clip's t = 0.  The window
+ * batch goes through the forwards above; only each window's kept columns are written back.  Sizes are in samples.
+ *   wv_window_gather       dst [W,1,L]: window w = src[offs[w] .. offs[w] + L), src the packed clips (n_src samples),
+ *                          offs [W] int64 device.  Windows lying outside src are skipped; nothing is zero-filled.
+ *   wv_window_scatter      y [W,C,L] -> out (n_out floats): desc [W][4] int64 device = {offset in out of the window's column 0,
+ *                          row stride of its clip's [C,T] output, keep lo, keep hi} (keep range relative to the window);
+ *                          out[desc0 + c*desc1 + j] = y[w][c][j] for j in [lo, hi).
+ *   wv_detector_forward_windowed   x [W,1,L]; keep_lo / keep_hi [W] int32 device (relative to the window); psum [W,nbits] =
+ *                          sum over t in [keep_lo, keep_hi) of sigmoid(logit) -- the logits are never stored.  Workspace
+ *                          of wv_detector_forward for (W, L); the _f16 twin runs the f16-operand mode.
+ *   wv_window_reduce_mean  mean_prob [B,nbits] = (sum over psum rows rows[ptr[b] .. ptr[b+1]) in that order, in f64) / lengths[b];
+ *                          ptr [B+1] / rows int32, lengths [B] int64, all device.
+ *   wv_session_advance     one tick of S lockstep sessions: stream s's samples are cat(hist[s][0 .. hv), x[s][0 .. n)) with
+ *                          hist [S,hcap], x [S,n]; win [S,1,wlen] = their first wlen samples (wlen may be 0), hist_out [S,hcap] =
+ *                          their samples [drop, drop + hv2); drop + hv2 == hv + n, hist_out != hist. */
+int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream);
+int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream);
+int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
+                                 int W, int L, void* workspace, size_t workspace_bytes, void* stream);
+int wv_detector_forward_windowed_f16(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
+                                     int W, int L, void* workspace, size_t workspace_bytes, void* stream);
+int wv_window_reduce_mean(const float* psum, int n_rows, const int* ptr, const int* rows, const int64_t* lengths,
+                          float* mean_prob, int B, int nb, void* stream);
+int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen,
+                       float* hist_out, int drop, int hv2, int S, void* stream);
 
 /* ---- single fused units ----------------------------------------------------------------
  * Activations (X, resid, film, Y, wav, P, H, x, Z, logits, mean_prob) are DEVICE pointers.

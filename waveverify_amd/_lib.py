@@ -52,6 +52,12 @@ SIGNATURES = {
                                        _VP, C.c_size_t, _VP]),
     "wv_detector_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_locator_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_window_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int, C.c_int, _VP]),
+    "wv_window_scatter": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_detector_forward_windowed": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_detector_forward_windowed_f16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_window_reduce_mean": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
+    "wv_session_advance": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_encoder_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP,
                                      C.c_size_t, _VP]),
     "wv_model_film": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP]),

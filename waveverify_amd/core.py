@@ -9,6 +9,7 @@ passes run in libwaveverify_hip.so (see nets.py); there is no CPU fallback.
 from __future__ import annotations
 
 import logging
+import math
 from pathlib import Path
 from types import SimpleNamespace
 from typing import Dict, Mapping, Optional, Tuple, Union
@@ -16,6 +17,7 @@ from typing import Dict, Mapping, Optional, Tuple, Union
 import numpy as np
 import torch
 
+from . import session, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
@@ -114,14 +116,66 @@ class WaveVerify:
         """-> sigmoid(locator logits) [B, T]."""
         return torch.sigmoid(self._need("locator").locator(audio, precision=self.locator_precision)).squeeze(1)
 
+    # ------------------------------------------------------------------ windowed: variable-length clips, live sessions (NOT in the reference)
+    def _window_samples(self, window_seconds: float) -> int:
+        """window_seconds -> samples, rounded up to the lcm of the nets' hops so one plan suits embed, detect and locate."""
+        if not window_seconds or window_seconds <= 0:
+            raise ValueError("window_seconds must be positive")
+        hop = window.pipeline_hop([c for c in self.configs.values()])
+        return -(-int(math.ceil(window_seconds * self.sample_rate)) // hop) * hop
+
+    def _messages(self, watermark_ids) -> torch.Tensor:
+        if isinstance(watermark_ids, (list, tuple)):
+            ids = [self._validate_watermark_id(w) for w in watermark_ids]
+        else:
+            ids = [self._validate_watermark_id(watermark_ids)]
+        return torch.cat([message_to_tensor(w.to_bits(), self.watermark_bits) for w in ids]).to(self.device)
+
+    @torch.no_grad()
+    def embed_clips(self, clips, watermark_ids, window_seconds: float = 30.0):
+        """clips: a list of 1-D tensors of any lengths (or [B,1,T]); watermark_ids: one per clip, or one for all
+        -> the watermarked clips, same kind as `clips`.  Long clips run as windows (window.py)."""
+        return window.windowed_generator(self._need("generator"), clips, self._messages(watermark_ids),
+                                         self._window_samples(window_seconds), self.generator_precision)
+
+    @torch.no_grad()
+    def detect_clips(self, clips, window_seconds: float = 30.0) -> Tuple[torch.Tensor, torch.Tensor]:
+        """-> (bits [B,16] int32, mean_prob [B,16]) for clips of any lengths, windowed."""
+        mp = window.windowed_detector_mean_prob(self._need("detector"), clips, self._window_samples(window_seconds),
+                                                self.detector_precision)
+        return (mp >= 0.5).to(torch.int32), mp
+
+    @torch.no_grad()
+    def locate_clips(self, clips, window_seconds: float = 30.0):
+        """-> sigmoid(locator logits) per clip: a list of [T] tensors, or [B, T] for a [B,1,T] input."""
+        out = window.windowed_locator(self._need("locator"), clips, self._window_samples(window_seconds), self.locator_precision)
+        if isinstance(out, torch.Tensor):
+            return torch.sigmoid(out).squeeze(1)
+        return [torch.sigmoid(o) for o in out]
+
+    def open_embed_session(self, watermark_ids) -> session.EmbedSession:
+        """Live watermarking of len(watermark_ids) streams in lockstep (session.py)."""
+        return session.EmbedSession(self._need("generator"), self._messages(watermark_ids), self.generator_precision)
+
+    def open_detect_session(self, n: int = 1) -> session.DetectSession:
+        return session.DetectSession(self._need("detector"), n, self.detector_precision)
+
+    def open_locate_session(self, n: int = 1) -> session.LocateSession:
+        return session.LocateSession(self._need("locator"), n, self.locator_precision)
+
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],
-              output_path: Optional[Union[str, Path]] = None) -> Tuple[np.ndarray, int, WatermarkID]:
+              output_path: Optional[Union[str, Path]] = None, *,
+              window_seconds: Optional[float] = None) -> Tuple[np.ndarray, int, WatermarkID]:
+        """window_seconds (NOT in the reference): run the clip as windows of that length; None = one whole-clip forward."""
         try:
             watermark_id = self._validate_watermark_id(watermark_id)
             audio, _ = load_audio(audio_path, self.sample_rate)
             msg = message_to_tensor(watermark_id.to_bits(), self.watermark_bits)
-            wm = self.embed_batch(audio.unsqueeze(0), msg).squeeze(0)          # [1, T]
+            if window_seconds is None:
+                wm = self.embed_batch(audio.unsqueeze(0), msg).squeeze(0)          # [1, T]
+            else:
+                wm = self.embed_clips(audio.unsqueeze(0), watermark_id, window_seconds).squeeze(0)
             if output_path:
                 save_audio(wm, output_path, self.sample_rate)
             return wm.cpu().numpy().squeeze(), self.sample_rate, watermark_id
@@ -129,10 +183,13 @@ class WaveVerify:
             logger.error(f"Embedding failed: {str(e)}")
             raise RuntimeError(f"Failed to embed watermark: {str(e)}") from e
 
-    def detect(self, audio_path: Union[str, Path]) -> Tuple[WatermarkID, float]:
+    def detect(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> Tuple[WatermarkID, float]:
         try:
             audio, _ = load_audio(audio_path, self.sample_rate)
-            _, mp = self.detect_batch(audio.unsqueeze(0))
+            if window_seconds is None:
+                _, mp = self.detect_batch(audio.unsqueeze(0))
+            else:
+                _, mp = self.detect_clips(audio.unsqueeze(0), window_seconds)
             confidence = mp.mean().item()              # mean of per-bit mean probabilities (core.py:583)
             detected = WatermarkID.custom(tensor_to_message(mp))
             return detected, confidence
@@ -140,10 +197,13 @@ class WaveVerify:
             logger.error(f"Detection failed: {str(e)}")
             raise RuntimeError(f"Failed to detect watermark: {str(e)}") from e
 
-    def locate(self, audio_path: Union[str, Path]) -> np.ndarray:
+    def locate(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> np.ndarray:
         try:
             audio, _ = load_audio(audio_path, self.sample_rate)
-            mask = self.locate_batch(audio.unsqueeze(0)).squeeze()
+            if window_seconds is None:
+                mask = self.locate_batch(audio.unsqueeze(0)).squeeze()
+            else:
+                mask = self.locate_clips(audio.unsqueeze(0), window_seconds).squeeze()
             n = audio.shape[-1]
             if mask.dim() == 1 and mask.shape[0] != n:          # core.py:638-644 (never hit: same length)
                 mask = torch.nn.functional.interpolate(mask[None, None], size=n, mode="linear",

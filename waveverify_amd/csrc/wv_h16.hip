@@ -1221,8 +1221,11 @@ hipError_t conv16u_launch(const Conv16Args& a, hipStream_t s) {
 // frame tile against wc[D][nb * hop], sigmoid, mean over time -- the [B, nb, T] logits never exist.  One workgroup per clip (fixed
 // summation order: deterministic); wave w owns bits nb/4 * w ..; the B fragments of a 64-frame tile (D <= 128: 16 of them) stay in
 // registers over all of a wave's row tiles, A fragments stream from L2.  hop % 32 == 0, nb % 4 == 0, D % 16 == 0.
-struct Head16Args { const float* Y; H16Weight w; const float* bc; float* mean_prob; int B, D, nb, hop, Fr, T; };
+// WIN (csrc/wv_window.hip): clip b is a window, only t in [keep_lo[b], keep_hi[b]) enters the sum, frame tiles wholly before keep_lo
+// are skipped and the SUM goes to psum[b][bit]; WIN = false is the whole-clip launch, unchanged.
+struct Head16Args { const float* Y; H16Weight w; const float* bc; float* mean_prob; int B, D, nb, hop, Fr, T; const int* keep_lo; const int* keep_hi; float* psum; };
 
+template <bool WIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void head16_kernel(Head16Args p) {
     __shared__ __attribute__((aligned(16))) float ys[128 * 64];       // y tile [D][64] f32
     __shared__ __attribute__((aligned(16))) h16 zs[16 * 64 * 8];       // z tile, c8 [D/8][64][8]
@@ -1237,7 +1240,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     float total[8];                                              // per bit of this wave (bpw <= 8), lane-partial
 #pragma unroll
     for (int i = 0; i < 8; ++i) total[i] = 0.f;
-    for (int f0 = 0; f0 < Fr; f0 += 64) {
+    const int lo = WIN ? p.keep_lo[b] : 0, hi = WIN ? p.keep_hi[b] : p.T;
+    for (int f0 = WIN ? (lo / p.hop) / 64 * 64 : 0; f0 < Fr; f0 += 64) {
         __syncthreads();
         for (int i = tid; i < D * 64; i += 256) {
             const int m = i >> 6, c = i & 63;
@@ -1294,7 +1298,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const int j = 32 * mt + 8 * (i >> 2) + 4 * h + (i & 3);
-                        const bool ok = f < Fr && f * p.hop + j < p.T;
+                        const int t = f * p.hop + j;
+                        const bool ok = f < Fr && t < p.T && (!WIN || (t >= lo && t < hi));
                         const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-(acc[e][i] + bcv)));   // 1-ulp reciprocal: a full-precision divide is ten more instructions per logit
                         s += ok ? sg : 0.f;
                     }
@@ -1310,7 +1315,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         if (i < bpw) {
             float v = total[i];
             for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-            if (lane == 0) p.mean_prob[(size_t)b * p.nb + wave * bpw + i] = v / (float)p.T;
+            if (lane == 0) {
+                if (WIN) p.psum[(size_t)b * p.nb + wave * bpw + i] = v;
+                else p.mean_prob[(size_t)b * p.nb + wave * bpw + i] = v / (float)p.T;
+            }
         }
     }
 }
@@ -1549,12 +1557,16 @@ hipError_t launch_spec16(const Spec16Args& a, hipStream_t s) {
     return hipErrorNotSupported;
 }
 
-hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s) {
-    if (!Y || !w.wq || !bc || !mean_prob || B < 1 || Fr < 1 || T < 1) return hipErrorInvalidValue;
+hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s,
+                         const int* keep_lo, const int* keep_hi, float* psum) {
+    const bool win = keep_lo || keep_hi || psum;
+    if (win && (!keep_lo || !keep_hi || !psum || mean_prob)) return hipErrorInvalidValue;
+    if (!Y || !w.wq || !bc || (!mean_prob && !win) || B < 1 || Fr < 1 || T < 1) return hipErrorInvalidValue;
     if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
     prof::Scope ps(s, "head16", 2.0 * B * D * (double)nb * hop * Fr, (double)B * (4.0 * D * Fr + 4.0 * nb));
-    Head16Args a{Y, w, bc, mean_prob, B, D, nb, hop, Fr, T};
-    hipLaunchKernelGGL(head16_kernel, dim3((unsigned)B), dim3(256), 0, s, a);
+    Head16Args a{Y, w, bc, mean_prob, B, D, nb, hop, Fr, T, keep_lo, keep_hi, psum};
+    if (win) hipLaunchKernelGGL(head16_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, a);
+    else hipLaunchKernelGGL(head16_kernel<false>, dim3((unsigned)B), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -244,7 +244,8 @@ inline void pack_stft16(const float* basis, int n_fft, std::vector<uint16_t> (&q
 }
 // detector head, mean-probability output only: L2Norm over channels of Y [B][D][Fr] (f32), composed head GEMM (w: [nb * hop][D] as A
 // fragments), sigmoid, mean over time.  hipErrorNotSupported outside D % 16 == 0, D <= 128, nb % 4 == 0, hop % 32 == 0.
-hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s);
+hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s,
+                         const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr);
 hipError_t launch_conv_pre16(const float* x, const float* w, const float* bias, void* Y, int B, int C, int T, int ks, float in_scale, hipStream_t s);
 hipError_t launch_f32_to_c8(const float* X, void* Y, int B, int C, int T, float scale, int elu, hipStream_t s);
 // L2Norm over channels (seanet.py:288-318: y / max(||y||, 1e-12) * sqrt(D)) of a latent [B][D][Fr] f32 -> c8 f16 (the f16 decoder's input)
@@ -346,6 +347,10 @@ struct HeadArgs {
     float* logits;        // [B, nb, T] or null
     float* mean_prob;     // [B, nb] or null
     int B, D, nb, hop, Fr, T;
+    // windowed mode (all three set, mean_prob null): psum[b][n] = sum of sigmoid(logit) over t in [keep_lo[b], keep_hi[b])
+    const int* keep_lo = nullptr;
+    const int* keep_hi = nullptr;
+    float* psum = nullptr;
 };
 hipError_t launch_head(const HeadArgs& a, hipStream_t s);
 

@@ -926,14 +926,19 @@ struct ZLoader {                       // A operand: rows = frames of one clip, 
     }
 };
 
-template <class T>
+// WIN: the windowed mode (csrc/wv_window.hip): clip b is a window whose kept samples are [keep_lo[b], keep_hi[b]); only those
+// enter the sum, frame tiles wholly before keep_lo are skipped, and the SUM (not the mean) goes to psum[b][bit].  WIN = false is
+// the whole-clip launch, unchanged.
+template <class T, bool WIN>
 __global__ __launch_bounds__(NT_) void head_kernel(HeadArgs p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int bit = blockIdx.x, b = blockIdx.y;
     const float bc = p.bc[bit];
     float psum = 0.f;
     const int nchunks = (p.D + BK - 1) / BK;
-    for (int f0 = 0; f0 < p.Fr; f0 += T::BM) {
+    const int lo = WIN ? p.keep_lo[b] : 0, hi = WIN ? p.keep_hi[b] : p.T;
+    const int fstart = WIN ? (lo / p.hop) / T::BM * T::BM : 0;
+    for (int f0 = fstart; f0 < p.Fr; f0 += T::BM) {
         for (int j0 = 0; j0 < p.hop; j0 += T::BN) {
             f32x16 acc[T::MT][T::NT];
             zero_acc<T>(acc);
@@ -944,7 +949,7 @@ __global__ __launch_bounds__(NT_) void head_kernel(HeadArgs p) {
             for_each_acc<T>(acc, [&](int row, int col, float v) {
                 const int f = f0 + row, j = j0 + col;
                 const int t = f * p.hop + j;
-                if (f < p.Fr && j < p.hop && t < p.T) {
+                if (f < p.Fr && j < p.hop && t < p.T && (!WIN || (t >= lo && t < hi))) {
                     const float lg = v + bc;
                     if (p.logits) p.logits[((size_t)b * p.nb + bit) * p.T + t] = lg;
                     psum += sigmoidf_(lg);
@@ -952,14 +957,16 @@ __global__ __launch_bounds__(NT_) void head_kernel(HeadArgs p) {
             });
         }
     }
-    if (p.mean_prob) {
+    if (WIN ? p.psum != nullptr : p.mean_prob != nullptr) {
         float* red = smem;
         __syncthreads();
         for (int off = 32; off > 0; off >>= 1) psum += __shfl_xor(psum, off);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = psum;
         __syncthreads();
-        if (threadIdx.x == 0)
-            p.mean_prob[(size_t)b * p.nb + bit] = (red[0] + red[1] + red[2] + red[3]) / (float)p.T;
+        if (threadIdx.x == 0) {
+            if (WIN) p.psum[(size_t)b * p.nb + bit] = red[0] + red[1] + red[2] + red[3];
+            else p.mean_prob[(size_t)b * p.nb + bit] = (red[0] + red[1] + red[2] + red[3]) / (float)p.T;
+        }
     }
 }
 
@@ -1354,7 +1361,12 @@ hipError_t launch_head(const HeadArgs& a, hipStream_t s) {
     static const std::string name = tile_name<T>("head");
     prof::Scope ps(s, name.c_str(), 2.0 * a.B * a.D * (double)a.nb * a.hop * a.Fr,
                    4.0 * a.B * ((double)a.D * a.Fr + (a.logits ? (double)a.nb * a.T : 0.0)));
-    hipLaunchKernelGGL(head_kernel<T>, grid, dim3(NT_), stage_bytes<T>(), s, a);
+    if (a.keep_lo || a.keep_hi || a.psum) {
+        if (!a.keep_lo || !a.keep_hi || a.mean_prob) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((head_kernel<T, true>), grid, dim3(NT_), stage_bytes<T>(), s, a);
+    } else {
+        hipLaunchKernelGGL((head_kernel<T, false>), grid, dim3(NT_), stage_bytes<T>(), s, a);
+    }
     return hipGetLastError();
 }
 

@@ -1145,12 +1145,14 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
     return WV_OK;
 }
 
+// keep_lo / keep_hi / psum: the windowed mean-probability mode (wv_detector_forward_windowed); all null otherwise.
 static int run_head_model(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,
-                          void* ws, size_t ws_bytes, void* stream, bool f16 = false) {
+                          void* ws, size_t ws_bytes, void* stream, bool f16 = false,
+                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr) {
     WsLayout L;
     int rc = check_common(m, B, T, ws, ws_bytes, &L);
     if (rc) return rc;
-    if (!x || (!logits && !mean_prob)) return fail(WV_EINVAL, "null tensor");
+    if (!x || (!logits && !mean_prob && !psum)) return fail(WV_EINVAL, "null tensor");
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
     float* latent = (float*)(w + L.off_lat);
@@ -1167,7 +1169,8 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
         if (rc) return rc;
         if (latent_done) {
             wv::prof::set_role("head16");
-            const hipError_t e2 = wv::launch_head16(latent, m->h16.back().head, m->head_bc, mean_prob, B, D, m->head_nb, hop, Fr, T, st);
+            const hipError_t e2 = wv::launch_head16(latent, m->h16.back().head, m->head_bc, mean_prob, B, D, m->head_nb, hop, Fr, T, st,
+                                                    keep_lo, keep_hi, psum);
             if (e2 != hipSuccess) return fail(WV_EHIP, std::string("launch_head16: ") + hipGetErrorString(e2));
             return WV_OK;
         }
@@ -1178,8 +1181,23 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
     wv::HeadArgs h{};
     h.Z = latent; h.wc = m->head_wc; h.bc = m->head_bc; h.logits = logits; h.mean_prob = mean_prob;
     h.B = B; h.D = m->cfg.dimension; h.nb = m->head_nb; h.hop = hop_of(m->cfg); h.Fr = Fr; h.T = T;
+    h.keep_lo = keep_lo; h.keep_hi = keep_hi; h.psum = psum;
     LAUNCH(wv::launch_head(h, st));
     return WV_OK;
+}
+
+int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum, int W, int L,
+                                 void* ws, size_t ws_bytes, void* stream) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
+    return run_head_model(m, x, nullptr, nullptr, W, L, ws, ws_bytes, stream, false, keep_lo, keep_hi, psum);
+}
+
+int wv_detector_forward_windowed_f16(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum, int W, int L,
+                                     void* ws, size_t ws_bytes, void* stream) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
+    return run_head_model(m, x, nullptr, nullptr, W, L, ws, ws_bytes, stream, true, keep_lo, keep_hi, psum);
 }
 
 int wv_detector_forward(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,

@@ -1,0 +1,123 @@
+// Windowed long-form and live-session execution.  A clip, or a stream, runs as a batch of WINDOWS: a run of
+// frames plus a left halo at least as long as the nets' receptive field; the window batch goes through the unchanged net forwards and
+// only each window's kept columns come back.  This file holds the data movement around those forwards:
+//   window_gather_kernel   packed multi-clip source -> [W, 1, L] window batch (16-byte loads / stores where aligned)
+//   window_scatter_kernel  kept columns of [W, C, L] window outputs -> each clip's [C, T] output
+//   window_mean_kernel     per-window sigmoid sums psum[W, nb] (head_kernel / head16_kernel in their windowed mode) -> mean_prob[B, nb],
+//                          windows of a clip added in a fixed order in f64: deterministic, no drift with length
+//   session_advance_kernel a live session's tick: [S, H] history + [S, n] new samples -> the tick's window and the next history
+// Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "../../include/waveverify_hip.h"
+
+namespace wv {
+
+constexpr int WIN_NT = 256, WIN_PER_THREAD = 4, WIN_TILE = WIN_NT * WIN_PER_THREAD;
+
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// grid (ceil(L / WIN_TILE), W): window w = src[offs[w] .. offs[w] + L)
+__global__ __launch_bounds__(WIN_NT) void window_gather_kernel(const float* __restrict__ src, int64_t n_src, const int64_t* __restrict__ offs,
+                                                               float* __restrict__ dst, int L) {
+    const int w = blockIdx.y;
+    const int64_t off = offs[w];
+    if (off < 0 || off + L > n_src) return;
+    const float* s = src + off;
+    float* d = dst + (size_t)w * L;
+    const int j = blockIdx.x * WIN_TILE + threadIdx.x * WIN_PER_THREAD;
+    if (aligned16(s) && aligned16(d) && j + WIN_PER_THREAD <= L) {
+        *reinterpret_cast<float4*>(d + j) = *reinterpret_cast<const float4*>(s + j);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < WIN_PER_THREAD; ++i)
+        if (j + i < L) d[j + i] = s[j + i];
+}
+
+// grid (ceil(L / WIN_TILE), C, W).  desc[w] = {dst offset of the window's column 0 (row 0), dst row stride, keep lo, keep hi}, the keep
+// range relative to the window: out[desc0 + c * desc1 + j] = y[w][c][j] for j in [lo, hi).
+__global__ __launch_bounds__(WIN_NT) void window_scatter_kernel(const float* __restrict__ y, const int64_t* __restrict__ desc, float* __restrict__ out,
+                                                                int64_t n_out, int C, int L) {
+    const int c = blockIdx.y, w = blockIdx.z;
+    const int64_t base = desc[4 * w], stride = desc[4 * w + 1], lo = desc[4 * w + 2], hi = desc[4 * w + 3];
+    if (lo < 0 || hi > L || lo >= hi || base + lo < 0 || base + (int64_t)(C - 1) * stride + hi > n_out) return;
+    const float* s = y + ((size_t)w * C + c) * L;
+    float* d = out + base + (int64_t)c * stride;
+    const int j = blockIdx.x * WIN_TILE + threadIdx.x * WIN_PER_THREAD;
+    if (aligned16(s) && aligned16(d) && j >= lo && j + WIN_PER_THREAD <= hi) {
+        *reinterpret_cast<float4*>(d + j) = *reinterpret_cast<const float4*>(s + j);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < WIN_PER_THREAD; ++i)
+        if (j + i >= lo && j + i < hi) d[j + i] = s[j + i];
+}
+
+// one thread per (clip, bit): mean[b][k] = (sum over rows[ptr[b] .. ptr[b+1]) of psum[row][k], in that order, in f64) / len[b]
+__global__ __launch_bounds__(WIN_NT) void window_mean_kernel(const float* __restrict__ psum, int n_rows, const int* __restrict__ ptr,
+                                                             const int* __restrict__ rows, const int64_t* __restrict__ len, float* __restrict__ mean,
+                                                             int B, int nb) {
+    const int i = blockIdx.x * WIN_NT + threadIdx.x;
+    if (i >= B * nb) return;
+    const int b = i / nb, k = i % nb;
+    double acc = 0.0;
+    for (int r = ptr[b]; r < ptr[b + 1]; ++r) {
+        const int row = rows[r];
+        if (row >= 0 && row < n_rows) acc += (double)psum[(size_t)row * nb + k];
+    }
+    mean[i] = len[b] > 0 ? (float)(acc / (double)len[b]) : 0.f;
+}
+
+// grid (ceil(max(wlen, hv2) / WIN_NT), S).  Stream s's samples are cat(hist[s][0 .. hv), x[s][0 .. n)); the window is that sequence's
+// first wlen samples, the next history its samples [drop, drop + hv2).
+__global__ __launch_bounds__(WIN_NT) void session_advance_kernel(const float* __restrict__ hist, int hcap, int hv, const float* __restrict__ x, int n,
+                                                                 float* __restrict__ win, int wlen, float* __restrict__ hist_out, int drop, int hv2) {
+    const int s = blockIdx.y, j = blockIdx.x * WIN_NT + threadIdx.x;
+    const float* h = hist + (size_t)s * hcap;
+    const float* xs = x + (size_t)s * n;
+    if (j < wlen) win[(size_t)s * wlen + j] = j < hv ? h[j] : xs[j - hv];
+    if (j < hv2) {
+        const int q = drop + j;
+        hist_out[(size_t)s * hcap + j] = q < hv ? h[q] : xs[q - hv];
+    }
+}
+
+}  // namespace wv
+
+static int launched() { return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP; }
+
+extern "C" int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream) {
+    if (!src || !offs || !dst || W < 1 || W > 65535 || L < 1 || n_src < L) return WV_EINVAL;
+    hipLaunchKernelGGL(wv::window_gather_kernel, dim3((L + wv::WIN_TILE - 1) / wv::WIN_TILE, W), dim3(wv::WIN_NT), 0, (hipStream_t)stream, src, n_src,
+                       offs, dst, L);
+    return launched();
+}
+
+extern "C" int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream) {
+    if (!y || !desc || !out || W < 1 || W > 65535 || C < 1 || C > 65535 || L < 1 || n_out < 1) return WV_EINVAL;
+    hipLaunchKernelGGL(wv::window_scatter_kernel, dim3((L + wv::WIN_TILE - 1) / wv::WIN_TILE, C, W), dim3(wv::WIN_NT), 0, (hipStream_t)stream, y, desc,
+                       out, n_out, C, L);
+    return launched();
+}
+
+extern "C" int wv_window_reduce_mean(const float* psum, int n_rows, const int* ptr, const int* rows, const int64_t* lengths, float* mean_prob, int B,
+                                     int nb, void* stream) {
+    if (!psum || !ptr || !rows || !lengths || !mean_prob || n_rows < 1 || B < 1 || nb < 1) return WV_EINVAL;
+    hipLaunchKernelGGL(wv::window_mean_kernel, dim3((B * nb + wv::WIN_NT - 1) / wv::WIN_NT), dim3(wv::WIN_NT), 0, (hipStream_t)stream, psum, n_rows, ptr,
+                       rows, lengths, mean_prob, B, nb);
+    return launched();
+}
+
+extern "C" int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen, float* hist_out, int drop, int hv2,
+                                  int S, void* stream) {
+    if (!hist || !hist_out || hist == hist_out || S < 1 || S > 65535 || hcap < 1 || hv < 0 || hv > hcap || n < 0 || (n > 0 && !x)) return WV_EINVAL;
+    if (wlen < 0 || wlen > hv + n || (wlen > 0 && !win) || drop < 0 || hv2 < 0 || hv2 > hcap || drop + hv2 != hv + n) return WV_EINVAL;
+    const int m = wlen > hv2 ? wlen : hv2;
+    if (m == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::session_advance_kernel, dim3((m + wv::WIN_NT - 1) / wv::WIN_NT, S), dim3(wv::WIN_NT), 0, (hipStream_t)stream, hist, hcap, hv,
+                       x, n, win, wlen, hist_out, drop, hv2);
+    return launched();
+}

@@ -211,6 +211,31 @@ class HipNet:
             raise RuntimeError("not a detector")
         return self._head(x, False, True, precision)[1]
 
+    def detector_window_psum(self, x: torch.Tensor, keep_lo, keep_hi, psum: Optional[torch.Tensor] = None,
+                             precision: str = "f32") -> torch.Tensor:
+        """Windowed mode of the mean-probability head (window.py): x [W,1,L] windows, keep_lo / keep_hi [W] (relative to the window)
+        -> psum [W, nbits] = sum over t in [keep_lo, keep_hi) of sigmoid(logit); written into `psum` when given."""
+        if self.cfg.kind != "detector":
+            raise RuntimeError("not a detector")
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16'")
+        x = self._prep(x)
+        W, _, L = x.shape
+        lo = torch.as_tensor(keep_lo, dtype=torch.int32).reshape(-1).to(self.device)
+        hi = torch.as_tensor(keep_hi, dtype=torch.int32).reshape(-1).to(self.device)
+        if lo.numel() != W or hi.numel() != W:
+            raise ValueError("keep_lo / keep_hi need one entry per window")
+        if psum is None:
+            psum = torch.empty((W, self.cfg.head_bits), dtype=torch.float32, device=self.device)
+        if tuple(psum.shape) != (W, self.cfg.head_bits) or not psum.is_contiguous() or psum.dtype != torch.float32:
+            raise ValueError(f"psum must be a contiguous float32 [{W},{self.cfg.head_bits}] tensor")
+        with torch.cuda.device(self.device):
+            ws = self._workspace(W, L)
+            fn = self._lib.wv_detector_forward_windowed_f16 if precision == "f16" else self._lib.wv_detector_forward_windowed
+            _lib.check(fn(self._h, x.data_ptr(), lo.data_ptr(), hi.data_ptr(), psum.data_ptr(), W, L, ws.data_ptr(), ws.numel(),
+                          self._stream()), "wv_detector_forward_windowed" + ("_f16" if precision == "f16" else ""))
+        return psum
+
     def locator(self, x: torch.Tensor, precision: str = "f32") -> torch.Tensor:
         """Locator.forward: logits [B, 1, T].  precision="f16": the f16-operand / f32-accumulate throughput mode."""
         if self.cfg.kind != "locator":
