@@ -252,6 +252,12 @@ int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* 
  *                     [M,K,1], bias [M] HOST; Y16 / Yact16 c8 [B, M/8, Tin*r, 8] (either may be NULL)
  *   wv_h16_tail       decoder tail on the pre-activated c8 stream: out[B,1,T] = tanh(out_scale * (b + Conv1d(C -> 1, ks)(a16))) (+ x)
  *   wv_h16_l2norm     L2Norm over channels of lat [B,D,Fr] f32 (seanet.py:288-318) -> c8 f16
+ *   wv_h16_head       the mean-probability head of wv_detector_forward_f16 in one launch: L2Norm of lat [B,D,Fr] f32, z as f16, the
+ *                     composed head GEMM against f16(wc) (wc [D][nb*hop] HOST, column bit*hop + j; bc [nb] HOST: the exact path's
+ *                     ConvTranspose1d(k = s = hop) -> Conv1d(O -> nb, 1) composition), sigmoid, and over t < T (t = frame*hop + j) either
+ *                     mean_prob [B,nb] = the mean, or -- keep_lo / keep_hi [B] int32 DEVICE, psum [B,nb] -- psum = the sum over
+ *                     t in [keep_lo[b], keep_hi[b]) (mean_prob NULL).  Fr = ceil(T / hop); D % 16 == 0, D <= 128, nb % 4 == 0,
+ *                     nb <= 32, hop % 32 == 0, else WV_EINVAL
  *   wv_h16_conv_film  wv_h16_conv with FiLM behind it (film [B, bands, 2] DEVICE: gamma, beta per clip and band of M / bands rows) */
 int wv_h16_round_host(const float* in, uint16_t* out, int64_t n);   /* HOST pointers: the weight packers' f32 -> f16 rounding (nearest even) */
 int wv_h16_from_f32(const float* X, void* Y16, int B, int C, int T, float scale, int elu, void* stream);
@@ -275,6 +281,8 @@ int wv_h16_upsample(const void* X16, const float* w_ct, const float* w_pw, const
 int wv_h16_tail(const void* A16, const float* w, const float* bias, const float* x, float* out, int B, int C, int Tin, int T, int ks,
                 float out_scale, void* stream);
 int wv_h16_l2norm(const float* lat, void* Y16, int B, int D, int Fr, void* stream);
+int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T,
+                const int* keep_lo, const int* keep_hi, float* psum, void* stream);
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
                      int B, int K, int M, int Tin, int ks, int stride, int pad, float act_scale, void* stream);
 

@@ -189,3 +189,47 @@ def test_api_clips_and_sessions_agree_with_batches(tmp_path):
     b, _, _ = wv.embed(path, 777, window_seconds=5)
     assert np.abs(a - b).max() <= 1e-6
     assert wv.detect(path, window_seconds=5)[0] == wv.detect(path)[0]
+
+
+def test_windowed_f16_detect_vs_the_oracle(nets):
+    """The windowed f16 detect (head16_kernel's windowed mode behind every window, then one f64 reduction per clip) on mixed lengths, two
+    of them windowed, against the oracle of the mode's arithmetic on the whole clip (oracle/wv_oracle_h16.detect_mean_prob), not only by
+    its decisions.  Measured on the MI355X: 3.1e-6 at most; the bar is the whole-clip test's det_mean_bar(T) (tests/test_gpu_h16.py)."""
+    from oracle import wv_oracle_h16 as O16
+    from oracle import wv_oracle_torch as OT
+    from waveverify_amd import window
+    lengths = [16000, 9001, 1000]
+    clips = [synthetic_clips(1, T, seed=90 + i)[0][0, 0] for i, T in enumerate(lengths)]
+    mp = window.windowed_detector_mean_prob(nets["detector"], [torch.from_numpy(c).cuda() for c in clips], window=6400, precision="f16")
+    cfg = default_config("detector")
+    net = OT.Net(cfg, random_state_dict(cfg, 0))
+    for b, c in enumerate(clips):
+        ref = O16.detect_mean_prob(net, c.reshape(1, 1, -1))[0]
+        err = _err(mp[b].cpu(), ref)
+        print(f"MEASURE windowed f16 detect T={lengths[b]}: {err:.2e}")
+        assert err <= 2e-5 + 2e-4 / lengths[b] ** 0.5, err
+
+
+def test_exact_window_psum_per_sample(nets):
+    """The exact path's windowed head (head_kernel's WIN mode): rows that are copies of one clip, each keeping a narrow range -- single
+    samples at frame and 64-frame tile edges, ranges across them, an empty one -- sum exactly what sigmoid(detector(x)) sums over the
+    same columns, to f32 order (measured 1e-7 per kept sample)."""
+    D = nets["detector"]
+    hop = D.cfg.hop_length
+    L = 70 * hop - 11
+    x = torch.from_numpy(synthetic_clips(1, L, seed=5)[0]).cuda()
+    E = 64 * hop
+    ranges = [(0, 1), (1, 2), (hop - 1, hop), (hop, hop + 1), (hop + 1, hop + 2), (E - 1, E), (E, E + 1), (E + 1, E + 2), (L - 1, L),
+              (E - 3, E + 4), (hop - 2, hop + 3), (E, L), (0, L), (7, 7), (E, E), (32 * hop - 1, 32 * hop + 1), (63 * hop + 5, 65 * hop + 9)]
+    lo, hi = [a for a, _ in ranges], [b for _, b in ranges]
+    ps = D.detector_window_psum(x.expand(len(ranges), 1, L).contiguous(), lo, hi).double().cpu()
+    p = torch.sigmoid(D.detector(x)[0].double()).cpu()                                # [nb, L]
+    worst = 0.0
+    for r, (a, b) in enumerate(ranges):
+        ref = p[:, a:b].sum(dim=1)
+        err = float((ps[r] - ref).abs().max())
+        worst = max(worst, err / max(1, b - a))
+        assert err <= 1e-6 * max(1, b - a), (a, b, err)
+        if a == b:
+            assert (ps[r] == 0).all()
+    print(f"MEASURE exact window psum: {worst:.2e} per kept sample")

@@ -139,6 +139,15 @@ inline std::vector<uint16_t> pack_h16(const float* pw, const float* dw, int M, i
     *out = w;
     return q;
 }
+// host: the detector head's composed weight wc [D][nb * hop] (rows d, columns bit * hop + j) -> A fragments of its transpose
+// [nb * hop][D], the operand head16_kernel reads (launch_head16)
+inline std::vector<uint16_t> pack_head16(const float* wc, int D, int nb, int hop, H16Weight* out) {
+    const int rows = nb * hop;
+    std::vector<float> wt((size_t)rows * D);
+    for (int d = 0; d < D; ++d)
+        for (int r = 0; r < rows; ++r) wt[(size_t)r * D + d] = wc[(size_t)d * rows + r];
+    return pack_h16(wt.data(), nullptr, rows, D, 1, out);
+}
 // whole ResnetBlock, c8 f16 in / out (C in {32, 64, 96, 128, 192, 256, 384, 512, 768}, k = 5, dilation 1).  The kernel keeps both
 // activations times log2(e) (one instruction less per ELU, wv_h16.hip elu_l2), so the operands arrive pre-scaled -- pack_rh_pw /
 // pack_rh_table: w1, w2 = the 1x1 weights DIVIDED by log2(e); tab1 = the first stencil's taps and bias TIMES log2(e)
@@ -243,7 +252,7 @@ inline void pack_stft16(const float* basis, int n_fft, std::vector<uint16_t> (&q
     for (int k = 0; k < 4; ++k) q[k] = pack_h16(m[k].data(), nullptr, R, n_fft, 1, &w[k]);
 }
 // detector head, mean-probability output only: L2Norm over channels of Y [B][D][Fr] (f32), composed head GEMM (w: [nb * hop][D] as A
-// fragments), sigmoid, mean over time.  hipErrorNotSupported outside D % 16 == 0, D <= 128, nb % 4 == 0, hop % 32 == 0.
+// fragments), sigmoid, mean over time.  hipErrorNotSupported outside D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0.
 hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s,
                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr);
 hipError_t launch_conv_pre16(const float* x, const float* w, const float* bias, void* Y, int B, int C, int T, int ks, float in_scale, hipStream_t s);

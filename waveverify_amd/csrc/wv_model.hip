@@ -510,11 +510,9 @@ int pack_model(wv_model* m) {
                                                              c.dimension, C, c.last_kernel_size, &w, true);
                 st.post = U.h16_up(q, w);
                 if (c.kind != WV_KIND_GENERATOR) {
-                    const int D = c.dimension, rows = m->head_nb * hop_of(c);
-                    std::vector<float> wt((size_t)rows * D);
-                    for (int d = 0; d < D; ++d)
-                        for (int r = 0; r < rows; ++r) wt[(size_t)r * D + d] = head_wc_host[(size_t)d * rows + r];
-                    st.head = U.h16(wt, nullptr, rows, D, 1);
+                    wv::H16Weight wh;
+                    const std::vector<uint16_t> qh = wv::pack_head16(head_wc_host.data(), c.dimension, m->head_nb, hop_of(c), &wh);
+                    st.head = U.h16_up(qh, wh);
                 }
             }
             m->h16.push_back(std::move(st));
@@ -1163,7 +1161,7 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
         // mean probabilities only: conv_post and the head run on the f16 pipe as well (L2Norm + composed head GEMM + sigmoid + time mean)
         const wv_config& c = m->cfg;
         const int D = c.dimension, hop = hop_of(c);
-        const bool head16 = !logits && (int)m->h16.size() > c.n_strides && m->h16.back().head.wq && D % 16 == 0 && D <= 128 && m->head_nb % 4 == 0 && hop % 32 == 0;
+        const bool head16 = !logits && (int)m->h16.size() > c.n_strides && m->h16.back().head.wq && D % 16 == 0 && D <= 128 && m->head_nb % 4 == 0 && m->head_nb <= 32 && hop % 32 == 0;
         bool latent_done = false;
         rc = run_encoder_stages_f16(m, x, nullptr, B, T, w, L, st, head16 ? H16_TAIL_LATENT : H16_TAIL_F32, &post_done, &latent_done, &Fr);
         if (rc) return rc;

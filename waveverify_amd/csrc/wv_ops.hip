@@ -270,6 +270,19 @@ int wv_h16_l2norm(const float* lat, void* Y16, int B, int D, int Fr, void* strea
     Tmp t;
     return done(t, wv::launch_l2norm_c8(lat, Y16, B, D, Fr, (hipStream_t)stream), (hipStream_t)stream);
 }
+int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T,
+                const int* keep_lo, const int* keep_hi, float* psum, void* stream) {
+    if (!lat || !wc || !bc || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return WV_EINVAL;
+    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return WV_EINVAL;      // Fr = ceil(T / hop), as the nets' latents have
+    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32) return WV_EINVAL;               // launch_head16's gate
+    Tmp t;
+    wv::H16Weight w;
+    const std::vector<uint16_t> q = wv::pack_head16(wc, D, nb, hop, &w);
+    w.wq = t.upb(q.data(), q.size() * sizeof(uint16_t));
+    const hipError_t e = wv::launch_head16(lat, w, t.up(bc, nb), mean_prob, B, D, nb, hop, Fr, T, (hipStream_t)stream, keep_lo, keep_hi, psum);
+    if (e == hipErrorNotSupported) return WV_EINVAL;
+    return done(t, e, (hipStream_t)stream);
+}
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
                      int B, int K, int M, int Tin, int ks, int stride, int pad, float act_scale, void* stream) {
     if (!X16 || !w_pw || !film || bands < 1 || B < 1 || K < 1 || M < 1 || Tin < 1 || ks < 1 || stride < 1 || pad < 0) return WV_EINVAL;

@@ -315,6 +315,32 @@ def h16_l2norm(lat) -> torch.Tensor:
     return Y
 
 
+def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None) -> torch.Tensor:
+    """The f16 mode's mean-probability head (head16_kernel): lat [B, D, Fr] f32 latent before its L2Norm, wc [D, nb * hop] the composed
+    head weight (column bit * hop + j), bc [nb].  -> mean over t < T of sigmoid(logits) [B, nb]; with keep_lo / keep_hi ([B] ints) the
+    windowed mode instead: the SUM over t in [keep_lo[b], keep_hi[b]) [B, nb]."""
+    lib = _lib.load()
+    lat = _dev(lat)
+    B, D, Fr = lat.shape
+    wc, bc = _w(wc), _w(bc)
+    nb = bc.shape[0]
+    hop = wc.shape[-1] // nb
+    if wc.shape != (D, nb * hop):
+        raise ValueError(f"wc must be [D, nb * hop] = [{D}, {nb} * hop], got {wc.shape}")
+    if (keep_lo is None) != (keep_hi is None):
+        raise ValueError("keep_lo and keep_hi go together")
+    out = torch.empty((B, nb), dtype=torch.float32, device=lat.device)
+    lo = hi = None
+    if keep_lo is not None:
+        lo = torch.as_tensor(keep_lo, dtype=torch.int32).reshape(-1).to(lat.device)
+        hi = torch.as_tensor(keep_hi, dtype=torch.int32).reshape(-1).to(lat.device)
+        if lo.numel() != B or hi.numel() != B:
+            raise ValueError("keep_lo / keep_hi need one entry per clip")
+    _lib.check(lib.wv_h16_head(lat.data_ptr(), _hp(wc), _hp(bc), None if lo is not None else out.data_ptr(), B, D, nb, hop, Fr, int(T),
+                               _dp(lo), _dp(hi), _dp(out) if lo is not None else None, _stream()), "wv_h16_head")
+    return out
+
+
 def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optional[float] = None, want_raw: bool = True):
     """wv_h16_conv with FiLM behind the conv: film [B, bands, 2] (gamma, beta) on the device."""
     lib = _lib.load()
