@@ -233,8 +233,10 @@ int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* 
  *                     and the SpecBlock's 1x1 + add (ks = 1; seanet.py:500-502).  Outputs: Y16 / Yact16 = ELU(act_scale*y) in c8 f16,
  *                     Yf32 [B,M,Tout] f32 row-major (any of them NULL).
  *   wv_h16_spec_block whole SpecBlock in one launch (seanet.py:463-511): the STFT on the f16 pipe with the waveform split in two f16 terms,
- *                     log-magnitude, the 1x1 and the add; the spectrogram stays in LDS.  (n_fft = M, hop) in {(64,1),(128,2),(256,8),(512,40)}
- *                     (the default detector's scales), else WV_EINVAL; x16 / Y16 / Yact16 c8 f16 [B, M/8, ceil(T/hop), 8]
+ *                     log-magnitude, the 1x1 and the add; the spectrogram stays in LDS.  Every row of the basis is applied (sin_0 and
+ *                     sin_{F-1} in f32 beside the matrix product).  (n_fft, hop) in {(64,1),(128,2),(256,8),(512,40),(1024,320)} with
+ *                     M = n_fft (generator / detector scales) or {(64,1),(128,4),(256,32)} with M = n_fft / 2 (the locator's), else
+ *                     WV_EINVAL; x16 / Y16 / Yact16 c8 f16 [B, M/8, ceil(T/hop), 8]
  *   wv_detector_forward_f16   Detector.forward (model/detector.py:366-391) in this mode: conv_pre, the ResnetBlocks, the SpecBlocks
  *                     (STFT as a split-f16 matrix product) incl. spec_post and the downsample units on the f16 pipe; with logits == NULL
  *                     (mean probabilities only) conv_post and the head as well, otherwise those two by the exact path's f32 kernels.

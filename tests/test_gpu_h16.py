@@ -265,10 +265,11 @@ def test_spec_block_in_one_launch_half_channels(ops, n_fft, hop, T):
     _spec_block_case(ops, n_fft, hop, T, n_fft // 2)
 
 
-def _spec_block_case(ops, n_fft, hop, T, C):
+def _spec_block_case(ops, n_fft, hop, T, C, basis=None, w_kind="random"):
     """STFT (waveform split in two f16 terms, f16 basis) -> log-magnitude -> 1x1 -> add in one launch, against the oracle's exact
     composition; silence in one clip (both clamps), a loud clip, tile-edge frame counts.  What separates the two: the basis rounded to
-    f16 (leakage around the 1e-5 clamp level, visible only on near-silent bins), P and x' rounded to f16."""
+    f16 (leakage around the 1e-5 clamp level, visible only on near-silent bins), P and x' rounded to f16.  basis: [2F, n_fft] or None
+    (the analytic one); w_kind "selector": W[m][f] = [m == f], so that bin 0 and the Nyquist bin each land in a channel of their own."""
     rng = np.random.default_rng(n_fft + hop + T + C)
     F, Tf = n_fft // 2 + 1, -(-T // hop)
     wav = np.clip(rnd(rng, 3, 1, T, scale=0.1), -1, 1)
@@ -276,21 +277,30 @@ def _spec_block_case(ops, n_fft, hop, T, C):
     wav[2] *= 8.0
     x = h(rnd(rng, 3, C, Tf))
     w = h(rnd(rng, C, F, 1, scale=F ** -0.5))
+    if w_kind == "selector":
+        w = np.zeros((C, F, 1), np.float32)
+        w[np.arange(min(C, F)), np.arange(min(C, F)), 0] = 1.0
+        if C < F:                                                # half-channel geometries: the Nyquist bin into the last channel
+            w[C - 1, C - 1, 0], w[C - 1, F - 1, 0] = 0.0, 1.0
     s_out, s_act = np.float32(0.53), np.float32(0.7071)
-    mag = O.causal_stft_mag(wav, n_fft, hop)
+    mag = O.causal_stft_mag(wav, n_fft, hop, basis)
     P = ((np.log(np.maximum(mag, np.float32(1e-5))) - np.float32(-4.3)) / np.float32(2.8)).astype(np.float32)
     ref = (x + s_out * O.sconv1d(P, w, None)).astype(np.float32)
-    got, gact = ops.h16_spec_block(cu(wav), w, ops.h16_from_f32(cu(x)), n_fft, hop, mean=-4.3, std=2.8, out_scale=float(s_out), act_scale=float(s_act))
+    got, gact = ops.h16_spec_block(cu(wav), w, ops.h16_from_f32(cu(x)), n_fft, hop, mean=-4.3, std=2.8, out_scale=float(s_out), act_scale=float(s_act),
+                                   basis=basis)
     g = ops.h16_to_f32(got, C).cpu().numpy()
     assert np.isfinite(g).all()
     # frames whose bins all sit clear of the clamp: the f16 bar; frames with near-silent bins (the silent third of clip 1): the clamp region's
     # log is steep (d log|X| = d|X| / |X|), the exact path's own test allows 5e-3 per unit of |w| there and so does this one
     quiet = (mag <= 1e-3).any(axis=1, keepdims=True)
     lim = TOL * max(1.0, float(np.abs(ref).max())) + np.where(quiet, 5e-3 * float(s_out) * float(np.abs(w).sum(1).max()), 0.0)
+    print(f"MEASURE spec16 n_fft={n_fft} hop={hop} T={T} C={C} {w_kind}{'' if basis is None else ' (given basis)'}: "
+          f"max|d| {float(np.abs(g - ref).max()):.2e}, over the bar {float((np.abs(g - ref) - lim).max()):.2e}")
     assert (np.abs(g - ref) <= lim).all(), float((np.abs(g - ref) - lim).max())
     ga = ops.h16_to_f32(gact, C).cpu().numpy()
     assert (np.abs(ga - O.elu(ref * s_act)) <= lim).all()
-    only_act = ops.h16_spec_block(cu(wav), w, ops.h16_from_f32(cu(x)), n_fft, hop, mean=-4.3, std=2.8, out_scale=float(s_out), act_scale=float(s_act), want_raw=False)
+    only_act = ops.h16_spec_block(cu(wav), w, ops.h16_from_f32(cu(x)), n_fft, hop, mean=-4.3, std=2.8, out_scale=float(s_out), act_scale=float(s_act), want_raw=False,
+                                  basis=basis)
     assert torch.equal(only_act, gact)
 
 

@@ -192,6 +192,20 @@ def test_full_size_generator_gradients_vs_oracle_and_a_step():
 def test_stft_feature_backward_vs_torch_autograd(n_fft, hop, T):
     """d<dP, P(wav)>/dwav against torch autograd of the reference's formula (conv1d with the windowed DFT basis, sqrt(clamp), log(clamp),
     normalise; conv.py:1055-1078, seanet.py:484-494) in float64, with the pinned basis."""
+    _stft_feature_case(n_fft, hop, T, None)
+
+
+@pytest.mark.parametrize("n_fft,hop,T", [(64, 1, 1000), (128, 2, 1000), (256, 8, 4000), (1024, 320, 16000), (64, 4, 37)])
+def test_stft_feature_backward_vs_torch_autograd_learned_basis(n_fft, hop, T):
+    """The same with a learned basis (2 % noise on every row, sin_0 and sin_{F-1} included): the forward features as well, against the
+    float64 formula, with test_stft_with_given_basis' bar on |X| > 1e-3 and the clamp allowance below."""
+    from waveverify_amd.checkpoint import stft_basis
+    b = stft_basis(n_fft).double()
+    g = torch.Generator().manual_seed(n_fft)
+    _stft_feature_case(n_fft, hop, T, (b + 0.02 * float(b.abs().max()) * torch.randn(b.shape, generator=g, dtype=torch.float64)).float())
+
+
+def _stft_feature_case(n_fft, hop, T, learned):
     from oracle import wv_oracle as O
     from waveverify_amd.train import StftFeatures
     import torch.nn.functional as F
@@ -199,14 +213,19 @@ def test_stft_feature_backward_vs_torch_autograd(n_fft, hop, T):
     B = 3
     wav = (0.1 * rng.standard_normal((B, 1, T))).astype(np.float32)
     wav[1, 0, : T // 3] = 0.0                                       # silence: the clamped region passes no gradient
-    st = StftFeatures(n_fft, hop, -4.3, 2.8)
+    st = StftFeatures(n_fft, hop, -4.3, 2.8, basis=learned)
     P = st(_cu(wav))
     dP = rng.standard_normal(tuple(P.shape)).astype(np.float32)
     w = torch.from_numpy(wav).double().requires_grad_(True)
-    basis = torch.from_numpy(O.dft_basis(n_fft)).double()[:, None, :]
+    basis = torch.from_numpy(O.dft_basis(n_fft)).double()[:, None, :] if learned is None else learned.double()
     c = F.conv1d(F.pad(w, (n_fft - 1, 0)), basis, None, stride=hop)
     Fq = n_fft // 2 + 1
-    y = (((c[:, :Fq] ** 2 + c[:, Fq:] ** 2).clamp_min(1e-12).sqrt().clamp_min(1e-5).log()) - (-4.3)) / 2.8
+    mag = (c[:, :Fq] ** 2 + c[:, Fq:] ** 2).clamp_min(1e-12).sqrt()
+    y = ((mag.clamp_min(1e-5).log()) - (-4.3)) / 2.8
+    if learned is not None:
+        d, m = (P.cpu().double() - y.detach()).abs(), mag.detach() > 1e-3
+        print(f"MEASURE StftFeatures forward, learned basis, n_fft={n_fft}: {float(d[m].max()):.2e}; quiet {float(d[~m].max()) if (~m).any() else 0.0:.2e}")
+        assert float(d[m].max()) <= 2e-5 * max(1.0, float(y.abs().max())) and (float(d[~m].max()) if (~m).any() else 0.0) <= 5e-3
     y.backward(torch.from_numpy(dP).double())
     dw = torch.zeros(B, 1, T, device="cuda")
     st.backward(_cu(wav), _cu(dP), dw, accumulate=False)
@@ -486,6 +505,14 @@ def test_a_checkpoints_dft_bases_are_used_and_kept(tmp_path):
     assert float((wm_t - wm_i).abs().max()) <= 2e-6
     mp_t = torch.sigmoid(tr.D.forward(wm_t)).mean(-1)
     assert float((wv.detect_batch(wm_t)[1] - mp_t).abs().max()) <= 2e-6
+    # the same file in the f16 mode (its fused SpecBlocks apply every row of the basis, sin_0 and sin_{F-1} included): wm within 1e-4 of
+    # the exact path, the same bits
+    wv16 = WaveVerify(str(tmp_path / "a"))
+    wv16.set_precision("f16")
+    wm16 = wv16.embed_batch(x, msg)
+    print(f"MEASURE WaveVerify f16 vs exact, learned bases: wm {float((wm16 - wm_i).abs().max()):.2e}")
+    assert float((wm16 - wm_i).abs().max()) <= 1e-4
+    assert torch.equal(wv16.detect_batch(wm16)[0], wv.detect_batch(wm_i)[0])
     # ... and the perturbation matters: the analytic-basis nets give something else
     plain = WatermarkTrainer(cfgs["generator"], random_state_dict(cfgs["generator"], 0, parametrized=True), cfgs["detector"],
                              random_state_dict(cfgs["detector"], 0, parametrized=True), cfgs["locator"], random_state_dict(cfgs["locator"], 0, parametrized=True))

@@ -352,3 +352,68 @@ def test_training_gradient_oracle_vs_whole_reference_generator(golden_dir):
     for k in ref_keys:
         r = g["g:" + k]
         assert np.abs(grads[k] - r).max() <= 2e-3 * max(np.abs(r).max(), 1e-12) + 1e-9, (k, np.abs(grads[k] - r).max(), np.abs(r).max())
+
+
+# ---- learned STFT bases (tests/golden/make_golden_learned_basis.py): the reference's nets with every `...spec.weight` replaced by a
+# perturbed basis (waveverify_amd.init.learned_stft_bases, 2 % noise on every row, sin_0 and sin_{F-1} included).  Pins the oracles'
+# reading of a [2F, 1, n_fft] basis to the reference's own; same bars as test_full_size_against_reference.
+def _learned_state_dicts(parametrized):
+    from waveverify_amd.init import learned_stft_bases
+    out = {}
+    for k in ("generator", "detector", "locator"):
+        cfg = default_config(k)
+        out[k] = (cfg, {**random_state_dict(cfg, 0, parametrized=parametrized), **learned_stft_bases(cfg, 0)})
+    return out
+
+
+def test_learned_bases_are_the_fixtures():
+    """The bases the tests rebuild from the seed are the ones the fixture's reference ran with (every 61st row, both side rows)."""
+    g = np.load(os.path.join(os.path.dirname(__file__), "golden", "learned_basis_rows.npz"))
+    step = int(g["row_step"])
+    n = 0
+    for kind, (cfg, sd) in _learned_state_dicts(False).items():
+        for key, b in sd.items():
+            if not key.endswith("spec.weight"):
+                continue
+            tag = f"{kind}.{key[: -len('.spec.weight')]}"
+            F = b.shape[0] // 2
+            assert np.array_equal(g[f"basis_strided.{tag}"], b[::step, 0]), tag
+            assert np.array_equal(g[f"basis_side.{tag}"], b[[F, 2 * F - 1], 0]), tag
+            assert np.abs(b[[F, 2 * F - 1], 0]).max() > 0.01 * np.abs(b).max()          # side rows of full size
+            n += 1
+    assert n == 13
+
+
+@pytest.mark.parametrize("T", [16000, 4800])
+def test_learned_bases_against_reference(golden_dir, T):
+    g = np.load(os.path.join(golden_dir, f"learned_basis_T{T}.npz"))
+    nets = {k: O._Net(cfg, sd) for k, (cfg, sd) in _learned_state_dicts(True).items()}
+    taps = {}
+    G = nets["generator"]
+    delta = O.generator_forward(G.cfg, G, g["x"], g["msg"], taps)
+    _close(taps["latent"], g["latent"], 5e-5, "latent")
+    _close(delta, g["delta"], 1e-5, "delta")
+    _close((delta + g["x"]).astype(np.float32), g["wm"], 1e-5, "wm")
+    D = nets["detector"]
+    logits = O.detector_forward(D.cfg, D, g["wm"])
+    _close(logits[..., ::37], g["det_logits_sub"], 1e-4, "det logits")
+    mp = O.mean_probabilities(logits)
+    _close(mp, g["det_mean_prob"], 1e-5, "mean prob")
+    assert (O.decide_bits(mp) == g["det_bits"]).all() and float(g["det_margin"]) > 0.1
+    L = nets["locator"]
+    _close(O.locator_forward(L.cfg, L, g["wm"])[..., ::7], g["loc_logits_sub"], 1e-4, "loc logits")
+
+
+def test_learned_bases_torch_flavoured_oracle_matches_reference(golden_dir):
+    from oracle import wv_oracle_torch as OT
+    g = np.load(os.path.join(golden_dir, "learned_basis_T16000.npz"))
+    sds = _learned_state_dicts(False)
+    G = OT.Net(sds["generator"][0], _learned_state_dicts(True)["generator"][1])
+    D, L = (OT.Net(*sds[k]) for k in ("detector", "locator"))
+    _close(OT.embed(G, g["x"], g["msg"]).numpy(), g["wm"], 1e-5, "wm (torch oracle)")
+    lg = OT.detector_logits(D, g["wm"])
+    _close(lg.numpy()[..., ::37], g["det_logits_sub"], 1e-4, "det logits (torch oracle)")
+    mp = OT.mean_probabilities(lg).numpy()
+    _close(mp, g["det_mean_prob"], 1e-5)
+    assert ((mp >= 0.5).astype(int) == g["det_bits"]).all()
+    _close(OT.detector_logits(L, g["wm"]).numpy()[..., ::7], g["loc_logits_sub"], 1e-4, "loc (torch oracle)")

@@ -568,7 +568,10 @@ __global__ __launch_bounds__(256) void conv16_kernel(Conv16Args p) {
 // aligned piece).  The cos rows f = 0 .. n_fft/2 - 1 and the sin rows are separate A tiles, so that a lane holds re and im of the same
 // bin in the same register slot; sin row 0 (identically zero) carries the Nyquist bin's cos row instead.  P is written to LDS in the c8
 // layout -- the B operand of GEMM 2 = the 1x1 -- and never leaves the CU.  Epilogue 2 adds x (c8 f16 from HBM) and stores y and / or
-// ELU(act_scale * y).  (The exact path's two side rows, sin_0 and sin_{F-1} of a reference-built basis, are rounding-level and dropped.)
+// ELU(act_scale * y).  The two rows left out of GEMM 1, sin_0 and sin_{F-1} (rounding-level in an analytic basis, of full size in a
+// trained one), are applied as the exact path does (StftArgs::side): per frame, two f32 dot products over the staged window (hi + lo
+// 2^-11, the 22 bits GEMM 1 sees), spread over the whole workgroup, reduced in LDS and added as the imaginary parts of bin 0 and the
+// Nyquist bin.
 // N = n_fft = rows of the 1x1 (the detector's scales: 64, 128, 256, 512; 1024 = spec_post, whose output goes on in f32), HOP in {1, 2, 4, 8 k}.  A wave's unit is 64 rows x 64 frames
 // (one cos/sin tile pair in GEMM 1, two row tiles in GEMM 2).
 // M = rows of the 1x1 = channels of the stream: n_fft (generator / detector: every scale has as many channels as DFT points) or n_fft / 2
@@ -586,9 +589,12 @@ struct SP {
     static constexpr int PSP = (PP + 13) / 16 * 16 + 2;          // copy stride in pieces, = 2 (mod 16): the 8 copies x 2 pieces a 16-lane group reads are 16 different banks
     static constexpr int Fp = N / 2 + 16, G2 = Fp / 8, NC1 = N / 16, NC2 = Fp / 16;
     static constexpr size_t WIN = (size_t)NPL * PSP * 16;        // bytes of one (hi or lo) window
-    static constexpr size_t SMEM = 2 * WIN + (size_t)G2 * BN * 16;
+    static constexpr size_t SIDE = 2 * WIN + (size_t)G2 * BN * 16;   // byte offset of the side rows' products, [2][BN] f32
+    static constexpr size_t SMEM = SIDE + (size_t)2 * BN * 4;
+    static constexpr int SS = 1024 / BN, SL = N / SS;            // side products: SS lanes per frame, SL samples each, 4 frames per lane
     static constexpr int PASSES2 = (NP2 * NQ + 3) / 4;
     static_assert(N % 64 == 0 && (HOP == 1 || HOP == 2 || HOP == 4 || HOP % 8 == 0) && NP * NQ % 4 == 0 && (M == N || 2 * M == N) && M % 32 == 0, "geometry");
+    static_assert(SS * BN == 1024 && SS <= 64 && SL % 8 == 0, "side products");
 };
 
 template <class R>
@@ -598,6 +604,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     h16* Whi = reinterpret_cast<h16*>(smem_raw);
     h16* Wlo = reinterpret_cast<h16*>(smem_raw + R::WIN);
     h16* P16 = reinterpret_cast<h16*>(smem_raw + 2 * R::WIN);    // [G2][BN][8]
+    float* SD = reinterpret_cast<float*>(smem_raw + R::SIDE);    // [2][BN]: sin_0 . frame, sin_{F-1} . frame
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int h = lane >> 5, r = lane & 31;
@@ -667,6 +674,48 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
     RH_BARRIER();
 
+    // ---- the side rows: lane group of SS lanes per frame, each lane SL samples of 4 frames (fg, fg + BN/4, ..); a frame's samples are
+    // read from the copy in which they start 16-byte aligned, as GEMM 1's B fragments are; the SS partial sums meet by shuffles
+    {
+        constexpr int SS = R::SS, SL = R::SL, FG = BN / 4;
+        const int q = tid % SS, fg = tid / SS;
+        int fo[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int off = (fg + FG * i) * HOP;
+            fo[i] = (((off & 7) / HOP) * R::PSP + (off >> 3)) * 8 + q * SL;
+        }
+        float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f};
+        const float* side0 = p.side + q * SL;
+        const float* side1 = p.side + N + q * SL;
+#pragma unroll 2
+        for (int c = 0; c < SL; c += 8) {
+            float w0[8], w1[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { w0[j] = side0[c + j]; w1[j] = side1[c + j]; }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const h16x8 hv = *reinterpret_cast<const h16x8*>(Whi + fo[i] + c);
+                const h16x8 lv = *reinterpret_cast<const h16x8*>(Wlo + fo[i] + c);
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float x = fmaf((float)lv[j], 1.f / 2048.f, (float)hv[j]);
+                    s0[i] = fmaf(w0[j], x, s0[i]);
+                    s1[i] = fmaf(w1[j], x, s1[i]);
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+#pragma unroll
+            for (int m = SS / 2; m >= 1; m /= 2) {
+                s0[i] += __shfl_xor(s0[i], m, SS);
+                s1[i] += __shfl_xor(s1[i], m, SS);
+            }
+            if (q == 0) { SD[fg + FG * i] = s0[i]; SD[BN + fg + FG * i] = s1[i]; }
+        }
+    }
+
     // ================= GEMM 1 + log-magnitude -> P16 =================
     for (int pass = 0; pass < R::PASSES; ++pass) {
         const int u = wave + 4 * pass, mp = u % NP, nq = u / NP;
@@ -709,6 +758,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
             asm volatile("" : "+v"(lre[0]), "+v"(lre[1]), "+v"(lim[0]), "+v"(lim[1]));
             __builtin_amdgcn_sched_barrier(0);
         }
+        if (pass == 0) RH_BARRIER();                             // SD complete (PASSES is the same for every wave)
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             const int col = 64 * nq + 32 * e + r;
@@ -720,7 +770,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 for (int rr = 0; rr < 4; ++rr) {
                     const float re = fmaf(lre[e][4 * j + rr], 1.f / 2048.f, are[e][4 * j + rr]);
                     float im = fmaf(lim[e][4 * j + rr], 1.f / 2048.f, aim[e][4 * j + rr]);
-                    if (j == 0 && rr == 0 && mp == 0 && h == 0) { nyq = im; im = 0.f; }      // bin 0: no imaginary part; its sin slot carried the Nyquist bin
+                    if (j == 0 && rr == 0 && mp == 0 && h == 0) { nyq = im; im = SD[col]; }  // bin 0: its sin slot carried the Nyquist bin's cos row
                     v[rr] = (h16)stft_logmag(re, im, p.c1, p.c0);
                 }
                 *reinterpret_cast<h16x4*>(P16 + (size_t)((4 * mp + j) * BN + col) * 8 + 4 * h) = v;
@@ -730,7 +780,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
                 for (int i = 0; i < 8; ++i) z[i] = (h16)0.f;
                 *reinterpret_cast<h16x8*>(P16 + (size_t)((N / 16 + 1) * BN + col) * 8) = z;
-                z[0] = (h16)stft_logmag(nyq, 0.f, p.c1, p.c0);
+                z[0] = (h16)stft_logmag(nyq, SD[BN + col], p.c1, p.c0);
                 *reinterpret_cast<h16x8*>(P16 + (size_t)((N / 16) * BN + col) * 8) = z;
             }
         }
@@ -1537,7 +1587,7 @@ hipError_t launch_conv16(const Conv16Args& a, hipStream_t s) {
 }
 
 hipError_t launch_spec16(const Spec16Args& a, hipStream_t s) {
-    if (!a.wav || !a.resid || (!a.Y && !a.Yact && !a.Yf32) || !a.cosw.wq || !a.sinw.wq || !a.cosl.wq || !a.sinl.wq || !a.pw.wq || a.B < 1 || a.T < 1) return hipErrorInvalidValue;
+    if (!a.wav || !a.side || !a.resid || (!a.Y && !a.Yact && !a.Yf32) || !a.cosw.wq || !a.sinw.wq || !a.cosl.wq || !a.sinl.wq || !a.pw.wq || a.B < 1 || a.T < 1) return hipErrorInvalidValue;
     const int N = a.n_fft, M = a.pw.M;
     if (a.Tf != (a.T + a.hop - 1) / a.hop || (M != N && 2 * M != N) || a.pw.K != N / 2 + 1 || a.pw.Mp != M || a.pw.Kp != N / 2 + 16 || a.cosw.M != N / 2 || a.cosw.K != N ||
         a.sinw.M != N / 2 || a.sinw.K != N || a.cosw.Mp != N / 2 || a.sinw.Mp != N / 2 || a.cosw.nchunks < N / 16 || a.sinw.nchunks < N / 16 || a.cosl.nchunks < N / 16 || a.sinl.nchunks < N / 16)

@@ -216,9 +216,12 @@ inline std::vector<uint16_t> pack_up16(const float* pw, const float* ct, int Mo,
 hipError_t launch_conv16(const Conv16Args& a, hipStream_t s);
 // whole SpecBlock (STFT on the f16 pipe with a two-term split of the waveform -> log-magnitude -> 1x1 -> + x), the spectrogram stays in LDS.
 // cosw / sinw: the basis' cos rows f = 0 .. n_fft/2 - 1 and sin rows (row 0 = the Nyquist bin's cos row) as A fragments (pack_stft16);
-// pw: the 1x1 [n_fft][F] with K padded to n_fft/2 + 16.  (n_fft, hop) in {(64,1), (128,2), (256,8), (512,40), (1024,320)}, else hipErrorNotSupported.
+// side: the two sin rows that leaves out, sin_0 and sin_{F-1}, f32 [2][n_fft] (as StftArgs::side / pack_stft_basis), applied in f32.
+// pw: the 1x1 [M][F] with K padded to n_fft/2 + 16.  (n_fft, hop, M) in {(64,1), (128,2), (256,8), (512,40), (1024,320)} with M = n_fft and
+// {(64,1), (128,4), (256,32)} with M = n_fft / 2, else hipErrorNotSupported.
 struct Spec16Args {
     const float* wav; H16Weight cosw, sinw, cosl, sinl, pw; const void* resid; void* Y; void* Yact;   // cosl / sinl: (basis - f16(basis)) * 2^11
+    const float* side;    // [2][n_fft] f32: sin_0 row, sin_{F-1} row
     float* Yf32;          // [B][n_fft][Tf] f32 row-major copy of y, or null
     float out_scale, act_scale, c1, c0; int B, T, Tf, n_fft, hop;
 };

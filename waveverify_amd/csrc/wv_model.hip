@@ -1060,7 +1060,7 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
         // x' = x + scale * (W @ P); only ELU(c * x') is consumed.  One launch where the scale is one of the fused kernel's (the default
         // detector's / generator's four), else the exact path's STFT kernel -> P in HBM -> f16 copy -> the 1x1 + add as a k = 1 conv
         wv::Spec16Args f{};
-        f.wav = x; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr; f.Yact = A0;
+        f.wav = x; f.side = sp.side; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr; f.Yact = A0;
         f.out_scale = sp.scale; f.act_scale = d.pre_scale; f.c1 = 0.5f * 0.6931471805599453f * sp.inv_std; f.c0 = -sp.mean * sp.inv_std;
         f.B = B; f.T = T; f.Tf = Tl; f.n_fft = sp.n_fft; f.hop = sp.hop;
         const hipError_t fe = (C == sp.n_fft || 2 * C == sp.n_fft) ? wv::launch_spec16(f, st) : hipErrorNotSupported;
@@ -1101,7 +1101,7 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
         bool done = false;
         if (hs.cosw.wq) {
             wv::Spec16Args f{};
-            f.wav = x; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr;
+            f.wav = x; f.side = sp.side; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr;
             f.Yact = latent ? A0 : nullptr; f.Yf32 = f32out;
             f.out_scale = sp.scale; f.act_scale = latent ? 1.f : 0.f; f.c1 = 0.5f * 0.6931471805599453f * sp.inv_std; f.c0 = -sp.mean * sp.inv_std;
             f.B = B; f.T = T; f.Tf = Tl; f.n_fft = sp.n_fft; f.hop = sp.hop;

@@ -304,6 +304,9 @@ int wv_h16_spec_block(const float* wav, const float* basis_or_null, const float*
     wv::pack_stft16(basis.data(), n_fft, q4, w4);
     for (int k = 0; k < 4; ++k) w4[k].wq = t.upb(q4[k].data(), q4[k].size() * sizeof(uint16_t));
     a.cosw = w4[0]; a.sinw = w4[1]; a.cosl = w4[2]; a.sinl = w4[3];
+    std::vector<float> bt, side;                                 // side: sin_0, sin_{F-1} (the exact path's layout)
+    wv::pack_stft_basis(basis.data(), n_fft, bt, side, nullptr);
+    a.side = t.up(side.data(), side.size());
     a.pw = t.h16(w_pw, nullptr, M, n_fft / 2 + 1, 1);
     a.wav = wav; a.resid = x16; a.Y = Y16; a.Yact = Yact16; a.out_scale = out_scale; a.act_scale = act_scale;
     a.c1 = 0.5f * 0.69314718055994531f / std_; a.c0 = -mean / std_;

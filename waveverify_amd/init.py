@@ -76,3 +76,23 @@ def synthetic_clips(B: int, T: int, seed: int = 1234, nbits: int = 16):
     x = np.clip(0.1 * r.standard_normal((B, 1, T), dtype=np.float32), -1.0, 1.0)
     msg = r.integers(0, 2, size=(B, nbits)).astype(np.float32)
     return x.astype(np.float32), msg
+
+
+def stft_basis_keys(cfg: NetConfig) -> Dict[str, int]:
+    """{`...spec.weight` key: n_fft} of a net: the SpecBlocks' scales, then spec_post at the last one (seanet.py:661-795)."""
+    S = len(cfg.strides)
+    return {("encoder.spec_post" if s == S else f"encoder.spec_blocks.{s}") + ".spec.weight": (2 ** s) * cfg.n_fft_base
+            for s in range(S + 1)}
+
+
+def learned_stft_bases(cfg: NetConfig, seed: int = 0, rel: float = 0.02) -> Dict[str, np.ndarray]:
+    """A stand-in for the bases a run with spec_learnable: true (conf/base.yml) leaves in a checkpoint: every `...spec.weight`
+    ([2F, 1, n_fft] float32) is the reference's windowed DFT basis plus rel * max|basis| * N(0, 1) on EVERY row, sin_0 and
+    sin_{F-1} included (seeded per net kind, seed and key)."""
+    from .checkpoint import stft_basis
+    out = {}
+    for key, n_fft in stft_basis_keys(cfg).items():
+        b = stft_basis(n_fft).numpy().astype(np.float64)
+        noise = _rng(seed, f"{cfg.kind}/learned/{key}").standard_normal(b.shape)
+        out[key] = (b + rel * float(np.abs(b).max()) * noise).astype(np.float32)
+    return out
