@@ -4,7 +4,7 @@
 batch: wm = G(x, msg) + x, then the detector's time-averaged bit probabilities on wm and the
 >= 0.5 decision.  Inputs are already in HBM when the timed region starts.
 
-    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -15,18 +15,19 @@ line and exits with the child's code.
 Clips are independent units, so N GPUs = N data-parallel shards with NO data-path collective
 (SURVEY.md section 8e); weak scaling (256 clips per GPU).  Rank 0 prints ONE JSON line.
 
-Two passes: `value` / `ms_per_step` come from a CLEAN pass (W warm-up + exactly K steps, no event
-recording, barrier + synchronize on both sides, MAX over ranks); the per-kernel table and the roofline
-blocks come from a second, PROFILED pass of the same K steps (a hipEvent pair around every launch on
-the launch stream, ~190 pairs per step), whose own wall time is reported as `profiled_ms_per_step`.
+A plain run does only what the headline needs: set-up, W warm-up steps, the CLEAN pass that gives `value` / `ms_per_step` (exactly
+K steps, no event recording, barrier + synchronize on both sides, MAX over ranks), --dump-outputs, the line.  `--full` adds, after
+the clean pass and without changing it, everything else the line can carry: a second, PROFILED pass of the same K steps (a hipEvent
+pair around every launch on the launch stream, ~190 pairs per step) for the per-kernel table and the roofline blocks, with its own
+wall time as `profiled_ms_per_step`; the other precision's pass; the locator's pass; the torch-CPU baseline and the parity against it.
 
 Other workloads (--workload): longform (configs[3]), detector_stress (configs[4]) and grad_allreduce
 (configs[2]: the training step's only exchange, a bucketed RCCL all-reduce of 56.1 + 170.1 MB of fp32
 gradients; reports ms per all-reduce and bus GB/s).  `--precision f16` (embed_detect, longform, detector_stress) runs the
 f16-operand / f32-accumulate mode of the three nets (csrc/wv_h16.hip; configs[1] "bf16" / configs[4] "fp16" as BASELINE words them) and
-prints ITS OWN line: dtype "f16", the exact-f32 mode timed beside it, both modes' outputs against each other and against the oracle.
-The default (exact f32) line carries a `reduced_precision` block -- that mode's ms per step, wm max|d| and BER on the same batch -- so
-the driver's record holds it; `value` is always the exact path's.
+prints ITS OWN line: dtype "f16"; with --full also the exact-f32 mode timed beside it, both modes' outputs against each other and
+against the oracle.  With --full the default (exact f32) line carries a `reduced_precision` block -- that mode's ms per step, wm
+max|d| and BER on the same batch; `value` is always the exact path's.
 """
 from __future__ import annotations
 
@@ -58,8 +59,11 @@ def parse():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=1.0)
-    ap.add_argument("--cpu-clips", type=int, default=16, help="clips of the CPU-baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also the profiled pass (per-kernel table, roofline blocks), the other precision's and the "
+                         "locator's passes, the CPU baseline and the parity checks; a plain run measures the headline alone")
+    ap.add_argument("--cpu-clips", type=int, default=16, help="--full: clips of the CPU-baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity against it")
     ap.add_argument("--workload", default="embed_detect",
                     choices=["embed_detect", "longform", "detector_stress", "grad_allreduce", "train_step", "rendezvous"],
                     help="embed_detect = BASELINE configs[1] (the headline); longform = configs[3] "
@@ -69,7 +73,7 @@ def parse():
     ap.add_argument("--bucket-mb", type=float, default=25.0, help="grad_allreduce: bucket size")
     ap.add_argument("--precision", default="f32", choices=["f32", "f16"],
                     help="f16 = the f16-operand / f32-accumulate mode of the nets (csrc/wv_h16.hip) for embed_detect / longform / detector_stress: "
-                         "its own line (dtype f16) with its own parity block and roofs; the headline `value` is always exact f32")
+                         "its own line (dtype f16), with --full its own parity block and roofs; the headline `value` is always exact f32")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / "
                          "float64, %d MB at most in all: larger outputs as a fixed seeded sample); inputs and weights are seeded, so two "
@@ -190,7 +194,6 @@ def train_step(a, dev, dist, world, rank):
     waveform loss, backward through D, L, the augmentation and G with live weight norm, mean all-reduce of the three flat gradient
     arenas (RCCL when N > 1), generator-only clipping, AdamW.  The reference's step also has audio effects, mel / STFT losses and a
     discriminator, which stay on PyTorch and are NOT in this number, so it is not the headline metric."""
-    from waveverify_amd import profile
     from waveverify_amd.config import default_config
     from waveverify_amd.init import random_state_dict, synthetic_clips
     from waveverify_amd.train import WatermarkTrainer
@@ -225,8 +228,32 @@ def train_step(a, dev, dist, world, rank):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     last_timed = outs[-1]
-    # anatomy: a second pass of the same K steps with a hipEvent pair around every instrumented launch (the K1 GEMMs of forward and
-    # backward, the dW GEMM); the stencil / reduction / optimizer kernels of the training library carry no events and make up the rest
+    ms = elapsed / a.steps * 1e3
+    anatomy = train_anatomy(a, step, ms) if a.full else {}
+    if rank == 0:
+        dumped = dump_outputs(a.dump_outputs, {k.replace("/", "_"): v for k, v in last_timed.items() if torch.is_tensor(v)}) \
+            if a.dump_outputs else None
+        pick = lambda o: {k: round(float(o[k].item()), 5) for k in ("dec/loss", "loc/loss", "waveform/loss")}       # noqa: E731
+        print(json.dumps(dict(
+            metric="clips/sec training step (generator update: G+D+L forward/backward, BCE + waveform losses), 1s@16kHz bs=64 per GPU",
+            value=round(world * B * a.steps / elapsed, 2), unit="clips/s", n_gpus=world, rccl_ranks=dist.get_world_size() if dist else 0,
+            steps=a.steps, warmup=a.warmup,
+            ms_per_step=round(ms, 3), higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
+            config=dict(workload=f"train_step: BASELINE.json configs[2] per-GPU batch ({B} clips x {a.seconds:g} s); the part of the reference's "
+                                 "generator update that runs on the HIP training units (no audio effects, mel/STFT losses or discriminator)",
+                        batch_per_gpu=B, global_batch=B * world, clip_samples=T,
+                        parallelism=f"dp{world} (three flat gradient arenas, bucketed mean all-reduce)",
+                        parameters=dict(generator=int(tr.G.arena.numel()), detector=int(tr.D.arena.numel()), locator=int(tr.L.arena.numel()))),
+            losses_first=pick(outs[0]), losses_last=pick(outs[-1]), **anatomy, dumped_outputs=dumped,
+            note="backward on saved activations (the blocks' 1x1 outputs kept from forward), activation derivative / residual / scale "
+                 "epilogues fused into the K1 GEMMs, parameter gradients written in place into one flat arena per net")), flush=True)
+
+
+def train_anatomy(a, step, ms):
+    """train_step --full: a second pass of the same K steps with a hipEvent pair around every instrumented launch (the K1 GEMMs of
+    forward and backward, the dW GEMM); the stencil / reduction / optimizer kernels of the training library carry no events and make up
+    the rest.  `ms` is the clean pass's ms per step."""
+    from waveverify_amd import profile
     profile.reset()
     profile.enable(True)
     torch.cuda.synchronize()
@@ -241,48 +268,31 @@ def train_step(a, dev, dist, world, rank):
         k = (stencil if e["kernel"].startswith("dw_bwd") else by).setdefault(e["kernel"], dict(ms=0.0, launches=0, flops=0.0, bytes=0.0))
         for f in ("ms", "launches", "flops", "bytes"):
             k[f] += e[f]
-    if rank == 0:
-        dumped = dump_outputs(a.dump_outputs, {k.replace("/", "_"): v for k, v in last_timed.items() if torch.is_tensor(v)}) \
-            if a.dump_outputs else None
-        ms = elapsed / a.steps * 1e3
-        kernels = sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3), "launches_per_step": v["launches"] // a.steps,
-                           "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] else 0.0,
-                           "frac_of_f32_mfma_peak": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 3) if v["ms"] else 0.0}
-                          for k, v in by.items()), key=lambda d: -d["ms_per_step"])
-        inst_ms = sum(v["ms"] for v in by.values()) / a.steps
-        inst_fl = sum(v["flops"] for v in by.values()) / a.steps
-        pick = lambda o: {k: round(float(o[k].item()), 5) for k in ("dec/loss", "loc/loss", "waveform/loss")}       # noqa: E731
-        print(json.dumps(dict(
-            metric="clips/sec training step (generator update: G+D+L forward/backward, BCE + waveform losses), 1s@16kHz bs=64 per GPU",
-            value=round(world * B * a.steps / elapsed, 2), unit="clips/s", n_gpus=world, rccl_ranks=dist.get_world_size() if dist else 0,
-            steps=a.steps, warmup=a.warmup,
-            ms_per_step=round(ms, 3), higher_is_better=True, scaling="weak", vs_baseline=None, dtype="f32", data="synthetic",
-            config=dict(workload=f"train_step: BASELINE.json configs[2] per-GPU batch ({B} clips x {a.seconds:g} s); the part of the reference's "
-                                 "generator update that runs on the HIP training units (no audio effects, mel/STFT losses or discriminator)",
-                        batch_per_gpu=B, global_batch=B * world, clip_samples=T,
-                        parallelism=f"dp{world} (three flat gradient arenas, bucketed mean all-reduce)",
-                        parameters=dict(generator=int(tr.G.arena.numel()), detector=int(tr.D.arena.numel()), locator=int(tr.L.arena.numel()))),
-            losses_first=pick(outs[0]), losses_last=pick(outs[-1]),
-            roofline=dict(bound="mfma", peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s",
-                          instrumented_ms_per_step=round(inst_ms, 3), instrumented_tflop_per_step=round(inst_fl / 1e12, 3),
-                          achieved=round(inst_fl / (inst_ms * 1e-3) / 1e12, 2) if inst_ms else None,
-                          frac=round(inst_fl / (inst_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4) if inst_ms else None,
-                          step_frac=round(inst_fl / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
-                          note="matrix kernels only (K1 forward / backward GEMMs, dW GEMM): their flops over their own event time; step_frac = the "
-                               "same flops over the whole step, i.e. with the bandwidth-bound stencil / reduction / optimizer kernels in the denominator"),
-            roofline_stencil_backward=dict(
-                bound="hbm", peak=PEAK_HBM_GBS, unit="GB/s",
-                ms_per_step=round(sum(v["ms"] for v in stencil.values()) / a.steps, 3),
-                achieved=round(sum(v["bytes"] for v in stencil.values()) / max(sum(v["ms"] for v in stencil.values()), 1e-9) / 1e6, 1),
-                frac=round(sum(v["bytes"] for v in stencil.values()) / max(sum(v["ms"] for v in stencil.values()), 1e-9) / 1e6 / PEAK_HBM_GBS, 4),
-                kernels=sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3), "launches_per_step": v["launches"] // a.steps,
-                                 "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] else 0.0} for k, v in stencil.items()),
-                               key=lambda d: -d["ms_per_step"]),
-                note="the depth-wise stencils' transposes (dh and the tap / bias sums; the second half's also the res_scale dot): algorithmic bytes "
-                     "= read dy, read h (and v), write dh, over their own event time") if stencil else None,
-            kernels=kernels[:12], profiled_ms_per_step=round(elapsed_prof / a.steps * 1e3, 3), dumped_outputs=dumped,
-            note="backward on saved activations (the blocks' 1x1 outputs kept from forward), activation derivative / residual / scale "
-                 "epilogues fused into the K1 GEMMs, parameter gradients written in place into one flat arena per net")), flush=True)
+    kernels = sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3), "launches_per_step": v["launches"] // a.steps,
+                       "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] else 0.0,
+                       "frac_of_f32_mfma_peak": round(v["flops"] / (v["ms"] * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 3) if v["ms"] else 0.0}
+                      for k, v in by.items()), key=lambda d: -d["ms_per_step"])
+    inst_ms = sum(v["ms"] for v in by.values()) / a.steps
+    inst_fl = sum(v["flops"] for v in by.values()) / a.steps
+    return dict(
+        roofline=dict(bound="mfma", peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s",
+                      instrumented_ms_per_step=round(inst_ms, 3), instrumented_tflop_per_step=round(inst_fl / 1e12, 3),
+                      achieved=round(inst_fl / (inst_ms * 1e-3) / 1e12, 2) if inst_ms else None,
+                      frac=round(inst_fl / (inst_ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4) if inst_ms else None,
+                      step_frac=round(inst_fl / (ms * 1e-3) / 1e12 / PEAK_F32_MFMA_TFLOPS, 4),
+                      note="matrix kernels only (K1 forward / backward GEMMs, dW GEMM): their flops over their own event time; step_frac = the "
+                           "same flops over the whole step, i.e. with the bandwidth-bound stencil / reduction / optimizer kernels in the denominator"),
+        roofline_stencil_backward=dict(
+            bound="hbm", peak=PEAK_HBM_GBS, unit="GB/s",
+            ms_per_step=round(sum(v["ms"] for v in stencil.values()) / a.steps, 3),
+            achieved=round(sum(v["bytes"] for v in stencil.values()) / max(sum(v["ms"] for v in stencil.values()), 1e-9) / 1e6, 1),
+            frac=round(sum(v["bytes"] for v in stencil.values()) / max(sum(v["ms"] for v in stencil.values()), 1e-9) / 1e6 / PEAK_HBM_GBS, 4),
+            kernels=sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3), "launches_per_step": v["launches"] // a.steps,
+                             "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] else 0.0} for k, v in stencil.items()),
+                           key=lambda d: -d["ms_per_step"]),
+            note="the depth-wise stencils' transposes (dh and the tap / bias sums; the second half's also the res_scale dot): algorithmic bytes "
+                 "= read dy, read h (and v), write dh, over their own event time") if stencil else None,
+        kernels=kernels[:12], profiled_ms_per_step=round(elapsed_prof / a.steps * 1e3, 3))
 
 
 def self_launch(a) -> int:
@@ -332,6 +342,93 @@ def rendezvous(a, dist, world, rank, backend):
         print(json.dumps(dict(metric="launcher rendezvous (no compute)", value=round(elapsed * 1e3, 3), unit="ms", n_gpus=world,
                               rccl_ranks=world if backend == "nccl" else 0, backend=backend, steps=0, warmup=0,
                               higher_is_better=False, config=dict(workload="rendezvous"))), flush=True)
+
+
+def kernel_figures(a, prof, elapsed_prof, B, T, f16):
+    """--full: the per-kernel table, the roofline blocks and the profiled pass's own figures from the live event timings of
+    that pass (`prof`, `elapsed_prof`)."""
+    by_kernel = {}
+    for e in prof:
+        k = by_kernel.setdefault(e["kernel"], dict(ms=0.0, launches=0, flops=0.0, bytes=0.0))
+        for f in ("ms", "launches", "flops", "bytes"):
+            k[f] += e[f]
+    total_ms = sum(k["ms"] for k in by_kernel.values())
+    dom_name, dom = max(by_kernel.items(), key=lambda kv: kv[1]["ms"])
+    dom_avg_s = dom["ms"] / dom["launches"] * 1e-3
+    ach = dom["flops"] / dom["launches"] / dom_avg_s / 1e12
+    pmc = None
+    try:        # HBM bytes per launch from separate rocprofv3 --pmc passes over this same command (profiles/), valid for the
+        pmc = json.load(open(PMC_FILE_F16 if f16 else PMC_FILE))   # library build they were taken on only: dropped when the kernel sources changed since
+        from waveverify_amd import _lib
+        if pmc.get("library") != _lib.load().wv_version().decode():
+            pmc = None
+    except Exception:
+        pmc = None
+    headline = a.workload == "embed_detect" and B == 256 and T == 16000   # the shape the counter passes ran on (both modes: tools/profile_bench.sh, profile_f16.sh)
+
+    def traffic_of(kernel):
+        kernel = kernel.replace(",flat", "")       # flat tiling is a launch-time property of the same kernel symbol
+        if pmc and headline and kernel in pmc.get("kernels", {}):
+            return round(pmc["kernels"][kernel]["traffic_bytes_per_launch"] / 1e9, 3)
+        return None
+
+    # which roof bounds the dominant kernel: its algorithmic arithmetic intensity against the f32-matrix ridge
+    dom_ai = dom["flops"] / max(dom["bytes"], 1.0)
+    # the matrix roof of the pipe the dominant kernel runs on: the f16 mode's own kernels (conv_pre16, resblock16, spec16, conv16) on the
+    # f16 pipe, everything else (incl. the f32 tail of the f16 mode) on the f32 pipe
+    on_f16 = f16 and ("16" in dom_name.split("<")[0])
+    peak_mfma = PEAK_F16_MFMA_TFLOPS if on_f16 else PEAK_F32_MFMA_TFLOPS
+    ridge = peak_mfma * 1e12 / (PEAK_HBM_GBS * 1e9)                    # 19.7 FLOP/B (f32), 312 FLOP/B (f16)
+    gbs_dom = dom["bytes"] / dom["launches"] / dom_avg_s / 1e9
+    if dom_ai >= ridge:
+        roof = dict(bound="mfma", achieved=round(ach, 2), peak=peak_mfma, unit="TFLOP/s",
+                    frac=round(ach / peak_mfma, 4))
+    else:
+        roof = dict(bound="hbm", achieved=round(gbs_dom, 1), peak=PEAK_HBM_GBS, unit="GB/s",
+                    frac=round(gbs_dom / PEAK_HBM_GBS, 4))
+    roofline = dict(kernel=dom_name, **roof, traffic=traffic_of(dom_name),
+                    traffic_source=(f"profiles/{os.path.basename(PMC_FILE_F16 if f16 else PMC_FILE)}: GB per launch = (2*FETCH_SIZE + WRITE_SIZE) KiB, "
+                                    "separate rocprofv3 --pmc passes over this command") if traffic_of(dom_name) else None,
+                    arithmetic_intensity_flop_per_byte=round(dom_ai, 1), ridge_flop_per_byte=round(ridge, 1),
+                    tflops=round(ach, 2), hbm_gbs=round(gbs_dom, 1),
+                    algorithmic_gb_per_launch=round(dom["bytes"] / dom["launches"] / 1e9, 3),
+                    avg_launch_us=round(dom_avg_s * 1e6, 1), launches_per_step=dom["launches"] // a.steps,
+                    share_of_kernel_time=round(dom["ms"] / total_ms, 3),
+                    algorithmic_gflop_per_launch=round(dom["flops"] / dom["launches"] / 1e9, 2))
+    film = [e for e in prof if e["role"] == "enc.down_film"]     # (the f16 mode's FiLM convs run under "enc16.down_film": no block for them)
+    roofline_film = None
+    if film:
+        ms = sum(e["ms"] for e in film); by = sum(e["bytes"] for e in film); fl = sum(e["flops"] for e in film)
+        n = sum(e["launches"] for e in film)
+        # the north_star's "fused Conv1d+FiLM" unit.  With the 1x1 expansion fused in it has
+        # AI ~ 70-95 FLOP/B, above the f32-matrix ridge (157.3 TF / 8 TB/s = 19.7), so its roofline is
+        # the matrix one; the HBM figures are given beside it.
+        tf = fl / (ms * 1e-3) / 1e12
+        gbs = by / (ms * 1e-3) / 1e9
+        roofline_film = dict(kernel="pw_dw (ELU(s*x) -> 1x1 -> strided DW conv -> FiLM [-> ELU copy])", bound="mfma",
+                             achieved=round(tf, 2), peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s",
+                             frac=round(tf / PEAK_F32_MFMA_TFLOPS, 4),
+                             algorithmic_gb_per_launch=round(by / n / 1e9, 3),
+                             hbm_gbs=round(gbs, 1), hbm_frac=round(gbs / PEAK_HBM_GBS, 4),
+                             arithmetic_intensity_flop_per_byte=round(fl / by, 1),
+                             launches_per_step=n // a.steps,
+                             per_launch=[dict(kernel=e["kernel"], us=round(e["ms"] / e["launches"] * 1e3, 1),
+                                              tflops=round(e["flops"] / (e["ms"] * 1e-3) / 1e12, 1),
+                                              launches_per_step=e["launches"] // a.steps) for e in film],
+                             algorithmic_mb_per_clip=round(by / a.steps / B / 1e6, 2),
+                             note="north_star prices this unit against the HBM roof; with the 1x1 expansion fused in (SURVEY 8d allows it) its "
+                                  "arithmetic intensity lies above the f32-matrix ridge (19.7 FLOP/B), so the MATRIX roof is the binding one: "
+                                  "`frac` is of that roof, `hbm_frac` is what its algorithmic bytes reach of 8 TB/s")
+    kernels = sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3),
+                       "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] else 0.0,
+                       "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] else 0.0}
+                      for k, v in by_kernel.items()), key=lambda d: -d["ms_per_step"])
+    step_flops = sum(v["flops"] for v in by_kernel.values()) / a.steps
+    return dict(roofline=roofline, roofline_film=roofline_film, kernels=kernels[:10],
+                profiled_pass=dict(profiler_on=True, ms_per_step=round(elapsed_prof / a.steps * 1e3, 3),
+                                   kernel_time_ms_per_step=round(total_ms / a.steps, 3),
+                                   step_tflops=round(step_flops / (total_ms / a.steps * 1e-3) / 1e12, 2),
+                                   note="hipEvent pair around every launch; `value` is from the clean pass before it"))
 
 
 def main():
@@ -438,10 +535,11 @@ def main():
         dump["wm"] = wm
     if "loc" in loc_out:
         dump["loc_logits"] = loc_out["loc"]
-    elapsed_prof, _ = timed(True)                 # the anatomy: same K steps with per-launch events
-    prof = profile.collect()
+    if a.full:
+        elapsed_prof, _ = timed(True)             # the anatomy: same K steps with per-launch events
+        prof = profile.collect()
     with_locator = None
-    if a.workload == "embed_detect":              # BASELINE configs[1] words the step "generator+locator+detector": the same K steps
+    if a.full and a.workload == "embed_detect":   # BASELINE configs[1] words the step "generator+locator+detector": the same K steps
         cfgL = default_config("locator")          # with the locator's forward on wm as well, reported beside the headline
         Lnet = HipNet(cfgL, random_state_dict(cfgL, 0), dev)
         step()
@@ -455,90 +553,11 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- per-kernel figures from the live event timings of the profiled pass --------------------
-    by_kernel = {}
-    for e in prof:
-        k = by_kernel.setdefault(e["kernel"], dict(ms=0.0, launches=0, flops=0.0, bytes=0.0))
-        for f in ("ms", "launches", "flops", "bytes"):
-            k[f] += e[f]
-    total_ms = sum(k["ms"] for k in by_kernel.values())
-    dom_name, dom = max(by_kernel.items(), key=lambda kv: kv[1]["ms"])
-    dom_avg_s = dom["ms"] / dom["launches"] * 1e-3
-    ach = dom["flops"] / dom["launches"] / dom_avg_s / 1e12
-    pmc = None
-    try:        # HBM bytes per launch from separate rocprofv3 --pmc passes over this same command (profiles/), valid for the
-        pmc = json.load(open(PMC_FILE_F16 if f16 else PMC_FILE))   # library build they were taken on only: dropped when the kernel sources changed since
-        from waveverify_amd import _lib
-        if pmc.get("library") != _lib.load().wv_version().decode():
-            pmc = None
-    except Exception:
-        pmc = None
-    headline = a.workload == "embed_detect" and B == 256 and T == 16000   # the shape the counter passes ran on (both modes: tools/profile_bench.sh, profile_f16.sh)
-
-    def traffic_of(kernel):
-        kernel = kernel.replace(",flat", "")       # flat tiling is a launch-time property of the same kernel symbol
-        if pmc and headline and kernel in pmc.get("kernels", {}):
-            return round(pmc["kernels"][kernel]["traffic_bytes_per_launch"] / 1e9, 3)
-        return None
-
-    # which roof bounds the dominant kernel: its algorithmic arithmetic intensity against the f32-matrix ridge
-    dom_ai = dom["flops"] / max(dom["bytes"], 1.0)
-    # the matrix roof of the pipe the dominant kernel runs on: the f16 mode's own kernels (conv_pre16, resblock16, spec16, conv16) on the
-    # f16 pipe, everything else (incl. the f32 tail of the f16 mode) on the f32 pipe
-    on_f16 = f16 and ("16" in dom_name.split("<")[0])
-    peak_mfma = PEAK_F16_MFMA_TFLOPS if on_f16 else PEAK_F32_MFMA_TFLOPS
-    ridge = peak_mfma * 1e12 / (PEAK_HBM_GBS * 1e9)                    # 19.7 FLOP/B (f32), 312 FLOP/B (f16)
-    gbs_dom = dom["bytes"] / dom["launches"] / dom_avg_s / 1e9
-    if dom_ai >= ridge:
-        roof = dict(bound="mfma", achieved=round(ach, 2), peak=peak_mfma, unit="TFLOP/s",
-                    frac=round(ach / peak_mfma, 4))
-    else:
-        roof = dict(bound="hbm", achieved=round(gbs_dom, 1), peak=PEAK_HBM_GBS, unit="GB/s",
-                    frac=round(gbs_dom / PEAK_HBM_GBS, 4))
-    roofline = dict(kernel=dom_name, **roof, traffic=traffic_of(dom_name),
-                    traffic_source=(f"profiles/{os.path.basename(PMC_FILE_F16 if f16 else PMC_FILE)}: GB per launch = (2*FETCH_SIZE + WRITE_SIZE) KiB, "
-                                    "separate rocprofv3 --pmc passes over this command") if traffic_of(dom_name) else None,
-                    arithmetic_intensity_flop_per_byte=round(dom_ai, 1), ridge_flop_per_byte=round(ridge, 1),
-                    tflops=round(ach, 2), hbm_gbs=round(gbs_dom, 1),
-                    algorithmic_gb_per_launch=round(dom["bytes"] / dom["launches"] / 1e9, 3),
-                    avg_launch_us=round(dom_avg_s * 1e6, 1), launches_per_step=dom["launches"] // a.steps,
-                    share_of_kernel_time=round(dom["ms"] / total_ms, 3),
-                    algorithmic_gflop_per_launch=round(dom["flops"] / dom["launches"] / 1e9, 2))
-    film = [e for e in prof if e["role"] == "enc.down_film"]     # (the f16 mode's FiLM convs run under "enc16.down_film": no block for them)
-    roofline_film = None
-    if film:
-        ms = sum(e["ms"] for e in film); by = sum(e["bytes"] for e in film); fl = sum(e["flops"] for e in film)
-        n = sum(e["launches"] for e in film)
-        # the north_star's "fused Conv1d+FiLM" unit.  With the 1x1 expansion fused in it has
-        # AI ~ 70-95 FLOP/B, above the f32-matrix ridge (157.3 TF / 8 TB/s = 19.7), so its roofline is
-        # the matrix one; the HBM figures are given beside it.
-        tf = fl / (ms * 1e-3) / 1e12
-        gbs = by / (ms * 1e-3) / 1e9
-        roofline_film = dict(kernel="pw_dw (ELU(s*x) -> 1x1 -> strided DW conv -> FiLM [-> ELU copy])", bound="mfma",
-                             achieved=round(tf, 2), peak=PEAK_F32_MFMA_TFLOPS, unit="TFLOP/s",
-                             frac=round(tf / PEAK_F32_MFMA_TFLOPS, 4),
-                             algorithmic_gb_per_launch=round(by / n / 1e9, 3),
-                             hbm_gbs=round(gbs, 1), hbm_frac=round(gbs / PEAK_HBM_GBS, 4),
-                             arithmetic_intensity_flop_per_byte=round(fl / by, 1),
-                             launches_per_step=n // a.steps,
-                             per_launch=[dict(kernel=e["kernel"], us=round(e["ms"] / e["launches"] * 1e3, 1),
-                                              tflops=round(e["flops"] / (e["ms"] * 1e-3) / 1e12, 1),
-                                              launches_per_step=e["launches"] // a.steps) for e in film],
-                             algorithmic_mb_per_clip=round(by / a.steps / B / 1e6, 2),
-                             note="north_star prices this unit against the HBM roof; with the 1x1 expansion fused in (SURVEY 8d allows it) its "
-                                  "arithmetic intensity lies above the f32-matrix ridge (19.7 FLOP/B), so the MATRIX roof is the binding one: "
-                                  "`frac` is of that roof, `hbm_frac` is what its algorithmic bytes reach of 8 TB/s")
-    kernels = sorted(({"kernel": k, "ms_per_step": round(v["ms"] / a.steps, 3),
-                       "tflops": round(v["flops"] / (v["ms"] * 1e-3) / 1e12, 2) if v["ms"] else 0.0,
-                       "gbs": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9, 1) if v["ms"] else 0.0}
-                      for k, v in by_kernel.items()), key=lambda d: -d["ms_per_step"])
-
     metric = {"embed_detect": "clips/sec embed+detect, 1s@16kHz bs=256",
               "longform": "clips/sec embed+locate+detect, 30s@16kHz bs=32",
               "detector_stress": "clips/sec detect, 1s@16kHz bs=1024"}[a.workload]
     if f16:
         metric = metric.replace(",", " (f16-operand / f32-accumulate mode),", 1)
-    step_flops = sum(v["flops"] for v in by_kernel.values()) / a.steps
     out = dict(metric=metric, value=round(world * B * a.steps / elapsed, 2),
                unit="clips/s", n_gpus=world, rccl_ranks=dist.get_world_size() if dist else 0, steps=a.steps, warmup=a.warmup,
                ms_per_step=round(elapsed / a.steps * 1e3, 3), higher_is_better=True, scaling="weak",
@@ -548,13 +567,10 @@ def main():
                                     "seeded random weights",
                            batch_per_gpu=B, global_batch=B * world, clip_samples=T,
                            parallelism=f"dp{world} (independent clip shards, no data-path collective)"),
-               with_locator=with_locator, roofline=roofline, roofline_film=roofline_film, kernels=kernels[:10],
-               profiled_pass=dict(profiler_on=True, ms_per_step=round(elapsed_prof / a.steps * 1e3, 3),
-                                  kernel_time_ms_per_step=round(total_ms / a.steps, 3),
-                                  step_tflops=round(step_flops / (total_ms / a.steps * 1e-3) / 1e12, 2),
-                                  note="hipEvent pair around every launch; `value` is from the clean pass before it"),
                scaling_measured=("N>1 not measured in this run" if world == 1 else "this line"))
-    if not a.no_cpu_baseline and a.workload == "embed_detect" and world == 1 and not f16:      # the CPU leg: rank 0 at N = 1 only
+    if a.full:
+        out.update(with_locator=with_locator, **kernel_figures(a, prof, elapsed_prof, B, T, f16))
+    if a.full and not a.no_cpu_baseline and a.workload == "embed_detect" and world == 1 and not f16:   # the CPU leg: rank 0 at N = 1 only
         cb, wm_ref, mp_ref = cpu_baseline(cfgG, cfgD, sdG, sdD, x_np, msg_np, min(a.cpu_clips, B))
         n = wm_ref.shape[0]
         out["cpu_baseline"] = cb
@@ -563,9 +579,9 @@ def main():
             wm_max_abs_err=float(np.abs(wm[:n].cpu().numpy() - wm_ref).max()),
             mean_prob_max_abs_err=float(np.abs(mp[:n].cpu().numpy() - mp_ref).max()),
             ber_vs_oracle=float(((mp_ref >= 0.5) != bits[:n].cpu().numpy()).mean()))
-    if not f16 and a.workload == "embed_detect":
-        # The f16-operand / f32-accumulate mode of the same step (BASELINE configs[1] words the step "bf16"), so that the driver's record of
-        # the DEFAULT run holds it: the same K steps, wm and bits against this run's exact outputs on the whole batch, and -- when the CPU
+    if a.full and not f16 and a.workload == "embed_detect":
+        # The f16-operand / f32-accumulate mode of the same step (BASELINE configs[1] words the step "bf16"), so that the full line of the
+        # DEFAULT run holds it: the same K steps, wm and bits against this run's exact outputs on the whole batch, and -- when the CPU
         # leg ran -- against the oracle on its sample.  A throughput mode beside the exact path: `value` above is exact f32.
         step("f16")
         torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -578,14 +594,14 @@ def main():
                   wm_max_abs_diff_vs_exact=float((wm16 - wm).abs().max()), wm_bar=1e-4,
                   mean_prob_max_abs_diff_vs_exact=float((mp16 - mp).abs().max()),
                   bits_compared=int(bits.numel()), bits_differ_vs_exact=int((bits16 != bits).sum()),
-                  note="rank 0's shard; same inputs and weights as the exact pass above; `python bench.py --precision f16` prints this mode's own line with its roofline")
+                  note="rank 0's shard; same inputs and weights as the exact pass above; `python bench.py --precision f16 --full` prints this mode's own line with its roofline")
         if "parity" in out:
             n = out["parity"]["clips_checked"]
             rp.update(clips_checked_vs_oracle=n, wm_max_abs_err_vs_oracle=float(np.abs(wm16[:n].cpu().numpy() - wm_ref).max()),
                       mean_prob_max_abs_err_vs_oracle=float(np.abs(mp16[:n].cpu().numpy() - mp_ref).max()),
                       ber_vs_oracle=float(((mp_ref >= 0.5) != bits16[:n].cpu().numpy()).mean()))
         out["reduced_precision"] = rp
-    if f16:
+    if a.full and f16:
         # The mode's own evidence: the exact-f32 path of this library on the same K steps (same input, same weights), the two modes'
         # outputs against each other on the whole batch, and against the torch-CPU port of the reference on a sample.
         step("f32")

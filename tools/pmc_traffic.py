@@ -114,7 +114,7 @@ def durations(d: str):
     return t, n
 
 
-def traffic(fetch_dir, write_dir, command="bench.py --steps 5 --warmup 2 --no-cpu-baseline` (tools/profile_bench.sh)"):
+def traffic(fetch_dir, write_dir, command="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline` (tools/profile_bench.sh)"):
     lib_f, lib_w = stamp(fetch_dir), stamp(write_dir)
     if lib_f != lib_w:
         raise SystemExit(f"refusing to merge counter passes from different builds: {fetch_dir}: {lib_f} / {write_dir}: {lib_w}")
