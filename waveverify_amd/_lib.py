@@ -205,3 +205,10 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load().wv_last_error().decode(errors="replace")
         raise RuntimeError(f"{what or 'waveverify_hip'} failed (code {rc}): {msg}")
+
+
+def scratch(nbytes: int, device) -> "torch.Tensor":
+    """A workspace / saved-activation buffer of exactly `nbytes` bytes (uint8) on `device`, contents undefined.  Every such
+    allocation of the package goes through here, so that a test can hand out poisoned, guarded buffers in its place."""
+    import torch
+    return torch.empty(int(nbytes), dtype=torch.uint8, device=device)

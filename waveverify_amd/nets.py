@@ -131,7 +131,7 @@ class HipNet:
         if ws is None or ws.numel() < need:
             if ws is not None:
                 self._retired.append(ws)
-            ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = _lib.scratch(need, self.device)
             self._ws[key] = ws
         return ws
 

@@ -39,9 +39,21 @@ def _stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def _out(given: Optional[torch.Tensor], shape, dtype, device, what: str = "out") -> torch.Tensor:
+    """An output buffer: the caller's (`out=` / `out_act=`: a test handle for guarded or misaligned placements; checked for shape,
+    dtype, device and contiguity, never reallocated) or a fresh one."""
+    shape = tuple(int(s) for s in shape)
+    if given is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if tuple(given.shape) != shape or given.dtype != dtype or given.device != torch.device(device) or not given.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous {dtype} tensor {list(shape)} on {device}, got {given.dtype} "
+                         f"{list(given.shape)} on {given.device}")
+    return given
+
+
 def pw_dw(X, w_pw, w_dw, dw_bias=None, film=None, resid=None, stride=1, dilation=1,
-          pre_scale=1.0, pre_elu=True, out_scale=1.0, bands=1, act_scale: Optional[float] = None):
-    """act_scale given: also returns the second output ELU(act_scale * y) -> (Y, Yact)."""
+          pre_scale=1.0, pre_elu=True, out_scale=1.0, bands=1, act_scale: Optional[float] = None, out=None, out_act=None):
+    """act_scale given: also returns the second output ELU(act_scale * y) -> (Y, Yact).  out / out_act: caller-owned outputs."""
     lib = _lib.load()
     X = _dev(X)
     B, K, Tin = X.shape
@@ -49,10 +61,10 @@ def pw_dw(X, w_pw, w_dw, dw_bias=None, film=None, resid=None, stride=1, dilation
     M, ks = w_dw.shape[0], w_dw.shape[-1]
     w_pw = w_pw.reshape(M, K)
     Tout = -(-Tin // stride)
-    Y = torch.empty((B, M, Tout), dtype=torch.float32, device=X.device)
+    Y = _out(out, (B, M, Tout), torch.float32, X.device)
     film = None if film is None else _dev(film)
     resid = None if resid is None else _dev(resid)
-    Yact = torch.empty_like(Y) if act_scale is not None else None
+    Yact = _out(out_act, Y.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_op_pw_dw(X.data_ptr(), _hp(w_pw), _hp(w_dw), _hp(dw_bias), _dp(film), _dp(resid),
                                Y.data_ptr(), B, K, M, Tin, ks, stride, dilation, pre_scale,
                                int(pre_elu), out_scale, bands, _dp(Yact), float(act_scale or 0.0),
@@ -61,7 +73,7 @@ def pw_dw(X, w_pw, w_dw, dw_bias=None, film=None, resid=None, stride=1, dilation
 
 
 def resblock(X, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_scale=1.0, act_scale: Optional[float] = None,
-             want_raw: bool = True):
+             want_raw: bool = True, out=None, out_act=None):
     """Fused SEANetResnetBlock, raw in / raw out: y = X + out_scale * half2(half1(ELU(pre_scale * X))).
     -> Y, or (Y, Yact) with act_scale given, or Yact alone with want_raw=False."""
     lib = _lib.load()
@@ -69,8 +81,8 @@ def resblock(X, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_scale=1.0
     B, Cc, T = X.shape
     ws = [_w(w_pw1).reshape(Cc, Cc), _w(w_dw1).reshape(Cc, -1), _w(b1), _w(w_pw2).reshape(Cc, Cc),
           _w(w_dw2).reshape(Cc, -1), _w(b2)]
-    Y = torch.empty_like(X) if want_raw else None
-    Yact = torch.empty_like(X) if act_scale is not None else None
+    Y = _out(out, X.shape, torch.float32, X.device) if want_raw else None
+    Yact = _out(out_act, X.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_op_resblock(X.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _dp(Y), _dp(Yact),
                                   B, Cc, T, out_scale, float(act_scale or 0.0), _stream()), "wv_op_resblock")
     if Y is None:
@@ -80,7 +92,7 @@ def resblock(X, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_scale=1.0
 
 def dw_pw(X, w_pw, bias=None, w_dw=None, mode=0, ks_or_ratio=0, pre_scale=1.0, pre_elu=False,
           l2norm=False, accumulate_into: Optional[torch.Tensor] = None, out_scale=1.0,
-          act_scale: Optional[float] = None):
+          act_scale: Optional[float] = None, out=None, out_act=None):
     lib = _lib.load()
     X = _dev(X)
     B, K, Tin = X.shape
@@ -92,8 +104,8 @@ def dw_pw(X, w_pw, bias=None, w_dw=None, mode=0, ks_or_ratio=0, pre_scale=1.0, p
         Y = accumulate_into
         assert Y.is_cuda and Y.is_contiguous() and tuple(Y.shape) == (B, M, Tout)
     else:
-        Y = torch.empty((B, M, Tout), dtype=torch.float32, device=X.device)
-    Yact = torch.empty_like(Y) if act_scale is not None else None
+        Y = _out(out, (B, M, Tout), torch.float32, X.device)
+    Yact = _out(out_act, Y.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_op_dw_pw(X.data_ptr(), _hp(w_dw), _hp(w_pw), _hp(bias), Y.data_ptr(), B, K, M,
                                Tin, mode, ks_or_ratio, pre_scale, int(pre_elu), int(l2norm),
                                int(accumulate_into is not None), out_scale, _dp(Yact),
@@ -101,12 +113,12 @@ def dw_pw(X, w_pw, bias=None, w_dw=None, mode=0, ks_or_ratio=0, pre_scale=1.0, p
     return Y if act_scale is None else (Y, Yact)
 
 
-def stft_logmag(wav, n_fft, hop, mean=0.0, std=1.0, basis=None) -> torch.Tensor:
+def stft_logmag(wav, n_fft, hop, mean=0.0, std=1.0, basis=None, out=None) -> torch.Tensor:
     lib = _lib.load()
     wav = _dev(wav)
     B, T = wav.shape[0], wav.shape[-1]
     Tf = -(-T // hop)
-    P = torch.empty((B, n_fft // 2 + 1, Tf), dtype=torch.float32, device=wav.device)
+    P = _out(out, (B, n_fft // 2 + 1, Tf), torch.float32, wav.device)
     basis = _w(basis)
     _lib.check(lib.wv_op_stft_logmag(wav.data_ptr(), _hp(basis), P.data_ptr(), B, T, n_fft, hop, mean,
                                      std, _stream()), "wv_op_stft_logmag")
@@ -114,15 +126,15 @@ def stft_logmag(wav, n_fft, hop, mean=0.0, std=1.0, basis=None) -> torch.Tensor:
 
 
 def spec_block(wav, w_pw, x, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_scale: Optional[float] = None, want_raw: bool = True,
-               basis=None):
+               basis=None, out=None, out_act=None):
     """Whole SpecBlock in one launch: y = x + out_scale * (W @ logmag(STFT(wav))) -> Y, (Y, Yact) or Yact alone."""
     lib = _lib.load()
     wav, x = _dev(wav), _dev(x)
     B, T = wav.shape[0], wav.shape[-1]
     M = x.shape[1]
     w_pw = _w(w_pw).reshape(M, n_fft // 2 + 1)
-    Y = torch.empty_like(x) if want_raw else None
-    Yact = torch.empty_like(x) if act_scale is not None else None
+    Y = _out(out, x.shape, torch.float32, x.device) if want_raw else None
+    Yact = _out(out_act, x.shape, torch.float32, x.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_op_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x.data_ptr(), _dp(Y), _dp(Yact), B, T, n_fft, hop, M,
                                     mean, std, out_scale, float(act_scale or 0.0), _stream()), "wv_op_spec_block")
     if Y is None:
@@ -130,19 +142,19 @@ def spec_block(wav, w_pw, x, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_s
     return Y if act_scale is None else (Y, Yact)
 
 
-def conv_pre(x, w, bias, in_scale) -> torch.Tensor:
+def conv_pre(x, w, bias, in_scale, out=None) -> torch.Tensor:
     lib = _lib.load()
     x = _dev(x)
     B, T = x.shape[0], x.shape[-1]
     w, bias = _w(w), _w(bias)
     Cc, ks = w.shape[0], w.shape[-1]
-    Y = torch.empty((B, Cc, T), dtype=torch.float32, device=x.device)
+    Y = _out(out, (B, Cc, T), torch.float32, x.device)
     _lib.check(lib.wv_op_conv_pre(x.data_ptr(), _hp(w), _hp(bias), Y.data_ptr(), B, Cc, T, ks, in_scale,
                                   _stream()), "wv_op_conv_pre")
     return Y
 
 
-def tail(H, w, bias, x=None, T=None, pre_scale=1.0, out_scale=1.0) -> torch.Tensor:
+def tail(H, w, bias, x=None, T=None, pre_scale=1.0, out_scale=1.0, out=None) -> torch.Tensor:
     lib = _lib.load()
     H = _dev(H)
     B, Cc, Tin = H.shape
@@ -150,13 +162,14 @@ def tail(H, w, bias, x=None, T=None, pre_scale=1.0, out_scale=1.0) -> torch.Tens
     w, bias = _w(w), _w(bias)
     ks = w.shape[-1]
     x = None if x is None else _dev(x)
-    out = torch.empty((B, 1, T), dtype=torch.float32, device=H.device)
+    out = _out(out, (B, 1, T), torch.float32, H.device)
     _lib.check(lib.wv_op_tail(H.data_ptr(), _hp(w), _hp(bias), _dp(x), out.data_ptr(), B, Cc, Tin, T, ks,
                               pre_scale, out_scale, _stream()), "wv_op_tail")
     return out
 
 
-def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True):
+def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True, out=None, out_mean=None):
+    """-> (logits [B, nb, T] or None, mean probabilities [B, nb] or None); out / out_mean: caller-owned outputs."""
     lib = _lib.load()
     Z = _dev(Z)
     B, D, Fr = Z.shape
@@ -164,8 +177,8 @@ def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True):
     O, hop = w_rev.shape[1], w_rev.shape[2]
     nb = w_last.shape[0]
     w_last = w_last.reshape(nb, O)
-    logits = torch.empty((B, nb, T), dtype=torch.float32, device=Z.device) if want_logits else None
-    mean = torch.empty((B, nb), dtype=torch.float32, device=Z.device) if want_mean else None
+    logits = _out(out, (B, nb, T), torch.float32, Z.device) if want_logits else None
+    mean = _out(out_mean, (B, nb), torch.float32, Z.device, "out_mean") if want_mean else None
     _lib.check(lib.wv_op_head(Z.data_ptr(), _hp(w_rev), _hp(b_rev), _hp(w_last), _hp(b_last),
                               _dp(logits), _dp(mean), B, D, O, nb, hop, Fr, T, _stream()), "wv_op_head")
     return logits, mean
@@ -178,47 +191,47 @@ def _c8(t: torch.Tensor) -> torch.Tensor:
     return t
 
 
-def h16_from_f32(X, scale: float = 1.0, elu: bool = False) -> torch.Tensor:
+def h16_from_f32(X, scale: float = 1.0, elu: bool = False, out=None) -> torch.Tensor:
     lib = _lib.load()
     X = _dev(X)
     B, Cc, T = X.shape
-    Y = torch.empty((B, (Cc + 15) // 16 * 2, T, 8), dtype=torch.float16, device=X.device)
+    Y = _out(out, (B, (Cc + 15) // 16 * 2, T, 8), torch.float16, X.device)
     _lib.check(lib.wv_h16_from_f32(X.data_ptr(), Y.data_ptr(), B, Cc, T, float(scale), int(elu), _stream()), "wv_h16_from_f32")
     return Y
 
 
-def h16_to_f32(X16, channels: int) -> torch.Tensor:
+def h16_to_f32(X16, channels: int, out=None) -> torch.Tensor:
     lib = _lib.load()
     X16 = _c8(X16)
     B, G, T, _ = X16.shape
     if (channels + 15) // 16 * 2 != G:
         raise ValueError("channel count does not match the tensor's groups")
-    Y = torch.empty((B, channels, T), dtype=torch.float32, device=X16.device)
+    Y = _out(out, (B, channels, T), torch.float32, X16.device)
     _lib.check(lib.wv_h16_to_f32(X16.data_ptr(), Y.data_ptr(), B, channels, T, _stream()), "wv_h16_to_f32")
     return Y
 
 
-def h16_conv_pre(x, w, bias, in_scale: float = 1.0) -> torch.Tensor:
+def h16_conv_pre(x, w, bias, in_scale: float = 1.0, out=None) -> torch.Tensor:
     lib = _lib.load()
     x = _dev(x)
     B, _, T = x.shape
     w, bias = _w(w), _w(bias)
     Cc, ks = w.shape[0], w.shape[-1]
-    Y = torch.empty((B, Cc // 8, T, 8), dtype=torch.float16, device=x.device)
+    Y = _out(out, (B, Cc // 8, T, 8), torch.float16, x.device)
     _lib.check(lib.wv_h16_conv_pre(x.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), Y.data_ptr(), B, Cc, T, ks, float(in_scale), _stream()),
                "wv_h16_conv_pre")
     return Y
 
 
 def h16_resblock(X16, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_scale=1.0, act_scale: Optional[float] = None,
-                 want_raw: bool = True):
+                 want_raw: bool = True, out=None, out_act=None):
     lib = _lib.load()
     X16 = _c8(X16)
     B, G, T, _ = X16.shape
     Cc = 8 * G
     ws = [_w(w_pw1).reshape(Cc, Cc), _w(w_dw1).reshape(Cc, -1), _w(b1), _w(w_pw2).reshape(Cc, Cc), _w(w_dw2).reshape(Cc, -1), _w(b2)]
-    Y = torch.empty_like(X16) if want_raw else None
-    Yact = torch.empty_like(X16) if act_scale is not None else None
+    Y = _out(out, X16.shape, torch.float16, X16.device) if want_raw else None
+    Yact = _out(out_act, X16.shape, torch.float16, X16.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_h16_resblock(X16.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _dp(Y), _dp(Yact), B, Cc, T, float(out_scale),
                                    float(act_scale or 0.0), _stream()), "wv_h16_resblock")
     if Y is None:
@@ -227,8 +240,9 @@ def h16_resblock(X16, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_sca
 
 
 def h16_conv(X16, w_pw, w_dw=None, bias=None, resid16=None, K: Optional[int] = None, ks=1, stride=1, pad=0, out_scale=1.0,
-             act_scale: Optional[float] = None, want_raw: bool = True, want_f32: bool = False):
-    """y = out_scale * (bias + conv(x)) + resid.  -> dict with the requested outputs: "raw" (c8 f16), "act" (c8 f16), "f32" ([B,M,Tout])."""
+             act_scale: Optional[float] = None, want_raw: bool = True, want_f32: bool = False, out=None, out_act=None, out_f32=None):
+    """y = out_scale * (bias + conv(x)) + resid.  -> dict with the requested outputs: "raw" (c8 f16), "act" (c8 f16), "f32" ([B,M,Tout]);
+    out / out_act / out_f32: caller-owned buffers for them."""
     lib = _lib.load()
     X16 = _c8(X16)
     B, G, Tin, _ = X16.shape
@@ -240,30 +254,31 @@ def h16_conv(X16, w_pw, w_dw=None, bias=None, resid16=None, K: Optional[int] = N
     w_pw = w_pw.reshape(M, K)
     Tout = (Tin + stride - 1) // stride
     Gm = (M + 15) // 16 * 2
-    out = {}
+    res = {}
     if want_raw:
-        out["raw"] = torch.empty((B, Gm, Tout, 8), dtype=torch.float16, device=X16.device)
+        res["raw"] = _out(out, (B, Gm, Tout, 8), torch.float16, X16.device)
     if act_scale is not None:
-        out["act"] = torch.empty((B, Gm, Tout, 8), dtype=torch.float16, device=X16.device)
+        res["act"] = _out(out_act, (B, Gm, Tout, 8), torch.float16, X16.device, "out_act")
     if want_f32:
-        out["f32"] = torch.empty((B, M, Tout), dtype=torch.float32, device=X16.device)
+        res["f32"] = _out(out_f32, (B, M, Tout), torch.float32, X16.device, "out_f32")
     if resid16 is not None:
         _c8(resid16)
     _lib.check(lib.wv_h16_conv(X16.data_ptr(), _hp(w_pw), _hp(None if w_dw is None else w_dw.reshape(M, ks)), _hp(bias), _dp(resid16),
-                               _dp(out.get("raw")), _dp(out.get("act")), _dp(out.get("f32")), B, K, M, Tin, ks, stride, pad, float(out_scale),
+                               _dp(res.get("raw")), _dp(res.get("act")), _dp(res.get("f32")), B, K, M, Tin, ks, stride, pad, float(out_scale),
                                float(act_scale or 0.0), _stream()), "wv_h16_conv")
-    return out
+    return res
 
 
-def h16_spec_block(wav, w_pw, x16, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_scale: Optional[float] = None, want_raw: bool = True, basis=None):
+def h16_spec_block(wav, w_pw, x16, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_scale: Optional[float] = None, want_raw: bool = True, basis=None,
+                   out=None, out_act=None):
     """Whole SpecBlock on the f16 pipe: y = x + out_scale * (W @ logmag(STFT(wav))) -> Y16, (Y16, Yact16) or Yact16 alone (c8 f16)."""
     lib = _lib.load()
     wav, x16 = _dev(wav), _c8(x16)
     B, T = wav.shape[0], wav.shape[-1]
     M = 8 * x16.shape[1]
     w_pw = _w(w_pw).reshape(M, n_fft // 2 + 1)
-    Y = torch.empty_like(x16) if want_raw else None
-    Yact = torch.empty_like(x16) if act_scale is not None else None
+    Y = _out(out, x16.shape, torch.float16, x16.device) if want_raw else None
+    Yact = _out(out_act, x16.shape, torch.float16, x16.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_h16_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x16.data_ptr(), _dp(Y), _dp(Yact), B, T, n_fft, hop, M,
                                      mean, std, out_scale, float(act_scale or 0.0), _stream()), "wv_h16_spec_block")
     if Y is None:
@@ -271,7 +286,7 @@ def h16_spec_block(wav, w_pw, x16, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0,
     return Y if act_scale is None else (Y, Yact)
 
 
-def h16_upsample(X16, w_ct, w_pw, bias, ratio: int, act_scale: Optional[float] = None, want_raw: bool = True):
+def h16_upsample(X16, w_ct, w_pw, bias, ratio: int, act_scale: Optional[float] = None, want_raw: bool = True, out=None, out_act=None):
     """The decoder's upsample unit (ELU -> depth-wise ConvTranspose1d(2r, r), trimmed -> 1x1 + bias; seanet.py:1147-1170) as one conv on
     the f16 pipe.  X16 = the PRE-ACTIVATED input, c8 f16 [B, K/8, Tin, 8] -> c8 f16 [B, M/8, Tin * r, 8]."""
     lib = _lib.load()
@@ -281,8 +296,8 @@ def h16_upsample(X16, w_ct, w_pw, bias, ratio: int, act_scale: Optional[float] =
     w_pw, w_ct, bias = _w(w_pw), _w(w_ct), _w(bias)
     M = w_pw.shape[0]
     w_pw, w_ct = w_pw.reshape(M, K), w_ct.reshape(K, 2 * ratio)
-    Y = torch.empty((B, M // 8, Tin * ratio, 8), dtype=torch.float16, device=X16.device) if want_raw else None
-    Yact = torch.empty((B, M // 8, Tin * ratio, 8), dtype=torch.float16, device=X16.device) if act_scale is not None else None
+    Y = _out(out, (B, M // 8, Tin * ratio, 8), torch.float16, X16.device) if want_raw else None
+    Yact = _out(out_act, (B, M // 8, Tin * ratio, 8), torch.float16, X16.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_h16_upsample(X16.data_ptr(), _hp(w_ct), _hp(w_pw), _hp(bias), _dp(Y), _dp(Yact), B, K, M, Tin, int(ratio),
                                    float(act_scale or 0.0), _stream()), "wv_h16_upsample")
     if Y is None:
@@ -290,7 +305,7 @@ def h16_upsample(X16, w_ct, w_pw, bias, ratio: int, act_scale: Optional[float] =
     return Y if act_scale is None else (Y, Yact)
 
 
-def h16_tail(A16, w, bias, T: int, out_scale: float, x=None) -> torch.Tensor:
+def h16_tail(A16, w, bias, T: int, out_scale: float, x=None, out=None) -> torch.Tensor:
     """Decoder tail on the pre-activated c8 stream: tanh(out_scale * (b + Conv1d(C -> 1, ks)(a))) (+ x) -> [B, 1, T] f32."""
     lib = _lib.load()
     A16 = _c8(A16)
@@ -300,22 +315,22 @@ def h16_tail(A16, w, bias, T: int, out_scale: float, x=None) -> torch.Tensor:
     if (Cc + 15) // 16 * 2 != G:
         raise ValueError("weight channels do not match the tensor's channel groups")
     xd = _dev(x) if x is not None else None
-    out = torch.empty((B, 1, T), dtype=torch.float32, device=A16.device)
+    out = _out(out, (B, 1, T), torch.float32, A16.device)
     _lib.check(lib.wv_h16_tail(A16.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), _dp(xd), out.data_ptr(), B, Cc, Tin, T, ks, float(out_scale), _stream()),
                "wv_h16_tail")
     return out
 
 
-def h16_l2norm(lat) -> torch.Tensor:
+def h16_l2norm(lat, out=None) -> torch.Tensor:
     lib = _lib.load()
     lat = _dev(lat)
     B, D, Fr = lat.shape
-    Y = torch.empty((B, (D + 15) // 16 * 2, Fr, 8), dtype=torch.float16, device=lat.device)
+    Y = _out(out, (B, (D + 15) // 16 * 2, Fr, 8), torch.float16, lat.device)
     _lib.check(lib.wv_h16_l2norm(lat.data_ptr(), Y.data_ptr(), B, D, Fr, _stream()), "wv_h16_l2norm")
     return Y
 
 
-def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None) -> torch.Tensor:
+def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None, out=None) -> torch.Tensor:
     """The f16 mode's mean-probability head (head16_kernel): lat [B, D, Fr] f32 latent before its L2Norm, wc [D, nb * hop] the composed
     head weight (column bit * hop + j), bc [nb].  -> mean over t < T of sigmoid(logits) [B, nb]; with keep_lo / keep_hi ([B] ints) the
     windowed mode instead: the SUM over t in [keep_lo[b], keep_hi[b]) [B, nb]."""
@@ -329,7 +344,7 @@ def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None) -> torch.Tensor:
         raise ValueError(f"wc must be [D, nb * hop] = [{D}, {nb} * hop], got {wc.shape}")
     if (keep_lo is None) != (keep_hi is None):
         raise ValueError("keep_lo and keep_hi go together")
-    out = torch.empty((B, nb), dtype=torch.float32, device=lat.device)
+    out = _out(out, (B, nb), torch.float32, lat.device)
     lo = hi = None
     if keep_lo is not None:
         lo = torch.as_tensor(keep_lo, dtype=torch.int32).reshape(-1).to(lat.device)
@@ -341,7 +356,8 @@ def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None) -> torch.Tensor:
     return out
 
 
-def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optional[float] = None, want_raw: bool = True):
+def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optional[float] = None, want_raw: bool = True, out=None,
+                  out_act=None):
     """wv_h16_conv with FiLM behind the conv: film [B, bands, 2] (gamma, beta) on the device."""
     lib = _lib.load()
     X16, film = _c8(X16), _dev(film)
@@ -351,8 +367,8 @@ def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optio
     K = w_pw.reshape(M, -1).shape[1]
     Tout = (Tin + stride - 1) // stride
     Gm = (M + 15) // 16 * 2
-    Y = torch.empty((B, Gm, Tout, 8), dtype=torch.float16, device=X16.device) if want_raw else None
-    Yact = torch.empty((B, Gm, Tout, 8), dtype=torch.float16, device=X16.device) if act_scale is not None else None
+    Y = _out(out, (B, Gm, Tout, 8), torch.float16, X16.device) if want_raw else None
+    Yact = _out(out_act, (B, Gm, Tout, 8), torch.float16, X16.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_h16_conv_film(X16.data_ptr(), _hp(w_pw.reshape(M, K)), _hp(w_dw.reshape(M, ks) if w_dw is not None else None), _hp(bias), film.data_ptr(),
                                     int(film.shape[1]), _dp(Y), _dp(Yact), B, K, M, Tin, ks, stride, pad, float(act_scale or 0.0), _stream()), "wv_h16_conv_film")
     if Y is None:

@@ -78,7 +78,7 @@ class TrainHalf:
         g_pw, v_pw, g_dw, v_dw, _ = self._p(p)
         out = dict(dx=torch.empty_like(x), dg_pw=torch.empty_like(g_pw), dv_pw=torch.empty_like(v_pw),
                    dg_dw=torch.empty_like(g_dw), dv_dw=torch.empty_like(v_dw), db_dw=torch.empty_like(g_dw))
-        ws = torch.empty(int(self._lib.wv_train_half_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_half_workspace_bytes(self._h, B, T)), x.device)
         rc = self._lib.wv_train_half_backward(
             self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), float(pre_scale),
             dy.data_ptr(), out["dx"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(), out["dg_dw"].data_ptr(),
@@ -128,9 +128,9 @@ class TrainUnit:
         B, _, T = x.shape
         g_pw, v_pw, g_dw, v_dw, _ = self._p(p)
         dev = x.device
-        out = dict(dx=torch.empty_like(x) if need_dx else None, dg_pw=_dst(into, "dg_pw", g_pw.shape, dev), dv_pw=_dst(into, "dv_pw", v_pw.shape, dev),
+        out = dict(dx=_dst(into, "dx", x.shape, dev) if need_dx else None, dg_pw=_dst(into, "dg_pw", g_pw.shape, dev), dv_pw=_dst(into, "dv_pw", v_pw.shape, dev),
                    dg_dw=_dst(into, "dg_dw", g_dw.shape, dev), dv_dw=_dst(into, "dv_dw", v_dw.shape, dev), db_dw=_dst(into, "db_dw", g_dw.shape, dev))
-        ws = torch.empty(int(self._lib.wv_train_unit_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_unit_workspace_bytes(self._h, B, T)), x.device)
         rc = self._lib.wv_train_unit_backward(
             self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), float(pre_scale), int(pre_elu),
             dy.data_ptr(), out["dx"].data_ptr() if need_dx else None, out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
@@ -206,7 +206,7 @@ class StftFeatures(_Handle):
         """dwav (+)= the gradient of <dP, features(wav)> towards the audio."""
         wav, dP = _f(wav), _f(dP)
         B, T = wav.shape[0], wav.shape[-1]
-        ws = torch.empty(int(self._lib.wv_stft_plan_backward_workspace_bytes(self._h, B, T, self.hop)), dtype=torch.uint8, device=wav.device)
+        ws = _lib.scratch(int(self._lib.wv_stft_plan_backward_workspace_bytes(self._h, B, T, self.hop)), wav.device)
         if self._lib.wv_stft_plan_backward(self._h, wav.data_ptr(), dP.data_ptr(), dwav.data_ptr(), int(accumulate), B, T, self.hop, self.std,
                                            ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
             raise RuntimeError("wv_stft_plan_backward failed")
@@ -236,7 +236,7 @@ class TrainConvPre(_Handle):
         g, v = _f(p["g"]).reshape(self.C), _f(p["v"]).reshape(self.C, self.ks)
         d = x.device
         out = dict(dx=torch.empty_like(x) if need_dx else None, dg=_dst(into, "dg", g.shape, d), dv=_dst(into, "dv", v.shape, d), db=_dst(into, "db", g.shape, d))
-        ws = torch.empty(int(self._lib.wv_train_convpre_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_convpre_workspace_bytes(self._h, B, T)), x.device)
         self._check(self._lib.wv_train_convpre_backward(
             self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), float(in_scale), dy.data_ptr(), out["dx"].data_ptr() if need_dx else None,
             out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream()),
@@ -272,7 +272,7 @@ class TrainSpecAdd(_Handle):
         out = dict(dg=_dst(into, "dg", g.shape, dy.device), dv=_dst(into, "dv", v.shape, dy.device),
                    d_scale_param=None if sp is None else _dst(into, "d_scale_param", (1,), dy.device),
                    dP=torch.empty_like(P) if need_dP else None)
-        ws = torch.empty(int(self._lib.wv_train_spec_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=dy.device)
+        ws = _lib.scratch(int(self._lib.wv_train_spec_workspace_bytes(self._h, B, T)), dy.device)
         self._check(self._lib.wv_train_spec_backward(
             self._h, P.data_ptr(), g.data_ptr(), v.data_ptr(), None if sp is None else sp.data_ptr(), float(res_scale), dy.data_ptr(),
             out["dg"].data_ptr(), out["dv"].data_ptr(), None if sp is None else out["d_scale_param"].data_ptr(),
@@ -310,7 +310,7 @@ class TrainConvPost(_Handle):
         d = x.device
         out = dict(dx=torch.empty_like(x), dg_dw=_dst(into, "dg_dw", g_dw.shape, d), dv_dw=_dst(into, "dv_dw", v_dw.shape, d),
                    dg_pw=_dst(into, "dg_pw", g_pw.shape, d), dv_pw=_dst(into, "dv_pw", v_pw.shape, d), db=_dst(into, "db", b.shape, d))
-        ws = torch.empty(int(self._lib.wv_train_convpost_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_convpost_workspace_bytes(self._h, B, T)), x.device)
         self._check(self._lib.wv_train_convpost_backward(
             self._h, x.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), b.data_ptr(), int(self.l2norm), dy.data_ptr(),
             out["dx"].data_ptr(), out["dg_dw"].data_ptr(), out["dv_dw"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
@@ -332,7 +332,7 @@ class TrainHead(_Handle):
                 _f(p["b_last"]).reshape(self.nb))
 
     def _ws(self, B, N, dev):
-        return torch.empty(int(self._lib.wv_train_head_workspace_bytes(self._h, B, N)), dtype=torch.uint8, device=dev)
+        return _lib.scratch(int(self._lib.wv_train_head_workspace_bytes(self._h, B, N)), dev)
 
     def forward(self, z, p, T: int):
         z = _f(z)
@@ -390,7 +390,7 @@ class TrainUp(_Handle):
         d = x.device
         out = dict(dx=torch.empty_like(x), dg_ct=_dst(into, "dg_ct", g_ct.shape, d), dv_ct=_dst(into, "dv_ct", v_ct.shape, d),
                    dg_pw=_dst(into, "dg_pw", g_pw.shape, d), dv_pw=_dst(into, "dv_pw", v_pw.shape, d), db=_dst(into, "db", b.shape, d))
-        ws = torch.empty(int(self._lib.wv_train_up_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_up_workspace_bytes(self._h, B, T)), x.device)
         self._check(self._lib.wv_train_up_backward(
             self._h, x.data_ptr(), g_ct.data_ptr(), v_ct.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), float(pre_scale), int(pre_elu),
             dy.data_ptr(), out["dx"].data_ptr(), out["dg_ct"].data_ptr(), out["dv_ct"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
@@ -422,7 +422,7 @@ class TrainTail(_Handle):
         g, v = _f(p["g"]).reshape(1), _f(p["v"]).reshape(self.C, self.ks)
         d = x.device
         out = dict(dx=torch.empty_like(x), dg=_dst(into, "dg", g.shape, d), dv=_dst(into, "dv", v.shape, d), db=_dst(into, "db", (1,), d))
-        ws = torch.empty(int(self._lib.wv_train_tail_workspace_bytes(self._h, B)), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch(int(self._lib.wv_train_tail_workspace_bytes(self._h, B)), x.device)
         self._check(self._lib.wv_train_tail_backward(
             self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), float(post), float(wav_std), delta.data_ptr(), dd.data_ptr(), out["dx"].data_ptr(),
             out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, Tin, delta.shape[-1], ws.data_ptr(), ws.numel(), TrainHalf._stream()),
@@ -469,7 +469,7 @@ class TrainBlock:
         arr, keep = self._params(ps)
         rsp = None if res_scale_param is None else _f(res_scale_param).reshape(1)
         y = torch.empty_like(x)
-        saved = torch.empty(int(self._lib.wv_train_block_saved_bytes(self._h, B, T)), dtype=torch.uint8, device=x.device)
+        saved = _lib.scratch(int(self._lib.wv_train_block_saved_bytes(self._h, B, T)), x.device)
         rc = self._lib.wv_train_block_forward(self._h, x.data_ptr(), arr, None if rsp is None else rsp.data_ptr(), float(pre_scale),
                                               float(res_scale), y.data_ptr(), saved.data_ptr(), saved.numel(), B, T, TrainHalf._stream())
         if rc != 0:
@@ -477,7 +477,7 @@ class TrainBlock:
         return y, saved
 
     def backward(self, x, ps, res_scale_param, pre_scale: float, res_scale: float, dy, saved, into=None):
-        """into: optional dict(halves=[{dg_pw, dv_pw, dg_dw, dv_dw, db_dw} x 2], d_res_scale_param) of destinations (see _dst)."""
+        """into: optional dict(halves=[{dg_pw, dv_pw, dg_dw, dv_dw, db_dw} x 2], d_res_scale_param, dx) of destinations (see _dst)."""
         x, dy = _f(x), _f(dy)
         B, _, T = x.shape
         arr, keep = self._params(ps)
@@ -490,9 +490,9 @@ class TrainBlock:
                      dv_dw=_dst(hi, "dv_dw", (self.C, 5), dev), db_dw=_dst(hi, "db_dw", (self.C,), dev))
             grads.append(g)
             garr[i] = _HalfGrads(g["dg_pw"].data_ptr(), g["dv_pw"].data_ptr(), g["dg_dw"].data_ptr(), g["dv_dw"].data_ptr(), g["db_dw"].data_ptr())
-        dx = torch.empty_like(x)
+        dx = _dst(into, "dx", x.shape, dev)
         drsp = None if rsp is None else _dst(into, "d_res_scale_param", (1,), dev)
-        ws = torch.empty(int(self._lib.wv_train_block_workspace_bytes(self._h, B, T)), dtype=torch.uint8, device=dev)
+        ws = _lib.scratch(int(self._lib.wv_train_block_workspace_bytes(self._h, B, T)), dev)
         rc = self._lib.wv_train_block_backward(
             self._h, x.data_ptr(), arr, None if rsp is None else rsp.data_ptr(), float(pre_scale), float(res_scale), dy.data_ptr(),
             saved.data_ptr(), dx.data_ptr(), garr, None if drsp is None else drsp.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
@@ -529,7 +529,7 @@ def bce_logits(logits: torch.Tensor, mask=None, msg=None, grad_scale: float = 1.
     g = None if msg is None else _f(msg)
     loss = torch.empty(1, device=z.device)
     dz = torch.empty_like(z) if want_grad else None
-    ws = torch.empty(int(lib.wv_train_bce_workspace_bytes()), dtype=torch.uint8, device=z.device)
+    ws = _lib.scratch(int(lib.wv_train_bce_workspace_bytes()), z.device)
     rc = lib.wv_train_bce_logits(z.data_ptr(), None if m is None else m.data_ptr(), None if g is None else g.data_ptr(), loss.data_ptr(),
                                  None if dz is None else dz.data_ptr(), float(grad_scale), B, Cz, T, ws.data_ptr(), ws.numel(),
                                  TrainHalf._stream())
@@ -551,7 +551,7 @@ class FlatAdamW:
         self.m = torch.zeros(numel, device=device)
         self.v = torch.zeros(numel, device=device)
         self.t = 0
-        self._ws = torch.empty(int(self._lib.wv_train_bce_workspace_bytes()), dtype=torch.uint8, device=device)
+        self._ws = _lib.scratch(int(self._lib.wv_train_bce_workspace_bytes()), device)
         self._ss = torch.zeros(1, device=device)
 
     @property
@@ -659,8 +659,7 @@ class FilmMlp:
         if self._packed.numel() != self.np or not self._packed.is_contiguous():
             raise ValueError("FilmMlp: packed parameter block of the wrong size / layout")
         film = torch.empty(B, self.NF, device=msg.device)
-        self._ws = torch.empty(int(self._lib.wv_train_film_workspace_bytes(B, self.Dm, self.E, self.L, self.S, self.bands)), dtype=torch.uint8,
-                               device=msg.device)
+        self._ws = _lib.scratch(int(self._lib.wv_train_film_workspace_bytes(B, self.Dm, self.E, self.L, self.S, self.bands)), msg.device)
         if self._lib.wv_train_film_forward(msg.data_ptr(), self._packed.data_ptr(), film.data_ptr(), B, self.Dm, self.E, self.L, self.S, self.bands,
                                            self._ws.data_ptr(), self._ws.numel(), TrainHalf._stream()) != 0:
             raise RuntimeError(f"wv_train_film_forward: {self._lib.wv_train_last_error().decode()}")
@@ -1134,7 +1133,7 @@ def l1_loss(a: torch.Tensor, b: torch.Tensor, grad_scale: float = 1.0, want_grad
     lib = _lib.load()
     loss = torch.empty(1, device=a.device)
     da = torch.empty_like(a) if want_grad else None
-    ws = torch.empty(int(lib.wv_train_bce_workspace_bytes()), dtype=torch.uint8, device=a.device)
+    ws = _lib.scratch(int(lib.wv_train_bce_workspace_bytes()), a.device)
     if lib.wv_train_l1(a.data_ptr(), b.data_ptr(), loss.data_ptr(), None if da is None else da.data_ptr(), float(grad_scale), a.numel(),
                        ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
         raise RuntimeError(f"wv_train_l1: {lib.wv_train_last_error().decode()}")
