@@ -301,6 +301,23 @@ int wv_stft_plan_logmag(const wv_stft_plan* p, const float* wav, float* P, int B
 size_t wv_stft_plan_backward_workspace_bytes(const wv_stft_plan* p, int B, int T, int hop);
 int wv_stft_plan_backward(const wv_stft_plan* p, const float* wav, const float* dP, float* dwav, int accumulate, int B, int T, int hop, float std,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* Multi-scale STFT and mel-spectrogram reconstruction losses with their gradient towards wm (waveverify_amd/spectral_loss.py holds
+ * the semantics).  A plan holds n_scales <= 16 scales; scale i has window length window_lengths[i] (a multiple of 4, >= 8), hop w/4,
+ * F = w/2 + 1 bins, and flags[i]: bit 0 = an STFT-magnitude term, bit 1 = a mel term with n_mels[i] bands.  params[8 i .. 8 i + 7] =
+ * the STFT term's (log_weight, mag_weight, pow, clamp_eps), then the mel term's.  HOST arrays: windows = the scales' analysis windows
+ * concatenated (w floats each); mel_filters = the mel scales' dense [n_mels][F] filters concatenated (scales without a mel term add
+ * nothing).  Each term is log_weight * mean|pow log10(max(S_wm, eps)) - pow log10(max(S_x, eps))| + mag_weight * mean|S_wm - S_x| over
+ * [B, bins or bands, T/hop + 1] of the centred, reflect-padded transform's magnitude S (or its mel projection). */
+typedef struct wv_specloss_plan wv_specloss_plan;
+int wv_specloss_plan_create(int n_scales, const int* window_lengths, const int* flags, const int* n_mels, const float* params,
+                            const float* windows, const float* mel_filters, wv_specloss_plan** out);
+void wv_specloss_plan_destroy(wv_specloss_plan* p);
+size_t wv_specloss_workspace_bytes(const wv_specloss_plan* p, int B, int T);
+/* wm, x [B,1,T] DEVICE; terms [n_scales][2] (STFT term, mel term; 0 where a scale has none) and totals [2] (sum of the STFT terms, sum
+ * of the mel terms) DEVICE float outputs.  dwm [B,1,T] or NULL: dwm += stft_grad_scale * d(STFT total)/dwm + mel_grad_scale *
+ * d(mel total)/dwm.  Deterministic (fixed-order sums, no atomics).  WV_EINVAL when T <= w/2 for some scale (reflect padding). */
+int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int B, int T, float* terms, float* totals, float* dwm,
+                float stft_grad_scale, float mel_grad_scale, void* workspace, size_t workspace_bytes, void* stream);
 int wv_op_conv_pre(const float* x, const float* w, const float* bias, float* Y, int B, int C,
                    int T, int ks, float in_scale, void* stream);
 

@@ -1150,14 +1150,20 @@ class WatermarkTrainer:
         mean all-reduce of the three gradient arenas; clip_grad_norm_ on the GENERATOR's parameters only (train.py:1351-1353); AdamW
         on all three nets.
 
-    Not on this path (they stay on PyTorch-ROCm): the audio effects between augmentation and detection (identity here),
-    the mel / multi-scale-STFT losses and the discriminator; `extra_d_wm` is where their gradient towards the watermarked audio enters."""
+    The multi-scale STFT and mel losses (weights 10 and 20) join with `spectral_losses=True` (waveverify_amd/spectral_loss.py).
+    Not on this path (they stay on PyTorch-ROCm): the audio effects between augmentation and detection (identity here)
+    and the discriminator; `extra_d_wm` is where their gradient towards the watermarked audio enters."""
 
     LAMBDAS = {"waveform/loss": 1000.0, "loc/loss": 100.0, "dec/loss": 10000.0}
+    SPECTRAL_LAMBDAS = {"stft/loss": 10.0, "mel/loss": 20.0}          # with spectral_losses=True (conf/base.yml:141-150)
 
     def __init__(self, cfgG, sdG, cfgD, sdD, cfgL, sdL, lr: float = 1e-4, max_norm: float = 1000.0, sample_rate: int = 16000,
-                 window_duration: float = 0.1, device="cuda", effect_scheduler=None, apply_effect=None, effect_backward=None):
-        """effect_scheduler: a waveverify_amd.effect_scheduler.EffectScheduler (watermarking.py:266-271); every step then selects
+                 window_duration: float = 0.1, device="cuda", effect_scheduler=None, apply_effect=None, effect_backward=None,
+                 spectral_losses: bool = False):
+        """spectral_losses: also minimise the reference's multi-scale STFT and mel reconstruction losses of wm against x
+        (waveverify_amd.spectral_loss, conf/base.yml configuration) with weights 10 and 20 (`lambdas["stft/loss"]`, `lambdas["mel/loss"]`):
+        their gradient joins d_wm before the generator's backward and both terms are in step()'s dict and its total.
+        effect_scheduler: a waveverify_amd.effect_scheduler.EffectScheduler (watermarking.py:266-271); every step then selects
         effects as `_apply_adaptive_effects` does (watermarking.py:537: select_effects(batch size), i.e. at most one per known effect,
         applied to the FIRST clips of the batch) and feeds per-clip BER / mIoU back (`_update_effect_metrics`, watermarking.py:697-752).
         apply_effect(name, params, audio [1,1,T], mask [1,1,T]) -> (audio, mask) runs the non-identity effects; without it only
@@ -1173,6 +1179,11 @@ class WatermarkTrainer:
         self.L = EncoderNetTrainer(cfgL, sdL, lr, max_norm, device)
         self.aug = TemporalAugmenter(sample_rate, window_duration)
         self.lambdas = dict(self.LAMBDAS)
+        self.spectral = None
+        if spectral_losses:
+            from .spectral_loss import SpectralLosses
+            self.lambdas.update(self.SPECTRAL_LAMBDAS)
+            self.spectral = SpectralLosses()
         self.effect_scheduler, self.apply_effect, self.effect_backward = effect_scheduler, apply_effect, effect_backward
         self.ber_calculator, self.miou_calculator = BER(threshold=0.5), MIOU()
         self.effect_update_count = 0
@@ -1284,6 +1295,8 @@ class WatermarkTrainer:
             d_wm = self.aug.backward(d_aug) if augment else d_aug
             wav, d_wav = l1_loss(wm, x, grad_scale=lam["waveform/loss"])
             d_wm = d_wm + d_wav
+            if self.spectral is not None:                                 # d_wm += 10 dSTFT/dwm + 20 dmel/dwm, in place
+                stft, mel, d_wm = self.spectral(wm, x, stft_grad_scale=lam["stft/loss"], mel_grad_scale=lam["mel/loss"], out=d_wm)
             if extra_d_wm is not None:
                 d_wm = d_wm + _f(extra_d_wm)
             self.G.begin_reduce()
@@ -1302,4 +1315,8 @@ class WatermarkTrainer:
         self.D.opt.step(self.D.arena, self.D.grads, None)
         self.L.opt.step(self.L.arena, self.L.grads, None)
         total = lam["dec/loss"] * dec + lam["loc/loss"] * loc + lam["waveform/loss"] * wav
-        return {"loss": total, "dec/loss": dec, "loc/loss": loc, "waveform/loss": wav, "grad_norm": norm, "stats": stats}
+        out = {"loss": total, "dec/loss": dec, "loc/loss": loc, "waveform/loss": wav, "grad_norm": norm, "stats": stats}
+        if self.spectral is not None:
+            out["loss"] = total + lam["stft/loss"] * stft + lam["mel/loss"] * mel
+            out["stft/loss"], out["mel/loss"] = stft, mel
+        return out
