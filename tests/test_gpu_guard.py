@@ -970,3 +970,55 @@ def test_fx_guarded_inputs(offset):
         ref, got = fresh(), guarded()
         g.check()
         assert torch.isfinite(got).all() and torch.equal(bits(got.contiguous()), bits(ref.contiguous())), what
+
+
+# ================================================================== spectral losses through the C ABI
+def _specloss_cases():
+    import specloss_cases as SC
+    return SC.guard_cases()
+
+
+@pytest.mark.parametrize("cid", [c[0] for c in _specloss_cases()])
+def test_specloss_guarded(cid):
+    """wv_specloss: wm, x, terms, totals and dwm between guard bands, the workspace exactly wv_specloss_workspace_bytes long and 0xFF.
+    The call adds into dwm, so dwm starts from a known pattern and must end as pattern + gradient; the float64 oracle at the bars of
+    test_gpu_spectral_loss.py; a second call on a re-poisoned workspace bit-identical.  The STFT-only plan never writes the mel
+    gradient region of the workspace (nothing may read it), the mel-only plan runs the bins kernel for its gradient alone."""
+    import specloss_cases as SC
+    from oracle import wv_oracle_specloss as OS
+    from waveverify_amd import _lib
+    from waveverify_amd import spectral_loss as SL
+    _, scales, B, T, seed, bar = next(c for c in _specloss_cases() if c[0] == cid)
+    wm, x = SC.clips(B, T, seed)
+    ref = OS.spectral_oracle(wm, x, scales, stft_grad_scale=10.0, mel_grad_scale=20.0)
+    plan = SL._Plan(scales)
+    g = Guards()
+    wm_g, x_g = g.input(wm, "wm"), g.input(x, "x")
+    terms, totals, dwm = g.output((len(scales), 2), name="terms"), g.output((2,), name="totals"), g.output((B, 1, T), name="dwm")
+    ws = g.workspace(int(_lib.load().wv_specloss_workspace_bytes(plan._h, B, T)), "workspace")
+    base = torch.from_numpy(np.random.default_rng(seed).standard_normal((B, 1, T)).astype(np.float32)).cuda()
+    runs = []
+    for _ in range(2):
+        g.repoison()
+        dwm.t.copy_(base)
+        _lib.check(SC.c_call(plan, wm_g.t, x_g.t, terms.t, totals.t, dwm.t, ws.t, 10.0, 20.0), "wv_specloss")
+        g.check()
+        runs.append([bits(a.t) for a in (terms, totals, dwm)])
+    for a, p, q in zip((terms, totals, dwm), *runs):
+        assert torch.equal(p, q), f"{a.name}: second run on a re-poisoned workspace differs from the first"
+    got_terms, got_totals = terms.t.cpu().numpy().astype(np.float64), totals.t.cpu().numpy().astype(np.float64)
+    grad = (dwm.t - base).cpu().numpy().astype(np.float64)
+    assert np.isfinite(got_terms).all() and np.isfinite(got_totals).all() and np.isfinite(grad).all()
+    for i, s in enumerate(ref["scales"]):
+        for j, part in enumerate(("stft", "mel")):
+            want = s[part] if s[part] is not None else 0.0
+            assert abs(got_terms[i, j] - want) <= SC.TERM_BAR * abs(want), (cid, s["w"], part, got_terms[i, j], want)
+    for j, part in enumerate(("stft", "mel")):
+        assert abs(got_totals[j] - ref[part + "_total"]) <= SC.TERM_BAR * abs(ref[part + "_total"]), (cid, part)
+    # dwm ends as pattern + gradient: the subtraction of the pattern costs one rounding of the sum, 1e-6 of the larger of the two
+    fresh = torch.zeros(B, 1, T, device="cuda")
+    _lib.check(SC.c_call(plan, wm_g.t, x_g.t, terms.t, totals.t, fresh, ws.t, 10.0, 20.0), "wv_specloss")
+    assert float((dwm.t - base - fresh).abs().max()) <= 1e-6 * max(float(fresh.abs().max()), float(base.abs().max()))
+    e = SC.rel_err(fresh.cpu().numpy(), ref["d_total"])
+    print(f"RECORD specloss guarded {cid}: gradient {e:.2e} of max")
+    assert e <= bar, (cid, e)
