@@ -569,6 +569,59 @@ int wv_fx_resample_adjoint(const float* dy, const float* kernels, float* dx, int
  * y[row][m] = sum_j kernels[m % nw][j] * xz[(m / nw)*orig + j - width] for m < Tout = ceil(nw * T / orig), xz zero outside [0,T). */
 int wv_fx_resample(const float* x, const float* kernels, float* y, int rows, int T, int orig, int nw, int L, int width, int Tout, void* stream);
 
+/* ---- plain-arithmetic time-domain effects (csrc/wv_fx_time.hip) ----------------------------------------------------------------
+ * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
+ * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding
+ * per sample, to 2e-5 of the peak where it is a float sum.  Device pointers, [rows][T] contiguous f32, rows <= 65535, rows * T < 2^32;
+ * any alignment of 4 bytes is accepted.  The random draws are made on the host (waveverify_amd/effects.py) and arrive as arguments. */
+/* pointwise pass, one rounding per operation in the reference's order (the library is built without contraction):
+ *   WV_FX_SCALE      y = x * a                          (amplitude_scaling)
+ *   WV_FX_ADD_NOISE  y = x + noise * a                  (random_noise / white_noise / pink_noise; noise [rows][T])
+ *   WV_FX_QUANTIZE   y = rint(x * a) / a, a = 2^(bits-1) - 1, half to even, IEEE divide (a = 0 gives NaN, as the reference does for 1 bit)
+ *   WV_FX_MUL        y = x * noise                      (shush's backward: gradient * keep mask; a is ignored)
+ * noise may be NULL for the two one-tensor ops. */
+#define WV_FX_SCALE 0
+#define WV_FX_ADD_NOISE 1
+#define WV_FX_QUANTIZE 2
+#define WV_FX_MUL 3
+int wv_fx_pointwise(const float* x, const float* noise, float* y, int rows, int T, int op, float a, void* stream);
+/* scipy.signal.medfilt: y[t] = median of x[t - k/2 .. t + k/2] with ZEROS outside [0, T); k odd.  k <= WV_FX_MEDIAN_NET_K sorts the
+ * window in registers, larger k up to WV_FX_MEDIAN_MAX_K counts ranks over the LDS tile (O(k^2) per sample); any other k is refused.
+ * A NaN in a window is outside the contract. */
+#define WV_FX_MEDIAN_NET_K 31
+#define WV_FX_MEDIAN_MAX_K 255
+int wv_fx_median(const float* x, float* y, int rows, int T, int k, void* stream);
+/* shush: per row, zero exactly k (0 <= k <= T - 1) samples: every sample whose |x| is below the k-th smallest, and the earliest ones
+ * equal to it until k are gone (torch.topk leaves the choice among equals open; this one is deterministic).  y = x * keep,
+ * keep [rows][T] = 0 / 1 (the backward's mask), and with mask_in: mask_out = mask_in * (y != 0) -- samples that were 0 already clear
+ * the mask too.  k = 0 copies.  mask_in / mask_out may both be NULL. */
+int wv_fx_shush(const float* x, const float* mask_in, float* y, float* keep, float* mask_out, int rows, int T, int k, void* stream);
+/* echo: c[r][t] = x[r][t] + volume * x[r][t + n - 1] for t < T - n + 1 (cross-correlation with [1, 0, .., 0, volume], n taps, 2 <= n <= T:
+ * the delayed copy comes BEFORE the sound, as in the reference), y = c / max|c| * max|x| with both maxima over the WHOLE tensor and only
+ * when both are > 0; the last n - 1 samples of each row are 0.  Two launches: the peaks call fills the record (WV_FX_ECHO_RECORD_BYTES,
+ * 8-byte aligned: two 64-bit words, (bits of the maximum) << 32 | ~(flat position), for x then for c), the apply call reads it.
+ * The backward is the reference's autograd through the correlation and both maxima; it needs x, the record of the forward and a
+ * workspace of the stated size (any contents), and sums g * c in a fixed order.  Ties for a maximum are outside the contract: the
+ * forward does not depend on which of two equal peaks is recorded, the backward sends the peak's gradient to the earliest. */
+#define WV_FX_ECHO_RECORD_BYTES 16
+int wv_fx_echo_peaks(const float* x, void* rec, int rows, int T, int n, float volume, void* stream);
+int wv_fx_echo_apply(const float* x, const void* rec, float* y, int rows, int T, int n, float volume, void* stream);
+size_t wv_fx_echo_backward_workspace_bytes(void);
+int wv_fx_echo_backward(const float* x, const float* g, const void* rec, float* dx, int rows, int T, int n, float volume, void* workspace,
+                        size_t workspace_bytes, void* stream);
+/* smooth: y[t] = sum_j xpad[t + j] / w over w taps, xpad = x REFLECT-padded by pad_l = (w-1)/2 in front and pad_r = w-1-pad_l behind
+ * (pad_r < T, w <= WV_FX_SMOOTH_MAX_W); with mask_in: mask_out[t] = (count / w >= valid_threshold) in f32, count = the window sum of the
+ * ZERO-padded mask.  The backward is the transposed box filter followed by the transpose of the reflect padding, in one kernel. */
+#define WV_FX_SMOOTH_MAX_W 2048
+int wv_fx_smooth(const float* x, const float* mask_in, float* y, float* mask_out, int rows, int T, int w, float valid_threshold, void* stream);
+int wv_fx_smooth_backward(const float* g, float* dx, int rows, int T, int w, void* stream);
+/* y[r][idx[r][j]] = 0 for j < num, in place, and the same on mask when it is not NULL; idx [rows][num] int32, entries outside [0, T) are
+ * skipped.  sample_suppression's forward (on a copy of the input) and, on the gradient, its backward. */
+int wv_fx_scatter_zero(float* y, float* mask, const int* idx, int rows, int T, int num, void* stream);
+/* torch.nn.functional.interpolate(mode='linear', align_corners=False) from Tin to Tout samples: source coordinate
+ * max(0, (m + 0.5) * Tin / Tout - 0.5) with the scale in f32 (AudioProcessor.adjust_audio_length(mode='stretch')). */
+int wv_fx_stretch_linear(const float* x, float* y, int rows, int Tin, int Tout, void* stream);
+
 /* ---- measurement hook (bench.py's roofline figures) ---------------------------------------
  * When enabled, every kernel launch is bracketed by a hipEvent pair on the launch stream and
  * aggregated by "<kernel>|<role>" together with its ALGORITHMIC flops and bytes (the per-unit

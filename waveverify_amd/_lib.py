@@ -137,6 +137,17 @@ SIGNATURES = {
     "wv_fx_fir_bank": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_fold_replicate": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_resample_adjoint": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_pointwise": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
+    "wv_fx_median": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_shush": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_echo_peaks": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
+    "wv_fx_echo_apply": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
+    "wv_fx_echo_backward_workspace_bytes": (C.c_size_t, []),
+    "wv_fx_echo_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_fx_smooth": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
+    "wv_fx_smooth_backward": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_scatter_zero": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_stretch_linear": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_profile_enable": (C.c_int, [C.c_int]),
     "wv_profile_reset": (C.c_int, []),
     "wv_profile_collect": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64),

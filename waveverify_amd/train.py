@@ -1171,7 +1171,8 @@ class WatermarkTrainer:
         effect: the reference differentiates through its julius filters and torchaudio resampler (plain torch ops,
         effect_augmentation.py:1451-1501,1684-1870), so their gradient is the transposed filter (`effects.apply_effect_backward`);
         its SoX / codec / quantisation effects are straight-through Functions (:462-500) whose gradient is the identity -- which is
-        also what a missing `effect_backward` means for every effect."""
+        also what a missing `effect_backward` means for every effect.  Effects whose backward needs memory of the forward (shush,
+        sample_suppression, echo, smooth, amplitude_scaling) get both hooks from one `effects.EffectTape` (`tape.apply`, `tape.backward`)."""
         from .augment import TemporalAugmenter
         from .metrics import BER, MIOU
         self.G = GeneratorTrainer(cfgG, sdG, lr, max_norm, device)
