@@ -516,6 +516,30 @@ int wv_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float
                    float weight_decay, int step, const float* grad_sumsq, float max_norm, void* stream);
 const char* wv_train_last_error(void);
 
+/* ---- per-clip metrics of a validation pass (csrc/wv_metrics.hip; semantics in waveverify_amd/metrics.py) ---------------------
+ * Three single-pass reductions, each with a caller-provided workspace sized by its *_workspace_bytes query (0 = bad shape).  Device
+ * pointers, contiguous; inputs may sit on any 4-byte boundary, the workspace and the double outputs on 8.  Rows are summed in chunks
+ * of 4096 samples in a fixed order, in f64 (or int32), and the chunks in ascending order: results are bit-identical from run to run
+ * and a clip's result does not depend on the batch it is part of.  B * W and B <= 65535.
+ *
+ * decode = scripts/evaluate.py BER.forward :442-516 up to the per-clip counts.  logits [B,W,T], bits [B,W] (float 0 / 1), mask [B,1,T]
+ * or NULL.  Per (clip, bit) S = sum sigmoid(l) * m and N = sum m are rounded to f32 and finished in f32 as the reference writes it:
+ * avg = S / (N + eps), valid = N > 0; without a mask avg = S / T and every bit is valid.  decoded = avg >= threshold.
+ * Outputs: avg [B,W] float, errors [B] int32 (valid bits with decoded != bit), valid [B] int32 (valid bits). */
+size_t wv_metrics_decode_workspace_bytes(int B, int W, int T);
+int wv_metrics_decode(const float* logits, const float* bits, const float* mask, float threshold, float eps, int B, int W, int T, float* avg,
+                      int* errors, int* valid, void* workspace, size_t workspace_bytes, void* stream);
+/* iou = the counts of MIOU.forward :591-665 on p = (pred > 0.5) (the RAW locator output, model/watermarking.py:797) and the 0 / 1 mask g:
+ * counts [B][4] int32 = |p and g=1|, |p or g=1|, |not p and g=0|, |not p or g=0|.  pred, mask [B,1,T]. */
+size_t wv_metrics_iou_workspace_bytes(int B, int T);
+int wv_metrics_iou(const float* pred, const float* mask, int B, int T, int* counts, void* workspace, size_t workspace_bytes, void* stream);
+/* sisnr = SISNR.forward :167-229 per clip.  estimate, reference [B,1,T].  moments [B][5] double = sum x, sum y, sum xx, sum xy, sum yy
+ * (x = estimate, y = reference); sisnr [B] double = 10 log10(|proj|^2 / (|x0 - proj|^2 + eps) + eps) in dB with x0, y0 the zero-meaned
+ * signals and proj = y0 [x0.y0] / (|y0|^2 + eps), evaluated on the moments in f64. */
+size_t wv_metrics_sisnr_workspace_bytes(int B, int T);
+int wv_metrics_sisnr(const float* estimate, const float* reference, int B, int T, double eps, double* sisnr, double* moments, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
 /* ---- temporal augmentations of the training step ------------------------------------
  * One bandwidth-bound pass that replaces the reference's per-clip / per-segment Python loops and its GPU->CPU->GPU
  * hop (model/watermarking.py:487-519,540).  All pointers are DEVICE pointers, tensors [B,C,T] contiguous f32.

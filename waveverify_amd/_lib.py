@@ -97,6 +97,12 @@ SIGNATURES = {
     "wv_specloss_plan_destroy": (None, [_VP]),
     "wv_specloss_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "wv_specloss": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_metrics_decode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "wv_metrics_decode": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "wv_metrics_iou_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "wv_metrics_iou": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
+    "wv_metrics_sisnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "wv_metrics_sisnr": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
     "wv_train_up_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     "wv_train_up_destroy": (None, [_VP]),
     "wv_train_up_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),

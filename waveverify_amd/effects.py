@@ -599,6 +599,18 @@ class AudioEffects:
 REFUSED = {"mp3_lossy_compression": "ffmpeg's codec", "aac_lossy_compression": "ffmpeg's codec", "encodec": "the transformers EnCodec model",
            "random_equalization": "SoX's biquad equaliser"}
 
+# the reference's shipped evaluation list, in its order (conf/effects_config.yml `eval_effects`, model/watermarking.py:135-143): what a
+# validation pass applies to the whole batch, one effect at a time.  tests/golden/eval_effects.json holds the same list as data.
+EVAL_EFFECTS = (
+    ("identity", {}),
+    ("resample", {"new_sample_rate": 32000}),
+    ("speed", {"speed": 0.8}),
+    ("random_noise", {"noise_std": 0.001}),
+    ("lowpass_filter", {"cutoff_freq": 2000}),
+    ("highpass_filter", {"cutoff_freq": 3500}),
+    ("bandpass_filter", {"cutoff_freq_low": 300, "cutoff_freq_high": 4000}),
+)
+
 
 def apply_effect(name: str, params: dict, audio: torch.Tensor, mask: Optional[torch.Tensor] = None, sample_rate: int = DEFAULT_SAMPLE_RATE):
     """Dispatcher with the (name, params, audio, mask) -> (audio, mask) shape WatermarkTrainer's `apply_effect` hook expects.  Effects

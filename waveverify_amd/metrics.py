@@ -4,10 +4,19 @@ Restated from /root/reference/scripts/evaluate.py: BER.forward :442-516 (mask-we
 time-averaged sigmoid, >= threshold, errors over valid bits) and MIOU.forward :591-665
 (mean of foreground and background IoU on binary masks; an empty union counts as IoU 1).
 Note model/watermarking.py:717,797 binarises the *raw* locator output at 0.5 before MIOU.
+
+Per-clip forms for a validation pass, fused on the GPU (csrc/wv_metrics.hip), one read of the inputs each:
+
+    errors, valid, avg = ber_per_clip(logits, bits, mask)      # BER of the batch = errors.sum() / valid.sum()
+    miou = miou_per_clip(locator_out, mask)                    # [B] float64, from iou_counts(...) -> [B,4] int32
+    sisnr = SISNR()(estimate, reference)                       # [B] float64 dB; SISNR().mean(...) is the reference's scalar
+
+Device tensors go through the kernels; CPU tensors take a torch route with the same arithmetic (f64 sums, then the reference's f32
+finish for the bit decision), so host-only callers need no GPU.  `BER` and `MIOU` above stay the reference's own formulation.
 """
 from __future__ import annotations
 
-from typing import Optional, Union
+from typing import Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -53,3 +62,148 @@ class MIOU:
             union = np.logical_or(p == cls, g == cls).sum()
             out.append((1.0 if inter == 0 else 0.0) if union == 0 else inter / union)
         return float(sum(out) / 2)
+
+
+# ---- per-clip metrics (the validation pass) --------------------------------------------------------------------------------------
+def _stream(t: torch.Tensor):
+    import ctypes as C
+    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
+def _f32(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().float().contiguous()
+
+
+def _ok(rc: int, what: str) -> None:
+    if rc != 0:
+        raise RuntimeError(f"{what} failed (code {rc})")
+
+
+def ber_per_clip(logits: torch.Tensor, bits: torch.Tensor, mask: Optional[torch.Tensor] = None, threshold: float = 0.5,
+                 eps: float = 1e-8) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """BER.forward (scripts/evaluate.py:442-516) split per clip -> (errors [B] int32, valid [B] int32, avg [B,W] float32) on the
+    logits' device: `valid` counts the bits of a clip whose mask has a live sample, `errors` those of them decoded wrongly, and the
+    reference's scalar is errors.sum() / valid.sum() (0 when nothing is valid).  Per (clip, bit) the masked sums of sigmoid(logits)
+    and of the mask are taken in float64 and rounded to float32; the decision is then the reference's own float32 expression,
+    avg = S / (N + eps) >= threshold (S / T without a mask), so a tie such as all-zero logits decodes as it does there."""
+    if logits.dim() != 3:
+        raise ValueError(f"logits must be [B, W, T], got {tuple(logits.shape)}")
+    B, W, T = logits.shape
+    if tuple(bits.shape) != (B, W):
+        raise ValueError(f"bits must be [B, W] = [{B}, {W}], got {tuple(bits.shape)}")
+    if mask is not None and (mask.dim() != 3 or mask.shape[0] != B or mask.shape[1] != 1 or mask.shape[2] != T):
+        raise ValueError(f"mask must be [B, 1, T] = [{B}, 1, {T}], got {tuple(mask.shape)}")
+    z, g = _f32(logits), _f32(bits).to(logits.device)
+    m = None if mask is None else _f32(mask).to(logits.device)
+    if z.is_cuda:
+        from . import _lib
+        lib = _lib.load()
+        avg = torch.empty(B, W, dtype=torch.float32, device=z.device)
+        errors = torch.empty(B, dtype=torch.int32, device=z.device)
+        valid = torch.empty(B, dtype=torch.int32, device=z.device)
+        ws = _lib.scratch(int(lib.wv_metrics_decode_workspace_bytes(B, W, T)), z.device)
+        _ok(lib.wv_metrics_decode(z.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(), float(threshold), float(eps), B, W, T,
+                                  avg.data_ptr(), errors.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), _stream(z)), "wv_metrics_decode")
+        return errors, valid, avg
+    p = torch.sigmoid(z.double())
+    if m is not None:
+        md = m.double().expand(-1, W, -1)
+        s, n = (p * md).sum(dim=2).float(), md.sum(dim=2).float()
+        avg = s / (n + torch.tensor(eps, dtype=torch.float32))
+        ok = n > 0
+    else:
+        avg = p.sum(dim=2).float() / torch.tensor(float(T), dtype=torch.float32)
+        ok = torch.ones(B, W, dtype=torch.bool)
+    decoded = (avg >= torch.tensor(threshold, dtype=torch.float32)).float()
+    errors = ((decoded != g) & ok).sum(dim=1).to(torch.int32)
+    return errors, ok.sum(dim=1).to(torch.int32), avg
+
+
+def iou_counts(locator_out: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+    """-> [B,4] int32 on the inputs' device: per clip |p & g1|, |p | g1|, |~p & g0|, |~p | g0| with p = locator_out > 0.5 (the RAW
+    locator output, as watermarking.py:797 binarises it), g1 = mask == 1, g0 = mask == 0.  Summed over clips they are the counts MIOU
+    takes on the whole batch tensor."""
+    if locator_out.shape != mask.shape or locator_out.dim() != 3 or locator_out.shape[1] != 1:
+        raise ValueError(f"locator output and mask must both be [B, 1, T], got {tuple(locator_out.shape)} and {tuple(mask.shape)}")
+    B, _, T = locator_out.shape
+    p, g = _f32(locator_out), _f32(mask).to(locator_out.device)
+    if p.is_cuda:
+        from . import _lib
+        lib = _lib.load()
+        counts = torch.empty(B, 4, dtype=torch.int32, device=p.device)
+        ws = _lib.scratch(int(lib.wv_metrics_iou_workspace_bytes(B, T)), p.device)
+        _ok(lib.wv_metrics_iou(p.data_ptr(), g.data_ptr(), B, T, counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(p)), "wv_metrics_iou")
+        return counts
+    fg, g1, g0 = (p > 0.5)[:, 0], (g == 1)[:, 0], (g == 0)[:, 0]
+    return torch.stack([(fg & g1).sum(1), (fg | g1).sum(1), (~fg & g0).sum(1), (~fg | g0).sum(1)], dim=1).to(torch.int32)
+
+
+def miou_from_counts(counts) -> np.ndarray:
+    """[..., 4] integer counts -> float64 mIoU: the mean of the foreground and the background IoU, an empty union counting as IoU 1
+    (MIOU.forward, scripts/evaluate.py:591-665)."""
+    c = (counts.detach().cpu().numpy() if torch.is_tensor(counts) else np.asarray(counts)).astype(np.float64)
+    out = np.zeros(c.shape[:-1], np.float64)
+    for k in (0, 2):
+        inter, union = c[..., k], c[..., k + 1]
+        out += np.where(union == 0, 1.0, inter / np.where(union == 0, 1.0, union))
+    return out / 2
+
+
+def miou_per_clip(locator_out: torch.Tensor, mask: torch.Tensor) -> np.ndarray:
+    """MIOU of every clip of a batch -> [B] float64 (host): exact integer counts from one pass over the RAW locator output and the
+    0 / 1 mask (`iou_counts`), the ratio formed on the host in float64."""
+    return miou_from_counts(iou_counts(locator_out, mask))
+
+
+class SISNR:
+    """The reference's scale-invariant signal-to-noise ratio (scripts/evaluate.py:146-229), per clip, in dB:
+
+        x0, y0 = estimate - mean, reference - mean;  proj = y0 <x0, y0> / (|y0|^2 + eps)
+        SI-SNR = 10 log10(|proj|^2 / (|x0 - proj|^2 + eps) + eps)
+
+    with all three eps of the reference; a silent reference gives 10 log10(eps).  One pass gathers the five moments sum x, sum y,
+    sum xx, sum xy, sum yy in float64 (`last_moments`, [B,5]); the rest is algebra on them in float64.  The noise power is taken as
+    (<x0,x0> - <x0,y0>^2 / |y0|^2) + (<x0,y0> eps)^2 / (|y0|^2 (|y0|^2 + eps)^2), which is the same number without the cancellation.
+    Calling returns [B] float64 on the inputs' device; `.mean(...)` is the scalar the reference's module returns."""
+
+    def __init__(self, eps: float = 1e-8):
+        self.eps = float(eps)
+        self.last_moments: Optional[torch.Tensor] = None
+
+    def __call__(self, estimates: torch.Tensor, references: torch.Tensor) -> torch.Tensor:
+        if estimates.shape != references.shape or estimates.dim() != 3 or estimates.shape[1] != 1:
+            raise ValueError(f"estimates and references must both be [B, 1, T], got {tuple(estimates.shape)} and {tuple(references.shape)}")
+        B, _, T = estimates.shape
+        y = _f32(references)
+        x = _f32(estimates).to(y.device)                        # the reference moves the estimate to the reference's device
+        if y.is_cuda:
+            from . import _lib
+            lib = _lib.load()
+            out = torch.empty(B, dtype=torch.float64, device=y.device)
+            mom = torch.empty(B, 5, dtype=torch.float64, device=y.device)
+            ws = _lib.scratch(int(lib.wv_metrics_sisnr_workspace_bytes(B, T)), y.device)
+            _ok(lib.wv_metrics_sisnr(x.data_ptr(), y.data_ptr(), B, T, self.eps, out.data_ptr(), mom.data_ptr(), ws.data_ptr(), ws.numel(),
+                                     _stream(y)), "wv_metrics_sisnr")
+            self.last_moments = mom
+            return out
+        xd, yd = x.double()[:, 0], y.double()[:, 0]
+        mom = torch.stack([xd.sum(1), yd.sum(1), (xd * xd).sum(1), (xd * yd).sum(1), (yd * yd).sum(1)], dim=1)
+        self.last_moments = mom
+        return self.from_moments(mom, T)
+
+    def from_moments(self, moments: torch.Tensor, T: int) -> torch.Tensor:
+        """[B,5] float64 moments of T-sample clips -> [B] float64 dB (the arithmetic the kernel's second launch runs)."""
+        m, eps, n = moments.double(), self.eps, float(T)
+        xx = (m[:, 2] - (m[:, 0] * m[:, 0]) / n).clamp_min(0.0)
+        xy = m[:, 3] - (m[:, 0] * m[:, 1]) / n
+        yy = (m[:, 4] - (m[:, 1] * m[:, 1]) / n).clamp_min(0.0)
+        e = yy + eps
+        a = xy / e
+        live = yy > 0
+        yys = torch.where(live, yy, torch.ones_like(yy))
+        k = xy * eps / (yys * e)
+        noise = torch.where(live, (xx - (xy / yys) * xy).clamp_min(0.0) + yy * k * k, xx)
+        return 10.0 * torch.log10((a * a * yy) / (noise + eps) + eps)
+
+    def mean(self, estimates: torch.Tensor, references: torch.Tensor) -> torch.Tensor:
+        return self(estimates, references).mean()

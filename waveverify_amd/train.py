@@ -1321,3 +1321,103 @@ class WatermarkTrainer:
             out["loss"] = total + lam["stft/loss"] * stft + lam["mel/loss"] * mel
             out["stft/loss"], out["mel/loss"] = stft, mel
         return out
+
+    def validate(self, x: torch.Tensor, msg: torch.Tensor, eval_effects=None, augment: bool = True, seed: int = 0):
+        """The reference's validation pass for the terms that live on this path (model/watermarking.py:443-483 `_forward_valid`,
+        :755-809 `_evaluate_single_effect`, scripts/train.py:956-1091 `val_loop`), without a gradient:
+
+            wm = G(x, msg) + x  ->  localisation + sequence augmentation, once  ->  for every (name, params) of `eval_effects`
+            (default: effects.EVAL_EFFECTS, the reference's shipped list in its order) the effect on the WHOLE batch, D and L on the
+            result, DecodingLoss / LocalizationLoss, per-clip BER and mIoU (metrics.ber_per_clip, metrics.iou_counts: one read each)
+
+        -> {"dec/loss", "loc/loss": means over the effects (train.py:1045-1049); "waveform/loss"; "stft/loss", "mel/loss" with
+        spectral_losses=True; "loss": the `lambdas`-weighted sum of those; "SISNR": the reference's mean over the batch, dB;
+        "<effect>/ber": wrong over valid bits of the batch; "<effect>/miou": MIOU of the whole batch tensor (from the batch-summed
+        counts); "per_clip": {"effects": names, "errors", "valid": [E,B] int, "ber", "miou": [E,B] float64 (BER nan where a clip
+        has no valid bit), "sisnr": [B] float64}}.  Losses are device tensors like step()'s; the metrics are host numbers.
+
+        Absent on purpose: STOI and PESQ, which the reference takes from the pystoi and pesq packages (arithmetic this project does
+        not have), and the adversarial terms (no discriminator on this path).
+
+        The trainer is left as it was found: no gradient, all-reduce or optimizer step; the effect scheduler is neither asked nor
+        told; the augmentation is drawn by an augmenter of validate's own, and the random streams the draws and the noise effects
+        use (numpy's, Python's and torch's global generators) are seeded with `seed` for the pass and put back afterwards -- so a
+        validation between two steps changes neither of them, and the same `seed` evaluates the same augmentation and noise every
+        time.  An effect of effects.REFUSED raises NotImplementedError by name before anything is launched."""
+        import random as _random
+        from . import effects as fx
+        from .augment import TemporalAugmenter
+        from .metrics import SISNR, ber_per_clip, iou_counts, miou_from_counts
+        plan = [(str(n), dict(q)) for n, q in (fx.EVAL_EFFECTS if eval_effects is None else eval_effects)]
+        if not plan:
+            raise ValueError("validate: eval_effects is empty")
+        for name, _ in plan:
+            if name in fx.REFUSED or name.startswith("_") or getattr(fx.AudioEffects, name, None) is None:
+                why = f" (needs {fx.REFUSED[name]})" if name in fx.REFUSED else ""
+                raise NotImplementedError(f"effect '{name}' is not available on the GPU path{why}")
+        x, msg = _f(x), _f(msg)
+        if msg.dim() == 1:
+            msg = msg[None]
+        if msg.shape[0] != x.shape[0]:
+            msg = msg.repeat(-(-x.shape[0] // msg.shape[0]), 1)[: x.shape[0]].contiguous()
+        if getattr(self, "_val_aug", None) is None:
+            self._val_aug = TemporalAugmenter(self.aug.sample_rate, self.aug.localization_augmenter.window_duration)
+        lam = self.lambdas
+        saved = [(net, k, getattr(net, k, None)) for net in (self.G, self.D, self.L) for k in ("_enc", "_dec", "_z")]
+        rng = (np.random.get_state(), _random.getstate(), torch.get_rng_state(), torch.cuda.get_rng_state(x.device))
+        try:
+            np.random.seed(seed)
+            _random.seed(seed)
+            torch.manual_seed(seed)
+            wm = self.G.forward(x, msg)
+            if augment:
+                sig, mask, _, _ = self._val_aug.forward(x, wm)
+                wm_aug = sig.audio_data
+            else:
+                wm_aug, mask = wm, torch.ones_like(wm)
+            dec_sum = loc_sum = None
+            errors, valid, counts = [], [], []
+            for name, params in plan:
+                a_e, m_e = fx.apply_effect(name, params, wm_aug, mask, sample_rate=self.aug.sample_rate)
+                logits_d = self.D.forward(a_e)
+                logits_l = self.L.forward(a_e)
+                dec, _ = bce_logits(logits_d, m_e, msg, want_grad=False)
+                loc, _ = bce_logits(logits_l, m_e, None, want_grad=False)
+                dec_sum = dec if dec_sum is None else dec_sum + dec
+                loc_sum = loc if loc_sum is None else loc_sum + loc
+                e, v, _ = ber_per_clip(logits_d, msg, m_e, threshold=self.ber_calculator.threshold, eps=self.ber_calculator.eps)
+                errors.append(e)
+                valid.append(v)
+                counts.append(iou_counts(logits_l, m_e))
+            out = {"dec/loss": dec_sum / len(plan), "loc/loss": loc_sum / len(plan)}
+            out["waveform/loss"], _ = l1_loss(wm, x, want_grad=False)
+            if self.spectral is not None:
+                out["stft/loss"], out["mel/loss"], _ = self.spectral(wm, x, want_grad=False)
+            sisnr = SISNR()(wm, x)
+            # one trip to the host for every count of the pass
+            errors, valid, counts, sisnr = (t.cpu().numpy() for t in (torch.stack(errors), torch.stack(valid), torch.stack(counts), sisnr))
+        finally:
+            np.random.set_state(rng[0])
+            _random.setstate(rng[1])
+            torch.set_rng_state(rng[2])
+            torch.cuda.set_rng_state(rng[3], x.device)
+            for net, k, v in saved:
+                if hasattr(net, k):
+                    setattr(net, k, v)
+        total = None
+        for k in ("dec/loss", "loc/loss", "waveform/loss", "stft/loss", "mel/loss"):
+            if k in out:
+                total = lam[k] * out[k] if total is None else total + lam[k] * out[k]
+        out["loss"] = total
+        out["SISNR"] = float(sisnr.mean())
+        errors, valid = errors.astype(np.int64), valid.astype(np.int64)
+        miou = miou_from_counts(counts)
+        batch_miou = miou_from_counts(counts.astype(np.int64).sum(axis=1))
+        for i, (name, _) in enumerate(plan):
+            n_valid = int(valid[i].sum())
+            out[f"{name}/ber"] = float(errors[i].sum() / n_valid) if n_valid > 0 else 0.0
+            out[f"{name}/miou"] = float(batch_miou[i])
+        with np.errstate(invalid="ignore", divide="ignore"):
+            ber = np.where(valid > 0, errors / np.where(valid > 0, valid, 1), np.nan)
+        out["per_clip"] = {"effects": [n for n, _ in plan], "errors": errors, "valid": valid, "ber": ber, "miou": miou, "sisnr": sisnr}
+        return out
