@@ -242,14 +242,19 @@ int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* 
  *                     (mean probabilities only) conv_post and the head as well, otherwise those two by the exact path's f32 kernels.
  *                     Same arguments and workspace as wv_detector_forward; WV_ESTATE for a model without an f16 plan.
  *   wv_locator_forward_f16    Locator.forward (model/locator.py:268-299) in this mode: the encoder stages on the f16 pipe (32- and
- *                     64-channel ResnetBlocks, composed downsample convs; its SpecBlocks, whose n_fft != C, by the exact path's STFT
- *                     kernel + the 1x1 on the f16 pipe), spec_post / conv_post / head by the exact f32 kernels.  Arguments of wv_locator_forward.
+ *                     64-channel ResnetBlocks, composed downsample convs).  Its SpecBlocks (n_fft = 2 C at every scale) and spec_post
+ *                     (256 points, hop 32, 128 channels) each run as ONE fused launch on the f16 pipe: the STFT as a split-f16
+ *                     matrix product, NOT the exact path's f32 STFT kernel, with the basis rows sin_0 and sin_{F-1} applied in f32
+ *                     beside it; a scale the fused kernel does not serve falls back to the exact STFT kernel + the 1x1 on the f16
+ *                     pipe.  conv_post and the head run on the exact f32 kernels (the locator always returns logits).  Arguments of
+ *                     wv_locator_forward.
  *   wv_generator_forward_f16  Generator.forward (model/generator.py:360-423; modules/seanet.py:883-976, 1067-1226) in this mode: the
  *                     encoder as above with FiLM in the downsample convs' epilogues, conv_post as one composed conv, L2Norm, then
  *                     the decoder: first conv pair as one composed conv, every upsample unit (ELU -> depth-wise ConvTranspose1d ->
  *                     1x1, seanet.py:1147-1170) as ONE two-tap conv over (phase, channel) rows, ResnetBlocks of 768 / 384 / 192 / 96
  *                     channels in one launch each, the tail (f32 sums, tanh, + x) on the c8 stream.  Message MLP / FiLM scalars in f32.
- *                     Arguments and workspace of wv_generator_forward; WV_ESTATE for a model without an f16 plan.
+ *                     Arguments and workspace of wv_generator_forward; WV_ESTATE for a model without an f16 plan; B <= 65535 (the tail's
+ *                     launch grid, wv_h16_tail's limit too).
  *   wv_h16_upsample   the decoder's upsample unit as that conv: x16 = the PRE-ACTIVATED input c8 [B, K/8, Tin, 8]; w_ct [K,1,2r], w_pw
  *                     [M,K,1], bias [M] HOST; Y16 / Yact16 c8 [B, M/8, Tin*r, 8] (either may be NULL)
  *   wv_h16_tail       decoder tail on the pre-activated c8 stream: out[B,1,T] = tanh(out_scale * (b + Conv1d(C -> 1, ks)(a16))) (+ x)
@@ -301,6 +306,19 @@ int wv_stft_plan_logmag(const wv_stft_plan* p, const float* wav, float* P, int B
 size_t wv_stft_plan_backward_workspace_bytes(const wv_stft_plan* p, int B, int T, int hop);
 int wv_stft_plan_backward(const wv_stft_plan* p, const float* wav, const float* dP, float* dwav, int accumulate, int B, int T, int hop, float std,
                           void* workspace, size_t workspace_bytes, void* stream);
+/* gradient of <dP, P(wav)> towards the BASIS itself (training a generator whose `spec.weight` tensors are nn.Parameters: SEANetEncoder(spec_learnable=True),
+ * modules/seanet.py:721,787, modules/conv.py:1023-1024): with C = Basis @ frames(wav), p = re^2 + im^2 and
+ * dC = dP * {re, im} / (std * p) where p > 1e-10 (else 0, the same clamp rule as above),
+ *     dBasis[m][n] = sum over clips b and frames t of dC[b][m][t] * frames[b][n][t]      ([2F, n_fft] device, overwritten)
+ * for all 2F rows (cos_0 .. cos_{F-1}, sin_0 .. sin_{F-1}).  Independent of wv_stft_plan_backward; the sum runs on the training step's
+ * time-contracting GEMM with a split plan that depends on the shapes only, so the result repeats bit for bit. */
+size_t wv_stft_plan_basis_grad_workspace_bytes(const wv_stft_plan* p, int B, int T, int hop);
+int wv_stft_plan_basis_grad(const wv_stft_plan* p, const float* wav, const float* dP, float* dBasis, int B, int T, int hop, float std,
+                            void* workspace, size_t workspace_bytes, void* stream);
+/* Replace the plan's basis by a DEVICE-resident one ([2F, n_fft], e.g. the parameter an optimizer has just stepped) without a host round
+ * trip: every pack of the plan is rewritten by one kernel on `stream`.  The plan then computes exactly what a plan created from the same
+ * values would. */
+int wv_stft_plan_set_basis_device(wv_stft_plan* p, const float* dev_basis, void* stream);
 /* Multi-scale STFT and mel-spectrogram reconstruction losses with their gradient towards wm (waveverify_amd/spectral_loss.py holds
  * the semantics).  A plan holds n_scales <= 16 scales; scale i has window length window_lengths[i] (a multiple of 4, >= 8), hop w/4,
  * F = w/2 + 1 bins, and flags[i]: bit 0 = an STFT-magnitude term, bit 1 = a mel term with n_mels[i] bands.  params[8 i .. 8 i + 7] =

@@ -93,6 +93,9 @@ SIGNATURES = {
     "wv_stft_plan_logmag": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
     "wv_stft_plan_backward_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
     "wv_stft_plan_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_stft_plan_basis_grad_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
+    "wv_stft_plan_basis_grad": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_stft_plan_set_basis_device": (C.c_int, [_VP, _VP, _VP]),
     "wv_specloss_plan_create": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
     "wv_specloss_plan_destroy": (None, [_VP]),
     "wv_specloss_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),

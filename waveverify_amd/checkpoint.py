@@ -236,14 +236,16 @@ _FIXED = {"activation": "ELU", "activation_kwargs": {"alpha": 1.0}, "norm": "wei
           "causal": True, "inout_norm": True, "channels_audio": 1}
 
 
-def argbind_config(cfgs: Mapping[str, NetConfig]) -> Dict[str, object]:
+def argbind_config(cfgs: Mapping[str, NetConfig], spec_learnable: bool = False) -> Dict[str, object]:
     """The flat 'Class.argument' dict the reference saves next to the weights (scripts/train.py:1652).  The reference's loader uses a
     present `config` INSTEAD of conf/base.yml and builds Generator / Detector / Locator under argbind.scope(config)
     (waveverify/core.py:226-236,272-276), so every constructor argument we leave out takes the CLASS default (zero_init=True,
     channels_enc=64, ...): the whole architecture is written, argument by argument (model/generator.py:63-104, detector.py:82-114,
     locator.py:84-115) -- the widths, strides, kernel sizes, residual scales, zero_init (which decides whether res_scale_param /
     scale_param exist at all), the heads' sizes, and the fixed options this library supports (apply_argbind_config's whitelist).
-    tests/golden/state_dict_keys.json pins that the reference's constructors, given this dict, produce exactly our key set and shapes."""
+    tests/golden/state_dict_keys.json pins that the reference's constructors, given this dict, produce exactly our key set and shapes.
+    spec_learnable: what `Generator.spec_learnable` says -- True for a trainer that trains the generator's STFT bases, so that a
+    reference fine-tune from the file keeps them nn.Parameters (modules/conv.py:1023-1024); the key set and shapes are the same either way."""
     flat: Dict[str, object] = {}
     for kind, cfg in cfgs.items():
         c = _CLASS[kind]
@@ -256,7 +258,7 @@ def argbind_config(cfgs: Mapping[str, NetConfig]) -> Dict[str, object]:
             args.update(msg_dimension=int(cfg.msg_dimension), channels_dec=int(cfg.channels_dec), n_residual_dec=int(cfg.n_residual_dec),
                         res_scale_dec=float(cfg.res_scale_dec), nbits=int(cfg.nbits), embedding_dim=int(cfg.embedding_dim),
                         embedding_layers=int(cfg.embedding_layers), freq_bands=int(cfg.freq_bands), final_activation="Tanh", spec_layer="1x1_zero",
-                        spec_learnable=False)
+                        spec_learnable=bool(spec_learnable))
         else:
             args.update(output_dim=int(cfg.output_dim))
             if kind == "detector":

@@ -378,6 +378,12 @@ struct FilmArgs {
 };
 hipError_t launch_film(const FilmArgs& a, hipStream_t s);
 
+// ---- the training step's time-contracting GEMM (wv_train.hip: gemm_nt_kernel + the fixed-order sum of its splits) ----
+// out[M][K] = sum_{b,t} A[b][m][t] * X[b][k][t], both operands [B][rows][T] with T contiguous; the split count is a function of the
+// shapes only, so the result repeats bit for bit.  parts: gemm_nt_sum_workspace_bytes(B, T, M, K) bytes of scratch.
+size_t gemm_nt_sum_workspace_bytes(int B, int T, int M, int K);
+hipError_t launch_gemm_nt_sum(hipStream_t s, const float* A, const float* X, float* out, float* parts, int B, int M, int K, int T);
+
 // ---- optional per-launch profiling with HIP events on the launch stream ---------------------
 // When enabled every launcher brackets its kernel with an event pair; entries aggregate by
 // "<kernel symbol>|<role>".  Roles are set by the model plan (e.g. "enc.down_film").

@@ -364,7 +364,42 @@ __global__ __launch_bounds__(256) void stft_overlap_add_kernel(const float* __re
     for (int t = t_lo; t <= t_hi; ++t) a += Q[((size_t)b * n_fft + (base - t * hop)) * Tf + t];
     dwav[(size_t)b * T + sidx] = accumulate ? dwav[(size_t)b * T + sidx] + a : a;
 }
+// Every pack of a plan from a device-resident basis [2F][n_fft] (a trained `spec.weight` in the optimizer's arena): one thread per basis
+// element copies it to its place in wt_fwd / wt_bwd (wv_stft_plan_create) and in basis_t + basis_q or side (pack_stft_basis,
+// pack_stft_q).  Pure copies, so the packs equal the host-made ones bit for bit; the packs' zero padding is never touched.
+__global__ __launch_bounds__(256) void stft_repack_kernel(const float* __restrict__ basis, float* __restrict__ bt, float* __restrict__ bq,
+                                                          float* __restrict__ side, float* __restrict__ wf, float* __restrict__ wb,
+                                                          int n_fft, int Mp, int Mp_f, int Mp_b) {
+    const int n = blockIdx.x * 256 + threadIdx.x, m = blockIdx.y;          // m < 2F
+    if (n >= n_fft) return;
+    const int F = n_fft / 2 + 1;
+    const float v = basis[(size_t)m * n_fft + n];
+    wf[(size_t)n * Mp_f + m] = v;
+    wb[(size_t)m * Mp_b + n] = v;
+    if (m == F) { side[n] = v; return; }                                 // sin_0
+    if (m == 2 * F - 1) { side[(size_t)n_fft + n] = v; return; }         // sin_{F-1}
+    // matrix part: column 0 = cos_0, 1 = cos_{F-1}, 2f / 2f+1 = cos_f / sin_f
+    const int col = m == 0 ? 0 : (m == F - 1 ? 1 : (m < F ? 2 * m : 2 * (m - F) + 1));
+    bt[(size_t)n * Mp + col] = v;
+    bq[((size_t)(n >> 2) * Mp + col) * 4 + (n & 3)] = v;
+}
 size_t al256o(size_t x) { return (x + 255) & ~(size_t)255; }
+// one GEMM of the plan on the generic core: Y[b][M][Tf] = W[M][K] @ Xin[b][K][Tf], wt = W's K-major pack
+hipError_t stft_plan_gemm(const float* Xin, int M, int K, const float* wt, float* Y, int B, int Tf, hipStream_t s) {
+    wv::DwPwArgs a{};
+    a.X = Xin; a.pw.M = M; a.pw.K = K; a.pw.Mp = wv::round_up(M, wv::M_ALIGN); a.pw.Kp = wv::round_up(K, wv::BK); a.pw.wt = wt; a.pw.wq = nullptr;
+    a.bias = nullptr; a.Y = Y; a.B = B; a.Tin = Tf; a.Tout = Tf; a.mode = 0; a.ks = 1; a.pre_scale = 1.f; a.pre_elu = 0; a.l2norm = 0; a.out_scale = 1.f;
+    return wv::launch_dw_pw(a, s);
+}
+// the part both gradients of a plan share: X = frames(wav) [B][n_fft][Tf], Cm = Basis @ X, then Cm <- dC in place
+hipError_t stft_plan_frames_dc(const wv_stft_plan* p, const float* wav, const float* dP, float* X, float* Cm, int B, int T, int hop, float std, hipStream_t s) {
+    const int n = p->n_fft, F = n / 2 + 1, Tf = (T + hop - 1) / hop;
+    hipLaunchKernelGGL(stft_frames_kernel, dim3((Tf + 255) / 256, n, B), dim3(256), 0, s, wav, X, T, Tf, n, hop);
+    const hipError_t e = stft_plan_gemm(X, 2 * F, n, p->wt_fwd, Cm, B, Tf, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(stft_dc_kernel, dim3((Tf + 255) / 256, F, B), dim3(256), 0, s, Cm, dP, F, Tf, 1.f / std);
+    return hipGetLastError();
+}
 }  // namespace
 
 extern "C" {
@@ -420,19 +455,39 @@ int wv_stft_plan_backward(const wv_stft_plan* p, const float* wav, const float* 
     const int n = p->n_fft, F = n / 2 + 1, Tf = (T + hop - 1) / hop;
     float* X = (float*)ws;
     float* Cm = (float*)((char*)ws + al256o((size_t)B * n * Tf * 4));
-    hipLaunchKernelGGL(stft_frames_kernel, dim3((Tf + 255) / 256, n, B), dim3(256), 0, s, wav, X, T, Tf, n, hop);
-    auto gemm = [&](const float* Xin, int M, int K, const float* wt, float* Y) {
-        wv::DwPwArgs a{};
-        a.X = Xin; a.pw.M = M; a.pw.K = K; a.pw.Mp = wv::round_up(M, wv::M_ALIGN); a.pw.Kp = wv::round_up(K, wv::BK); a.pw.wt = wt; a.pw.wq = nullptr;
-        a.bias = nullptr; a.Y = Y; a.B = B; a.Tin = Tf; a.Tout = Tf; a.mode = 0; a.ks = 1; a.pre_scale = 1.f; a.pre_elu = 0; a.l2norm = 0; a.out_scale = 1.f;
-        return wv::launch_dw_pw(a, s);
-    };
-    hipError_t e = gemm(X, 2 * F, n, p->wt_fwd, Cm);
-    if (e != hipSuccess) return WV_EHIP;
-    hipLaunchKernelGGL(stft_dc_kernel, dim3((Tf + 255) / 256, F, B), dim3(256), 0, s, Cm, dP, F, Tf, 1.f / std);
-    e = gemm(Cm, n, 2 * F, p->wt_bwd, X);                          // Q into the frames buffer
-    if (e != hipSuccess) return WV_EHIP;
+    if (stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s) != hipSuccess) return WV_EHIP;
+    if (stft_plan_gemm(Cm, n, 2 * F, p->wt_bwd, X, B, Tf, s) != hipSuccess) return WV_EHIP;      // Q into the frames buffer
     hipLaunchKernelGGL(stft_overlap_add_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, X, dwav, T, Tf, n, hop, accumulate);
+    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+}
+
+// dBasis[m][n] = sum_{b,t} dC[b][m][t] * frames[b][n][t]: frames, the forward GEMM and dC exactly as wv_stft_plan_backward forms them,
+// then the training step's time-contracting dW GEMM (wv_train.hip) -- every one of the 2F rows, sin_0 and sin_{F-1} included
+size_t wv_stft_plan_basis_grad_workspace_bytes(const wv_stft_plan* p, int B, int T, int hop) {
+    if (!p || B < 1 || T < 1 || hop < 1) return 0;
+    const int Tf = (T + hop - 1) / hop, F = p->n_fft / 2 + 1;
+    return wv_stft_plan_backward_workspace_bytes(p, B, T, hop) + wv::gemm_nt_sum_workspace_bytes(B, Tf, 2 * F, p->n_fft);
+}
+
+int wv_stft_plan_basis_grad(const wv_stft_plan* p, const float* wav, const float* dP, float* dBasis, int B, int T, int hop, float std,
+                            void* ws, size_t ws_bytes, void* stream) {
+    if (!p || !wav || !dP || !dBasis || B < 1 || T < 1 || hop < 1 || !(std > 0.f) || B > 65535 || p->n_fft > 65535) return WV_EINVAL;
+    if (!ws || ws_bytes < wv_stft_plan_basis_grad_workspace_bytes(p, B, T, hop)) return WV_ENOMEM;
+    hipStream_t s = (hipStream_t)stream;
+    const int n = p->n_fft, F = n / 2 + 1, Tf = (T + hop - 1) / hop;
+    float* X = (float*)ws;
+    float* Cm = (float*)((char*)ws + al256o((size_t)B * n * Tf * 4));
+    float* parts = (float*)((char*)ws + wv_stft_plan_backward_workspace_bytes(p, B, T, hop));
+    if (stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s) != hipSuccess) return WV_EHIP;
+    const hipError_t e = wv::launch_gemm_nt_sum(s, Cm, X, dBasis, parts, B, 2 * F, n, Tf);
+    return e == hipSuccess ? WV_OK : (e == hipErrorInvalidValue ? WV_EINVAL : WV_EHIP);
+}
+
+int wv_stft_plan_set_basis_device(wv_stft_plan* p, const float* dev_basis, void* stream) {
+    if (!p || !dev_basis || p->n_fft > 65535) return WV_EINVAL;
+    const int n = p->n_fft, M2 = n + 2;
+    hipLaunchKernelGGL(stft_repack_kernel, dim3((n + 255) / 256, M2), dim3(256), 0, (hipStream_t)stream, dev_basis, p->basis_t, p->basis_q, p->side,
+                       p->wt_fwd, p->wt_bwd, n, p->Mp, wv::round_up(M2, wv::M_ALIGN), wv::round_up(n, wv::M_ALIGN));
     return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
 }
 

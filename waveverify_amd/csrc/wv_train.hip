@@ -2127,3 +2127,20 @@ int wv_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float
 }
 
 }  // extern "C"
+
+// The dW product for callers outside this file (the STFT plan's basis gradient, wv_ops.hip): the same kernel, split plan and
+// fixed-order finish as every dW above.
+namespace wv {
+size_t gemm_nt_sum_workspace_bytes(int B, int T, int M, int K) {
+    if (B < 1 || T < 1 || M < 1 || K < 1) return 0;
+    return al256((size_t)nt_plan(B, T, M, K).S * M * K * 4);
+}
+hipError_t launch_gemm_nt_sum(hipStream_t s, const float* A, const float* X, float* out, float* parts, int B, int M, int K, int T) {
+    if (!A || !X || !out || !parts || B < 1 || T < 1 || M < 1 || K < 1) return hipErrorInvalidValue;
+    const NtPlan np_ = nt_plan(B, T, M, K);
+    const hipError_t e = launch_gemm_nt(s, A, X, parts, 1.f, 0, B, M, K, T, np_.S, np_.TC);
+    if (e != hipSuccess) return e;
+    launch_sum_parts(s, parts, out, np_.S, (size_t)M * K);
+    return hipGetLastError();
+}
+}  // namespace wv

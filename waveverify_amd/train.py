@@ -211,6 +211,24 @@ class StftFeatures(_Handle):
                                            ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
             raise RuntimeError("wv_stft_plan_backward failed")
 
+    def basis_grad(self, wav: torch.Tensor, dP: torch.Tensor, dbasis: torch.Tensor) -> None:
+        """dbasis ([2F, 1, n_fft] or [2F, n_fft], overwritten) = the gradient of <dP, features(wav)> towards the basis, all 2F rows."""
+        wav, dP = _f(wav), _f(dP)
+        B, T = wav.shape[0], wav.shape[-1]
+        if dbasis.dtype != torch.float32 or not dbasis.is_contiguous() or dbasis.numel() != (self.n_fft + 2) * self.n_fft or dbasis.device != wav.device:
+            raise ValueError(f"basis gradient for n_fft={self.n_fft}: need a contiguous float32 tensor of {(self.n_fft + 2) * self.n_fft} elements on {wav.device}")
+        ws = _lib.scratch(int(self._lib.wv_stft_plan_basis_grad_workspace_bytes(self._h, B, T, self.hop)), wav.device)
+        if self._lib.wv_stft_plan_basis_grad(self._h, wav.data_ptr(), dP.data_ptr(), dbasis.data_ptr(), B, T, self.hop, self.std,
+                                             ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
+            raise RuntimeError("wv_stft_plan_basis_grad failed")
+
+    def set_basis_device(self, basis: torch.Tensor) -> None:
+        """Run on `basis` from now on: a CUDA float32 tensor of (n_fft + 2) * n_fft values (e.g. the arena view an optimizer stepped)."""
+        if not basis.is_cuda or basis.dtype != torch.float32 or not basis.is_contiguous() or basis.numel() != (self.n_fft + 2) * self.n_fft:
+            raise ValueError(f"spec.weight for n_fft={self.n_fft}: need a contiguous float32 CUDA tensor of {(self.n_fft + 2) * self.n_fft} values")
+        if self._lib.wv_stft_plan_set_basis_device(self._h, basis.data_ptr(), TrainHalf._stream()) != 0:
+            raise RuntimeError("wv_stft_plan_set_basis_device failed")
+
 
 class TrainConvPre(_Handle):
     """conv_pre with live weight norm (/root/reference/modules/seanet.py:657-664): Scale(1/wav_std) -> causal SConv1d(1, C, ks).
@@ -706,10 +724,10 @@ class _NetTrainer:
     """Shared part of the net-level training steps: the flat parameter / gradient arenas keyed by the reference's PARAMETRIZED
     state-dict names, and SEANetEncoder.forward / backward on the training units (/root/reference/modules/seanet.py:883-976)."""
 
-    def _build(self, cfg, state_dict, with_msg: bool, lr: float, max_norm: float, device):
+    def _build(self, cfg, state_dict, with_msg: bool, lr: float, max_norm: float, device, spec_learnable: bool = False):
         if cfg.dilation_base != 1:
             raise NotImplementedError("training units: dilation_base = 1 only")
-        self.cfg, self.max_norm, self.with_msg = cfg, float(max_norm), with_msg
+        self.cfg, self.max_norm, self.with_msg, self.spec_learnable = cfg, float(max_norm), with_msg, bool(spec_learnable)
         skip = () if with_msg else ("encoder.msg_embedding.", "encoder.film_layers.")
         items = [(k, np.asarray(v, dtype=np.float32)) for k, v in state_dict.items()
                  if not (skip and k.startswith(skip)) and not k.endswith("spec.weight")]
@@ -718,7 +736,7 @@ class _NetTrainer:
         self.frozen = {k: torch.from_numpy(np.array(v, dtype=np.float32)) for k, v in state_dict.items() if skip and k.startswith(skip)}
         # the DFT bases the state dict came with (`...spec.weight`: a buffer, or a learned parameter of a reference run with
         # spec_learnable: true, modules/conv.py:1023): the training forward uses THEM (as the inference nets do through
-        # wv_model_set_stft_basis) and state_dict() writes them back unchanged; they are not trained here (no gradient towards the basis)
+        # wv_model_set_stft_basis) and state_dict() writes them back -- unchanged, unless this trainer has spec_learnable (below)
         self.spec_basis = {k: torch.from_numpy(np.array(v, dtype=np.float32)) for k, v in state_dict.items() if k.endswith("spec.weight")}
         # a state dict without them (fresh nets): the reference's own buffers (checkpoint.stft_basis, bit-equal to its CausalSTFT.weight:
         # tests/golden/dft_basis.npz), so that what the forward used is exactly what state_dict() writes and a resumed run repeats it
@@ -726,6 +744,12 @@ class _NetTrainer:
         for s_ in range(len(cfg.ratios_enc) + 1):
             key = ("encoder.spec_post" if s_ == len(cfg.ratios_enc) else f"encoder.spec_blocks.{s_}") + ".spec.weight"
             self.spec_basis.setdefault(key, _basis((2 ** s_) * cfg.n_fft_base))
+        if self.spec_learnable:
+            # SEANetEncoder(spec_learnable=True): the bases are nn.Parameters like any other (one AdamW over generator.parameters(),
+            # one clip_grad_norm_), so they join the arenas under their own keys, in scale order
+            self.spec_keys = [("encoder.spec_post" if s_ == len(cfg.ratios_enc) else f"encoder.spec_blocks.{s_}") + ".spec.weight"
+                              for s_ in range(len(cfg.ratios_enc) + 1)]
+            items += [(k, self.spec_basis[k].numpy().reshape(-1, 1, self.spec_basis[k].shape[-1])) for k in self.spec_keys]
         # the message MLP + FiLM parameters sit together, in the order the FiLM kernels read them: their packed block and its gradient
         # are then plain slices of the arenas (no gather before the forward, no scatter after the backward)
         self.film = FilmMlp(cfg) if with_msg else None
@@ -888,7 +912,7 @@ class _NetTrainer:
         for s in range(len(self.cfg.ratios_enc) + 1):
             pre = "encoder.spec_post" if s == len(self.cfg.ratios_enc) else f"encoder.spec_blocks.{s}"
             n_fft = (2 ** s) * self.cfg.n_fft_base
-            kept = self.spec_basis.get(pre + ".spec.weight")
+            kept = self.params[pre + ".spec.weight"].detach().cpu() if self.spec_learnable else self.spec_basis.get(pre + ".spec.weight")
             out[pre + ".spec.weight"] = kept.reshape(n_fft + 2, 1, n_fft).clone() if kept is not None else stft_basis(n_fft)
         return out
 
@@ -958,7 +982,9 @@ class _NetTrainer:
             into = dict(dg=self.gviews[b + "original0"], dv=self.gviews[b + "original1"])
             if scp is not None:
                 into["d_scale_param"] = self.gviews[pre + ".scale_param"]
-            gs = unit.backward(P, sp, scp, rs, dy, need_dx, into)
+            gs = unit.backward(P, sp, scp, rs, dy, need_dx or self.spec_learnable, into)
+            if self.spec_learnable:
+                stft.basis_grad(sv["x"], gs["dP"], self.gviews[pre + ".spec.weight"])
             if need_dx:
                 stft.backward(sv["x"], gs["dP"], dx_spec, True)
         spec_back(self.spec_post, self.stft_post, "encoder.spec_post", sv["P_post"], dh)
@@ -986,9 +1012,19 @@ class _NetTrainer:
         self._done("encoder.conv_pre.")
         return gp["dx"] + dx_spec if need_dx else None
 
+    def refresh_spec_plans(self) -> None:
+        """After an optimizer step with spec_learnable: every scale's STFT plan re-packed from the stepped basis in the arena."""
+        if not self.spec_learnable:
+            return
+        for s, sc in enumerate(self.scales):
+            sc["stft"].set_basis_device(self.params[f"encoder.spec_blocks.{s}.spec.weight"])
+        self.stft_post.set_basis_device(self.params["encoder.spec_post.spec.weight"])
+
     def _optimizer_step(self):
         self.finish_reduce()
-        return self.opt.step(self.arena, self.grads, self.max_norm)
+        norm = self.opt.step(self.arena, self.grads, self.max_norm)
+        self.refresh_spec_plans()
+        return norm
 
 
 class EncoderNetTrainer(_NetTrainer):
@@ -1000,9 +1036,12 @@ class EncoderNetTrainer(_NetTrainer):
     untouched in the reference (grad None).  One process per GPU: `step` all-reduces the gradient arena over RCCL.
     Clip lengths must keep every ResnetBlock stage a multiple of 4 samples (T = 16000 does for both nets)."""
 
-    def __init__(self, cfg, state_dict, lr: float = 1e-4, max_norm: float = 1000.0, device="cuda"):
+    def __init__(self, cfg, state_dict, lr: float = 1e-4, max_norm: float = 1000.0, device="cuda", spec_learnable: bool = False):
         if cfg.kind not in ("detector", "locator"):
             raise ValueError("EncoderNetTrainer: detector or locator")
+        if spec_learnable:
+            raise ValueError(f"spec_learnable: the reference's {cfg.kind.capitalize()}.__init__ has no such argument (its STFT bases are buffers); "
+                             "only Generator.__init__ takes spec_learnable (model/generator.py:95)")
         self._build(cfg, state_dict, False, lr, max_norm, device)
         self.nb = cfg.nbits if cfg.kind == "detector" else 1
         self.head = TrainHead(cfg.dimension, cfg.output_dim, self.nb, cfg.hop_length)
@@ -1044,11 +1083,17 @@ class GeneratorTrainer(_NetTrainer):
     the watermarked audio; `backward(d_wm)` takes the gradient of ANY loss on it (the reference's waveform / spectral / adversarial
     losses stay on PyTorch-ROCm) and fills `self.grads`; `apply_gradients()` all-reduces and steps AdamW."""
 
-    def __init__(self, cfg, state_dict, lr: float = 1e-4, max_norm: float = 1000.0, device="cuda"):
+    def __init__(self, cfg, state_dict, lr: float = 1e-4, max_norm: float = 1000.0, device="cuda", spec_learnable: bool = False):
+        """spec_learnable: train the five STFT bases (`encoder.spec_blocks.{s}.spec.weight`, `encoder.spec_post.spec.weight`) as the
+        reference's SEANetEncoder(spec_learnable=True) does (modules/seanet.py:721,787 -> CausalSTFT(learnable=True), conv.py:1023-1024:
+        nn.Parameters under the generator's one AdamW and clip_grad_norm_.  Generator.__init__ takes the argument, model/generator.py:95,
+        and conf/base.yml sets it, but does not hand it to the encoder, :177-209 -- the reference as shipped keeps buffers): they
+        live in the arenas like every other parameter (same AdamW, inside clip_grad_norm_), backward fills their gradient
+        (StftFeatures.basis_grad) and every optimizer step re-packs the plans from the arena.  Off (the default): buffers, as before."""
         from .params import decoder_layout
         if cfg.kind != "generator":
             raise ValueError("GeneratorTrainer: generator")
-        self._build(cfg, state_dict, True, lr, max_norm, device)
+        self._build(cfg, state_dict, True, lr, max_norm, device, spec_learnable)
         self.i_pw0, self.i_dw0, self.ups, self.i_last = decoder_layout(cfg)
         Ctop = (2 ** len(cfg.strides)) * cfg.channels_dec
         self.dec_in = TrainUnit(cfg.dimension, Ctop, cfg.kernel_size, 1)
@@ -1159,8 +1204,10 @@ class WatermarkTrainer:
 
     def __init__(self, cfgG, sdG, cfgD, sdD, cfgL, sdL, lr: float = 1e-4, max_norm: float = 1000.0, sample_rate: int = 16000,
                  window_duration: float = 0.1, device="cuda", effect_scheduler=None, apply_effect=None, effect_backward=None,
-                 spectral_losses: bool = False):
-        """spectral_losses: also minimise the reference's multi-scale STFT and mel reconstruction losses of wm against x
+                 spectral_losses: bool = False, spec_learnable: bool = False):
+        """spec_learnable: the generator's STFT bases are trained parameters (GeneratorTrainer(spec_learnable=True); the reference's
+        Generator.spec_learnable argument, conf/base.yml:37, had it reached its encoder); the detector's and the locator's stay buffers, as in the reference.
+        spectral_losses: also minimise the reference's multi-scale STFT and mel reconstruction losses of wm against x
         (waveverify_amd.spectral_loss, conf/base.yml configuration) with weights 10 and 20 (`lambdas["stft/loss"]`, `lambdas["mel/loss"]`):
         their gradient joins d_wm before the generator's backward and both terms are in step()'s dict and its total.
         effect_scheduler: a waveverify_amd.effect_scheduler.EffectScheduler (watermarking.py:266-271); every step then selects
@@ -1175,7 +1222,7 @@ class WatermarkTrainer:
         sample_suppression, echo, smooth, amplitude_scaling) get both hooks from one `effects.EffectTape` (`tape.apply`, `tape.backward`)."""
         from .augment import TemporalAugmenter
         from .metrics import BER, MIOU
-        self.G = GeneratorTrainer(cfgG, sdG, lr, max_norm, device)
+        self.G = GeneratorTrainer(cfgG, sdG, lr, max_norm, device, spec_learnable)
         self.D = EncoderNetTrainer(cfgD, sdD, lr, max_norm, device)
         self.L = EncoderNetTrainer(cfgL, sdL, lr, max_norm, device)
         self.aug = TemporalAugmenter(sample_rate, window_duration)
@@ -1207,7 +1254,7 @@ class WatermarkTrainer:
         opts = {k: n.optimizer_state() for k, n in (("generator", self.G), ("detector", self.D), ("locator", self.L))}
         cfgs = {"generator": self.G.cfg, "detector": self.D.cfg, "locator": self.L.cfg}
         return save_atomic_checkpoint(save_path, tag, self.state_dicts(parametrized), self.G.opt.t if step is None else step,
-                                      argbind_config(cfgs), {OPT_KEY: opts})
+                                      argbind_config(cfgs, spec_learnable=self.G.spec_learnable), {OPT_KEY: opts})
 
     @classmethod
     def from_checkpoint(cls, path, **kwargs) -> "WatermarkTrainer":
@@ -1313,6 +1360,7 @@ class WatermarkTrainer:
         for net in (self.G, self.D, self.L):
             net.finish_reduce()
         norm = self.G.opt.step(self.G.arena, self.G.grads, self.G.max_norm)          # clipping: the generator only
+        self.G.refresh_spec_plans()                                                 # spec_learnable: the plans follow the stepped bases
         self.D.opt.step(self.D.arena, self.D.grads, None)
         self.L.opt.step(self.L.arena, self.L.grads, None)
         total = lam["dec/loss"] * dec + lam["loc/loss"] * loc + lam["waveform/loss"] * wav
