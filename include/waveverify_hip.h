@@ -608,7 +608,8 @@ int wv_fx_fold_replicate(const float* dxp, float* dx, int rows, int T, int pad_l
 int wv_fx_resample_adjoint(const float* dy, const float* kernels, float* dx, int rows, int T, int orig, int new_, int L, int width, int Tout,
                            void* stream);
 /* polyphase sinc resampling by orig : nw (both already divided by their gcd), torchaudio's formulation: kernels [nw][L], L = 2*width + orig;
- * y[row][m] = sum_j kernels[m % nw][j] * xz[(m / nw)*orig + j - width] for m < Tout = ceil(nw * T / orig), xz zero outside [0,T). */
+ * y[row][m] = sum_j kernels[m % nw][j] * xz[(m / nw)*orig + j - width] for m < Tout = ceil(nw * T / orig), xz zero outside [0,T).
+ * Any 1 <= Tout <= (ceil(T / orig) + 1) * nw is served (the same formula, continued or cut short); a longer one is refused. */
 int wv_fx_resample(const float* x, const float* kernels, float* y, int rows, int T, int orig, int nw, int L, int width, int Tout, void* stream);
 
 /* ---- plain-arithmetic time-domain effects (csrc/wv_fx_time.hip) ----------------------------------------------------------------

@@ -116,3 +116,23 @@ def apply_seqmap(x, mode, a=0, b=0, c=0, perm=None):
     y[..., a:a + c] = x[..., b:b + c]
     y[..., b:b + c] = x[..., a:a + c]
     return y
+
+
+def backward_to_watermarked(d_out, plan, seg_len, mode, a=0, b=0, c=0, perm=None, T=None):
+    """Gradient of the augmented watermarked audio towards the watermarked input, from the FORWARD above (no inverse map is formed):
+    `apply_seqmap` on arange(T) gives the source src[t] of every output sample; d_wm[b, ch, src[t]] += d_out[b, ch, t] where the plan
+    kept that segment (code 0; plan None keeps all).  Every other sample is 0, the ones no output reads (a permutation's dropped tail)
+    included."""
+    d_out = np.asarray(d_out)
+    B, C, t_out = d_out.shape
+    T = t_out if T is None else T
+    src = apply_seqmap(np.arange(T), mode, a, b, c, perm)
+    assert src.shape == (t_out,)
+    d_wm = np.zeros((B, C, T), d_out.dtype)
+    for bi in range(B):
+        for ch in range(C):
+            for t in range(t_out):
+                s = int(src[t])
+                if plan is None or plan[bi][s // seg_len] == 0:
+                    d_wm[bi, ch, s] += d_out[bi, ch, t]
+    return d_wm

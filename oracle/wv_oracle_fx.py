@@ -80,3 +80,91 @@ def filter_gradient(name: str, x: np.ndarray, d: np.ndarray, cutoff: float, zero
     y = low if name == "lowpass_filter" else xt - low
     (y * torch.from_numpy(d.astype(np.float64))).sum().backward()
     return xt.grad.numpy()
+
+
+# ---- the published contract of csrc/wv_fx.hip, kernel by kernel ----------------------------------------------------------------------
+def _padded(x: np.ndarray, pad_l: int, pad_r: int, replicate) -> np.ndarray:
+    x = np.asarray(x, np.float64)
+    if replicate:
+        return np.concatenate([np.repeat(x[..., :1], pad_l, -1), x, np.repeat(x[..., -1:], pad_r, -1)], -1)
+    return np.concatenate([np.zeros(x.shape[:-1] + (pad_l,)), x, np.zeros(x.shape[:-1] + (pad_r,))], -1)
+
+
+def fir_bank(x: np.ndarray, taps: np.ndarray, stride: int = 1, pad_l: int = 0, pad_r: int = 0, replicate=0, interleave=0, dtype=np.float64) -> np.ndarray:
+    """include/waveverify_hip.h's formula for wv_fx_fir_bank, tap by tap in plain order:
+        y[row][f][n] = sum_j taps[f][j] * xpad[n * stride + j],   n < (T + pad_l + pad_r - L) // stride + 1
+    x [rows, T], taps [n_filters, L] -> [rows, n_filters, Tout], or [rows, Tout * n_filters] as y[row][n * n_filters + f] with
+    `interleave`.  `dtype` is the accumulator's (and the product's) type: float64 is the oracle, float32 the plain single-precision chain
+    that tests/test_oracle_fx_dense.py measures the GPU bar against."""
+    taps = np.asarray(taps)
+    nf, L = taps.shape
+    xp = _padded(x, pad_l, pad_r, replicate).astype(dtype)
+    tp = taps.astype(dtype)
+    n_out = (xp.shape[-1] - L) // stride + 1
+    if n_out < 1:
+        raise ValueError("the padded signal is shorter than the taps")
+    y = np.zeros((xp.shape[0], nf, n_out), dtype)
+    for j in range(L):
+        y += tp[None, :, j, None] * xp[:, None, j:j + (n_out - 1) * stride + 1:stride]
+    return np.ascontiguousarray(y.transpose(0, 2, 1)).reshape(xp.shape[0], n_out * nf) if interleave else y
+
+
+def resample_matrix(kernels: np.ndarray, T: int, orig: int, new: int, width: int, t_out: int) -> np.ndarray:
+    """The dense [t_out, T] float64 operator of wv_fx_resample for a GIVEN kernel table [new, L] (effects.resample_kernels' float32 output,
+    widened): A[m, s] = K[m % new][s - (m // new) * orig + width] where that index lies in [0, L), else 0.  `A @ x` is the forward,
+    `A.T @ d` the adjoint: the kernels' index arithmetic, apart from how the taps were made."""
+    K = np.asarray(kernels, np.float64)
+    L = K.shape[1]
+    A = np.zeros((t_out, T), np.float64)
+    for m in range(t_out):
+        n, f = divmod(m, new)
+        s0 = n * orig - width                                # the input sample under tap 0
+        lo, hi = max(0, s0), min(T, s0 + L)
+        if hi > lo:
+            A[m, lo:hi] = K[f, lo - s0:hi - s0]
+    return A
+
+
+def fold_replicate(dxp: np.ndarray, T: int, pad_l: int, pad_r: int) -> np.ndarray:
+    """Transpose of replicate padding: dxp [..., pad_l + T + pad_r] -> dx [..., T]; the pads' gradients go to the end samples they copy."""
+    dxp = np.asarray(dxp, np.float64)
+    assert dxp.shape[-1] == pad_l + T + pad_r
+    dx = dxp[..., pad_l:pad_l + T].copy()
+    dx[..., 0] += dxp[..., :pad_l].sum(-1)
+    dx[..., T - 1] += dxp[..., pad_l + T:].sum(-1)
+    return dx
+
+
+def resample_operator(T: int, orig_freq: int, new_freq: int) -> np.ndarray:
+    """`resample` above as a dense float64 matrix [t_out, T] (its own float64 taps)."""
+    return np.ascontiguousarray(resample(np.eye(T), orig_freq, new_freq).T)
+
+
+def effect_gradient(name: str, params: dict, d: np.ndarray, sample_rate: int = 16000, zeros: float = 8) -> np.ndarray:
+    """d/dx of <effect(x), d> for the band-pass filter and the resample round trip, by torch autograd (float64) through this file's
+    restatement -- `filter_gradient`'s sibling.  d [B, C, T].  Band-pass: lowpass(high) - lowpass(low) over one replicate padding of the
+    lower cutoff's half width, cutoffs clamped and divided by nyquist as the wrapper does.  Resample: to the new rate, back, then cropped
+    or zero-padded to T, exactly as effects.AudioEffects.resample / apply_effect do.  Both are linear, so x is arbitrary."""
+    import torch
+    import torch.nn.functional as F
+    dt = torch.from_numpy(np.asarray(d, np.float64))
+    B, C, T = dt.shape
+    xt = torch.zeros(B, C, T, dtype=torch.float64, requires_grad=True)
+    if name == "bandpass_filter":
+        nyquist = sample_rate / 2.0
+        lo = max(0.0, min(params["cutoff_freq_low"], nyquist - 1e-5)) / nyquist
+        hi = max(0.0, min(params["cutoff_freq_high"], nyquist - 1e-5)) / nyquist
+        half = int(zeros / lo / 2)
+        xp = F.pad(xt.reshape(B * C, 1, T), (half, half), mode="replicate")
+        low = [F.conv1d(xp, torch.from_numpy(lowpass_filter_taps(c, half)).view(1, 1, -1)).reshape(B, C, T) for c in (lo, hi)]
+        y = low[1] - low[0]
+    elif name == "resample":
+        new_sr = int(params["new_sample_rate"])
+        down = torch.from_numpy(resample_operator(T, sample_rate, new_sr))
+        up = torch.from_numpy(resample_operator(down.shape[0], new_sr, sample_rate))
+        y = xt @ down.T @ up.T
+        y = y[..., :T] if y.shape[-1] >= T else F.pad(y, (0, T - y.shape[-1]))
+    else:
+        raise ValueError(name)
+    (y * dt).sum().backward()
+    return xt.grad.numpy()

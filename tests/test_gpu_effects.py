@@ -88,8 +88,9 @@ def _dot(a, b):
 def test_effect_adjoints_are_the_transposed_operators(name, params, T):
     """The reference differentiates through its julius filters and torchaudio resampler (plain torch ops), so the generator's gradient is
     A^T d for the linear effect A.  <A x, d> == <x, A^T d> for random x, d pins apply_effect_backward to apply_effect on the device (the
-    replicate padding's transpose, the crop / zero pad of the resample round trip and the pass-through cases included), and the
-    float64 restatement's autograd gives the same gradient."""
+    replicate padding's transpose, the crop / zero pad of the resample round trip and the pass-through cases included).  For the low- and
+    high-pass filters the float64 restatement's autograd is compared sample by sample here as well; the band-pass and resample gradients
+    are held per sample in tests/test_gpu_fx_contract.py (test_bandpass_and_resample_gradients_per_sample)."""
     g = torch.Generator(device="cuda").manual_seed(T + len(name))
     x = torch.randn(2, 1, T, device="cuda", generator=g) * 0.1
     d = torch.randn(2, 1, T, device="cuda", generator=g)
