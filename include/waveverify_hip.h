@@ -22,7 +22,7 @@
  * Tensors are float32, contiguous, [B, C, T] with time innermost, in DEVICE memory unless the
  * parameter is documented as host memory.  The caller owns every buffer; the library owns only
  * the packed weights inside a wv_model.  Every function returns 0 on success or a negative
- * WV_E* code; wv_last_error() gives the message (thread-local).
+ * WV_E* code; after a non-zero return wv_last_error() gives the reason (thread-local).
  */
 #ifndef WAVEVERIFY_HIP_H
 #define WAVEVERIFY_HIP_H
@@ -79,12 +79,15 @@ typedef struct wv_config {
 
 typedef struct wv_model wv_model;
 
+/* The message of the calling thread's most recent FAILED call.  Like errno it is defined only after a non-zero return: a successful
+ * call neither clears nor touches it.  Every non-zero return of every function below stores its reason here. */
 const char* wv_last_error(void);
 const char* wv_version(void);
 
 /* Fill cfg with the reference defaults for `kind`. */
 int wv_config_default(int kind, wv_config* cfg);
 
+/* ==== csrc/wv_model.hip ================================================================== */
 /* ---- model lifetime --------------------------------------------------------------------- */
 int wv_model_create(const wv_config* cfg, wv_model** out);
 void wv_model_destroy(wv_model* m);
@@ -130,6 +133,30 @@ int wv_locator_forward(wv_model* m, const float* x, float* logits, int B, int T,
 int wv_encoder_forward(wv_model* m, const float* x, const float* msg, int msg_rows, float* latent,
                        int B, int T, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same three forwards in the f16-operand mode (described with the wv_h16_* units below). */
+int wv_detector_forward_f16(wv_model* m, const float* x, float* logits, float* mean_prob,
+                            int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+int wv_locator_forward_f16(wv_model* m, const float* x, float* logits, int B, int T,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int msg_rows,
+                             float* out, int add_input, int B, int T,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/* message MLP + all FiLM gammas/betas (seanet.py:831-846,905-912): msg [rows,msg_dim] ->
+ * film [B,n_scales,bands,2]; uses the model's parameters. */
+int wv_model_film(wv_model* m, const float* msg, int msg_rows, float* film, int B, void* stream);
+
+/* ---- measurement hook (bench.py's roofline figures) ---------------------------------------
+ * When enabled, every kernel launch is bracketed by a hipEvent pair on the launch stream and
+ * aggregated by "<kernel>|<role>" together with its ALGORITHMIC flops and bytes (the per-unit
+ * figures of DESIGN.md).  wv_profile_collect(-1, ...) synchronises, snapshots and returns the
+ * number of entries; wv_profile_collect(i, ...) reads entry i of that snapshot. */
+int wv_profile_enable(int on);
+int wv_profile_reset(void);
+int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launches,
+                       double* total_ms, double* flops, double* bytes);
+
+/* ==== csrc/wv_window.hip (the two windowed forwards: csrc/wv_model.hip) ===================== */
 /* ---- windowed long-form and live sessions (waveverify_amd/window.py, session.py) -----------
  * A clip or a stream runs as a batch of WINDOWS of L samples: a run of frames plus a left halo no shorter than the net's
  * receptive field (window.halo), window starts and keep edges on hop multiples counted from the clip's t = 0.  The window
@@ -158,6 +185,7 @@ int wv_window_reduce_mean(const float* psum, int n_rows, const int* ptr, const i
 int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen,
                        float* hist_out, int drop, int hv2, int S, void* stream);
 
+/* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------
  * Activations (X, resid, film, Y, wav, P, H, x, Z, logits, mean_prob) are DEVICE pointers.
  * Weights / biases (w_*, *_bias, bias, basis) are HOST pointers in the reference's own layouts;
@@ -221,6 +249,22 @@ int wv_op_stft_logmag(const float* wav, const float* host_basis, float* P, int B
 int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* w_pw, const float* x, float* Y, float* Yact, int B, int T,
                      int n_fft, int hop, int M, float mean, float std, float out_scale, float act_scale, void* stream);
 
+/* conv_pre: Y = Conv1d(1->C,k)(x * in_scale) + bias  (seanet.py:657-664). x [B,1,T], w [C,1,k]. */
+int wv_op_conv_pre(const float* x, const float* w, const float* bias, float* Y, int B, int C,
+                   int T, int ks, float in_scale, void* stream);
+
+/* decoder tail: out = tanh(out_scale*(Conv1d(C->1,k)(ELU(pre_scale*H)) + bias)) (+ x)
+ * (seanet.py:1177-1202, generator.py:410, watermarking.py:440). H [B,C,Tin>=T], w [1,C,k]. */
+int wv_op_tail(const float* H, const float* w, const float* bias, const float* x_or_null,
+               float* out, int B, int C, int Tin, int T, int ks, float pre_scale, float out_scale,
+               void* stream);
+
+/* detector / locator head: ConvTranspose1d(D->O,k=s=hop)+bias -> trim to T -> Conv1d(O->nb,1)+bias
+ * (detector.py:300-310). Z [B,D,Fr]; w_rev [D,O,hop]; w_last [nb,O]; either output may be NULL. */
+int wv_op_head(const float* Z, const float* w_rev, const float* b_rev,
+               const float* w_last, const float* b_last, float* logits, float* mean_prob,
+               int B, int D, int O, int nb, int hop, int Fr, int T, void* stream);
+
 /* ---- f16-operand / f32-accumulate mode (BASELINE.json configs[4] "MFMA linears fp16"; csrc/wv_h16.hip): a throughput mode of the
  * detector next to the exact-f32 path.  Activations are f16 in the "c8" layout [B][roundup(C,16)/8][T][8] (channel groups of eight,
  * time-major inside a group = the B operand of v_mfma_f32_32x32x16_f16 as it lies in memory); accumulation, stencils, ELU, bias and
@@ -276,13 +320,6 @@ int wv_h16_conv(const void* X16, const float* w_pw, const float* w_dw, const flo
                 int B, int K, int M, int Tin, int ks, int stride, int pad, float out_scale, float act_scale, void* stream);
 int wv_h16_spec_block(const float* wav, const float* basis_or_null, const float* w_pw, const void* x16, void* Y16, void* Yact16, int B, int T,
                       int n_fft, int hop, int M, float mean, float std, float out_scale, float act_scale, void* stream);
-int wv_detector_forward_f16(wv_model* m, const float* x, float* logits, float* mean_prob,
-                            int B, int T, void* workspace, size_t workspace_bytes, void* stream);
-int wv_locator_forward_f16(wv_model* m, const float* x, float* logits, int B, int T,
-                           void* workspace, size_t workspace_bytes, void* stream);
-int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int msg_rows,
-                             float* out, int add_input, int B, int T,
-                             void* workspace, size_t workspace_bytes, void* stream);
 int wv_h16_upsample(const void* X16, const float* w_ct, const float* w_pw, const float* bias, void* Y16, void* Yact16,
                     int B, int K, int M, int Tin, int ratio, float act_scale, void* stream);
 int wv_h16_tail(const void* A16, const float* w, const float* bias, const float* x, float* out, int B, int C, int Tin, int T, int ks,
@@ -292,8 +329,6 @@ int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_
                 const int* keep_lo, const int* keep_hi, float* psum, void* stream);
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
                      int B, int K, int M, int Tin, int ks, int stride, int pad, float act_scale, void* stream);
-
-/* conv_pre: Y = Conv1d(1->C,k)(x * in_scale) + bias  (seanet.py:657-664). x [B,1,T], w [C,1,k]. */
 
 /* The same op with the basis packed and uploaded ONCE (a training step computes these features for every scale at every step):
  * basis_or_null as in wv_op_stft_logmag (NULL = the reference's windowed DFT basis). */
@@ -319,6 +354,8 @@ int wv_stft_plan_basis_grad(const wv_stft_plan* p, const float* wav, const float
  * trip: every pack of the plan is rewritten by one kernel on `stream`.  The plan then computes exactly what a plan created from the same
  * values would. */
 int wv_stft_plan_set_basis_device(wv_stft_plan* p, const float* dev_basis, void* stream);
+
+/* ==== csrc/wv_specloss.hip ================================================================ */
 /* Multi-scale STFT and mel-spectrogram reconstruction losses with their gradient towards wm (waveverify_amd/spectral_loss.py holds
  * the semantics).  A plan holds n_scales <= 16 scales; scale i has window length window_lengths[i] (a multiple of 4, >= 8), hop w/4,
  * F = w/2 + 1 bins, and flags[i]: bit 0 = an STFT-magnitude term, bit 1 = a mel term with n_mels[i] bands.  params[8 i .. 8 i + 7] =
@@ -336,52 +373,19 @@ size_t wv_specloss_workspace_bytes(const wv_specloss_plan* p, int B, int T);
  * d(mel total)/dwm.  Deterministic (fixed-order sums, no atomics).  WV_EINVAL when T <= w/2 for some scale (reflect padding). */
 int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int B, int T, float* terms, float* totals, float* dwm,
                 float stft_grad_scale, float mel_grad_scale, void* workspace, size_t workspace_bytes, void* stream);
-int wv_op_conv_pre(const float* x, const float* w, const float* bias, float* Y, int B, int C,
-                   int T, int ks, float in_scale, void* stream);
 
-/* decoder tail: out = tanh(out_scale*(Conv1d(C->1,k)(ELU(pre_scale*H)) + bias)) (+ x)
- * (seanet.py:1177-1202, generator.py:410, watermarking.py:440). H [B,C,Tin>=T], w [1,C,k]. */
-int wv_op_tail(const float* H, const float* w, const float* bias, const float* x_or_null,
-               float* out, int B, int C, int Tin, int T, int ks, float pre_scale, float out_scale,
-               void* stream);
-
-/* detector / locator head: ConvTranspose1d(D->O,k=s=hop)+bias -> trim to T -> Conv1d(O->nb,1)+bias
- * (detector.py:300-310). Z [B,D,Fr]; w_rev [D,O,hop]; w_last [nb,O]; either output may be NULL. */
-int wv_op_head(const float* Z, const float* w_rev, const float* b_rev,
-               const float* w_last, const float* b_last, float* logits, float* mean_prob,
-               int B, int D, int O, int nb, int hop, int Fr, int T, void* stream);
-
-/* message MLP + all FiLM gammas/betas (seanet.py:831-846,905-912): msg [rows,msg_dim] ->
- * film [B,n_scales,bands,2]; uses the model's parameters. */
-int wv_model_film(wv_model* m, const float* msg, int msg_rows, float* film, int B, void* stream);
-
-/* ---- first training-step slice ------------------------------------------------------
- * Forward and backward of one SEANetResnetBlock half with LIVE weight normalisation
- * (modules/seanet.py:39-116 dws_conv_block; modules/conv.py:47-88 weight norm recomputed every step;
- *  scripts/train.py:1421-1480):
- *     y = DW5( (g_pw v_pw/||v_pw||) @ ELU(pre_scale * x) ; g_dw v_dw/||v_dw|| ) + bias
- * ALL pointers are DEVICE pointers (parameters live on the GPU while training): x, y, dy, dx [B,C,T];
- * g_pw [C], v_pw [C,C] (the 1x1), g_dw [C], v_dw [C,5] (the depth-wise conv), bias [C]; gradients have the
- * shapes of what they differentiate.  Any C and T: shapes off the LDS-DMA core's grid (C <= 32, T % 4 != 0) run on the round-1 core.
- * The weight-norm fold runs on the device in every call (wv_train_half_forward and _backward both fold). */
-typedef struct wv_train_unit wv_train_unit;
-typedef wv_train_unit wv_train_half;
-int wv_train_half_create(int C, wv_train_half** out);
-void wv_train_half_destroy(wv_train_half* h);
-size_t wv_train_half_workspace_bytes(const wv_train_half* h, int B, int T);   /* backward only */
-int wv_train_half_forward(wv_train_half* h, const float* x, const float* g_pw, const float* v_pw,
-                          const float* g_dw, const float* v_dw, const float* bias, float pre_scale,
-                          float* y, int B, int T, void* stream);
-int wv_train_half_backward(wv_train_half* h, const float* x, const float* g_pw, const float* v_pw,
-                           const float* g_dw, const float* v_dw, float pre_scale, const float* dy,
-                           float* dx, float* dg_pw, float* dv_pw, float* dg_dw, float* dv_dw, float* db,
-                           int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+/* ==== csrc/wv_train.hip: the training step =======================================================
+ * Forward and backward of the nets' fused units with LIVE weight normalisation (modules/conv.py:47-88: the norm is recomputed every
+ * step; scripts/train.py:1421-1480).  ALL pointers are DEVICE pointers (parameters live on the GPU while training); gradients have the
+ * shapes of what they differentiate.  The weight-norm fold runs on the device in every call (forward and backward both fold). */
 
 /* The general fused unit of the encoder/decoder trunk, forward and backward:
  *     y[B,M,Tout] = DW_{ks,stride}( (g_pw v_pw/||v_pw||) @ act(pre_scale * x[B,K,Tin]) ; g_dw v_dw/||v_dw|| ) + bias
  * act = ELU (pre_elu = 1) or identity; causal SConv1d geometry (conv.py:715-763): left pad ks - stride, Tout = ceil(Tin/stride).
- * K = M, ks = 5, stride = 1 is the ResnetBlock half above; M = 2K, ks = 2r, stride = r is the encoder's Downsample unit
- * (seanet.py:733-772).  v_pw [M,K], v_dw [M,ks]; ks <= 16.  dx may be NULL (first layer: no input gradient). */
+ * K = M = C, ks = 5, stride = 1, pre_elu = 1 is one half of a SEANetResnetBlock (modules/seanet.py:39-116 dws_conv_block); M = 2K,
+ * ks = 2r, stride = r is the encoder's Downsample unit (seanet.py:733-772).  v_pw [M,K], v_dw [M,ks]; ks <= 16.  dx may be NULL (first
+ * layer: no input gradient).  Any K, M and Tin: shapes off the LDS-DMA core's grid (C <= 32, T % 4 != 0) run on the round-1 core. */
+typedef struct wv_train_unit wv_train_unit;
 int wv_train_unit_create(int K, int M, int ks, int stride, wv_train_unit** out);
 void wv_train_unit_destroy(wv_train_unit* u);
 size_t wv_train_unit_workspace_bytes(const wv_train_unit* u, int B, int Tin);   /* backward only */
@@ -395,7 +399,7 @@ int wv_train_unit_backward(wv_train_unit* u, const float* x, const float* g_pw, 
  *     y = x + s * half2(half1(pre_scale * x)),   s = res_scale * res_scale_param[0]  (res_scale_param may be NULL: s = res_scale)
  * forward keeps the two intermediate activations and the two 1x1 outputs in `saved` (wv_train_block_saved_bytes: four activation-sized
  * tensors; the forward kernels store the 1x1 outputs themselves, backward then has no GEMM to recompute) for backward, which returns
- * dx, both halves' parameter gradients and d(res_scale_param).  Same shape limits as the half.
+ * dx, both halves' parameter gradients and d(res_scale_param).  Both halves are units with K = M = C, ks = 5, stride = 1.
  * CONTRACT: wv_train_block_backward reuses the weight folds (W, its packed copies, 1/||v||) that the forward left in the handle, so it
  * must follow the wv_train_block_forward that produced `saved` with the SAME parameter tensors, and nothing may change their values or
  * run another forward on this handle in between (optimizer steps come after backward).  Other parameter pointers fail with WV_ESTATE. */
@@ -532,9 +536,8 @@ int wv_train_fold_weight(const float* g, const float* v, float* w, float* inv_no
 int wv_train_sumsq(const float* g, size_t n, float* out, void* workspace, size_t workspace_bytes /* wv_train_bce_workspace_bytes() */, void* stream);
 int wv_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, const float* grad_sumsq, float max_norm, void* stream);
-const char* wv_train_last_error(void);
 
-/* ---- per-clip metrics of a validation pass (csrc/wv_metrics.hip; semantics in waveverify_amd/metrics.py) ---------------------
+/* ==== csrc/wv_metrics.hip: per-clip metrics of a validation pass (semantics in waveverify_amd/metrics.py) ---------------------
  * Three single-pass reductions, each with a caller-provided workspace sized by its *_workspace_bytes query (0 = bad shape).  Device
  * pointers, contiguous; inputs may sit on any 4-byte boundary, the workspace and the double outputs on 8.  Rows are summed in chunks
  * of 4096 samples in a fixed order, in f64 (or int32), and the chunks in ascending order: results are bit-identical from run to run
@@ -558,7 +561,7 @@ size_t wv_metrics_sisnr_workspace_bytes(int B, int T);
 int wv_metrics_sisnr(const float* estimate, const float* reference, int B, int T, double eps, double* sisnr, double* moments, void* workspace,
                      size_t workspace_bytes, void* stream);
 
-/* ---- temporal augmentations of the training step ------------------------------------
+/* ==== csrc/wv_aug.hip: temporal augmentations of the training step ------------------------------------
  * One bandwidth-bound pass that replaces the reference's per-clip / per-segment Python loops and its GPU->CPU->GPU
  * hop (model/watermarking.py:487-519,540).  All pointers are DEVICE pointers, tensors [B,C,T] contiguous f32.
  *
@@ -591,7 +594,7 @@ int wv_aug_backward(const float* d_out, const int* plan, int nseg, int seg_len, 
 int wv_aug_sequence(const float* in0, const float* in1, const float* in2, float* out0, float* out1, float* out2,
                     int seq_mode, int seq_a, int seq_b, int seq_c, const int* perm, int rows, int T, int T_out, void* stream);
 
-/* ---- sinc-filter / resample effects -------------------------------------------------------------
+/* ==== csrc/wv_fx.hip: sinc-filter / resample effects -------------------------------------------------------------
  * A FIR filter bank over a padded signal (device pointers):  y[row][f][n] = sum_j taps[f][j] * xpad[n*stride + j], n < Tout =
  * (T + pad_l + pad_r - L) / stride + 1; replicate = 1 pads with the edge samples (julius' filters), 0 with zeros (the polyphase resampler);
  * interleave = 1 stores y[row][n*n_filters + f].  n_filters <= 8.  The taps are built on the host the way julius 0.2.7 / torchaudio
@@ -612,7 +615,7 @@ int wv_fx_resample_adjoint(const float* dy, const float* kernels, float* dx, int
  * Any 1 <= Tout <= (ceil(T / orig) + 1) * nw is served (the same formula, continued or cut short); a longer one is refused. */
 int wv_fx_resample(const float* x, const float* kernels, float* y, int rows, int T, int orig, int nw, int L, int width, int Tout, void* stream);
 
-/* ---- plain-arithmetic time-domain effects (csrc/wv_fx_time.hip) ----------------------------------------------------------------
+/* ==== csrc/wv_fx_time.hip: plain-arithmetic time-domain effects ----------------------------------------------------------------
  * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
  * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding
  * per sample, to 2e-5 of the peak where it is a float sum.  Device pointers, [rows][T] contiguous f32, rows <= 65535, rows * T < 2^32;
@@ -664,16 +667,6 @@ int wv_fx_scatter_zero(float* y, float* mask, const int* idx, int rows, int T, i
 /* torch.nn.functional.interpolate(mode='linear', align_corners=False) from Tin to Tout samples: source coordinate
  * max(0, (m + 0.5) * Tin / Tout - 0.5) with the scale in f32 (AudioProcessor.adjust_audio_length(mode='stretch')). */
 int wv_fx_stretch_linear(const float* x, float* y, int rows, int Tin, int Tout, void* stream);
-
-/* ---- measurement hook (bench.py's roofline figures) ---------------------------------------
- * When enabled, every kernel launch is bracketed by a hipEvent pair on the launch stream and
- * aggregated by "<kernel>|<role>" together with its ALGORITHMIC flops and bytes (the per-unit
- * figures of DESIGN.md).  wv_profile_collect(-1, ...) synchronises, snapshots and returns the
- * number of entries; wv_profile_collect(i, ...) reads entry i of that snapshot. */
-int wv_profile_enable(int on);
-int wv_profile_reset(void);
-int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launches,
-                       double* total_ms, double* flops, double* bytes);
 
 #ifdef __cplusplus
 }

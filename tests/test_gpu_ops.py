@@ -237,6 +237,24 @@ def test_pw_dw_no_prologue_no_bias(ops):
     close(ops.pw_dw(cu(X), w_pw, w_dw, None, pre_elu=False), ref, what="dec head")
 
 
+def test_pw_dw_refusal_names_its_reason_and_leaves_no_state(ops):
+    """ks = 5 with stride = 8 has a negative left pad: wv_op_pw_dw refuses it before any launch, the exception carries the entry point
+    and the reason, and the same unit with stride = 1 then computes bit for bit what it computed before the refused call."""
+    rng = np.random.default_rng(11)
+    X, w_pw, w_dw, b_dw = cu(rnd(rng, 1, 64, 16)), rnd(rng, 64, 64, 1, scale=0.125), rnd(rng, 64, 1, 5), rnd(rng, 64, scale=0.1)
+    before = ops.pw_dw(X, w_pw, w_dw, b_dw, stride=1).cpu()
+    with pytest.raises(RuntimeError, match=r"wv_op_pw_dw failed \(code -1\): negative left pad"):
+        ops.pw_dw(X, w_pw, w_dw, b_dw, stride=8)
+    assert torch.equal(ops.pw_dw(X, w_pw, w_dw, b_dw, stride=1).cpu(), before)
+
+
+def test_h16_tail_refusal_names_the_limit_the_launcher_tests(ops):
+    """A kernel size the f16 tail has no instance for (9) is the launcher's `not supported`: the message names ks, not another limit."""
+    A16 = torch.zeros(1, 2, 16, 8, dtype=torch.float16, device="cuda")
+    with pytest.raises(RuntimeError, match=r"wv_h16_tail failed \(code -1\): .*ks in \{3, 5, 7\}"):
+        ops.h16_tail(A16, np.zeros((1, 16, 9), np.float32), np.zeros(1, np.float32), 16, 1.0)
+
+
 @pytest.mark.parametrize("K,M,Tin,r", [(1536, 768, 50, 8), (768, 384, 400, 5), (384, 192, 333, 4),
                                        (192, 96, 1000, 2), (16, 8, 9, 2), (24, 12, 1, 3),
                                        # every addressing mode of the ConvTranspose loader, ragged and tiny shapes

@@ -72,7 +72,7 @@ def test_basis_gradient_guard_bands_and_poisoned_workspace(fixture, offset):
     """One ragged case (n_fft 128, hop 2, T 131, noisy basis) with every operand between guard bands, aligned and one float off, and
     exactly the promised workspace filled with NaN bytes: nothing outside is touched, nothing stale is read, every element written."""
     from waveverify_amd import _lib
-    from waveverify_amd.train import StftFeatures, TrainHalf
+    from waveverify_amd.train import StftFeatures
     c = SLC.load_unit(fixture, 2, "noisy")
     n, F = c["n_fft"], c["n_fft"] // 2 + 1
     st = StftFeatures(n, c["hop"], SLC.MEAN, SLC.STD, basis=c["basis"])
@@ -85,13 +85,13 @@ def test_basis_gradient_guard_bands_and_poisoned_workspace(fixture, offset):
     for _ in range(2):
         g.repoison()
         assert lib.wv_stft_plan_basis_grad(st._h, wav.t.data_ptr(), dP.t.data_ptr(), out.t.data_ptr(), c["B"], c["T"], c["hop"], SLC.STD,
-                                           ws.t.data_ptr(), ws.t.numel(), TrainHalf._stream()) == 0
+                                           ws.t.data_ptr(), ws.t.numel(), _lib.stream()) == 0
         g.check()
         assert torch.isfinite(out.t).all()
         d = float((out.t - ref).abs().max())
         assert torch.equal(out.t, ref) if offset == 0 else d <= BAR * c["peak"], d     # one float off: the scalar-load path of the GEMM
     assert lib.wv_stft_plan_basis_grad(st._h, wav.t.data_ptr(), dP.t.data_ptr(), out.t.data_ptr(), c["B"], c["T"], c["hop"], SLC.STD,
-                                       ws.t.data_ptr(), ws.t.numel() - 1, TrainHalf._stream()) != 0          # a short workspace is refused
+                                       ws.t.data_ptr(), ws.t.numel() - 1, _lib.stream()) != 0          # a short workspace is refused
 
 
 @pytest.mark.parametrize("n_fft,hop", [(64, 1), (256, 8), (1024, 320)])

@@ -232,6 +232,7 @@ def test_c_abi_loads_and_exports_every_declared_symbol():
     declared = set(re.findall(r"\b(wv_[a-z0-9_]+)\s*\(", header))
     assert declared, "no declarations parsed"
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    assert "wv_train_last_error" not in declared and not [n for n in declared if n.startswith("wv_train_half_")]   # one channel, no half exports
     for name in declared:
         assert getattr(lib, name) is not None
     assert b"gfx950" in lib.wv_version()
@@ -266,6 +267,43 @@ def test_c_param_table_matches_python_grammar(kind):
             assert lib.wv_workspace_bytes(h, 4, 16000) > 0
         finally:
             lib.wv_model_destroy(h)
+
+
+# entry points whose all-null / all-zero call is refused before the library's first HIP call; the four training calls with the reason
+# their own (former) error channel gave
+_REFUSED_NULL_CALLS = ["wv_op_pw_dw", "wv_op_head", "wv_h16_head", "wv_stft_plan_create", "wv_stft_plan_logmag", "wv_specloss", "wv_metrics_iou",
+                       "wv_metrics_decode", "wv_fx_median", "wv_fx_pointwise", "wv_fx_resample", "wv_aug_sequence", "wv_aug_backward",
+                       "wv_window_gather", "wv_session_advance"]
+_REFUSED_TRAIN_CALLS = {"wv_train_unit_create": "bad kernel size / stride", "wv_train_bce_logits": "null / bad argument",
+                        "wv_train_adamw": "null / bad argument", "wv_train_film_forward": "null / bad argument (E <= 256, layers <= 4)"}
+
+
+def test_c_every_refusal_states_its_own_reason():
+    """One error channel: a call refused with a non-zero status leaves ITS reason in wv_last_error(), whichever source file exports it --
+    never the message of an earlier, unrelated failure."""
+    from waveverify_amd.nets import _fill_config
+    lib = _lib.load()
+    h = C.c_void_p()
+    c = _fill_config(default_config("detector"))
+    _lib.check(lib.wv_model_create(C.byref(c), C.byref(h)))
+    try:
+        for name in _REFUSED_NULL_CALLS + list(_REFUSED_TRAIN_CALLS):
+            buf = (C.c_float * 4)()
+            assert lib.wv_model_set_param(h, b"no.such.key", buf, 4) == -2
+            assert b"unknown parameter: no.such.key" in lib.wv_last_error()
+            if name == "wv_train_unit_create":
+                out = C.c_void_p()
+                rc = lib.wv_train_unit_create(64, 64, 17, 1, C.byref(out))
+                assert not out.value
+            else:
+                zero = {C.c_int: 0, C.c_int64: 0, C.c_size_t: 0, C.c_float: 0.0, C.c_double: 0.0}
+                rc = getattr(lib, name)(*[zero.get(t) for t in _lib.SIGNATURES[name][1]])
+            msg = lib.wv_last_error().decode()
+            assert rc == -1, (name, rc)
+            assert msg and "unknown parameter" not in msg, (name, msg)
+            assert _REFUSED_TRAIN_CALLS.get(name, "") in msg, (name, msg)
+    finally:
+        lib.wv_model_destroy(h)
 
 
 def test_c_config_default_matches_python():

@@ -39,7 +39,7 @@ def main():
             def launch():
                 rc = lib.wv_aug_localize_sequence(x.data_ptr(), w.data_ptr(), plan_d.data_ptr(), plan.shape[1], 1600, sm.mode, sm.a,
                                                   sm.b, sm.c, perm_d.data_ptr() if perm_d is not None else None, outs[0].data_ptr(),
-                                                  outs[1].data_ptr(), outs[2].data_ptr(), B, 1, T, T, A._stream())
+                                                  outs[1].data_ptr(), outs[2].data_ptr(), B, 1, T, T, A._lib.stream())
                 assert rc == 0
             for _ in range(5):
                 launch()

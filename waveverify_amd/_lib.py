@@ -52,21 +52,75 @@ SIGNATURES = {
                                        _VP, C.c_size_t, _VP]),
     "wv_detector_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_locator_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_encoder_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP,
+                                     C.c_size_t, _VP]),
+    "wv_detector_forward_f16": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_locator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_generator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_model_film": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP]),
+    "wv_profile_enable": (C.c_int, [C.c_int]),
+    "wv_profile_reset": (C.c_int, []),
+    "wv_profile_collect": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double)]),
     "wv_window_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int, C.c_int, _VP]),
     "wv_window_scatter": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_detector_forward_windowed": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_detector_forward_windowed_f16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_window_reduce_mean": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "wv_session_advance": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP]),
-    "wv_encoder_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP,
-                                     C.c_size_t, _VP]),
-    "wv_model_film": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP]),
+    "wv_op_pw_dw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                              C.c_int, _VP, C.c_float, _VP]),
+    "wv_op_resblock": (C.c_int, [_VP, C.c_float] + [_VP] * 8 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
+    "wv_op_dw_pw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                              C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_float, _VP]),
+    "wv_op_stft_logmag": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                    C.c_float, _VP]),
+    "wv_op_spec_block": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float] * 4 + [_VP]),
+    "wv_op_conv_pre": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_float, _VP]),
+    "wv_op_tail": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.c_float, C.c_float, _VP]),
+    "wv_op_head": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
+                             C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_h16_round_host": (C.c_int, [_VP, _VP, C.c_int64]),
+    "wv_h16_from_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _VP]),
+    "wv_h16_to_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_h16_conv_pre": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
+    "wv_h16_resblock": (C.c_int, [_VP, C.c_float] + [_VP] * 8 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
+    "wv_h16_conv": (C.c_int, [_VP] * 8 + [C.c_int] * 7 + [C.c_float, C.c_float, _VP]),
+    "wv_h16_spec_block": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float] * 4 + [_VP]),
+    "wv_h16_upsample": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float, _VP]),
+    "wv_h16_tail": (C.c_int, [_VP] * 5 + [C.c_int] * 5 + [C.c_float, _VP]),
+    "wv_h16_l2norm": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_h16_head": (C.c_int, [_VP] * 4 + [C.c_int] * 6 + [_VP] * 4),
+    "wv_h16_conv_film": (C.c_int, [_VP] * 5 + [C.c_int] + [_VP] * 2 + [C.c_int] * 7 + [C.c_float, _VP]),
+    "wv_stft_plan_create": (C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
+    "wv_stft_plan_destroy": (None, [_VP]),
+    "wv_stft_plan_logmag": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
+    "wv_stft_plan_backward_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
+    "wv_stft_plan_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_stft_plan_basis_grad_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
+    "wv_stft_plan_basis_grad": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
+    "wv_stft_plan_set_basis_device": (C.c_int, [_VP, _VP, _VP]),
+    "wv_specloss_plan_create": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
+    "wv_specloss_plan_destroy": (None, [_VP]),
+    "wv_specloss_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "wv_specloss": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, C.c_float, _VP, C.c_size_t, _VP]),
     "wv_train_unit_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     "wv_train_unit_destroy": (None, [_VP]),
     "wv_train_unit_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "wv_train_unit_forward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_int, _VP, C.c_int, C.c_int, _VP]),
     "wv_train_unit_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_float, C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                          C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_train_block_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
+    "wv_train_block_destroy": (None, [_VP]),
+    "wv_train_block_saved_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "wv_train_block_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
+    "wv_train_block_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP]),
+    "wv_train_block_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int,
+                                          _VP, C.c_size_t, _VP]),
     "wv_train_convpre_create": (C.c_int, [C.c_int, C.c_int, C.POINTER(_VP)]),
     "wv_train_convpre_destroy": (None, [_VP]),
     "wv_train_convpre_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
@@ -88,24 +142,6 @@ SIGNATURES = {
     "wv_train_head_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
     "wv_train_head_forward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_train_head_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_stft_plan_create": (C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
-    "wv_stft_plan_destroy": (None, [_VP]),
-    "wv_stft_plan_logmag": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
-    "wv_stft_plan_backward_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
-    "wv_stft_plan_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
-    "wv_stft_plan_basis_grad_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int, C.c_int]),
-    "wv_stft_plan_basis_grad": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP]),
-    "wv_stft_plan_set_basis_device": (C.c_int, [_VP, _VP, _VP]),
-    "wv_specloss_plan_create": (C.c_int, [C.c_int, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(_VP)]),
-    "wv_specloss_plan_destroy": (None, [_VP]),
-    "wv_specloss_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
-    "wv_specloss": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, _VP, _VP, C.c_float, C.c_float, _VP, C.c_size_t, _VP]),
-    "wv_metrics_decode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "wv_metrics_decode": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
-    "wv_metrics_iou_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "wv_metrics_iou": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
-    "wv_metrics_sisnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "wv_metrics_sisnr": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
     "wv_train_up_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(_VP)]),
     "wv_train_up_destroy": (None, [_VP]),
     "wv_train_up_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
@@ -124,28 +160,28 @@ SIGNATURES = {
     "wv_train_film_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_train_film_apply": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_train_film_apply_backward": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_train_block_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
-    "wv_train_block_destroy": (None, [_VP]),
-    "wv_train_block_saved_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
-    "wv_train_block_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
-    "wv_train_block_forward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, C.c_size_t, C.c_int, C.c_int, _VP]),
-    "wv_train_block_backward": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_float, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int,
-                                          _VP, C.c_size_t, _VP]),
     "wv_train_bce_workspace_bytes": (C.c_size_t, []),
     "wv_train_bce_logits": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_float, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_train_l1": (C.c_int, [_VP, _VP, _VP, _VP, C.c_float, C.c_size_t, _VP, C.c_size_t, _VP]),
+    "wv_train_fold_weight": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
     "wv_train_sumsq": (C.c_int, [_VP, C.c_size_t, _VP, _VP, C.c_size_t, _VP]),
     "wv_train_adamw": (C.c_int, [_VP, _VP, _VP, _VP, C.c_size_t, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                  _VP, C.c_float, _VP]),
+    "wv_metrics_decode_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "wv_metrics_decode": (C.c_int, [_VP, _VP, _VP, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "wv_metrics_iou_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "wv_metrics_iou": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
+    "wv_metrics_sisnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "wv_metrics_sisnr": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
     "wv_aug_localize_sequence": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                            _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_aug_backward": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_aug_sequence": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                   C.c_int, C.c_int, C.c_int, _VP]),
-    "wv_fx_resample": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_fir_bank": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_fold_replicate": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_resample_adjoint": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_fx_resample": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_pointwise": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
     "wv_fx_median": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_shush": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
@@ -157,48 +193,6 @@ SIGNATURES = {
     "wv_fx_smooth_backward": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_scatter_zero": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_stretch_linear": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
-    "wv_profile_enable": (C.c_int, [C.c_int]),
-    "wv_profile_reset": (C.c_int, []),
-    "wv_profile_collect": (C.c_int, [C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int64),
-                                     C.POINTER(C.c_double), C.POINTER(C.c_double),
-                                     C.POINTER(C.c_double)]),
-    "wv_op_pw_dw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
-                              C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
-                              C.c_int, _VP, C.c_float, _VP]),
-    "wv_train_half_create": (C.c_int, [C.c_int, C.POINTER(_VP)]),
-    "wv_train_half_destroy": (None, [_VP]),
-    "wv_train_half_workspace_bytes": (C.c_size_t, [_VP, C.c_int, C.c_int]),
-    "wv_train_half_forward": (C.c_int, [_VP] * 7 + [C.c_float, _VP, C.c_int, C.c_int, _VP]),
-    "wv_train_half_backward": (C.c_int, [_VP] * 6 + [C.c_float] + [_VP] * 7 + [C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_train_last_error": (C.c_char_p, []),
-    "wv_train_fold_weight": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
-    "wv_op_spec_block": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float] * 4 + [_VP]),
-    "wv_h16_round_host": (C.c_int, [_VP, _VP, C.c_int64]),
-    "wv_h16_from_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _VP]),
-    "wv_h16_to_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
-    "wv_h16_conv_pre": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
-    "wv_h16_resblock": (C.c_int, [_VP, C.c_float] + [_VP] * 8 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
-    "wv_h16_conv": (C.c_int, [_VP] * 8 + [C.c_int] * 7 + [C.c_float, C.c_float, _VP]),
-    "wv_h16_spec_block": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float] * 4 + [_VP]),
-    "wv_detector_forward_f16": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_locator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_generator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
-    "wv_h16_upsample": (C.c_int, [_VP] * 6 + [C.c_int] * 5 + [C.c_float, _VP]),
-    "wv_h16_tail": (C.c_int, [_VP] * 5 + [C.c_int] * 5 + [C.c_float, _VP]),
-    "wv_h16_l2norm": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
-    "wv_h16_head": (C.c_int, [_VP] * 4 + [C.c_int] * 6 + [_VP] * 4),
-    "wv_h16_conv_film": (C.c_int, [_VP] * 5 + [C.c_int] + [_VP] * 2 + [C.c_int] * 7 + [C.c_float, _VP]),
-    "wv_op_resblock": (C.c_int, [_VP, C.c_float] + [_VP] * 8 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _VP]),
-    "wv_op_dw_pw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                              C.c_int, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, _VP, C.c_float, _VP]),
-    "wv_op_stft_logmag": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
-                                    C.c_float, _VP]),
-    "wv_op_conv_pre": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
-                                 C.c_float, _VP]),
-    "wv_op_tail": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
-                             C.c_float, C.c_float, _VP]),
-    "wv_op_head": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
-                             C.c_int, C.c_int, C.c_int, _VP]),
 }
 
 _lib: Optional[C.CDLL] = None
@@ -225,10 +219,30 @@ def load() -> C.CDLL:
     return lib
 
 
+# The call convention of every binding module: a status goes through check(), a stream comes from stream(), an activation from dev(),
+# an optional tensor's address from ptr().
 def check(rc: int, what: str = "") -> None:
+    """The one place a status becomes an exception (the library's message is defined only after a non-zero return)."""
     if rc != 0:
         msg = load().wv_last_error().decode(errors="replace")
         raise RuntimeError(f"{what or 'waveverify_hip'} failed (code {rc}): {msg}")
+
+
+def stream(device=None) -> C.c_void_p:
+    """torch's current stream on `device` (default: the current device) as the ABI's `void* stream`."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def dev(t: "torch.Tensor", what: str) -> "torch.Tensor":
+    """`t` as the float32 contiguous tensor the kernels read; a CPU tensor is refused with the caller's wording `what`."""
+    if not t.is_cuda:
+        raise RuntimeError(what)
+    return t.float().contiguous()
+
+
+def ptr(t: "Optional[torch.Tensor]"):
+    return None if t is None else t.data_ptr()
 
 
 def scratch(nbytes: int, device) -> "torch.Tensor":

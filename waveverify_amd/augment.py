@@ -16,7 +16,6 @@ The reference wraps the augmented audio in audiotools' AudioSignal; `Signal` bel
 its callers read (`audio_data`, `sample_rate`)."""
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Tuple
 
@@ -24,6 +23,8 @@ import numpy as np
 import torch
 
 from . import _lib
+
+_ON_GPU = "augmentation tensors must live on the GPU (no CPU fallback)"
 
 ORIGINAL_REVERT_PROB = 0.33          # localization_augmentation.py:35-37
 ZERO_REPLACE_PROB = 0.66
@@ -55,16 +56,6 @@ class SeqMap:
     t_out: int = 0
 
 
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError("augmentation tensors must live on the GPU (no CPU fallback)")
-    return t.float().contiguous()
-
-
 def _launch(original, watermarked, plan, seg_len, sm: SeqMap):
     lib = _lib.load()
     B, Cc, T = watermarked.shape
@@ -83,11 +74,10 @@ def _launch(original, watermarked, plan, seg_len, sm: SeqMap):
             raise ValueError("segment permutation out of range")
         perm_d = torch.from_numpy(perm).to(watermarked.device)
     rc = lib.wv_aug_localize_sequence(
-        original.data_ptr(), watermarked.data_ptr(), plan_d.data_ptr() if plan_d is not None else None, nseg, int(seg_len),
-        sm.mode, sm.a, sm.b, sm.c, perm_d.data_ptr() if perm_d is not None else None,
-        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), B, Cc, T, sm.t_out, _stream())
-    if rc != 0:
-        raise RuntimeError(f"wv_aug_localize_sequence failed ({rc})")
+        original.data_ptr(), watermarked.data_ptr(), _lib.ptr(plan_d), nseg, int(seg_len),
+        sm.mode, sm.a, sm.b, sm.c, _lib.ptr(perm_d),
+        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), B, Cc, T, sm.t_out, _lib.stream())
+    _lib.check(rc, "wv_aug_localize_sequence")
     return outs
 
 
@@ -105,7 +95,7 @@ def inverse_map(sm: SeqMap, t_in: int) -> SeqMap:
 def backward_to_watermarked(d_out: torch.Tensor, plan, seg_len: int, sm: SeqMap, t_in: int) -> torch.Tensor:
     """Gradient of the augmented audio towards the watermarked input of `_launch` (the select passes it where the sample was kept)."""
     lib = _lib.load()
-    d_out = _dev(d_out)
+    d_out = _lib.dev(d_out, _ON_GPU)
     B, Cc, T_out = d_out.shape
     inv = inverse_map(sm, t_in)
     plan_d = perm_d = None
@@ -117,10 +107,9 @@ def backward_to_watermarked(d_out: torch.Tensor, plan, seg_len: int, sm: SeqMap,
     if inv.mode == SEQ_PERMUTE:
         perm_d = torch.from_numpy(np.ascontiguousarray(inv.perm, dtype=np.int32)).to(d_out.device)
     d_wm = torch.empty(B, Cc, t_in, dtype=torch.float32, device=d_out.device)
-    rc = lib.wv_aug_backward(d_out.data_ptr(), plan_d.data_ptr() if plan_d is not None else None, nseg, int(seg_len), inv.mode, inv.a, inv.b, inv.c,
-                             perm_d.data_ptr() if perm_d is not None else None, d_wm.data_ptr(), B, Cc, t_in, T_out, _stream())
-    if rc != 0:
-        raise RuntimeError(f"wv_aug_backward failed ({rc})")
+    rc = lib.wv_aug_backward(d_out.data_ptr(), _lib.ptr(plan_d), nseg, int(seg_len), inv.mode, inv.a, inv.b, inv.c,
+                             _lib.ptr(perm_d), d_wm.data_ptr(), B, Cc, t_in, T_out, _lib.stream())
+    _lib.check(rc, "wv_aug_backward")
     return d_wm
 
 
@@ -129,7 +118,7 @@ def apply_sequence_map(tensors: List[Optional[torch.Tensor]], sm: SeqMap) -> Lis
     lib = _lib.load()
     ref = next(t for t in tensors if t is not None)
     B, Cc, T = ref.shape
-    ins = [None if t is None else _dev(t) for t in tensors] + [None] * (3 - len(tensors))
+    ins = [None if t is None else _lib.dev(t, _ON_GPU) for t in tensors] + [None] * (3 - len(tensors))
     outs = [None if t is None else torch.empty(B, Cc, sm.t_out, dtype=torch.float32, device=ref.device) for t in ins]
     perm_d = None
     if sm.mode == SEQ_PERMUTE:
@@ -137,11 +126,9 @@ def apply_sequence_map(tensors: List[Optional[torch.Tensor]], sm: SeqMap) -> Lis
         if perm.size * sm.a != sm.t_out or perm.min() < 0 or (int(perm.max()) + 1) * sm.a > T:
             raise ValueError("segment permutation out of range")
         perm_d = torch.from_numpy(perm).to(ref.device)
-    ptr = lambda t: None if t is None else t.data_ptr()          # noqa: E731
-    rc = lib.wv_aug_sequence(ptr(ins[0]), ptr(ins[1]), ptr(ins[2]), ptr(outs[0]), ptr(outs[1]), ptr(outs[2]),
-                             sm.mode, sm.a, sm.b, sm.c, ptr(perm_d), B * Cc, T, sm.t_out, _stream())
-    if rc != 0:
-        raise RuntimeError(f"wv_aug_sequence failed ({rc})")
+    rc = lib.wv_aug_sequence(_lib.ptr(ins[0]), _lib.ptr(ins[1]), _lib.ptr(ins[2]), _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]),
+                             sm.mode, sm.a, sm.b, sm.c, _lib.ptr(perm_d), B * Cc, T, sm.t_out, _lib.stream())
+    _lib.check(rc, "wv_aug_sequence")
     return outs[:len(tensors)]
 
 
@@ -199,7 +186,7 @@ class LocalizationAugmentation:
     def forward(self, original: torch.Tensor, watermarked: torch.Tensor):
         if original.shape != watermarked.shape:
             raise ValueError(f"Shape mismatch: original {original.shape} != watermarked {watermarked.shape}")
-        original, watermarked = _dev(original), _dev(watermarked)
+        original, watermarked = _lib.dev(original, _ON_GPU), _lib.dev(watermarked, _ON_GPU)
         B, _, T = watermarked.shape
         plan = self.draw_plan(B, T)
         wm, upd, mask = _launch(original, watermarked, plan, self.segment_length, SeqMap(t_out=T))
@@ -301,7 +288,7 @@ class TemporalAugmenter:
     def forward(self, original: torch.Tensor, watermarked: torch.Tensor):
         if original.shape != watermarked.shape:
             raise ValueError(f"Shape mismatch: original {original.shape} != watermarked {watermarked.shape}")
-        original, watermarked = _dev(original), _dev(watermarked)
+        original, watermarked = _lib.dev(original, _ON_GPU), _lib.dev(watermarked, _ON_GPU)
         B, _, T = watermarked.shape
         loc, seq = self.localization_augmenter, self.seq_augmenter
         plan = loc.draw_plan(B, T)

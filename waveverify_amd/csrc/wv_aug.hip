@@ -14,7 +14,7 @@
 // Pure copies and constants: results are bit-identical to the reference's.
 #include <hip/hip_runtime.h>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 #include "wv_kernels.h"
 
 namespace wv {
@@ -156,45 +156,52 @@ static bool seq_ok(int mode, int a, int b, int c, const int* perm, int T, int T_
 
 }  // namespace wv
 
+using wv::fail;
+static const char* const SEQ_REFUSED =
+    "sequence map refused: unknown mode, a roll / chunk / segment outside [0, T), a permutation without perm, or a T_out the map does not give";
+
 extern "C" {
 
 int wv_aug_localize_sequence(const float* original, const float* watermarked, const int* plan, int nseg, int seg_len,
                              int seq_mode, int seq_a, int seq_b, int seq_c, const int* perm,
                              float* wm_out, float* orig_out, float* mask_out, int B, int C, int T, int T_out, void* stream) {
-    if (!original || !watermarked || !wm_out || !orig_out || !mask_out || B < 1 || C < 1 || T < 1) return WV_EINVAL;
-    if (plan && (seg_len < 1 || nseg != (T + seg_len - 1) / seg_len)) return WV_EINVAL;
-    if (!wv::seq_ok(seq_mode, seq_a, seq_b, seq_c, perm, T, T_out)) return WV_EINVAL;
-    if ((long long)B * C > 65535) return WV_EINVAL;
+    if (!original || !watermarked || !wm_out || !orig_out || !mask_out || B < 1 || C < 1 || T < 1) return fail(WV_EINVAL, "null pointer (original, watermarked or an output) or B, C, T < 1");
+    if (plan && (seg_len < 1 || nseg != (T + seg_len - 1) / seg_len)) return fail(WV_EINVAL, "plan given with seg_len < 1 or nseg != ceil(T / seg_len)");
+    if (!wv::seq_ok(seq_mode, seq_a, seq_b, seq_c, perm, T, T_out)) return fail(WV_EINVAL, SEQ_REFUSED);
+    if ((long long)B * C > 65535) return fail(WV_EINVAL, "B * C > 65535 rows");
     wv::AugArgs a{original, watermarked, plan, wm_out, orig_out, mask_out, B, C, T, T_out, nseg, plan ? seg_len : 1,
                   wv::SeqMap{seq_mode, seq_a, seq_b, seq_c, perm, T}};
     hipStream_t s = (hipStream_t)stream;
     wv::prof::Scope ps(s, "augment", 0.0, 4.0 * B * C * (2.0 * T + 3.0 * T_out));
     hipLaunchKernelGGL(wv::aug_kernel, dim3((T_out + 1023) / 1024, B * C), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 int wv_aug_sequence(const float* in0, const float* in1, const float* in2, float* out0, float* out1, float* out2,
                     int seq_mode, int seq_a, int seq_b, int seq_c, const int* perm, int rows, int T, int T_out, void* stream) {
-    if (rows < 1 || T < 1 || rows > 65535 || (!in0 && !in1 && !in2)) return WV_EINVAL;
-    if ((in0 && !out0) || (in1 && !out1) || (in2 && !out2)) return WV_EINVAL;
-    if (!wv::seq_ok(seq_mode, seq_a, seq_b, seq_c, perm, T, T_out)) return WV_EINVAL;
+    if (rows < 1 || T < 1 || rows > 65535 || (!in0 && !in1 && !in2)) return fail(WV_EINVAL, "rows or T < 1, rows > 65535, or no input at all");
+    if ((in0 && !out0) || (in1 && !out1) || (in2 && !out2)) return fail(WV_EINVAL, "an input without its output");
+    if (!wv::seq_ok(seq_mode, seq_a, seq_b, seq_c, perm, T, T_out)) return fail(WV_EINVAL, SEQ_REFUSED);
     wv::SeqArgs a{{in0, in1, in2}, {out0, out1, out2}, rows, T, T_out, wv::SeqMap{seq_mode, seq_a, seq_b, seq_c, perm, T}};
     const int n = (in0 ? 1 : 0) + (in1 ? 1 : 0) + (in2 ? 1 : 0);
     hipStream_t s = (hipStream_t)stream;
     wv::prof::Scope ps(s, "augment_seq", 0.0, 4.0 * rows * n * ((double)T_out * 2.0));
     hipLaunchKernelGGL(wv::seq_kernel, dim3((T_out + 1023) / 1024, rows), dim3(256), 0, s, a);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 int wv_aug_backward(const float* d_out, const int* plan, int nseg, int seg_len, int inv_mode, int inv_a, int inv_b, int inv_c, const int* inv_perm,
                     float* d_wm, int B, int C, int T, int T_out, void* stream) {
-    if (!d_out || !d_wm || B < 1 || C < 1 || T < 1 || (long long)B * C > 65535) return WV_EINVAL;
-    if (plan && (seg_len < 1 || nseg != (T + seg_len - 1) / seg_len)) return WV_EINVAL;
+    if (!d_out || !d_wm || B < 1 || C < 1 || T < 1 || (long long)B * C > 65535) return fail(WV_EINVAL, "null pointer (d_out, d_wm), B, C, T < 1 or B * C > 65535 rows");
+    if (plan && (seg_len < 1 || nseg != (T + seg_len - 1) / seg_len)) return fail(WV_EINVAL, "plan given with seg_len < 1 or nseg != ceil(T / seg_len)");
     // the inverse map runs over the OUTPUT axis: it is a map of length T_out (identity / reverse / roll / chunk swap: T_out == T)
-    if (!wv::seq_ok(inv_mode, inv_a, inv_b, inv_c, inv_perm, T_out, T_out)) return WV_EINVAL;
+    if (!wv::seq_ok(inv_mode, inv_a, inv_b, inv_c, inv_perm, T_out, T_out)) return fail(WV_EINVAL, SEQ_REFUSED);
     wv::AugBwdArgs a{d_out, plan, d_wm, B, C, T, T_out, nseg, plan ? seg_len : 1, wv::SeqMap{inv_mode, inv_a, inv_b, inv_c, inv_perm, T_out}};
     hipLaunchKernelGGL(wv::aug_bwd_kernel, dim3((T + 255) / 256, B * C), dim3(256), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 }  // extern "C"

@@ -9,7 +9,7 @@
 // through LDS together with the matching piece of every filter.
 #include <hip/hip_runtime.h>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 
 namespace wv {
 
@@ -117,38 +117,44 @@ __global__ __launch_bounds__(256) void resample_adjoint_kernel(const float* __re
 
 }  // namespace wv
 
+using wv::fail;
+
 extern "C" int wv_fx_fold_replicate(const float* dxp, float* dx, int rows, int T, int pad_l, int pad_r, void* stream) {
-    if (!dxp || !dx || rows < 1 || T < 1 || pad_l < 0 || pad_r < 0) return WV_EINVAL;
+    if (!dxp || !dx || rows < 1 || T < 1 || pad_l < 0 || pad_r < 0) return fail(WV_EINVAL, "null pointer (dxp, dx), rows or T < 1, or a negative pad");
     hipLaunchKernelGGL(wv::fold_replicate_kernel, dim3(rows), dim3(256), 0, (hipStream_t)stream, dxp, dx, T, pad_l, pad_r);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 extern "C" int wv_fx_resample_adjoint(const float* dy, const float* kernels, float* dx, int rows, int T, int orig, int nw, int L, int width, int Tout,
                                       void* stream) {
-    if (!dy || !kernels || !dx || rows < 1 || rows > 65535 || T < 1 || orig < 1 || nw < 1 || L < 1 || width < 0 || Tout < 1) return WV_EINVAL;
+    if (!dy || !kernels || !dx || rows < 1 || rows > 65535 || T < 1 || orig < 1 || nw < 1 || L < 1 || width < 0 || Tout < 1) return fail(WV_EINVAL, "null pointer (dy, kernels, dx), rows outside [1, 65535], T, orig, nw, L, Tout < 1 or width < 0");
     hipLaunchKernelGGL(wv::resample_adjoint_kernel, dim3((T + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, dy, kernels, dx, T, Tout, orig, nw, L,
                        width);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 extern "C" int wv_fx_resample(const float* x, const float* kernels, float* y, int rows, int T, int orig, int nw, int L, int width, int Tout, void* stream) {
-    if (!x || !kernels || !y || rows < 1 || rows > 65535 || T < 1 || orig < 1 || nw < 1 || L < 1 || width < 0 || Tout < 1) return WV_EINVAL;
-    if ((long long)Tout > ((long long)T + orig - 1) / orig * nw + nw) return WV_EINVAL;
+    if (!x || !kernels || !y || rows < 1 || rows > 65535 || T < 1 || orig < 1 || nw < 1 || L < 1 || width < 0 || Tout < 1) return fail(WV_EINVAL, "null pointer (x, kernels, y), rows outside [1, 65535], T, orig, nw, L, Tout < 1 or width < 0");
+    if ((long long)Tout > ((long long)T + orig - 1) / orig * nw + nw) return fail(WV_EINVAL, "Tout > (ceil(T / orig) + 1) * nw");
     hipLaunchKernelGGL(wv::resample_kernel, dim3((Tout + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, x, kernels, y, T, Tout, orig, nw, L, width);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 extern "C" int wv_fx_fir_bank(const float* x, const float* taps, float* y, int rows, int T, int n_filters, int L, int stride, int pad_l, int pad_r,
                               int replicate, int interleave, void* stream) {
     if (!x || !taps || !y || rows < 1 || T < 1 || n_filters < 1 || n_filters > wv::FX_MAX_F || L < 1 || stride < 1 || pad_l < 0 || pad_r < 0 ||
         rows > 65535)
-        return WV_EINVAL;
+        return fail(WV_EINVAL, "null pointer (x, taps, y), rows outside [1, 65535], T, L, stride < 1, a negative pad, or n_filters outside [1, " + std::to_string(wv::FX_MAX_F) + "]");
     const long long padded = (long long)T + pad_l + pad_r;
-    if (padded < L) return WV_EINVAL;
+    if (padded < L) return fail(WV_EINVAL, "the padded signal is shorter than the filter (T + pad_l + pad_r < L)");
     const int Tout = (int)((padded - L) / stride + 1);
     const size_t smem = ((size_t)(wv::FX_TILE - 1) * stride + wv::FX_JC + (size_t)n_filters * wv::FX_JC) * sizeof(float);
-    if (smem > 64 * 1024) return WV_EINVAL;                       // stride <= ~50 with the default LDS budget
+    if (smem > 64 * 1024) return fail(WV_EINVAL, "stride too large: the tile of (FX_TILE - 1) * stride samples exceeds 64 KB of LDS");                       // stride <= ~50 with the default LDS budget
     hipLaunchKernelGGL(wv::fir_bank_kernel, dim3((Tout + wv::FX_TILE - 1) / wv::FX_TILE, rows), dim3(256), smem, (hipStream_t)stream, x, taps, y, T, Tout, L,
                        n_filters, stride, pad_l, replicate, interleave);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }

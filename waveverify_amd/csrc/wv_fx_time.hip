@@ -10,7 +10,7 @@
 
 #include <cstdint>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 
 namespace wv {
 
@@ -389,20 +389,25 @@ static inline bool rows_ok(int rows, int T) { return rows >= 1 && rows <= 65535 
 
 }  // namespace wv
 
-#define WV_LAUNCHED() (hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP)
+using wv::fail;
+
+static int launched() {
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
 
 extern "C" int wv_fx_pointwise(const float* x, const float* noise, float* y, int rows, int T, int op, float a, void* stream) {
-    if (!x || !y || !wv::rows_ok(rows, T) || op < WV_FX_SCALE || op > WV_FX_MUL) return WV_EINVAL;
+    if (!x || !y || !wv::rows_ok(rows, T) || op < WV_FX_SCALE || op > WV_FX_MUL) return fail(WV_EINVAL, "null pointer (x, y), rows outside [1, 65535], T < 1 or rows * T >= 2^32, or an unknown op");
     const bool two = op == WV_FX_ADD_NOISE || op == WV_FX_MUL;
-    if (two && !noise) return WV_EINVAL;
+    if (two && !noise) return fail(WV_EINVAL, "this op reads noise, which is null");
     const size_t n = (size_t)rows * T;
     const int vec = (((uintptr_t)x | (uintptr_t)y | (uintptr_t)(two ? noise : x)) & 15u) == 0;
     hipLaunchKernelGGL(wv::pointwise_kernel, dim3(wv::flat_grid(vec ? n / 4 + 3 : n, 256, 2048)), dim3(256), 0, (hipStream_t)stream, x, noise, y, n, op, a, vec);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_median(const float* x, float* y, int rows, int T, int k, void* stream) {
-    if (!x || !y || !wv::rows_ok(rows, T) || k < 1 || k > WV_FX_MEDIAN_MAX_K || (k & 1) == 0) return WV_EINVAL;
+    if (!x || !y || !wv::rows_ok(rows, T) || k < 1 || k > WV_FX_MEDIAN_MAX_K || (k & 1) == 0) return fail(WV_EINVAL, "null pointer (x, y), rows outside [1, 65535], T < 1 or rows * T >= 2^32, or k not odd in [1, " WV_STR(WV_FX_MEDIAN_MAX_K) "]");
     const dim3 grid((T + wv::FXT_TILE - 1) / wv::FXT_TILE, rows), block(256);
     const size_t smem = (size_t)(wv::FXT_TILE + k - 1) * sizeof(float);
     hipStream_t s = (hipStream_t)stream;
@@ -415,29 +420,29 @@ extern "C" int wv_fx_median(const float* x, float* y, int rows, int T, int k, vo
     }
 #undef WV_MEDIAN_NET
     static_assert(WV_FX_MEDIAN_NET_K == 31, "the switch above lists the network sizes");
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_shush(const float* x, const float* mask_in, float* y, float* keep, float* mask_out, int rows, int T, int k, void* stream) {
-    if (!x || !y || !keep || !wv::rows_ok(rows, T) || k < 0 || k > T - 1 || (mask_in && !mask_out)) return WV_EINVAL;
+    if (!x || !y || !keep || !wv::rows_ok(rows, T) || k < 0 || k > T - 1 || (mask_in && !mask_out)) return fail(WV_EINVAL, "null pointer (x, y, keep), rows outside [1, 65535], T < 1 or rows * T >= 2^32, k outside [0, T - 1], or mask_in without mask_out");
     hipLaunchKernelGGL(wv::shush_kernel, dim3(rows), dim3(wv::SHUSH_THREADS), 0, (hipStream_t)stream, x, mask_in, y, keep, mask_out, T, k);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_echo_peaks(const float* x, void* rec, int rows, int T, int n, float volume, void* stream) {
-    if (!x || !rec || !wv::rows_ok(rows, T) || n < 2 || n > T || ((uintptr_t)rec & 7u)) return WV_EINVAL;
-    if (hipMemsetAsync(rec, 0, WV_FX_ECHO_RECORD_BYTES, (hipStream_t)stream) != hipSuccess) return WV_EHIP;
+    if (!x || !rec || !wv::rows_ok(rows, T) || n < 2 || n > T || ((uintptr_t)rec & 7u)) return fail(WV_EINVAL, "null pointer (x, rec), rows outside [1, 65535], T < 1 or rows * T >= 2^32, n outside [2, T], or rec not 8-byte aligned");
+    WV_HIP_TRY(hipMemsetAsync(rec, 0, WV_FX_ECHO_RECORD_BYTES, (hipStream_t)stream));
     const size_t N = (size_t)rows * T;
     hipLaunchKernelGGL(wv::echo_peaks_kernel, dim3(wv::flat_grid(N, 1024, 1024)), dim3(256), 0, (hipStream_t)stream, x, (unsigned long long*)rec, N, T, n, volume);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_echo_apply(const float* x, const void* rec, float* y, int rows, int T, int n, float volume, void* stream) {
-    if (!x || !rec || !y || !wv::rows_ok(rows, T) || n < 2 || n > T || ((uintptr_t)rec & 7u)) return WV_EINVAL;
+    if (!x || !rec || !y || !wv::rows_ok(rows, T) || n < 2 || n > T || ((uintptr_t)rec & 7u)) return fail(WV_EINVAL, "null pointer (x, rec, y), rows outside [1, 65535], T < 1 or rows * T >= 2^32, n outside [2, T], or rec not 8-byte aligned");
     const size_t N = (size_t)rows * T;
     hipLaunchKernelGGL(wv::echo_apply_kernel, dim3(wv::flat_grid(N, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, x, (const unsigned long long*)rec, y, N, T, n,
                        volume);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" size_t wv_fx_echo_backward_workspace_bytes(void) { return (size_t)wv::ECHO_PARTS * sizeof(float); }
@@ -446,38 +451,38 @@ extern "C" int wv_fx_echo_backward(const float* x, const float* g, const void* r
                                    size_t workspace_bytes, void* stream) {
     if (!x || !g || !rec || !dx || !workspace || !wv::rows_ok(rows, T) || n < 2 || n > T || ((uintptr_t)rec & 7u) || ((uintptr_t)workspace & 3u) ||
         workspace_bytes < wv_fx_echo_backward_workspace_bytes())
-        return WV_EINVAL;
+        return fail(WV_EINVAL, "null pointer (x, g, rec, dx, workspace), rows outside [1, 65535], T < 1 or rows * T >= 2^32, n outside [2, T], rec not 8-byte or workspace not 4-byte aligned, or workspace too small");
     const size_t N = (size_t)rows * T;
     const int parts = wv::flat_grid(N, 1024, wv::ECHO_PARTS);
     hipLaunchKernelGGL(wv::echo_dot_kernel, dim3(parts), dim3(256), 0, (hipStream_t)stream, x, g, (float*)workspace, N, T, n, volume);
     hipLaunchKernelGGL(wv::echo_backward_kernel, dim3(wv::flat_grid(N, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, x, g, (const unsigned long long*)rec,
                        (const float*)workspace, parts, dx, N, T, n, volume);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_smooth(const float* x, const float* mask_in, float* y, float* mask_out, int rows, int T, int w, float valid_threshold, void* stream) {
-    if (!x || !y || !wv::rows_ok(rows, T) || w < 1 || w > WV_FX_SMOOTH_MAX_W || w - 1 - (w - 1) / 2 >= T || (mask_in && !mask_out)) return WV_EINVAL;
+    if (!x || !y || !wv::rows_ok(rows, T) || w < 1 || w > WV_FX_SMOOTH_MAX_W || w - 1 - (w - 1) / 2 >= T || (mask_in && !mask_out)) return fail(WV_EINVAL, "null pointer (x, y), rows outside [1, 65535], T < 1 or rows * T >= 2^32, w outside [1, " WV_STR(WV_FX_SMOOTH_MAX_W) "], right pad w - 1 - (w - 1) / 2 >= T, or mask_in without mask_out");
     const size_t smem = 2 * (size_t)(wv::FXT_TILE + w - 1) * sizeof(float);
     hipLaunchKernelGGL(wv::smooth_kernel, dim3((T + wv::FXT_TILE - 1) / wv::FXT_TILE, rows), dim3(256), smem, (hipStream_t)stream, x, mask_in, y, mask_out, T, w,
                        valid_threshold);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_smooth_backward(const float* g, float* dx, int rows, int T, int w, void* stream) {
-    if (!g || !dx || !wv::rows_ok(rows, T) || w < 1 || w > WV_FX_SMOOTH_MAX_W || w - 1 - (w - 1) / 2 >= T) return WV_EINVAL;
+    if (!g || !dx || !wv::rows_ok(rows, T) || w < 1 || w > WV_FX_SMOOTH_MAX_W || w - 1 - (w - 1) / 2 >= T) return fail(WV_EINVAL, "null pointer (g, dx), rows outside [1, 65535], T < 1 or rows * T >= 2^32, w outside [1, " WV_STR(WV_FX_SMOOTH_MAX_W) "] or right pad w - 1 - (w - 1) / 2 >= T");
     hipLaunchKernelGGL(wv::smooth_backward_kernel, dim3((T + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, g, dx, T, w);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_scatter_zero(float* y, float* mask, const int* idx, int rows, int T, int num, void* stream) {
-    if (!y || !wv::rows_ok(rows, T) || num < 0 || num > T || (num > 0 && !idx)) return WV_EINVAL;
+    if (!y || !wv::rows_ok(rows, T) || num < 0 || num > T || (num > 0 && !idx)) return fail(WV_EINVAL, "null y, rows outside [1, 65535], T < 1 or rows * T >= 2^32, num outside [0, T], or indices wanted without idx");
     if (num == 0) return WV_OK;
     hipLaunchKernelGGL(wv::scatter_zero_kernel, dim3((num + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, y, mask, idx, T, num);
-    return WV_LAUNCHED();
+    return launched();
 }
 
 extern "C" int wv_fx_stretch_linear(const float* x, float* y, int rows, int Tin, int Tout, void* stream) {
-    if (!x || !y || !wv::rows_ok(rows, Tin) || !wv::rows_ok(rows, Tout)) return WV_EINVAL;
+    if (!x || !y || !wv::rows_ok(rows, Tin) || !wv::rows_ok(rows, Tout)) return fail(WV_EINVAL, "null pointer (x, y), or rows outside [1, 65535], Tin or Tout < 1, or rows * Tin or rows * Tout >= 2^32");
     hipLaunchKernelGGL(wv::stretch_kernel, dim3((Tout + 255) / 256, rows), dim3(256), 0, (hipStream_t)stream, x, y, Tin, Tout);
-    return WV_LAUNCHED();
+    return launched();
 }

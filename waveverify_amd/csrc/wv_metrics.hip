@@ -14,7 +14,7 @@
 
 #include <cstdint>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 
 namespace {
 
@@ -207,9 +207,12 @@ __global__ __launch_bounds__(64) void metrics_sisnr_finish_kernel(const double* 
     sisnr[b] = 10.0 * log10(ratio + eps);
 }
 
-inline size_t mt_al(size_t x) { return (x + 255) & ~(size_t)255; }
+using wv::fail;
 inline bool mt_shape_ok(long long rows, int T) { return rows >= 1 && rows <= MT_MAX_ROWS && T >= 1; }
-inline int mt_launched() { return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP; }
+inline int mt_launched() {
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
 
 }  // namespace
 
@@ -217,13 +220,13 @@ extern "C" {
 
 size_t wv_metrics_decode_workspace_bytes(int B, int W, int T) {
     if (B < 1 || W < 1 || !mt_shape_ok((long long)B * W, T)) return 0;
-    return mt_al((size_t)B * W * mt_chunks(T) * 2 * sizeof(double));
+    return wv::al256((size_t)B * W * mt_chunks(T) * 2 * sizeof(double));
 }
 
 int wv_metrics_decode(const float* logits, const float* bits, const float* mask, float threshold, float eps, int B, int W, int T, float* avg,
                       int* errors, int* valid, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits || !bits || !avg || !errors || !valid || B < 1 || W < 1 || !mt_shape_ok((long long)B * W, T)) return WV_EINVAL;
-    if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < wv_metrics_decode_workspace_bytes(B, W, T)) return WV_ENOMEM;
+    if (!logits || !bits || !avg || !errors || !valid || B < 1 || W < 1 || !mt_shape_ok((long long)B * W, T)) return fail(WV_EINVAL, "null pointer (logits, bits, avg, errors, valid), B or W < 1, T < 1 or B * W > " + std::to_string(MT_MAX_ROWS));
+    if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < wv_metrics_decode_workspace_bytes(B, W, T)) return fail(WV_ENOMEM, "workspace missing, not 8-byte aligned, or too small");
     hipStream_t st = (hipStream_t)stream;
     const int nc = mt_chunks(T);
     hipLaunchKernelGGL(metrics_decode_kernel, dim3(nc, B * W), dim3(MT_NT), 0, st, logits, mask, (double*)ws, W, T);
@@ -234,12 +237,12 @@ int wv_metrics_decode(const float* logits, const float* bits, const float* mask,
 
 size_t wv_metrics_iou_workspace_bytes(int B, int T) {
     if (!mt_shape_ok(B, T)) return 0;
-    return mt_al((size_t)B * mt_chunks(T) * 4 * sizeof(int));
+    return wv::al256((size_t)B * mt_chunks(T) * 4 * sizeof(int));
 }
 
 int wv_metrics_iou(const float* pred, const float* mask, int B, int T, int* counts, void* ws, size_t ws_bytes, void* stream) {
-    if (!pred || !mask || !counts || !mt_shape_ok(B, T)) return WV_EINVAL;
-    if (!ws || ((uintptr_t)ws & 3u) || ws_bytes < wv_metrics_iou_workspace_bytes(B, T)) return WV_ENOMEM;
+    if (!pred || !mask || !counts || !mt_shape_ok(B, T)) return fail(WV_EINVAL, "null pointer (pred, mask, counts), T < 1 or B outside [1, " + std::to_string(MT_MAX_ROWS) + "]");
+    if (!ws || ((uintptr_t)ws & 3u) || ws_bytes < wv_metrics_iou_workspace_bytes(B, T)) return fail(WV_ENOMEM, "workspace missing, not 4-byte aligned, or too small");
     hipStream_t st = (hipStream_t)stream;
     const int nc = mt_chunks(T);
     hipLaunchKernelGGL(metrics_iou_kernel, dim3(nc, B), dim3(MT_NT), 0, st, pred, mask, (int*)ws, T);
@@ -249,14 +252,14 @@ int wv_metrics_iou(const float* pred, const float* mask, int B, int T, int* coun
 
 size_t wv_metrics_sisnr_workspace_bytes(int B, int T) {
     if (!mt_shape_ok(B, T)) return 0;
-    return mt_al((size_t)B * mt_chunks(T) * 5 * sizeof(double));
+    return wv::al256((size_t)B * mt_chunks(T) * 5 * sizeof(double));
 }
 
 int wv_metrics_sisnr(const float* estimate, const float* reference, int B, int T, double eps, double* sisnr, double* moments, void* ws,
                      size_t ws_bytes, void* stream) {
-    if (!estimate || !reference || !sisnr || !moments || !mt_shape_ok(B, T)) return WV_EINVAL;
-    if (((uintptr_t)sisnr & 7u) || ((uintptr_t)moments & 7u)) return WV_EINVAL;
-    if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < wv_metrics_sisnr_workspace_bytes(B, T)) return WV_ENOMEM;
+    if (!estimate || !reference || !sisnr || !moments || !mt_shape_ok(B, T)) return fail(WV_EINVAL, "null pointer (estimate, reference, sisnr, moments), T < 1 or B outside [1, " + std::to_string(MT_MAX_ROWS) + "]");
+    if (((uintptr_t)sisnr & 7u) || ((uintptr_t)moments & 7u)) return fail(WV_EINVAL, "sisnr / moments not 8-byte aligned");
+    if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < wv_metrics_sisnr_workspace_bytes(B, T)) return fail(WV_ENOMEM, "workspace missing, not 8-byte aligned, or too small");
     hipStream_t st = (hipStream_t)stream;
     const int nc = mt_chunks(T);
     hipLaunchKernelGGL(metrics_sisnr_kernel, dim3(nc, B), dim3(MT_NT), 0, st, estimate, reference, (double*)ws, T);

@@ -11,19 +11,13 @@
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 #include "wv_kernels.h"
 
 namespace {
 
-thread_local std::string g_err;
-int fail(int code, const std::string& msg) { g_err = msg; return code; }
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(WV_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
+thread_local std::string g_err;      // the library's one error string: written by wv::fail only, read by wv_last_error only
+using wv::fail;
 
 struct Param {
     std::string name;
@@ -58,6 +52,8 @@ struct UpLayer {
 };
 
 }  // namespace
+
+int wv::fail(int code, std::string msg) { g_err = std::move(msg); return code; }
 
 struct wv_model {
     wv_config cfg{};
@@ -590,13 +586,6 @@ WsLayout layout(const wv_model* m, int B, int T) {
 }
 
 // ------------------------------------------------------------------------------ forward
-#define LAUNCH(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(WV_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));          \
-    } while (0)
-
 // The residual stream of a net: `raw` = x, `act` = ELU(s * x) for the NEXT consumer's scale s (written
 // by the producer's epilogue, PwDwArgs::Yact, so that the consumer stages it by LDS-DMA), either may be
 // null.  r[2] / a[2] are the ping-pong buffers behind them, u the ResnetBlock intermediate.
@@ -640,7 +629,7 @@ int run_resblock(const ResBlock& r, Stream& st, bool want_raw, float next_scale,
     a.pw = r.pw1; a.dw_w = r.dw1_w; a.dw_b = r.dw1_b; a.Y = nullptr; a.Yact = st.u; a.act_scale = 1.f;
     a.B = B; a.Tin = T; a.Tout = T; a.ks = r.ks; a.stride = 1; a.dil = r.dil1; a.pad = (r.ks - 1) * r.dil1;
     a.out_scale = 1.f; a.bands = 1;
-    LAUNCH(wv::launch_pw_dw(a, s));
+    WV_HIP_TRY(wv::launch_pw_dw(a, s));
     wv::PwDwArgs b{};
     float* yr = want_raw ? st.other_raw() : nullptr;
     float* ya = next_scale > 0.f ? st.other_act() : nullptr;
@@ -648,7 +637,7 @@ int run_resblock(const ResBlock& r, Stream& st, bool want_raw, float next_scale,
     b.act_scale = next_scale;
     b.B = B; b.Tin = T; b.Tout = T; b.ks = r.ks; b.stride = 1; b.dil = r.dil2; b.pad = (r.ks - 1) * r.dil2;
     b.pre_scale = 1.f; b.pre_elu = 0; b.out_scale = r.out_scale; b.bands = 1;
-    LAUNCH(wv::launch_pw_dw(b, s));
+    WV_HIP_TRY(wv::launch_pw_dw(b, s));
     st.raw = yr; st.act = ya;
     return WV_OK;
 }
@@ -663,7 +652,7 @@ int run_film(wv_model* m, const float* msg, int msg_rows, float* film, int B, hi
     f.n_layers = c.embedding_layers; f.n_out = c.n_strides * c.freq_bands * 2;
     f.w0 = m->f_w0; f.b0 = m->f_b0; f.wl = m->f_wl; f.bl = m->f_bl; f.wf = m->f_wf; f.bf = m->f_bf;
     f.film = film; f.B = B;
-    LAUNCH(wv::launch_film(f, st));
+    WV_HIP_TRY(wv::launch_film(f, st));
     return WV_OK;
 }
 
@@ -697,7 +686,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
     } else {
         wv::prof::set_role("enc.conv_pre");
         sm.act = (m->enc_blocks[0].empty() || !wants_act_copy(c, c.channels_enc, T)) ? nullptr : sm.a[0];   // also ELU(c1 * y) for the first ResnetBlock
-        LAUNCH(wv::launch_conv_pre(x, m->pre_w, m->pre_b, sm.raw, sm.act, sm.act ? m->enc_blocks[0][0].pre_scale : 0.f,
+        WV_HIP_TRY(wv::launch_conv_pre(x, m->pre_w, m->pre_b, sm.raw, sm.act, sm.act ? m->enc_blocks[0][0].pre_scale : 0.f,
                                    B, c.channels_enc, T, c.kernel_size, 1.f / c.wav_std, st));
     }
     const int film_stride = c.n_strides * c.freq_bands * 2;
@@ -736,7 +725,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
             } else if (e != hipErrorNotSupported) return fail(WV_EHIP, std::string("launch_stft_spec: ") + hipGetErrorString(e));
         }
         if (!fused_spec) {
-        LAUNCH(wv::launch_stft_logmag(sa, st));
+        WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
         // x += scale * (W @ P)  (seanet.py:500-502).  Runs on K1 with an identity stencil (taps 0,0,0,0,1
         // are exact: fmaf(0,h,0) = 0, fmaf(1,h,0) = h) and x as the residual operand.  Before a
         // downsample only ELU(s * x') is consumed, so only that is written; spec_post keeps x' raw
@@ -747,7 +736,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
             k2.X = P; k2.pw = sp.pw; k2.Y = sm.raw; k2.B = B; k2.Tin = Tl; k2.Tout = Tl; k2.mode = 0;
             k2.pre_scale = 1.f; k2.pre_elu = 0; k2.accumulate = 1; k2.out_scale = sp.scale;
             k2.Yact = post ? nullptr : sm.other_act(); k2.act_scale = down_scale;    // the downsample's ELU(s * x')
-            LAUNCH(wv::launch_dw_pw(k2, st));
+            WV_HIP_TRY(wv::launch_dw_pw(k2, st));
             sm.act = k2.Yact;
         } else {
             wv::PwDwArgs acc{};
@@ -757,7 +746,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
             acc.B = B; acc.Tin = Tl; acc.Tout = Tl; acc.ks = 5; acc.stride = 1; acc.dil = 1; acc.pad = 4;
             acc.pre_scale = 1.f; acc.pre_elu = 0; acc.out_scale = sp.scale; acc.bands = 1;
             acc.spec_add = 1;
-            LAUNCH(wv::launch_pw_dw(acc, st));
+            WV_HIP_TRY(wv::launch_pw_dw(acc, st));
             if (!post) { sm.act = acc.Yact; sm.raw = nullptr; }
         }
         }
@@ -778,7 +767,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
         a.bands = c.freq_bands; a.film_stride = film_stride;
         a.film = film ? film + (size_t)s * c.freq_bands * 2 : nullptr;
         if (film && (2 * C) % c.freq_bands) return fail(WV_EINVAL, "channels not divisible by freq_bands");
-        LAUNCH(wv::launch_pw_dw(a, st));
+        WV_HIP_TRY(wv::launch_pw_dw(a, st));
         sm.raw = yr; sm.act = ya;
         Tl = a.Tout; C *= 2;
     }
@@ -788,7 +777,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
     cp.B = B; cp.Tin = Tl; cp.Tout = Tl; cp.mode = 1; cp.ks = c.last_kernel_size;
     cp.pre_scale = 1.f; cp.pre_elu = 1; cp.l2norm = 1;
     if (c.dimension > 128) return fail(WV_EINVAL, "dimension > 128 not supported by the fused L2-norm epilogue");
-    LAUNCH(wv::launch_dw_pw(cp, st));
+    WV_HIP_TRY(wv::launch_dw_pw(cp, st));
     *Fr_out = Tl;
     return WV_OK;
 }
@@ -935,7 +924,7 @@ int wv_model_finalize(wv_model* m) {
         return fail(WV_ENOKEY, "message-MLP / FiLM tensors must be given all or none");
     int rc = pack_model(m);
     if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
+    WV_HIP_TRY(hipDeviceSynchronize());
     m->finalized = true;
     for (Param& p : m->params) { p.data.clear(); p.data.shrink_to_fit(); }
     return WV_OK;
@@ -980,7 +969,7 @@ int wv_generator_forward(wv_model* m, const float* x, const float* msg, int msg_
     h.Y = nullptr; h.Yact = sm.a[0]; h.act_scale = m->ups.empty() ? 1.f : m->ups[0].pre_scale;
     h.B = B; h.Tin = Fr; h.Tout = Fr; h.ks = c.kernel_size; h.stride = 1; h.dil = 1; h.pad = c.kernel_size - 1;
     h.pre_scale = 1.f; h.pre_elu = 0; h.out_scale = 1.f; h.bands = 1;
-    LAUNCH(wv::launch_pw_dw(h, st));
+    WV_HIP_TRY(wv::launch_pw_dw(h, st));
     sm.raw = nullptr; sm.act = sm.a[0];
     int Tl = Fr;
     for (size_t i = 0; i < m->ups.size(); ++i) {
@@ -1001,7 +990,7 @@ int wv_generator_forward(wv_model* m, const float* x, const float* msg, int msg_
         a.act_scale = has_blocks ? u.res[0].pre_scale : stage_next;
         a.B = B; a.Tin = Tl; a.Tout = Tl * u.ratio; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
         a.pre_scale = 1.f; a.pre_elu = 0; a.out_scale = 1.f; a.bands = 1;
-        LAUNCH(wv::launch_pw_dw(a, st));
+        WV_HIP_TRY(wv::launch_pw_dw(a, st));
         sm.raw = a.Y; sm.act = a.Yact;
         Tl = a.Tout;
         for (size_t j = 0; j < u.res.size(); ++j) {
@@ -1012,7 +1001,7 @@ int wv_generator_forward(wv_model* m, const float* x, const float* msg, int msg_
         }
     }
     wv::prof::set_role("dec.tail");
-    LAUNCH(wv::launch_tail(sm.raw, m->last_w, m->last_b, add_input ? x : nullptr, out, B, c.channels_dec,
+    WV_HIP_TRY(wv::launch_tail(sm.raw, m->last_w, m->last_b, add_input ? x : nullptr, out, B, c.channels_dec,
                            Tl, T, c.last_kernel_size, m->dec_post, c.wav_std, st));
     return WV_OK;
 }
@@ -1036,7 +1025,7 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
     int cur = 0, Tl = T, C = c.channels_enc;
     const int film_stride = c.n_strides * c.freq_bands * 2;
     wv::prof::set_role("enc16.conv_pre");
-    LAUNCH(wv::launch_conv_pre16(x, m->pre_w, m->pre_b, R[0], B, C, T, c.kernel_size, 1.f / c.wav_std, st));
+    WV_HIP_TRY(wv::launch_conv_pre16(x, m->pre_w, m->pre_b, R[0], B, C, T, c.kernel_size, 1.f / c.wav_std, st));
     for (int s = 0; s < S; ++s) {
         const wv_model::H16Stage& hs = m->h16[s];
         wv::prof::set_role("enc16.resblock");
@@ -1067,12 +1056,12 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
         if (fe != hipSuccess && fe != hipErrorNotSupported) return fail(WV_EHIP, std::string("launch_spec16: ") + hipGetErrorString(fe));
         if (fe == hipErrorNotSupported) {
             if ((size_t)B * round_up_int(sp.F, 16) * Tl * 2 > L.act * 4) return fail(WV_ESTATE, "f16 mode: the spectrogram of this scale does not fit its staging buffer");
-            LAUNCH(wv::launch_stft_logmag(sa, st));
-            LAUNCH(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
+            WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
+            WV_HIP_TRY(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
             wv::Conv16Args q{};
             q.X = P16; q.w = hs.spec; q.bias = nullptr; q.resid = R[cur]; q.Y = nullptr; q.Yact = A0; q.Yf32 = nullptr;
             q.out_scale = sp.scale; q.act_scale = d.pre_scale; q.B = B; q.M = C; q.Tin = Tl; q.Tout = Tl; q.ks = 1; q.stride = 1; q.pad = 0;
-            LAUNCH(wv::launch_conv16(q, st));
+            WV_HIP_TRY(wv::launch_conv16(q, st));
         }
         wv::prof::set_role(film ? "enc16.down_film" : "enc16.down");
         const bool last = s + 1 == S, post16 = (int)m->h16.size() > S;
@@ -1084,7 +1073,7 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
             if ((2 * C) % c.freq_bands) return fail(WV_EINVAL, "channels not divisible by freq_bands");
             g.film = film + (size_t)s * c.freq_bands * 2; g.bands = c.freq_bands; g.film_stride = film_stride;
         }
-        LAUNCH(wv::launch_conv16(g, st));
+        WV_HIP_TRY(wv::launch_conv16(g, st));
         cur ^= 1; Tl = g.Tout; C *= 2;
     }
     *post_done = false; *latent_done = false; *Fr_out = Tl;
@@ -1114,12 +1103,12 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
             wv::StftArgs sa{};
             sa.wav = x; sa.basis_t = sp.basis_t; sa.basis_q = sp.basis_q; sa.side = sp.side; sa.P = P; sa.B = B; sa.T = T;
             sa.Tf = Tl; sa.n_fft = sp.n_fft; sa.hop = sp.hop; sa.F = sp.F; sa.Mp = sp.Mp; sa.mean = sp.mean; sa.inv_std = sp.inv_std;
-            LAUNCH(wv::launch_stft_logmag(sa, st));
-            LAUNCH(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
+            WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
+            WV_HIP_TRY(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
             wv::Conv16Args q{};
             q.X = P16; q.w = hs.spec; q.bias = nullptr; q.resid = R[cur]; q.Y = nullptr; q.Yact = latent ? A0 : nullptr; q.Yf32 = f32out;
             q.out_scale = sp.scale; q.act_scale = latent ? 1.f : 0.f; q.B = B; q.M = C; q.Tin = Tl; q.Tout = Tl; q.ks = 1; q.stride = 1; q.pad = 0;
-            LAUNCH(wv::launch_conv16(q, st));
+            WV_HIP_TRY(wv::launch_conv16(q, st));
             done = true;
         }
         if (done && latent) {
@@ -1128,17 +1117,17 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
             g.X = A0; g.w = hs.post; g.bias = m->post_b; g.resid = nullptr; g.Y = nullptr; g.Yact = nullptr; g.Yf32 = (float*)(ws + L.off_lat);
             g.out_scale = 1.f; g.act_scale = 0.f; g.B = B; g.M = c.dimension; g.Tin = Tl; g.Tout = Tl; g.ks = c.last_kernel_size; g.stride = 1;
             g.pad = c.last_kernel_size - 1;
-            LAUNCH(wv::launch_conv16(g, st));
+            WV_HIP_TRY(wv::launch_conv16(g, st));
             *post_done = true; *latent_done = true;
             return WV_OK;
         }
         if (done) {
-            if ((cur ^ 1) != 0) LAUNCH(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
+            if ((cur ^ 1) != 0) WV_HIP_TRY(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
             *post_done = true;
             return WV_OK;
         }
-        LAUNCH(wv::launch_c8_to_f32(R[cur], (float*)R[cur ^ 1], B, C, Tl, st));     // the exact path's spec_post takes it from here
-        if ((cur ^ 1) != 0) LAUNCH(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
+        WV_HIP_TRY(wv::launch_c8_to_f32(R[cur], (float*)R[cur ^ 1], B, C, Tl, st));     // the exact path's spec_post takes it from here
+        if ((cur ^ 1) != 0) WV_HIP_TRY(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     return WV_OK;
 }
@@ -1180,7 +1169,7 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
     h.Z = latent; h.wc = m->head_wc; h.bc = m->head_bc; h.logits = logits; h.mean_prob = mean_prob;
     h.B = B; h.D = m->cfg.dimension; h.nb = m->head_nb; h.hop = hop_of(m->cfg); h.Fr = Fr; h.T = T;
     h.keep_lo = keep_lo; h.keep_hi = keep_hi; h.psum = psum;
-    LAUNCH(wv::launch_head(h, st));
+    WV_HIP_TRY(wv::launch_head(h, st));
     return WV_OK;
 }
 
@@ -1249,14 +1238,14 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
     void* R[2] = {w + L.off_r0, w + L.off_r1};
     void* A0 = w + L.off_a0;
     wv::prof::set_role("dec16.l2norm");
-    LAUNCH(wv::launch_l2norm_c8(latent, A0, B, c.dimension, Fr, st));
+    WV_HIP_TRY(wv::launch_l2norm_c8(latent, A0, B, c.dimension, Fr, st));
     wv::prof::set_role("dec16.head");
     {
         wv::Conv16Args g{};
         g.X = A0; g.w = m->h16_dec_head; g.bias = m->dec_dw0_b; g.resid = nullptr; g.Y = nullptr; g.Yact = R[0]; g.Yf32 = nullptr;
         g.out_scale = 1.f; g.act_scale = m->ups[0].pre_scale; g.B = B; g.M = m->dec_pw0.M; g.Tin = Fr; g.Tout = Fr; g.ks = c.kernel_size; g.stride = 1;
         g.pad = c.kernel_size - 1;
-        LAUNCH(wv::launch_conv16(g, st));
+        WV_HIP_TRY(wv::launch_conv16(g, st));
     }
     void* act = R[0];                                            // the activated stream the next unit consumes
     int Tl = Fr;
@@ -1272,7 +1261,7 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
         g.B = B; g.M = u.pw.M * u.ratio; g.Tin = Tl; g.Tout = Tl; g.ks = 2; g.stride = 1; g.pad = 1; g.up = u.ratio; g.up_mb = hu.mb;
         if (u.res.empty()) { g.Y = nullptr; g.Yact = free1; g.act_scale = stage_next; }
         else { g.Y = free1; g.Yact = nullptr; g.act_scale = 0.f; }
-        LAUNCH(wv::launch_conv16(g, st));
+        WV_HIP_TRY(wv::launch_conv16(g, st));
         Tl *= u.ratio;
         void* bufs[3] = {R[0], R[1], A0};
         void* curb = free1;

@@ -9,12 +9,13 @@
 #include <string>
 #include <vector>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 #include "wv_kernels.h"
 
 namespace {
 
-extern "C" const char* wv_last_error(void);
+using wv::al256;
+using wv::fail;
 
 struct Tmp {                       // scoped device uploads
     std::vector<void*> d;
@@ -57,10 +58,22 @@ struct Tmp {                       // scoped device uploads
     ~Tmp() { (void)hipDeviceSynchronize(); for (void* p : d) (void)hipFree(p); }
 };
 
+// a launcher's status as the ABI's: hipErrorInvalidValue is the launchers' own refusal of an argument
+int launched(hipError_t e) {
+    if (e == hipErrorInvalidValue) return fail(WV_EINVAL, "the launcher refused the arguments (a shape or pointer outside the kernel's limits)");
+    WV_HIP_TRY(e);
+    return WV_OK;
+}
+// hipErrorNotSupported from a launcher: `covers` states everything that launcher tests before it answers so
+int unsupported(const std::string& covers) { return fail(WV_EINVAL, "the call is outside what the fused kernel covers: " + covers); }
+// the gates every fused kernel adds to its shapes: 16-byte aligned activations, and one clip's tensor within the kernel's 32-bit offsets
+const char* const FUSED_GATES = "; activations 16-byte aligned, one clip's tensor within the kernel's 32-bit byte offsets";
+
 int done(Tmp& t, hipError_t e, hipStream_t s) {
-    if (!t.ok) return WV_EHIP;
-    if (e != hipSuccess) return e == hipErrorInvalidValue ? WV_EINVAL : WV_EHIP;
-    return hipStreamSynchronize(s) == hipSuccess ? WV_OK : WV_EHIP;
+    if (!t.ok) return fail(WV_EHIP, "device allocation or upload of the weights failed");
+    if (int rc = launched(e)) return rc;
+    WV_HIP_TRY(hipStreamSynchronize(s));
+    return WV_OK;
 }
 
 }  // namespace
@@ -71,7 +84,7 @@ int wv_op_pw_dw(const float* X, const float* w_pw, const float* w_dw, const floa
                 const float* film, const float* resid, float* Y, int B, int K, int M, int Tin,
                 int ks, int stride, int dilation, float pre_scale, int pre_elu, float out_scale,
                 int bands, float* Yact, float act_scale, void* stream) {
-    if (!X || !w_pw || !w_dw || (!Y && !Yact) || B < 1 || K < 1 || M < 1 || Tin < 1) return WV_EINVAL;
+    if (!X || !w_pw || !w_dw || (!Y && !Yact) || B < 1 || K < 1 || M < 1 || Tin < 1) return fail(WV_EINVAL, "null pointer (X, w_pw, w_dw, or both Y and Yact) or B, K, M, Tin < 1");
     Tmp t;
     wv::PwDwArgs a{};
     a.X = X; a.pw = t.pw(w_pw, M, K); a.dw_w = t.up(w_dw, (size_t)M * ks);
@@ -80,28 +93,28 @@ int wv_op_pw_dw(const float* X, const float* w_pw, const float* w_dw, const floa
     a.dil = dilation; a.pad = (ks - 1) * dilation - (stride - 1);
     a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = out_scale;
     a.bands = bands > 0 ? bands : 1; a.film_stride = 2 * a.bands;
-    if (a.pad < 0) return WV_EINVAL;
+    if (a.pad < 0) return fail(WV_EINVAL, "negative left pad: (ks - 1) * dilation < stride - 1");
     return done(t, wv::launch_pw_dw(a, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 int wv_op_resblock(const float* X, float pre_scale, const float* w_pw1, const float* w_dw1, const float* b1,
                    const float* w_pw2, const float* w_dw2, const float* b2, float* Y, float* Yact,
                    int B, int C, int T, float out_scale, float act_scale, void* stream) {
-    if (!X || !w_pw1 || !w_dw1 || !w_pw2 || !w_dw2 || (!Y && !Yact) || B < 1 || C < 1 || T < 1) return WV_EINVAL;
+    if (!X || !w_pw1 || !w_dw1 || !w_pw2 || !w_dw2 || (!Y && !Yact) || B < 1 || C < 1 || T < 1) return fail(WV_EINVAL, "null pointer (X, a weight, or both Y and Yact) or B, C, T < 1");
     Tmp t;
     wv::RbArgs a{};
     a.X = X; a.pre_scale = pre_scale; a.pw1 = t.pw(w_pw1, C, C); a.pw2 = t.pw(w_pw2, C, C);
     a.tab1 = t.upv(wv::pack_rb_table(w_dw1, b1, C)); a.tab2 = t.upv(wv::pack_rb_table(w_dw2, b2, C));
     a.Y = Y; a.Yact = Yact; a.out_scale = out_scale; a.act_scale = act_scale; a.B = B; a.C = C; a.T = T;
     const hipError_t e = wv::launch_resblock(a, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported(std::string("C in {64, 96, 128, 192}, T % 4 == 0") + FUSED_GATES);
     return done(t, e, (hipStream_t)stream);
 }
 
 // ---- the f16 mode's units (wv_h16.hip): activations in the c8 f16 layout, weights as HOST f32 pointers in the reference's layouts
 // host-side f32 -> f16 rounding the weight packers use (round to nearest even; no device needed)
 int wv_h16_round_host(const float* in, uint16_t* out, int64_t n) {
-    if (!in || !out || n < 0) return WV_EINVAL;
+    if (!in || !out || n < 0) return fail(WV_EINVAL, "null pointer or n < 0");
     for (int64_t i = 0; i < n; ++i) out[i] = wv::f32_to_f16_bits(in[i]);
     return WV_OK;
 }
@@ -114,13 +127,13 @@ int wv_h16_to_f32(const void* X16, float* Y, int B, int C, int T, void* stream) 
     return done(t, wv::launch_c8_to_f32(X16, Y, B, C, T, (hipStream_t)stream), (hipStream_t)stream);
 }
 int wv_h16_conv_pre(const float* x, const float* w, const float* bias, void* Y16, int B, int C, int T, int ks, float in_scale, void* stream) {
-    if (!x || !w || !Y16 || C < 1 || ks < 1) return WV_EINVAL;
+    if (!x || !w || !Y16 || C < 1 || ks < 1) return fail(WV_EINVAL, "null pointer (x, w, Y16) or C, ks < 1");
     Tmp t;
     return done(t, wv::launch_conv_pre16(x, t.up(w, (size_t)C * ks), t.up(bias, C), Y16, B, C, T, ks, in_scale, (hipStream_t)stream), (hipStream_t)stream);
 }
 int wv_h16_resblock(const void* X16, float pre_scale, const float* w_pw1, const float* w_dw1, const float* b1, const float* w_pw2, const float* w_dw2,
                     const float* b2, void* Y16, void* Yact16, int B, int C, int T, float out_scale, float act_scale, void* stream) {
-    if (!X16 || !w_pw1 || !w_dw1 || !w_pw2 || !w_dw2 || (!Y16 && !Yact16) || B < 1 || C < 1 || T < 1) return WV_EINVAL;
+    if (!X16 || !w_pw1 || !w_dw1 || !w_pw2 || !w_dw2 || (!Y16 && !Yact16) || B < 1 || C < 1 || T < 1) return fail(WV_EINVAL, "null pointer (X16, a weight, or both Y16 and Yact16) or B, C, T < 1");
     Tmp t;
     wv::RhArgs a{};
     a.X = X16; a.pre_scale = pre_scale;
@@ -129,12 +142,12 @@ int wv_h16_resblock(const void* X16, float pre_scale, const float* w_pw1, const 
     a.tab1 = t.upv(wv::pack_rh_table(w_dw1, b1, C, wv::RH_LOG2E)); a.tab2 = t.upv(wv::pack_rh_table(w_dw2, b2, C, 1.0));
     a.Y = Y16; a.Yact = Yact16; a.out_scale = out_scale; a.act_scale = act_scale; a.B = B; a.C = C; a.T = T;
     const hipError_t e = wv::launch_resblock16(a, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported(std::string("C in {32, 64, 96, 128, 192, 256, 384, 512, 768}") + FUSED_GATES);
     return done(t, e, (hipStream_t)stream);
 }
 int wv_h16_conv(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const void* resid16, void* Y16, void* Yact16, float* Yf32,
                 int B, int K, int M, int Tin, int ks, int stride, int pad, float out_scale, float act_scale, void* stream) {
-    if (!X16 || !w_pw || B < 1 || K < 1 || M < 1 || Tin < 1 || ks < 1 || stride < 1 || pad < 0) return WV_EINVAL;
+    if (!X16 || !w_pw || B < 1 || K < 1 || M < 1 || Tin < 1 || ks < 1 || stride < 1 || pad < 0) return fail(WV_EINVAL, "null pointer (X16, w_pw), B, K, M, Tin, ks, stride < 1 or pad < 0");
     Tmp t;
     wv::Conv16Args a{};
     a.X = X16; a.w = t.h16(w_pw, w_dw, M, K, ks); a.bias = t.up(bias, M); a.resid = resid16; a.Y = Y16; a.Yact = Yact16; a.Yf32 = Yf32;
@@ -146,10 +159,10 @@ int wv_h16_conv(const void* X16, const float* w_pw, const float* w_dw, const flo
 int wv_op_dw_pw(const float* X, const float* w_dw, const float* w_pw, const float* bias, float* Y,
                 int B, int K, int M, int Tin, int mode, int ks_or_ratio, float pre_scale, int pre_elu,
                 int l2norm, int accumulate, float out_scale, float* Yact, float act_scale, void* stream) {
-    if (!X || !w_pw || !Y || B < 1 || K < 1 || M < 1 || Tin < 1) return WV_EINVAL;
+    if (!X || !w_pw || !Y || B < 1 || K < 1 || M < 1 || Tin < 1) return fail(WV_EINVAL, "null pointer (X, w_pw, Y) or B, K, M, Tin < 1");
     if (mode == 2 && !l2norm && !accumulate) {
         // upsample unit = K1 kernel with the ConvTranspose producer in its loader (as the model runs it)
-        if (!w_dw || ks_or_ratio < 1) return WV_EINVAL;
+        if (!w_dw || ks_or_ratio < 1) return fail(WV_EINVAL, "mode 2 (upsample) needs w_dw and a ratio >= 1");
         Tmp t;
         std::vector<float> taps((size_t)M * 5, 0.f);
         for (int m = 0; m < M; ++m) taps[(size_t)m * 5 + 4] = 1.f;
@@ -166,9 +179,9 @@ int wv_op_dw_pw(const float* X, const float* w_dw, const float* w_pw, const floa
     wv::DwPwArgs a{};
     a.X = X; a.pw = t.pw(w_pw, M, K); a.bias = t.up(bias, M); a.Y = Y;
     a.B = B; a.Tin = Tin; a.mode = mode; a.Tout = Tin;
-    if (mode == 2) return WV_EINVAL;                  // the upsample unit has neither L2-norm nor accumulate
+    if (mode == 2) return fail(WV_EINVAL, "mode 2 (upsample) has neither L2-norm nor accumulate");                  // the upsample unit has neither L2-norm nor accumulate
     const bool k1_form = mode == 0 && accumulate && !l2norm && !bias && M >= 128;
-    if (Yact && !k1_form) return WV_EINVAL;           // the second output exists on the pw_dw kernel only
+    if (Yact && !k1_form) return fail(WV_EINVAL, "Yact exists only in mode 2 and in the accumulate form with M >= 128");           // the second output exists on the pw_dw kernel only
     if (mode == 0 && accumulate && !l2norm && !bias && M >= 128) {
         // SpecBlock add as the model runs it for M >= 128: K1 kernel, identity stencil, Y as residual
         Tmp t;
@@ -212,8 +225,8 @@ static std::vector<float> stft_basis_host(const float* basis_or_null, int n_fft)
 
 int wv_op_stft_logmag(const float* wav, const float* basis_or_null, float* P, int B, int T, int n_fft,
                       int hop, float mean, float std, void* stream) {
-    if (!wav || !P || B < 1 || T < 1 || hop < 1) return WV_EINVAL;
-    if (n_fft < 4 || (n_fft & 1)) return WV_EINVAL;
+    if (!wav || !P || B < 1 || T < 1 || hop < 1) return fail(WV_EINVAL, "null pointer (wav, P) or B, T, hop < 1");
+    if (n_fft < 4 || (n_fft & 1)) return fail(WV_EINVAL, "n_fft must be even and >= 4");
     const int F = n_fft / 2 + 1;
     const std::vector<float> basis = stft_basis_host(basis_or_null, n_fft);
     std::vector<float> bt, side;
@@ -228,8 +241,8 @@ int wv_op_stft_logmag(const float* wav, const float* basis_or_null, float* P, in
 
 int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* w_pw, const float* x, float* Y, float* Yact, int B, int T,
                      int n_fft, int hop, int M, float mean, float std, float out_scale, float act_scale, void* stream) {
-    if (!wav || !w_pw || !x || (!Y && !Yact) || B < 1 || T < 1 || hop < 1 || M < 1) return WV_EINVAL;
-    if (n_fft < 4 || (n_fft & 1)) return WV_EINVAL;
+    if (!wav || !w_pw || !x || (!Y && !Yact) || B < 1 || T < 1 || hop < 1 || M < 1) return fail(WV_EINVAL, "null pointer (wav, w_pw, x, or both Y and Yact) or B, T, hop, M < 1");
+    if (n_fft < 4 || (n_fft & 1)) return fail(WV_EINVAL, "n_fft must be even and >= 4");
     const int F = n_fft / 2 + 1;
     const std::vector<float> basis = stft_basis_host(basis_or_null, n_fft);
     std::vector<float> bt, side;
@@ -242,13 +255,13 @@ int wv_op_spec_block(const float* wav, const float* basis_or_null, const float* 
     wv::SpecAddArgs q{};
     q.pw = t.pw(w_pw, M, F); q.resid = x; q.Y = Y; q.Yact = Yact; q.out_scale = out_scale; q.act_scale = act_scale;
     const hipError_t e = wv::launch_stft_spec(a, q, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported(std::string("n_fft = M in {64, 128}, more than 64 frames, ceil(T / hop) % 4 == 0") + FUSED_GATES);
     return done(t, e, (hipStream_t)stream);
 }
 
 int wv_h16_upsample(const void* X16, const float* w_ct, const float* w_pw, const float* bias, void* Y16, void* Yact16,
                     int B, int K, int M, int Tin, int ratio, float act_scale, void* stream) {
-    if (!X16 || !w_ct || !w_pw || (!Y16 && !Yact16) || B < 1 || K < 1 || M < 1 || Tin < 1 || ratio < 1) return WV_EINVAL;
+    if (!X16 || !w_ct || !w_pw || (!Y16 && !Yact16) || B < 1 || K < 1 || M < 1 || Tin < 1 || ratio < 1) return fail(WV_EINVAL, "null pointer (X16, w_ct, w_pw, or both Y16 and Yact16) or B, K, M, Tin, ratio < 1");
     Tmp t;
     wv::Conv16Args a{};
     const int mb = wv::up16_block(M, ratio) ? wv::up16_block(M, ratio) : M;
@@ -260,10 +273,10 @@ int wv_h16_upsample(const void* X16, const float* w_ct, const float* w_pw, const
 }
 int wv_h16_tail(const void* A16, const float* w, const float* bias, const float* x, float* out, int B, int C, int Tin, int T, int ks,
                 float out_scale, void* stream) {
-    if (!A16 || !w || !out || C < 1 || ks < 1) return WV_EINVAL;
+    if (!A16 || !w || !out || C < 1 || ks < 1) return fail(WV_EINVAL, "null pointer (A16, w, out) or C, ks < 1");
     Tmp t;
     const hipError_t e = wv::launch_tail16(A16, t.up(w, (size_t)C * ks), t.up(bias, 1), x, out, B, C, Tin, T, ks, out_scale, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported("ks in {3, 5, 7}");
     return done(t, e, (hipStream_t)stream);
 }
 int wv_h16_l2norm(const float* lat, void* Y16, int B, int D, int Fr, void* stream) {
@@ -272,20 +285,20 @@ int wv_h16_l2norm(const float* lat, void* Y16, int B, int D, int Fr, void* strea
 }
 int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T,
                 const int* keep_lo, const int* keep_hi, float* psum, void* stream) {
-    if (!lat || !wc || !bc || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return WV_EINVAL;
-    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return WV_EINVAL;      // Fr = ceil(T / hop), as the nets' latents have
-    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32) return WV_EINVAL;               // launch_head16's gate
+    if (!lat || !wc || !bc || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return fail(WV_EINVAL, "null pointer (lat, wc, bc) or B, D, nb, hop, Fr, T < 1");
+    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return fail(WV_EINVAL, "Fr is not ceil(T / hop)");      // Fr = ceil(T / hop), as the nets' latents have
+    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0");               // launch_head16's gate
     Tmp t;
     wv::H16Weight w;
     const std::vector<uint16_t> q = wv::pack_head16(wc, D, nb, hop, &w);
     w.wq = t.upb(q.data(), q.size() * sizeof(uint16_t));
     const hipError_t e = wv::launch_head16(lat, w, t.up(bc, nb), mean_prob, B, D, nb, hop, Fr, T, (hipStream_t)stream, keep_lo, keep_hi, psum);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported("D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, and a weight pack of exactly that shape");
     return done(t, e, (hipStream_t)stream);
 }
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
                      int B, int K, int M, int Tin, int ks, int stride, int pad, float act_scale, void* stream) {
-    if (!X16 || !w_pw || !film || bands < 1 || B < 1 || K < 1 || M < 1 || Tin < 1 || ks < 1 || stride < 1 || pad < 0) return WV_EINVAL;
+    if (!X16 || !w_pw || !film || bands < 1 || B < 1 || K < 1 || M < 1 || Tin < 1 || ks < 1 || stride < 1 || pad < 0) return fail(WV_EINVAL, "null pointer (X16, w_pw, film), bands, B, K, M, Tin, ks, stride < 1 or pad < 0");
     Tmp t;
     wv::Conv16Args a{};
     a.X = X16; a.w = t.h16(w_pw, w_dw, M, K, ks); a.bias = t.up(bias, M); a.Y = Y16; a.Yact = Yact16;
@@ -295,7 +308,7 @@ int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, cons
 }
 int wv_h16_spec_block(const float* wav, const float* basis_or_null, const float* w_pw, const void* x16, void* Y16, void* Yact16, int B, int T,
                       int n_fft, int hop, int M, float mean, float std_, float out_scale, float act_scale, void* stream) {
-    if (!wav || !w_pw || !x16 || (!Y16 && !Yact16) || B < 1 || T < 1 || n_fft < 2 || (n_fft & 1) || hop < 1 || (M != n_fft && 2 * M != n_fft) || !(std_ > 0.f)) return WV_EINVAL;
+    if (!wav || !w_pw || !x16 || (!Y16 && !Yact16) || B < 1 || T < 1 || n_fft < 2 || (n_fft & 1) || hop < 1 || (M != n_fft && 2 * M != n_fft) || !(std_ > 0.f)) return fail(WV_EINVAL, "null pointer (wav, w_pw, x16, or both Y16 and Yact16), B, T, hop < 1, n_fft odd or < 2, M not n_fft or n_fft / 2, or std <= 0");
     Tmp t;
     const std::vector<float> basis = stft_basis_host(basis_or_null, n_fft);
     std::vector<uint16_t> q4[4];
@@ -312,7 +325,7 @@ int wv_h16_spec_block(const float* wav, const float* basis_or_null, const float*
     a.c1 = 0.5f * 0.69314718055994531f / std_; a.c0 = -mean / std_;
     a.B = B; a.T = T; a.Tf = (T + hop - 1) / hop; a.n_fft = n_fft; a.hop = hop;
     const hipError_t e = wv::launch_spec16(a, (hipStream_t)stream);
-    if (e == hipErrorNotSupported) return WV_EINVAL;
+    if (e == hipErrorNotSupported) return unsupported(std::string("(n_fft, hop) in {(64,1),(128,2),(256,8),(512,40),(1024,320)} with M = n_fft, {(64,1),(128,4),(256,32)} with M = n_fft / 2") + FUSED_GATES);
     return done(t, e, (hipStream_t)stream);
 }
 
@@ -383,7 +396,6 @@ __global__ __launch_bounds__(256) void stft_repack_kernel(const float* __restric
     bt[(size_t)n * Mp + col] = v;
     bq[((size_t)(n >> 2) * Mp + col) * 4 + (n & 3)] = v;
 }
-size_t al256o(size_t x) { return (x + 255) & ~(size_t)255; }
 // one GEMM of the plan on the generic core: Y[b][M][Tf] = W[M][K] @ Xin[b][K][Tf], wt = W's K-major pack
 hipError_t stft_plan_gemm(const float* Xin, int M, int K, const float* wt, float* Y, int B, int Tf, hipStream_t s) {
     wv::DwPwArgs a{};
@@ -405,7 +417,7 @@ hipError_t stft_plan_frames_dc(const wv_stft_plan* p, const float* wav, const fl
 extern "C" {
 
 int wv_stft_plan_create(int n_fft, const float* basis_or_null, wv_stft_plan** out) {
-    if (!out || n_fft < 4 || (n_fft & 1)) return WV_EINVAL;
+    if (!out || n_fft < 4 || (n_fft & 1)) return fail(WV_EINVAL, "null out, or n_fft not even and >= 4");
     const std::vector<float> basis = stft_basis_host(basis_or_null, n_fft);
     std::vector<float> bt, side;
     auto* p = new wv_stft_plan();
@@ -425,7 +437,7 @@ int wv_stft_plan_create(int n_fft, const float* basis_or_null, wv_stft_plan** ou
         return hipMalloc((void**)d, v.size() * sizeof(float)) == hipSuccess &&
                hipMemcpy(*d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
     };
-    if (!(up(&p->basis_t, bt) && up(&p->basis_q, bq) && up(&p->side, side) && up(&p->wt_fwd, wf) && up(&p->wt_bwd, wb))) { delete p; return WV_EHIP; }
+    if (!(up(&p->basis_t, bt) && up(&p->basis_q, bq) && up(&p->side, side) && up(&p->wt_fwd, wf) && up(&p->wt_bwd, wb))) { delete p; return fail(WV_EHIP, "device allocation or upload of the basis packs failed"); }
     *out = p;
     return WV_OK;
 }
@@ -433,32 +445,33 @@ int wv_stft_plan_create(int n_fft, const float* basis_or_null, wv_stft_plan** ou
 void wv_stft_plan_destroy(wv_stft_plan* p) { delete p; }
 
 int wv_stft_plan_logmag(const wv_stft_plan* p, const float* wav, float* P, int B, int T, int hop, float mean, float std, void* stream) {
-    if (!p || !wav || !P || B < 1 || T < 1 || hop < 1 || !(std > 0.f)) return WV_EINVAL;
+    if (!p || !wav || !P || B < 1 || T < 1 || hop < 1 || !(std > 0.f)) return fail(WV_EINVAL, "null pointer (plan, wav, P), B, T, hop < 1 or std <= 0");
     wv::StftArgs a{};
     a.wav = wav; a.basis_t = p->basis_t; a.basis_q = p->basis_q; a.side = p->side; a.P = P; a.B = B; a.T = T; a.Tf = (T + hop - 1) / hop;
     a.n_fft = p->n_fft; a.hop = hop; a.F = p->n_fft / 2 + 1; a.Mp = p->Mp; a.mean = mean; a.inv_std = 1.f / std;
     const hipError_t e = wv::launch_stft_logmag(a, (hipStream_t)stream);
-    return e == hipSuccess ? WV_OK : (e == hipErrorInvalidValue ? WV_EINVAL : WV_EHIP);
+    return launched(e);
 }
 
 size_t wv_stft_plan_backward_workspace_bytes(const wv_stft_plan* p, int B, int T, int hop) {
     if (!p || B < 1 || T < 1 || hop < 1) return 0;
     const int Tf = (T + hop - 1) / hop, F = p->n_fft / 2 + 1;
-    return al256o((size_t)B * p->n_fft * Tf * 4) + al256o((size_t)B * 2 * F * Tf * 4);
+    return al256((size_t)B * p->n_fft * Tf * 4) + al256((size_t)B * 2 * F * Tf * 4);
 }
 
 int wv_stft_plan_backward(const wv_stft_plan* p, const float* wav, const float* dP, float* dwav, int accumulate, int B, int T, int hop, float std,
                           void* ws, size_t ws_bytes, void* stream) {
-    if (!p || !wav || !dP || !dwav || B < 1 || T < 1 || hop < 1 || !(std > 0.f) || B > 65535) return WV_EINVAL;
-    if (!ws || ws_bytes < wv_stft_plan_backward_workspace_bytes(p, B, T, hop)) return WV_ENOMEM;
+    if (!p || !wav || !dP || !dwav || B < 1 || T < 1 || hop < 1 || !(std > 0.f) || B > 65535) return fail(WV_EINVAL, "null pointer (plan, wav, dP, dwav), B, T, hop < 1, std <= 0 or B > 65535");
+    if (!ws || ws_bytes < wv_stft_plan_backward_workspace_bytes(p, B, T, hop)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int n = p->n_fft, F = n / 2 + 1, Tf = (T + hop - 1) / hop;
     float* X = (float*)ws;
-    float* Cm = (float*)((char*)ws + al256o((size_t)B * n * Tf * 4));
-    if (stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s) != hipSuccess) return WV_EHIP;
-    if (stft_plan_gemm(Cm, n, 2 * F, p->wt_bwd, X, B, Tf, s) != hipSuccess) return WV_EHIP;      // Q into the frames buffer
+    float* Cm = (float*)((char*)ws + al256((size_t)B * n * Tf * 4));
+    WV_HIP_TRY(stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s));
+    WV_HIP_TRY(stft_plan_gemm(Cm, n, 2 * F, p->wt_bwd, X, B, Tf, s));      // Q into the frames buffer
     hipLaunchKernelGGL(stft_overlap_add_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, X, dwav, T, Tf, n, hop, accumulate);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 // dBasis[m][n] = sum_{b,t} dC[b][m][t] * frames[b][n][t]: frames, the forward GEMM and dC exactly as wv_stft_plan_backward forms them,
@@ -471,29 +484,30 @@ size_t wv_stft_plan_basis_grad_workspace_bytes(const wv_stft_plan* p, int B, int
 
 int wv_stft_plan_basis_grad(const wv_stft_plan* p, const float* wav, const float* dP, float* dBasis, int B, int T, int hop, float std,
                             void* ws, size_t ws_bytes, void* stream) {
-    if (!p || !wav || !dP || !dBasis || B < 1 || T < 1 || hop < 1 || !(std > 0.f) || B > 65535 || p->n_fft > 65535) return WV_EINVAL;
-    if (!ws || ws_bytes < wv_stft_plan_basis_grad_workspace_bytes(p, B, T, hop)) return WV_ENOMEM;
+    if (!p || !wav || !dP || !dBasis || B < 1 || T < 1 || hop < 1 || !(std > 0.f) || B > 65535 || p->n_fft > 65535) return fail(WV_EINVAL, "null pointer (plan, wav, dP, dBasis), B, T, hop < 1, std <= 0, B > 65535 or n_fft > 65535");
+    if (!ws || ws_bytes < wv_stft_plan_basis_grad_workspace_bytes(p, B, T, hop)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int n = p->n_fft, F = n / 2 + 1, Tf = (T + hop - 1) / hop;
     float* X = (float*)ws;
-    float* Cm = (float*)((char*)ws + al256o((size_t)B * n * Tf * 4));
+    float* Cm = (float*)((char*)ws + al256((size_t)B * n * Tf * 4));
     float* parts = (float*)((char*)ws + wv_stft_plan_backward_workspace_bytes(p, B, T, hop));
-    if (stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s) != hipSuccess) return WV_EHIP;
+    WV_HIP_TRY(stft_plan_frames_dc(p, wav, dP, X, Cm, B, T, hop, std, s));
     const hipError_t e = wv::launch_gemm_nt_sum(s, Cm, X, dBasis, parts, B, 2 * F, n, Tf);
-    return e == hipSuccess ? WV_OK : (e == hipErrorInvalidValue ? WV_EINVAL : WV_EHIP);
+    return launched(e);
 }
 
 int wv_stft_plan_set_basis_device(wv_stft_plan* p, const float* dev_basis, void* stream) {
-    if (!p || !dev_basis || p->n_fft > 65535) return WV_EINVAL;
+    if (!p || !dev_basis || p->n_fft > 65535) return fail(WV_EINVAL, "null pointer (plan, dev_basis) or n_fft > 65535");
     const int n = p->n_fft, M2 = n + 2;
     hipLaunchKernelGGL(stft_repack_kernel, dim3((n + 255) / 256, M2), dim3(256), 0, (hipStream_t)stream, dev_basis, p->basis_t, p->basis_q, p->side,
                        p->wt_fwd, p->wt_bwd, n, p->Mp, wv::round_up(M2, wv::M_ALIGN), wv::round_up(n, wv::M_ALIGN));
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 int wv_op_conv_pre(const float* x, const float* w, const float* bias, float* Y, int B, int C, int T,
                    int ks, float in_scale, void* stream) {
-    if (!x || !w || !Y) return WV_EINVAL;
+    if (!x || !w || !Y) return fail(WV_EINVAL, "null pointer (x, w, Y)");
     Tmp t;
     return done(t, wv::launch_conv_pre(x, t.up(w, (size_t)C * ks), t.up(bias, C), Y, nullptr, 0.f, B, C, T, ks,
                                        in_scale, (hipStream_t)stream), (hipStream_t)stream);
@@ -501,7 +515,7 @@ int wv_op_conv_pre(const float* x, const float* w, const float* bias, float* Y, 
 
 int wv_op_tail(const float* H, const float* w, const float* bias, const float* x_or_null, float* out,
                int B, int C, int Tin, int T, int ks, float pre_scale, float out_scale, void* stream) {
-    if (!H || !w || !out) return WV_EINVAL;
+    if (!H || !w || !out) return fail(WV_EINVAL, "null pointer (H, w, out)");
     Tmp t;
     return done(t, wv::launch_tail(H, t.up(w, (size_t)C * ks), t.up(bias, 1), x_or_null, out, B, C, Tin,
                                    T, ks, pre_scale, out_scale, (hipStream_t)stream), (hipStream_t)stream);
@@ -510,8 +524,8 @@ int wv_op_tail(const float* H, const float* w, const float* bias, const float* x
 int wv_op_head(const float* Z, const float* w_rev, const float* b_rev, const float* w_last,
                const float* b_last, float* logits, float* mean_prob, int B, int D, int O, int nb,
                int hop, int Fr, int T, void* stream) {
-    if (!Z || !w_rev || !b_rev || !w_last || !b_last || (!logits && !mean_prob)) return WV_EINVAL;
-    if (T > Fr * hop) return WV_EINVAL;
+    if (!Z || !w_rev || !b_rev || !w_last || !b_last || (!logits && !mean_prob)) return fail(WV_EINVAL, "null pointer (Z, a weight or bias, or both logits and mean_prob)");
+    if (T > Fr * hop) return fail(WV_EINVAL, "T > Fr * hop");
     std::vector<float> wc((size_t)D * nb * hop), bc(nb);
     for (int d = 0; d < D; ++d)
         for (int n = 0; n < nb; ++n)

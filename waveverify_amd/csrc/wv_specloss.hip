@@ -20,7 +20,7 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 #include "wv_kernels.h"
 
 namespace {
@@ -226,7 +226,8 @@ __global__ __launch_bounds__(SL_NT) void specloss_reduce_kernel(const float* __r
     }
 }
 
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+using wv::al256;
+using wv::fail;
 
 }  // namespace
 
@@ -298,11 +299,11 @@ extern "C" {
 
 int wv_specloss_plan_create(int n_scales, const int* window_lengths, const int* flags, const int* n_mels, const float* params,
                             const float* windows, const float* mel_filters, wv_specloss_plan** out) {
-    if (!out || n_scales < 1 || n_scales > SL_MAX_SCALES || !window_lengths || !flags || !params || !windows) return WV_EINVAL;
+    if (!out || n_scales < 1 || n_scales > SL_MAX_SCALES || !window_lengths || !flags || !params || !windows) return fail(WV_EINVAL, "null pointer (out, window_lengths, flags, params, windows) or n_scales outside [1, " + std::to_string(SL_MAX_SCALES) + "]");
     for (int i = 0; i < n_scales; ++i) {
         const int w = window_lengths[i];
-        if (w < 8 || (w & 3) || w > 65536 || flags[i] < 1 || flags[i] > 3) return WV_EINVAL;
-        if ((flags[i] & 2) && (!n_mels || n_mels[i] < 1 || !mel_filters)) return WV_EINVAL;
+        if (w < 8 || (w & 3) || w > 65536 || flags[i] < 1 || flags[i] > 3) return fail(WV_EINVAL, "a window length that is not a multiple of 4 in [8, 65536], or flags outside [1, 3]");
+        if ((flags[i] & 2) && (!n_mels || n_mels[i] < 1 || !mel_filters)) return fail(WV_EINVAL, "a mel term without n_mels >= 1 or without mel_filters");
     }
     auto* p = new wv_specloss_plan();
     auto up = [](auto** d, const auto& v) {
@@ -360,7 +361,7 @@ int wv_specloss_plan_create(int n_scales, const int* window_lengths, const int* 
             ok = up(&s.mel_wt, wt) && up(&s.mel_idx, idx);
         }
         p->sc.push_back(s);
-        if (!ok) { delete p; return WV_EHIP; }
+        if (!ok) { delete p; return fail(WV_EHIP, "device allocation or upload of a scale's packs failed"); }
     }
     *out = p;
     return WV_OK;
@@ -375,13 +376,13 @@ size_t wv_specloss_workspace_bytes(const wv_specloss_plan* p, int B, int T) {
 
 int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int B, int T, float* terms, float* totals, float* dwm,
                 float stft_grad_scale, float mel_grad_scale, void* ws, size_t ws_bytes, void* stream) {
-    if (!p || !wm || !x || !terms || !totals || B < 1 || T < 1 || B > 65535) return WV_EINVAL;
+    if (!p || !wm || !x || !terms || !totals || B < 1 || T < 1 || B > 65535) return fail(WV_EINVAL, "null pointer (plan, wm, x, terms, totals), B outside [1, 65535] or T < 1");
     for (const auto& s : p->sc) {
-        if (T <= s.w / 2) return WV_EINVAL;                       // reflect padding needs w/2 < T
-        if ((long long)B * (T / (s.w / 4) + 1) * (s.w + 2) > (1LL << 31) - 1) return WV_EINVAL;
+        if (T <= s.w / 2) return fail(WV_EINVAL, "T <= w / 2 for some scale: the reflect padding needs more samples");                       // reflect padding needs w/2 < T
+        if ((long long)B * (T / (s.w / 4) + 1) * (s.w + 2) > (1LL << 31) - 1) return fail(WV_EINVAL, "B * frames * (w + 2) exceeds 2^31 - 1 for some scale");
     }
     const SlLayout L = sl_layout(p, B, T);
-    if (!ws || ws_bytes < L.total) return WV_ENOMEM;
+    if (!ws || ws_bytes < L.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t st = (hipStream_t)stream;
     char* base = (char*)ws;
     float* Fr = (float*)(base + L.fr);
@@ -397,7 +398,7 @@ int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int 
         const int nvalid = B * q.Tf, F = q.F;
         const double n_stft = (double)B * F * q.Tf, n_mel = (double)B * s.n_mels * q.Tf;
         hipLaunchKernelGGL(specloss_frames_kernel, dim3(sl_nb(q.ncols), q.w, 2), dim3(SL_NT), 0, st, wm, x, Fr, B, T, q.Tf, q.ncols, q.w, q.hop);
-        if (sl_gemm(Fr, 2 * F, q.w, s.wt_fwd, C, 2, q.ncols, st) != hipSuccess) return WV_EHIP;
+        WV_HIP_TRY(sl_gemm(Fr, 2 * F, q.w, s.wt_fwd, C, 2, q.ncols, st));
         SlMel mel{};
         if (s.flags & 2) {
             mel.lo = s.mel_idx; mel.hi = mel.lo + s.n_mels; mel.off = mel.hi + s.n_mels; mel.mlo = mel.off + s.n_mels; mel.mhi = mel.mlo + F;
@@ -413,7 +414,7 @@ int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int 
                                (dwm && (s.flags & 2)) ? dm : nullptr, dwm ? G : nullptr, (s.flags & 1) ? part + L.poff[i] : nullptr);
         }
         if (dwm) {
-            if (sl_gemm(G, q.w, 2 * F, s.wt_bwd, Fr, 1, q.ncols, st) != hipSuccess) return WV_EHIP;
+            WV_HIP_TRY(sl_gemm(G, q.w, 2 * F, s.wt_bwd, Fr, 1, q.ncols, st));
             hipLaunchKernelGGL(specloss_ola_kernel, dim3((T + SL_NT - 1) / SL_NT, B), dim3(SL_NT), 0, st, Fr, dwm, T, q.Tf, q.ncols, q.w, q.hop);
         }
         r.flags[i] = s.flags; r.off[i] = L.poff[i]; r.nb_bins[i] = L.nb_bins[i]; r.nb_mel[i] = L.nb_mel[i];
@@ -421,7 +422,8 @@ int wv_specloss(const wv_specloss_plan* p, const float* wm, const float* x, int 
         r.stft_lw[i] = s.stft[0]; r.stft_mw[i] = s.stft[1]; r.mel_lw[i] = s.mel[0]; r.mel_mw[i] = s.mel[1];
     }
     hipLaunchKernelGGL(specloss_reduce_kernel, dim3(1), dim3(SL_NT), 0, st, part, r, terms, totals);
-    return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP;
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
 }
 
 }  // extern "C"

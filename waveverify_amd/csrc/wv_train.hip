@@ -30,8 +30,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/waveverify_hip.h"
 #include "wv_dev.h"
+#include "wv_host.h"
 
 namespace wv {
 
@@ -1108,55 +1108,63 @@ __global__ __launch_bounds__(256) void bce_kernel(const float* __restrict__ z, c
 }  // namespace wv
 
 // ================================================================================================ C ABI
-namespace {
-thread_local std::string g_terr;
-int tfail(int code, const std::string& msg) { g_terr = msg; return code; }
-size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-}  // namespace
+using wv::al256;
+using wv::fail;
 
-struct wv_train_unit {
+namespace wv {
+// What the training handles share: each owns its device buffers.
+struct TrainHandle {
+    std::vector<void*> owned;
+    TrainHandle() = default;
+    TrainHandle(const TrainHandle&) = delete;
+    TrainHandle& operator=(const TrainHandle&) = delete;
+    ~TrainHandle() { for (void* p : owned) (void)hipFree(p); }
+    // n floats, zeroed on request; nullptr when the allocation (or the memset) fails
+    float* alloc(size_t n, bool zero) {
+        void* p = nullptr;
+        if (hipMalloc(&p, n * sizeof(float)) != hipSuccess) return nullptr;
+        owned.push_back(p);
+        return (!zero || hipMemset(p, 0, n * sizeof(float)) == hipSuccess) ? (float*)p : nullptr;
+    }
+    // [rows][5] = (0, 0, 0, 0, 1): the identity stencil that makes the pw_dw kernel a plain GEMM
+    float* identity_taps(int rows) {
+        std::vector<float> taps((size_t)rows * 5, 0.f);
+        for (int m = 0; m < rows; ++m) taps[(size_t)m * 5 + 4] = 1.f;
+        float* d = alloc(taps.size(), false);
+        return (d && hipMemcpy(d, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess) ? d : nullptr;
+    }
+};
+}  // namespace wv
+
+struct wv_train_unit : wv::TrainHandle {
     int K = 0, M = 0, ks = 5, stride = 1, pad = 4, Mp = 0, KpT = 0;
     float *w_pw = nullptr, *inv_pw = nullptr, *wq = nullptr, *wqT = nullptr, *wt = nullptr, *wtT = nullptr;   // folded 1x1 weight + packs
     float *w_dw = nullptr, *inv_dw = nullptr, *id_taps = nullptr;                 // folded taps [M][ks]; identity stencil rows
     float *dW = nullptr, *dwdb = nullptr, *dw_taps = nullptr;                     // weight-gradient scratch
     const float* folded[4] = {nullptr, nullptr, nullptr, nullptr};               // the (g_pw, v_pw, g_dw, v_dw) the folded copies were made from
-    std::vector<void*> owned;
-    ~wv_train_unit() { for (void* p : owned) (void)hipFree(p); }
 };
 
 extern "C" {
 
-const char* wv_train_last_error(void) { return g_terr.c_str(); }
-
 int wv_train_unit_create(int K, int M, int ks, int stride, wv_train_unit** out) {
-    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096) return tfail(WV_EINVAL, "bad channel count");
-    if (ks < 1 || ks > wv::TRAIN_MAX_KS || stride < 1 || ks - stride < 0) return tfail(WV_EINVAL, "bad kernel size / stride");
+    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096) return fail(WV_EINVAL, "bad channel count");
+    if (ks < 1 || ks > wv::TRAIN_MAX_KS || stride < 1 || ks - stride < 0) return fail(WV_EINVAL, "bad kernel size / stride");
     auto* h = new wv_train_unit();
     h->K = K; h->M = M; h->ks = ks; h->stride = stride; h->pad = ks - stride;
     h->Mp = wv::round_up(M, wv::M_ALIGN); h->KpT = wv::round_up(K, wv::M_ALIGN);
     const size_t nq = (size_t)wv::round_up(K, 32) * h->Mp, nqT = (size_t)wv::round_up(M, 32) * h->KpT;
-    auto alloc = [&](float** p, size_t n, bool zero) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return !zero || hipMemset(*p, 0, n * sizeof(float)) == hipSuccess;
-    };
     const int R = std::max(K, M);
-    std::vector<float> taps((size_t)R * 5, 0.f);
-    for (int m = 0; m < R; ++m) taps[(size_t)m * 5 + 4] = 1.f;
-    bool ok = alloc(&h->w_pw, (size_t)M * K, false) && alloc(&h->inv_pw, M, false) && alloc(&h->wq, nq, true) &&
-              alloc(&h->wqT, nqT, true) && alloc(&h->wt, (size_t)wv::round_up(K, wv::BK) * h->Mp, true) &&
-              alloc(&h->wtT, (size_t)wv::round_up(M, wv::BK) * h->KpT, true) && alloc(&h->w_dw, (size_t)M * ks, false) && alloc(&h->inv_dw, M, false) &&
-              alloc(&h->id_taps, taps.size(), false) && alloc(&h->dW, (size_t)M * K, false) &&
-              alloc(&h->dwdb, (size_t)M * (ks + 1), false) && alloc(&h->dw_taps, (size_t)M * ks, false) &&
-              hipMemcpy(h->id_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete h; return tfail(WV_EHIP, "device allocation failed"); }
+    bool ok = (h->w_pw = h->alloc((size_t)M * K, false)) && (h->inv_pw = h->alloc(M, false)) && (h->wq = h->alloc(nq, true)) &&
+              (h->wqT = h->alloc(nqT, true)) && (h->wt = h->alloc((size_t)wv::round_up(K, wv::BK) * h->Mp, true)) &&
+              (h->wtT = h->alloc((size_t)wv::round_up(M, wv::BK) * h->KpT, true)) && (h->w_dw = h->alloc((size_t)M * ks, false)) && (h->inv_dw = h->alloc(M, false)) &&
+              (h->id_taps = h->identity_taps(R)) && (h->dW = h->alloc((size_t)M * K, false)) &&
+              (h->dwdb = h->alloc((size_t)M * (ks + 1), false)) && (h->dw_taps = h->alloc((size_t)M * ks, false));
+    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
 
 void wv_train_unit_destroy(wv_train_unit* h) { delete h; }
-int wv_train_half_create(int C, wv_train_unit** out) { return wv_train_unit_create(C, C, 5, 1, out); }
-void wv_train_half_destroy(wv_train_unit* h) { delete h; }
 
 // splits of the dW GEMM: enough workgroups to fill the chip even when the weight matrix is one 64 x 64 tile (C = 64 layers), within
 // a 128 MB scratch; a function of the shapes only, so the summation order -- and the result -- is reproducible
@@ -1177,17 +1185,13 @@ size_t wv_train_unit_workspace_bytes(const wv_train_unit* h, int B, int Tin) {
     const size_t am = al256((size_t)B * h->M * Tin * 4), ak = al256((size_t)B * h->K * Tin * 4);
     return 2 * am + ak + al256((size_t)B * h->M * (h->ks + 1) * 4) + al256((size_t)nt_plan(B, Tin, h->M, h->K).S * h->M * h->K * 4);
 }
-size_t wv_train_half_workspace_bytes(const wv_train_unit* h, int B, int T) { return wv_train_unit_workspace_bytes(h, B, T); }
-
-#define T_LAUNCH(expr)                                                                              \
-    do { hipError_t e_ = (expr); if (e_ != hipSuccess) return tfail(WV_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)
 
 // fold both weights of the unit for this step (live weight norm)
 static int fold_step(wv_train_unit* h, const float* g_pw, const float* v_pw, const float* g_dw, const float* v_dw, hipStream_t s) {
     const wv::WnFoldArgs fa{g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->M, h->K, h->Mp, h->KpT, nullptr, 1.f, h->wt, h->wtT};
     const wv::WnFoldArgs fb{g_dw, v_dw, h->w_dw, h->inv_dw, nullptr, nullptr, h->M, h->ks, 0, 0, nullptr, 1.f, nullptr, nullptr};
     hipLaunchKernelGGL(wv::wn_fold_pair_kernel, dim3(2 * h->M), dim3(256), 0, s, fa, fb);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     h->folded[0] = g_pw; h->folded[1] = v_pw; h->folded[2] = g_dw; h->folded[3] = v_dw;
     return WV_OK;
 }
@@ -1208,7 +1212,7 @@ static int unit_forward_impl(wv_train_unit* h, const float* x, const float* g_pw
                              const float* sum_x = nullptr, const float* sum_scale_ptr = nullptr, float sum_scale = 1.f, float* ysum = nullptr,
                              bool* summed = nullptr) {
     if (summed) *summed = false;
-    if (!h || !x || !g_pw || !v_pw || !g_dw || !v_dw || !y || B < 1 || Tin < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !g_pw || !v_pw || !g_dw || !v_dw || !y || B < 1 || Tin < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     int rc = fold_step(h, g_pw, v_pw, g_dw, v_dw, s);
     if (rc) return rc;
@@ -1217,29 +1221,24 @@ static int unit_forward_impl(wv_train_unit* h, const float* x, const float* g_pw
     a.B = B; a.Tin = Tin; a.Tout = t_out(h, Tin); a.ks = h->ks; a.stride = h->stride; a.dil = 1; a.pad = h->pad;
     a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
     if (h_out) {
-        if (h->stride != 1) return tfail(WV_EINVAL, "saved 1x1 output: stride-1 units only");
+        if (h->stride != 1) return fail(WV_EINVAL, "saved 1x1 output: stride-1 units only");
         wv::PwDwArgs f = a;
         f.Yraw = h_out;
         if (ysum && sum_x) { f.resid = sum_x; f.Ysum = ysum; f.scale_ptr = sum_scale_ptr; f.out_scale = sum_scale; }
         const hipError_t e = wv::launch_pw_dw(f, s);
         if (e == hipSuccess) { if (summed && ysum && sum_x) *summed = true; return WV_OK; }
-        if (e != hipErrorNotSupported) T_LAUNCH(e);
+        if (e != hipErrorNotSupported) WV_HIP_TRY(e);
         wv::PwDwArgs r = a;                                   // ragged / narrow layers: H by the identity stencil, as the backward used to
         r.dw_w = h->id_taps; r.dw_b = nullptr; r.Y = h_out; r.Tout = Tin; r.ks = 5; r.stride = 1; r.pad = 4;
-        T_LAUNCH(wv::launch_pw_dw(r, s));
+        WV_HIP_TRY(wv::launch_pw_dw(r, s));
     }
-    T_LAUNCH(wv::launch_pw_dw(a, s));
+    WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
 
 int wv_train_unit_forward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
                           const float* v_dw, const float* bias, float pre_scale, int pre_elu, float* y, int B, int Tin, void* stream) {
     return unit_forward_impl(h, x, g_pw, v_pw, g_dw, v_dw, bias, pre_scale, pre_elu, y, nullptr, B, Tin, stream);
-}
-
-int wv_train_half_forward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                          const float* v_dw, const float* bias, float pre_scale, float* y, int B, int T, void* stream) {
-    return wv_train_unit_forward(h, x, g_pw, v_pw, g_dw, v_dw, bias, pre_scale, 1, y, B, T, stream);
 }
 
 // h_saved (optional): the forward's 1x1 output (unit_forward_impl), else it is recomputed here.  dx_add (optional, with pre_elu): a
@@ -1264,8 +1263,8 @@ static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_p
                               const float* dot_v, float* dot_partial) {
     if (added) *added = false;
     if (!h || !x || !g_pw || !v_pw || !g_dw || !v_dw || !dy || !dg_pw || !dv_pw || !dg_dw || !dv_dw || !db)
-        return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_unit_workspace_bytes(h, B, Tin)) return tfail(WV_ENOMEM, "workspace too small");
+        return fail(WV_EINVAL, "null argument");
+    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_unit_workspace_bytes(h, B, Tin)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int M = h->M, K = h->K, ks = h->ks, Tout = t_out(h, Tin);
     const size_t am = al256((size_t)B * M * Tin * 4), ak = al256((size_t)B * K * Tin * 4);
@@ -1279,7 +1278,7 @@ static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_p
     // A backward on saved activations reuses the folds (W, its packs, 1 / ||v||) its forward left in the handle: it must follow THAT forward,
     // with the same parameter tensors and no parameter update or other forward on this handle in between.  Other tensors are caught here.
     if (h_saved && (h->folded[0] != g_pw || h->folded[1] != v_pw || h->folded[2] != g_dw || h->folded[3] != v_dw))
-        return tfail(WV_ESTATE, "backward on saved activations: the parameters are not the ones this handle's last forward folded");
+        return fail(WV_ESTATE, "backward on saved activations: the parameters are not the ones this handle's last forward folded");
     int rc = h_saved ? WV_OK : fold_step(h, g_pw, v_pw, g_dw, v_dw, s);
     if (rc) return rc;
     if (!h_saved) {
@@ -1288,12 +1287,12 @@ static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_p
         a.X = x; a.pw = pack_of(h, false); a.dw_w = h->id_taps; a.dw_b = nullptr; a.Y = Hws;
         a.B = B; a.Tin = Tin; a.Tout = Tin; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
         a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
-        T_LAUNCH(wv::launch_pw_dw(a, s));
+        WV_HIP_TRY(wv::launch_pw_dw(a, s));
     }
     // dh, and the per-clip partial sums of the tap / bias gradients
     wv::launch_dw_bwd(s, dy, H, h->w_dw, DH, partial, M, B, Tin, Tout, ks, h->stride, h->pad, 0, dy_scale_ptr, dy_scale, dot_v, dot_partial);
     hipLaunchKernelGGL(wv::dw_param_grads_kernel, dim3(M), dim3(256), 0, s, partial, g_dw, v_dw, h->inv_dw, dg_dw, dv_dw, db, B, M, ks);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     if (dx) {
         // da = W^T @ dh on the forward's GEMM kernel, then through the activation
         wv::PwDwArgs t{};
@@ -1307,10 +1306,10 @@ static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_p
             f.Y = dx; f.resid = x; f.res_mode = 2; f.out_scale = pre_scale; f.resid2 = dx_add;
             const hipError_t e = wv::launch_pw_dw(f, s);
             if (e == hipSuccess) { fused = true; if (added && dx_add) *added = true; }
-            else if (e != hipErrorNotSupported) T_LAUNCH(e);
+            else if (e != hipErrorNotSupported) WV_HIP_TRY(e);
         }
         if (!fused) {
-            T_LAUNCH(wv::launch_pw_dw(t, s));
+            WV_HIP_TRY(wv::launch_pw_dw(t, s));
             if (pre_elu) {
                 const size_t n = (size_t)B * K * Tin, n4 = n / 4;
                 if (n4) hipLaunchKernelGGL(wv::elu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, DA, x, dx, pre_scale, n4);
@@ -1321,18 +1320,11 @@ static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_p
     // dW = sum dh a^T, then the weight-norm backward
     const NtPlan np_ = nt_plan(B, Tin, M, K);
     const int S = np_.S;
-    T_LAUNCH(wv::launch_gemm_nt(s, DH, x, parts, pre_scale, pre_elu, B, M, K, Tin, S, np_.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, DH, x, parts, pre_scale, pre_elu, B, M, K, Tin, S, np_.TC));
     wv::launch_sum_parts(s, parts, h->dW, S, (size_t)M * K);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(M), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, K);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
-}
-
-int wv_train_half_backward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                           const float* v_dw, float pre_scale, const float* dy, float* dx, float* dg_pw, float* dv_pw,
-                           float* dg_dw, float* dv_dw, float* db, int B, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!dx) return tfail(WV_EINVAL, "null argument");
-    return wv_train_unit_backward(h, x, g_pw, v_pw, g_dw, v_dw, pre_scale, 1, dy, dx, dg_pw, dv_pw, dg_dw, dv_dw, db, B, T, ws, ws_bytes, stream);
 }
 
 // ---- whole SEANetResnetBlock: y = x + s * half2(half1(pre_scale * x)) (seanet.py:245-281) ------------------------------
@@ -1344,12 +1336,12 @@ struct wv_train_block {
 };
 
 int wv_train_block_create(int C, wv_train_block** out) {
-    if (!out) return tfail(WV_EINVAL, "null argument");
+    if (!out) return fail(WV_EINVAL, "null argument");
     auto* b = new wv_train_block();
-    int rc = wv_train_half_create(C, &b->h[0]);
-    if (!rc) rc = wv_train_half_create(C, &b->h[1]);
-    if (!rc && hipMalloc((void**)&b->partial, wv::RED_BLOCKS * sizeof(float)) != hipSuccess) rc = tfail(WV_EHIP, "device allocation failed");
-    if (!rc && hipMalloc((void**)&b->tab, (size_t)2 * C * 8 * sizeof(float)) != hipSuccess) rc = tfail(WV_EHIP, "device allocation failed");
+    int rc = wv_train_unit_create(C, C, 5, 1, &b->h[0]);
+    if (!rc) rc = wv_train_unit_create(C, C, 5, 1, &b->h[1]);
+    if (!rc && hipMalloc((void**)&b->partial, wv::RED_BLOCKS * sizeof(float)) != hipSuccess) rc = fail(WV_EHIP, "device allocation failed");
+    if (!rc && hipMalloc((void**)&b->tab, (size_t)2 * C * 8 * sizeof(float)) != hipSuccess) rc = fail(WV_EHIP, "device allocation failed");
     if (rc) { delete b; return rc; }
     *out = b;
     return WV_OK;
@@ -1363,13 +1355,13 @@ size_t wv_train_block_saved_bytes(const wv_train_block* b, int B, int T) {
 
 size_t wv_train_block_workspace_bytes(const wv_train_block* b, int B, int T) {
     if (!b || B < 1 || T < 1) return 0;
-    return wv_train_half_workspace_bytes(b->h[0], B, T) + 2 * al256((size_t)B * b->h[0]->M * T * 4);
+    return wv_train_unit_workspace_bytes(b->h[0], B, T) + 2 * al256((size_t)B * b->h[0]->M * T * 4);
 }
 
 int wv_train_block_forward(wv_train_block* b, const float* x, const wv_half_params* p, const float* res_scale_param,
                            float pre_scale, float res_scale, float* y, void* saved, size_t saved_bytes, int B, int T, void* stream) {
-    if (!b || !x || !p || !y || !saved) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || (T & 3) || saved_bytes < wv_train_block_saved_bytes(b, B, T)) return tfail(WV_ENOMEM, "saved-activation buffer too small (or T % 4 != 0)");
+    if (!b || !x || !p || !y || !saved) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || T < 1 || (T & 3) || saved_bytes < wv_train_block_saved_bytes(b, B, T)) return fail(WV_ENOMEM, "saved-activation buffer too small (or T % 4 != 0)");
     hipStream_t s = (hipStream_t)stream;
     const size_t act = al256((size_t)B * b->h[0]->M * T * 4);
     float* u = (float*)saved; float* v = (float*)((char*)saved + act);
@@ -1390,8 +1382,8 @@ int wv_train_block_forward(wv_train_block* b, const float* x, const wv_half_para
             if (rc) return rc;
             hipLaunchKernelGGL(wv::rb_table_pair_kernel, dim3((2 * C * 8 + 255) / 256), dim3(256), 0, s, b->h[0]->w_dw, p[0].bias, b->tab,
                                b->h[1]->w_dw, p[1].bias, b->tab + (size_t)C * 8, C);
-            T_LAUNCH(hipGetLastError());
-            T_LAUNCH(wv::launch_resblock(f, s));
+            WV_HIP_TRY(hipGetLastError());
+            WV_HIP_TRY(wv::launch_resblock(f, s));
             return WV_OK;
         }
     }
@@ -1404,16 +1396,16 @@ int wv_train_block_forward(wv_train_block* b, const float* x, const wv_half_para
     if (!summed)
         hipLaunchKernelGGL(wv::axpy_res_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float4*)x, (const float4*)v, (float4*)y,
                            res_scale_param, res_scale, n4);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_block_backward(wv_train_block* b, const float* x, const wv_half_params* p, const float* res_scale_param,
                             float pre_scale, float res_scale, const float* dy, const void* saved, float* dx, const wv_half_grads* g,
                             float* d_res_scale_param, int B, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!b || !x || !p || !dy || !saved || !dx || !g) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || (T & 3) || !ws || ws_bytes < wv_train_block_workspace_bytes(b, B, T)) return tfail(WV_ENOMEM, "workspace too small (or T % 4 != 0)");
-    if (res_scale_param && !d_res_scale_param) return tfail(WV_EINVAL, "res_scale_param without a gradient slot");
+    if (!b || !x || !p || !dy || !saved || !dx || !g) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || T < 1 || (T & 3) || !ws || ws_bytes < wv_train_block_workspace_bytes(b, B, T)) return fail(WV_ENOMEM, "workspace too small (or T % 4 != 0)");
+    if (res_scale_param && !d_res_scale_param) return fail(WV_EINVAL, "res_scale_param without a gradient slot");
     hipStream_t s = (hipStream_t)stream;
     const int C = b->h[0]->M;
     const size_t act = al256((size_t)B * C * T * 4), n4 = (size_t)B * C * T / 4;
@@ -1432,13 +1424,13 @@ int wv_train_block_backward(wv_train_block* b, const float* x, const wv_half_par
                                 g[1].dg_dw, g[1].dv_dw, g[1].db, B, T, hws, hws_bytes, stream, H1, nullptr, nullptr, res_scale_param, res_scale, v, DV);
         if (!rc && d_res_scale_param) {
             hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, DV, B * C, res_scale, d_res_scale_param);
-            T_LAUNCH(hipGetLastError());
+            WV_HIP_TRY(hipGetLastError());
         }
     } else {
         hipLaunchKernelGGL(wv::scale_dot_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, (const float4*)dy, (const float4*)v, (float4*)DV,
                            res_scale_param, res_scale, b->partial, n4);
         if (d_res_scale_param) hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, b->partial, wv::RED_BLOCKS, res_scale, d_res_scale_param);
-        T_LAUNCH(hipGetLastError());
+        WV_HIP_TRY(hipGetLastError());
         rc = unit_backward_impl(b->h[1], u, p[1].g_pw, p[1].v_pw, p[1].g_dw, p[1].v_dw, 1.f, 1, DV, DU, g[1].dg_pw, g[1].dv_pw,
                                 g[1].dg_dw, g[1].dv_dw, g[1].db, B, T, hws, hws_bytes, stream, H1, nullptr, nullptr);
     }
@@ -1447,7 +1439,7 @@ int wv_train_block_backward(wv_train_block* b, const float* x, const wv_half_par
                                      g[0].dg_dw, g[0].dv_dw, g[0].db, B, T, hws, hws_bytes, stream, H0, dy, &added);      // + the identity shortcut
     if (rc) return rc;
     if (!added) hipLaunchKernelGGL(wv::add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)dx, (const float4*)dy, n4);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
@@ -1456,37 +1448,30 @@ size_t wv_train_bce_workspace_bytes(void) { return wv::RED_BLOCKS * sizeof(float
 
 int wv_train_bce_logits(const float* logits, const float* mask, const float* msg, float* loss, float* dlogits, float grad_scale,
                         int B, int Cz, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits || !loss || B < 1 || Cz < 1 || T < 1) return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return tfail(WV_ENOMEM, "workspace too small");
+    if (!logits || !loss || B < 1 || Cz < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t n = (size_t)B * Cz * T;
     hipLaunchKernelGGL(wv::bce_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, logits, mask, msg, dlogits, (float*)ws,
                        grad_scale / (float)n, Cz, T, n);
     hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, (const float*)ws, wv::RED_BLOCKS, 1.f / (float)n, loss);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- conv_pre: y = conv1d(in_scale * x[B,1,T], W(g,v)[C,1,ks]) + b, causal (seanet.py:657-664) ------------------------------
-struct wv_train_convpre {
+struct wv_train_convpre : wv::TrainHandle {
     int C = 0, ks = 0;
     float *w = nullptr, *inv = nullptr, *dwdb = nullptr, *taps = nullptr;
-    std::vector<void*> owned;
-    ~wv_train_convpre() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_convpre_create(int C, int ks, wv_train_convpre** out) {
-    if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return tfail(WV_EINVAL, "bad channel count / kernel size");
+    if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size");
     auto* h = new wv_train_convpre();
     h->C = C; h->ks = ks;
-    auto alloc = [&](float** p, size_t n) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return true;
-    };
-    if (!(alloc(&h->w, (size_t)C * ks) && alloc(&h->inv, C) && alloc(&h->dwdb, (size_t)C * (ks + 1)) && alloc(&h->taps, (size_t)C * ks))) {
+    if (!((h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(C, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) && (h->taps = h->alloc((size_t)C * ks, false)))) {
         delete h;
-        return tfail(WV_EHIP, "device allocation failed");
+        return fail(WV_EHIP, "device allocation failed");
     }
     *out = h;
     return WV_OK;
@@ -1498,19 +1483,19 @@ size_t wv_train_convpre_workspace_bytes(const wv_train_convpre* h, int B, int T)
 
 int wv_train_convpre_forward(wv_train_convpre* h, const float* x, const float* g, const float* v, const float* bias, float in_scale,
                              float* y, int B, int T, void* stream) {
-    if (!h || !x || !g || !v || !y || B < 1 || T < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !g || !v || !y || B < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, h->C, h->ks, 0, 0,
                        (const float*)nullptr, 1.f);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(wv::launch_conv_pre(x, h->w, bias, y, nullptr, 0.f, B, h->C, T, h->ks, in_scale, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(wv::launch_conv_pre(x, h->w, bias, y, nullptr, 0.f, B, h->C, T, h->ks, in_scale, s));
     return WV_OK;
 }
 
 int wv_train_convpre_backward(wv_train_convpre* h, const float* x, const float* g, const float* v, float in_scale, const float* dy,
                               float* dx, float* dg, float* dv, float* db, int B, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !x || !g || !v || !dy || !dg || !dv || !db) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpre_workspace_bytes(h, B, T)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !x || !g || !v || !dy || !dg || !dv || !db) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpre_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, ks = h->ks;
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, C, ks, 0, 0,
@@ -1521,36 +1506,26 @@ int wv_train_convpre_backward(wv_train_convpre* h, const float* x, const float* 
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((C + 255) / 256), dim3(256), 0, s, h->dwdb, h->taps, db, C, ks, in_scale);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(C), dim3(256), 0, s, g, v, h->inv, h->taps, dg, dv, ks);
     if (dx) hipLaunchKernelGGL(wv::convpre_dx_kernel, dim3((T + 255) / 256, B), dim3(256), (size_t)C * ks * 4, s, dy, h->w, dx, C, T, ks, in_scale);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- SpecBlock add: y = x + s * (W(g,v)[C,F] @ P[B,F,T]),  s = res_scale * scale_param[0] (seanet.py:463-511) ----------------
-struct wv_train_spec {
+struct wv_train_spec : wv::TrainHandle {
     int C = 0, F = 0, Mp = 0;
     float *w = nullptr, *inv = nullptr, *wq = nullptr, *wt = nullptr, *wqT = nullptr, *wtT = nullptr, *dW = nullptr, *id_taps = nullptr;
     int KpT = 0;
-    std::vector<void*> owned;
-    ~wv_train_spec() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_spec_create(int C, int F, wv_train_spec** out) {
-    if (!out || C < 1 || C > 4096 || F < 1 || F > 4096) return tfail(WV_EINVAL, "bad channel count");
+    if (!out || C < 1 || C > 4096 || F < 1 || F > 4096) return fail(WV_EINVAL, "bad channel count");
     auto* h = new wv_train_spec();
     h->C = C; h->F = F; h->Mp = wv::round_up(C, wv::M_ALIGN); h->KpT = wv::round_up(F, wv::M_ALIGN);
-    auto alloc = [&](float** p, size_t n, bool zero) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return !zero || hipMemset(*p, 0, n * sizeof(float)) == hipSuccess;
-    };
     const int R = std::max(C, F);
-    std::vector<float> taps((size_t)R * 5, 0.f);
-    for (int m = 0; m < R; ++m) taps[(size_t)m * 5 + 4] = 1.f;
-    bool ok = alloc(&h->wqT, (size_t)wv::round_up(C, 32) * h->KpT, true) && alloc(&h->wtT, (size_t)wv::round_up(C, wv::BK) * h->KpT, true) &&
-              alloc(&h->w, (size_t)C * F, false) && alloc(&h->inv, C, false) && alloc(&h->wq, (size_t)wv::round_up(F, 32) * h->Mp, true) &&
-              alloc(&h->wt, (size_t)wv::round_up(F, wv::BK) * h->Mp, true) && alloc(&h->dW, (size_t)C * F, false) && alloc(&h->id_taps, taps.size(), false) &&
-              hipMemcpy(h->id_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete h; return tfail(WV_EHIP, "device allocation failed"); }
+    bool ok = (h->wqT = h->alloc((size_t)wv::round_up(C, 32) * h->KpT, true)) && (h->wtT = h->alloc((size_t)wv::round_up(C, wv::BK) * h->KpT, true)) &&
+              (h->w = h->alloc((size_t)C * F, false)) && (h->inv = h->alloc(C, false)) && (h->wq = h->alloc((size_t)wv::round_up(F, 32) * h->Mp, true)) &&
+              (h->wt = h->alloc((size_t)wv::round_up(F, wv::BK) * h->Mp, true)) && (h->dW = h->alloc((size_t)C * F, false)) && (h->id_taps = h->identity_taps(R));
+    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
@@ -1561,26 +1536,26 @@ size_t wv_train_spec_workspace_bytes(const wv_train_spec* h, int B, int T) {
 
 int wv_train_spec_forward(wv_train_spec* h, const float* x, const float* P, const float* g, const float* v, const float* scale_param,
                           float res_scale, float* y, int B, int T, void* stream) {
-    if (!h || !x || !P || !g || !v || !y || B < 1 || T < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !P || !g || !v || !y || B < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     // the scalar s rides in the GEMM operand: wq = s * W
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->C), dim3(256), 0, s, g, v, h->w, h->inv, h->wq, (float*)nullptr, h->C, h->F, h->Mp, 0,
                        scale_param, res_scale, h->wt, (float*)nullptr);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     wv::PwDwArgs a{};
     a.X = P; a.pw.M = h->C; a.pw.K = h->F; a.pw.Mp = h->Mp; a.pw.Kp = wv::round_up(h->F, wv::BK); a.pw.wq = h->wq; a.pw.wt = h->wt;
     a.dw_w = h->id_taps; a.dw_b = nullptr; a.resid = x; a.Y = y;
     a.B = B; a.Tin = T; a.Tout = T; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
     a.pre_scale = 1.f; a.pre_elu = 0; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
-    T_LAUNCH(wv::launch_pw_dw(a, s));
+    WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
 
 int wv_train_spec_backward(wv_train_spec* h, const float* P, const float* g, const float* v, const float* scale_param, float res_scale,
                            const float* dy, float* dg, float* dv, float* d_scale_param, float* dP, int B, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !P || !g || !v || !dy || !dg || !dv) return tfail(WV_EINVAL, "null argument");
-    if (scale_param && !d_scale_param) return tfail(WV_EINVAL, "scale_param without a gradient slot");
-    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_spec_workspace_bytes(h, B, T)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !P || !g || !v || !dy || !dg || !dv) return fail(WV_EINVAL, "null argument");
+    if (scale_param && !d_scale_param) return fail(WV_EINVAL, "scale_param without a gradient slot");
+    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_spec_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, F = h->F;
     const NtPlan np_ = nt_plan(B, T, C, F);
@@ -1590,16 +1565,16 @@ int wv_train_spec_backward(wv_train_spec* h, const float* P, const float* g, con
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, dP ? h->wqT : (float*)nullptr, C, F, 0, h->KpT,
                        scale_param, res_scale, (float*)nullptr, dP ? h->wtT : (float*)nullptr);
     if (dP) {                                                   // dP = (s W)^T @ dy
-        T_LAUNCH(hipGetLastError());
+        WV_HIP_TRY(hipGetLastError());
         wv::PwDwArgs t{};
         t.X = dy; t.pw.M = F; t.pw.K = C; t.pw.Mp = h->KpT; t.pw.Kp = wv::round_up(C, wv::BK); t.pw.wq = h->wqT; t.pw.wt = h->wtT;
         t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = dP;
         t.B = B; t.Tin = T; t.Tout = T; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
         t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-        T_LAUNCH(wv::launch_pw_dw(t, s));
+        WV_HIP_TRY(wv::launch_pw_dw(t, s));
     }
     // G = sum_{b,t} dy P^T;  d scale_param = res_scale * <W, G>  (= res_scale * sum dy . (W @ P));  dW = s * G
-    T_LAUNCH(wv::launch_gemm_nt(s, dy, P, (float*)ws, 1.f, 0, B, C, F, T, S, np_.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, dy, P, (float*)ws, 1.f, 0, B, C, F, T, S, np_.TC));
     wv::launch_sum_parts(s, (const float*)ws, h->dW, S, n);
     if (d_scale_param) {
         if (ws_bytes >= wv::RED_BLOCKS * sizeof(float)) {        // the split partials have been summed: their buffer takes the dot's partials
@@ -1609,37 +1584,27 @@ int wv_train_spec_backward(wv_train_spec* h, const float* P, const float* g, con
     }
     hipLaunchKernelGGL(wv::scale_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->dW, n, scale_param, res_scale);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(C), dim3(256), 0, s, g, v, h->inv, h->dW, dg, dv, F);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- conv_post: ELU -> causal depth-wise conv (ks, no bias) -> 1x1 (C -> D, bias) -> L2Norm * sqrt(D) (seanet.py:795-822) --------
-struct wv_train_convpost {
+struct wv_train_convpost : wv::TrainHandle {
     int C = 0, D = 0, ks = 0, Mp = 0, KpT = 0;
     float *w_dw = nullptr, *inv_dw = nullptr, *w_pw = nullptr, *inv_pw = nullptr, *wt = nullptr, *wtT = nullptr, *wq = nullptr, *wqT = nullptr;
     float *dW = nullptr, *dwdb = nullptr, *taps = nullptr, *dbsum = nullptr, *junk = nullptr, *id_taps = nullptr;
-    std::vector<void*> owned;
-    ~wv_train_convpost() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_convpost_create(int C, int D, int ks, wv_train_convpost** out) {
-    if (!out || C < 1 || C > 4096 || D < 1 || D > 128 || ks < 1 || ks > wv::TRAIN_MAX_KS) return tfail(WV_EINVAL, "bad channel count / kernel size (D <= 128)");
+    if (!out || C < 1 || C > 4096 || D < 1 || D > 128 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size (D <= 128)");
     auto* h = new wv_train_convpost();
     h->C = C; h->D = D; h->ks = ks; h->Mp = wv::round_up(D, wv::M_ALIGN); h->KpT = wv::round_up(C, wv::M_ALIGN);
-    auto alloc = [&](float** p, size_t n, bool zero) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return !zero || hipMemset(*p, 0, n * sizeof(float)) == hipSuccess;
-    };
-    std::vector<float> taps((size_t)C * 5, 0.f);
-    for (int m = 0; m < C; ++m) taps[(size_t)m * 5 + 4] = 1.f;
-    bool ok = alloc(&h->w_dw, (size_t)C * ks, false) && alloc(&h->inv_dw, C, false) && alloc(&h->w_pw, (size_t)D * C, false) && alloc(&h->inv_pw, D, false) &&
-              alloc(&h->wt, (size_t)wv::round_up(C, wv::BK) * h->Mp, true) && alloc(&h->wtT, (size_t)wv::round_up(D, wv::BK) * h->KpT, true) &&
-              alloc(&h->wq, (size_t)wv::round_up(C, 32) * h->Mp, true) && alloc(&h->wqT, (size_t)wv::round_up(D, 32) * h->KpT, true) &&
-              alloc(&h->dW, (size_t)D * C, false) && alloc(&h->dwdb, (size_t)std::max(C * (ks + 1), D * 2), false) && alloc(&h->taps, (size_t)C * ks, false) &&
-              alloc(&h->dbsum, (size_t)D, false) && alloc(&h->junk, (size_t)std::max(C, D), false) && alloc(&h->id_taps, taps.size(), false) &&
-              hipMemcpy(h->id_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete h; return tfail(WV_EHIP, "device allocation failed"); }
+    bool ok = (h->w_dw = h->alloc((size_t)C * ks, false)) && (h->inv_dw = h->alloc(C, false)) && (h->w_pw = h->alloc((size_t)D * C, false)) && (h->inv_pw = h->alloc(D, false)) &&
+              (h->wt = h->alloc((size_t)wv::round_up(C, wv::BK) * h->Mp, true)) && (h->wtT = h->alloc((size_t)wv::round_up(D, wv::BK) * h->KpT, true)) &&
+              (h->wq = h->alloc((size_t)wv::round_up(C, 32) * h->Mp, true)) && (h->wqT = h->alloc((size_t)wv::round_up(D, 32) * h->KpT, true)) &&
+              (h->dW = h->alloc((size_t)D * C, false)) && (h->dwdb = h->alloc((size_t)std::max(C * (ks + 1), D * 2), false)) && (h->taps = h->alloc((size_t)C * ks, false)) &&
+              (h->dbsum = h->alloc((size_t)D, false)) && (h->junk = h->alloc((size_t)std::max(C, D), false)) && (h->id_taps = h->identity_taps(C));
+    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
@@ -1656,7 +1621,7 @@ static int convpost_fold(wv_train_convpost* h, const float* g_dw, const float* v
                        (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->D), dim3(256), 0, s, g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->D, h->C, h->Mp, h->KpT,
                        (const float*)nullptr, 1.f, h->wt, h->wtT);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
@@ -1669,22 +1634,22 @@ static wv::PwWeight convpost_pack(const wv_train_convpost* h, bool transposed) {
 
 int wv_train_convpost_forward(wv_train_convpost* h, const float* x, const float* g_dw, const float* v_dw, const float* g_pw, const float* v_pw,
                               const float* bias, int l2norm, float* y, int B, int T, void* stream) {
-    if (!h || !x || !g_dw || !v_dw || !g_pw || !v_pw || !y || B < 1 || T < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !g_dw || !v_dw || !g_pw || !v_pw || !y || B < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     int rc = convpost_fold(h, g_dw, v_dw, g_pw, v_pw, s);
     if (rc) return rc;
     wv::DwPwArgs a{};
     a.X = x; a.dw_w = h->w_dw; a.pw = convpost_pack(h, false); a.bias = bias; a.Y = y;
     a.B = B; a.Tin = T; a.Tout = T; a.mode = 1; a.ks = h->ks; a.pre_scale = 1.f; a.pre_elu = 1; a.l2norm = l2norm; a.out_scale = 1.f;
-    T_LAUNCH(wv::launch_dw_pw(a, s));
+    WV_HIP_TRY(wv::launch_dw_pw(a, s));
     return WV_OK;
 }
 
 int wv_train_convpost_backward(wv_train_convpost* h, const float* x, const float* g_dw, const float* v_dw, const float* g_pw, const float* v_pw,
                                const float* bias, int l2norm, const float* dy, float* dx, float* dg_dw, float* dv_dw, float* dg_pw, float* dv_pw,
                                float* db, int B, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !x || !g_dw || !v_dw || !g_pw || !v_pw || !dy || !dx || !dg_dw || !dv_dw || !dg_pw || !dv_pw || !db) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpost_workspace_bytes(h, B, T)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !x || !g_dw || !v_dw || !g_pw || !v_pw || !dy || !dx || !dg_dw || !dv_dw || !dg_pw || !dv_pw || !db) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpost_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, D = h->D, ks = h->ks;
     const NtPlan np_ = nt_plan(B, T, D, C);
@@ -1698,13 +1663,13 @@ int wv_train_convpost_backward(wv_train_convpost* h, const float* x, const float
     if (rc) return rc;
     // recompute a = ELU(x), h = DW(a), z = W h + b
     hipLaunchKernelGGL(wv::elu_dw_fwd_kernel, dim3(C, B), dim3(256), 0, s, x, h->w_dw, A, H, C, T, ks);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     const float* dZ = dy;
     if (l2norm) {
         wv::DwPwArgs a{};
         a.X = H; a.pw = convpost_pack(h, false); a.bias = bias; a.Y = Z;
         a.B = B; a.Tin = T; a.Tout = T; a.mode = 0; a.ks = 1; a.pre_scale = 1.f; a.pre_elu = 0; a.l2norm = 0; a.out_scale = 1.f;
-        T_LAUNCH(wv::launch_dw_pw(a, s));
+        WV_HIP_TRY(wv::launch_dw_pw(a, s));
         hipLaunchKernelGGL(wv::l2norm_bwd_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, Z, dy, D, T, 1e-12f);
         dZ = Z;
     }
@@ -1712,16 +1677,16 @@ int wv_train_convpost_backward(wv_train_convpost* h, const float* x, const float
     wv::launch_dw_bwd(s, dZ, dZ, h->junk, (float*)nullptr, partial, D, B, T, T, 1, 1, 0, 0);
     wv::launch_sum_parts(s, partial, h->dwdb, B, (size_t)D * 2);
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((D + 255) / 256), dim3(256), 0, s, h->dwdb, h->junk, db, D, 1, 1.f);
-    T_LAUNCH(wv::launch_gemm_nt(s, dZ, H, parts, 1.f, 0, B, D, C, T, S, np_.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, dZ, H, parts, 1.f, 0, B, D, C, T, S, np_.TC));
     wv::launch_sum_parts(s, parts, h->dW, S, (size_t)D * C);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(D), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, C);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     // dh = W^T dz
     wv::PwDwArgs t{};
     t.X = dZ; t.pw = convpost_pack(h, true); t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = DH;
     t.B = B; t.Tin = T; t.Tout = T; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
     t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-    T_LAUNCH(wv::launch_pw_dw(t, s));
+    WV_HIP_TRY(wv::launch_pw_dw(t, s));
     // through the depth-wise conv (da into the H buffer) and the ELU
     wv::launch_dw_bwd(s, DH, A, h->w_dw, H, partial, C, B, T, T, ks, 1, ks - 1, 0);
     wv::launch_sum_parts(s, partial, h->dwdb, B, (size_t)C * (ks + 1));
@@ -1730,35 +1695,28 @@ int wv_train_convpost_backward(wv_train_convpost* h, const float* x, const float
     const size_t n = (size_t)B * C * T, n4 = n / 4;
     if (n4) hipLaunchKernelGGL(wv::elu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, H, x, dx, 1.f, n4);
     if (n % 4) hipLaunchKernelGGL(wv::elu_bwd_tail_kernel, dim3(1), dim3(256), 0, s, H, x, dx, 1.f, n4 * 4, n);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- head ------------------------------------------------------------------------------------------------------------------------
-struct wv_train_head {
+struct wv_train_head : wv::TrainHandle {
     int D = 0, O = 0, nb = 0, hop = 0;
     float *wt_q = nullptr, *wt_dz = nullptr, *wt_l = nullptr, *wt_lT = nullptr, *bias_q = nullptr, *scr = nullptr, *junk = nullptr;
-    std::vector<void*> owned;
-    ~wv_train_head() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_head_create(int D, int O, int nb, int hop, wv_train_head** out) {
-    if (!out || D < 1 || D > 4096 || O < 1 || O > 4096 || nb < 1 || nb > 4096 || hop < 1 || (long long)O * hop > (1 << 20)) return tfail(WV_EINVAL, "bad head shape");
+    if (!out || D < 1 || D > 4096 || O < 1 || O > 4096 || nb < 1 || nb > 4096 || hop < 1 || (long long)O * hop > (1 << 20)) return fail(WV_EINVAL, "bad head shape");
     auto* h = new wv_train_head();
     h->D = D; h->O = O; h->nb = nb; h->hop = hop;
     const int OH = O * hop;
-    auto alloc = [&](float** p, size_t n) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return hipMemset(*p, 0, n * sizeof(float)) == hipSuccess;
-    };
     const size_t big = std::max<size_t>((size_t)std::max(nb, O) * 2, 64);
-    bool ok = alloc(&h->wt_q, (size_t)wv::round_up(D, wv::BK) * wv::round_up(OH, wv::M_ALIGN)) &&
-              alloc(&h->wt_dz, (size_t)wv::round_up(OH, wv::BK) * wv::round_up(D, wv::M_ALIGN)) &&
-              alloc(&h->wt_l, (size_t)wv::round_up(O, wv::BK) * wv::round_up(nb, wv::M_ALIGN)) &&
-              alloc(&h->wt_lT, (size_t)wv::round_up(nb, wv::BK) * wv::round_up(O, wv::M_ALIGN)) && alloc(&h->bias_q, (size_t)OH) &&
-              alloc(&h->scr, big) && alloc(&h->junk, big);
-    if (!ok) { delete h; return tfail(WV_EHIP, "device allocation failed"); }
+    bool ok = (h->wt_q = h->alloc((size_t)wv::round_up(D, wv::BK) * wv::round_up(OH, wv::M_ALIGN), true)) &&
+              (h->wt_dz = h->alloc((size_t)wv::round_up(OH, wv::BK) * wv::round_up(D, wv::M_ALIGN), true)) &&
+              (h->wt_l = h->alloc((size_t)wv::round_up(O, wv::BK) * wv::round_up(nb, wv::M_ALIGN), true)) &&
+              (h->wt_lT = h->alloc((size_t)wv::round_up(nb, wv::BK) * wv::round_up(O, wv::M_ALIGN), true)) && (h->bias_q = h->alloc((size_t)OH, true)) &&
+              (h->scr = h->alloc(big, true)) && (h->junk = h->alloc(big, true));
+    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
@@ -1788,25 +1746,25 @@ static int head_q(wv_train_head* h, const float* z, const float* w_rev, const fl
     const int OH = h->O * h->hop;
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)OH * h->D + 255) / 256)), dim3(256), 0, s, w_rev, h->wt_q, OH, h->D, wv::round_up(OH, wv::M_ALIGN), 1);
     hipLaunchKernelGGL(wv::expand_bias_kernel, dim3((OH + 255) / 256), dim3(256), 0, s, b_rev, h->bias_q, h->O, h->hop);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(head_gemm(z, head_pw(OH, h->D, h->wt_q), b_rev ? h->bias_q : nullptr, q, B, N, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(head_gemm(z, head_pw(OH, h->D, h->wt_q), b_rev ? h->bias_q : nullptr, q, B, N, s));
     return WV_OK;
 }
 
 int wv_train_head_forward(wv_train_head* h, const float* z, const float* w_rev, const float* b_rev, const float* w_last, const float* b_last,
                           float* logits, int B, int N, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !z || !w_rev || !w_last || !logits || B < 1 || N < 1 || T < 1 || T > N * h->hop) return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !z || !w_rev || !w_last || !logits || B < 1 || N < 1 || T < 1 || T > N * h->hop) return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t hn = (size_t)h->hop * N, aq = al256((size_t)B * h->O * hn * 4);
     float* q = (float*)ws; float* lq = (float*)((char*)ws + 2 * aq);
     int rc = head_q(h, z, w_rev, b_rev, q, B, N, s);
     if (rc) return rc;
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)h->nb * h->O + 255) / 256)), dim3(256), 0, s, w_last, h->wt_l, h->nb, h->O, wv::round_up(h->nb, wv::M_ALIGN), 0);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(head_gemm(q, head_pw(h->nb, h->O, h->wt_l), b_last, lq, B, (int)hn, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(head_gemm(q, head_pw(h->nb, h->O, h->wt_l), b_last, lq, B, (int)hn, s));
     hipLaunchKernelGGL(wv::frames_to_time_kernel, dim3((T + 255) / 256, B * h->nb), dim3(256), 0, s, lq, logits, T, h->hop, N);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
@@ -1814,8 +1772,8 @@ int wv_train_head_backward(wv_train_head* h, const float* z, const float* w_rev,
                            float* dz, float* dw_rev, float* db_rev, float* dw_last, float* db_last, int B, int N, int T,
                            void* ws, size_t ws_bytes, void* stream) {
     if (!h || !z || !w_rev || !w_last || !dlogits || !dz || !dw_rev || !db_rev || !dw_last || !db_last || B < 1 || N < 1 || T < 1 || T > N * h->hop)
-        return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return tfail(WV_ENOMEM, "workspace too small");
+        return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int D = h->D, O = h->O, nb = h->nb, hop = h->hop, OH = O * hop;
     const size_t hn = (size_t)hop * N, aq = al256((size_t)B * O * hn * 4), al = al256((size_t)B * nb * hn * 4);
@@ -1830,55 +1788,45 @@ int wv_train_head_backward(wv_train_head* h, const float* z, const float* w_rev,
     hipLaunchKernelGGL(wv::time_to_frames_kernel, dim3((unsigned)((hn + 255) / 256), B * nb), dim3(256), 0, s, dlogits, dlq, T, hop, N);
     // last layer: dw_last[k][o] = sum dlq[k] . q[o] over (b, j, n);  db_last[k] = sum dlogits
     const int S2 = np2.S;
-    T_LAUNCH(wv::launch_gemm_nt(s, dlq, q, parts, 1.f, 0, B, nb, O, (int)hn, S2, np2.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, dlq, q, parts, 1.f, 0, B, nb, O, (int)hn, S2, np2.TC));
     wv::launch_sum_parts(s, parts, dw_last, S2, (size_t)nb * O);
     wv::launch_dw_bwd(s, dlq, dlq, h->junk, (float*)nullptr, partial, nb, B, (int)hn, (int)hn, 1, 1, 0, 0);
     wv::launch_sum_parts(s, partial, h->scr, B, (size_t)nb * 2);
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db_last, nb, 1, 1.f);
     // dq = w_last^T @ dlq
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)O * nb + 255) / 256)), dim3(256), 0, s, w_last, h->wt_lT, O, nb, wv::round_up(O, wv::M_ALIGN), 1);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(head_gemm(dlq, head_pw(O, nb, h->wt_lT), nullptr, dq, B, (int)hn, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(head_gemm(dlq, head_pw(O, nb, h->wt_lT), nullptr, dq, B, (int)hn, s));
     // db_rev[o] = sum dq[o];  dw_rev[d][(o,j)] = sum_{b,n} z[d][n] dq[(o,j)][n];  dz = w_rev @ dq
     wv::launch_dw_bwd(s, dq, dq, h->junk, (float*)nullptr, partial, O, B, (int)hn, (int)hn, 1, 1, 0, 0);
     wv::launch_sum_parts(s, partial, h->scr, B, (size_t)O * 2);
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((O + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db_rev, O, 1, 1.f);
     const int S1 = np1.S;
-    T_LAUNCH(wv::launch_gemm_nt(s, z, dq, parts, 1.f, 0, B, D, OH, N, S1, np1.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, z, dq, parts, 1.f, 0, B, D, OH, N, S1, np1.TC));
     wv::launch_sum_parts(s, parts, dw_rev, S1, (size_t)D * OH);
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)D * OH + 255) / 256)), dim3(256), 0, s, w_rev, h->wt_dz, D, OH, wv::round_up(D, wv::M_ALIGN), 0);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(head_gemm(dq, head_pw(D, OH, h->wt_dz), nullptr, dz, B, N, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(head_gemm(dq, head_pw(D, OH, h->wt_dz), nullptr, dz, B, N, s));
     return WV_OK;
 }
 
 // ---- upsample unit: y[B,M,r*Tin] = W(g,v)[M,K] @ ConvT_dw(act(s x[B,K,Tin]); taps(g,v)[K,2r]) + bias (seanet.py:1110-1135) -------
-struct wv_train_up {
+struct wv_train_up : wv::TrainHandle {
     int K = 0, M = 0, r = 0, Mp = 0, KpT = 0, Kp = 0;
     float *w_ct = nullptr, *inv_ct = nullptr, *ct_wt = nullptr, *w_pw = nullptr, *inv_pw = nullptr, *wq = nullptr, *wqT = nullptr, *wt = nullptr, *wtT = nullptr;
     float *id_taps = nullptr, *dW = nullptr, *taps = nullptr, *scr = nullptr, *junk = nullptr;
-    std::vector<void*> owned;
-    ~wv_train_up() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_up_create(int K, int M, int ratio, wv_train_up** out) {
-    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096 || ratio < 1 || 2 * ratio > wv::TRAIN_MAX_KS) return tfail(WV_EINVAL, "bad upsample shape (ratio <= 8)");
+    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096 || ratio < 1 || 2 * ratio > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad upsample shape (ratio <= 8)");
     auto* h = new wv_train_up();
     h->K = K; h->M = M; h->r = ratio; h->Mp = wv::round_up(M, wv::M_ALIGN); h->KpT = wv::round_up(K, wv::M_ALIGN); h->Kp = wv::round_up(K, wv::BK);
-    auto alloc = [&](float** p, size_t n) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return hipMemset(*p, 0, n * sizeof(float)) == hipSuccess;
-    };
     const int R = std::max(K, M), ks = 2 * ratio;
-    std::vector<float> taps((size_t)R * 5, 0.f);
-    for (int m = 0; m < R; ++m) taps[(size_t)m * 5 + 4] = 1.f;
-    bool ok = alloc(&h->w_ct, (size_t)K * ks) && alloc(&h->inv_ct, K) && alloc(&h->ct_wt, (size_t)ks * h->Kp) && alloc(&h->w_pw, (size_t)M * K) &&
-              alloc(&h->inv_pw, M) && alloc(&h->wq, (size_t)wv::round_up(K, 32) * h->Mp) && alloc(&h->wqT, (size_t)wv::round_up(M, 32) * h->KpT) &&
-              alloc(&h->wt, (size_t)h->Kp * h->Mp) && alloc(&h->wtT, (size_t)wv::round_up(M, wv::BK) * h->KpT) && alloc(&h->id_taps, taps.size()) &&
-              alloc(&h->dW, (size_t)M * K) && alloc(&h->taps, (size_t)K * ks) && alloc(&h->scr, (size_t)R * 2) && alloc(&h->junk, (size_t)R) &&
-              hipMemcpy(h->id_taps, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { delete h; return tfail(WV_EHIP, "device allocation failed"); }
+    bool ok = (h->w_ct = h->alloc((size_t)K * ks, true)) && (h->inv_ct = h->alloc(K, true)) && (h->ct_wt = h->alloc((size_t)ks * h->Kp, true)) && (h->w_pw = h->alloc((size_t)M * K, true)) &&
+              (h->inv_pw = h->alloc(M, true)) && (h->wq = h->alloc((size_t)wv::round_up(K, 32) * h->Mp, true)) && (h->wqT = h->alloc((size_t)wv::round_up(M, 32) * h->KpT, true)) &&
+              (h->wt = h->alloc((size_t)h->Kp * h->Mp, true)) && (h->wtT = h->alloc((size_t)wv::round_up(M, wv::BK) * h->KpT, true)) && (h->id_taps = h->identity_taps(R)) &&
+              (h->dW = h->alloc((size_t)M * K, true)) && (h->taps = h->alloc((size_t)K * ks, true)) && (h->scr = h->alloc((size_t)R * 2, true)) && (h->junk = h->alloc((size_t)R, true));
+    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
@@ -1898,13 +1846,13 @@ static int up_fold(wv_train_up* h, const float* g_ct, const float* v_ct, const f
     hipLaunchKernelGGL(wv::pack_ct_wt_kernel, dim3((h->K * ks + 255) / 256), dim3(256), 0, s, h->w_ct, h->ct_wt, h->K, h->Kp, ks);
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->M), dim3(256), 0, s, g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->M, h->K, h->Mp, h->KpT,
                        (const float*)nullptr, 1.f, h->wt, h->wtT);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_up_forward(wv_train_up* h, const float* x, const float* g_ct, const float* v_ct, const float* g_pw, const float* v_pw, const float* bias,
                         float pre_scale, int pre_elu, float* y, int B, int Tin, void* stream) {
-    if (!h || !x || !g_ct || !v_ct || !g_pw || !v_pw || !y || B < 1 || Tin < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !g_ct || !v_ct || !g_pw || !v_pw || !y || B < 1 || Tin < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     int rc = up_fold(h, g_ct, v_ct, g_pw, v_pw, s);
     if (rc) return rc;
@@ -1913,15 +1861,15 @@ int wv_train_up_forward(wv_train_up* h, const float* x, const float* g_ct, const
     a.ct_w = h->w_ct; a.ct_wt = h->ct_wt; a.ratio = h->r; a.dw_w = h->id_taps; a.dw_b = bias; a.Y = y;
     a.B = B; a.Tin = Tin; a.Tout = Tin * h->r; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
     a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
-    T_LAUNCH(wv::launch_pw_dw(a, s));
+    WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
 
 int wv_train_up_backward(wv_train_up* h, const float* x, const float* g_ct, const float* v_ct, const float* g_pw, const float* v_pw, float pre_scale,
                          int pre_elu, const float* dy, float* dx, float* dg_ct, float* dv_ct, float* dg_pw, float* dv_pw, float* db, int B, int Tin,
                          void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !x || !g_ct || !v_ct || !g_pw || !v_pw || !dy || !dx || !dg_ct || !dv_ct || !dg_pw || !dv_pw || !db) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_up_workspace_bytes(h, B, Tin)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !x || !g_ct || !v_ct || !g_pw || !v_pw || !dy || !dx || !dg_ct || !dv_ct || !dg_pw || !dv_pw || !db) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_up_workspace_bytes(h, B, Tin)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int K = h->K, M = h->M, r = h->r, ks = 2 * r, Tout = Tin * r;
     const size_t au = al256((size_t)B * K * Tout * 4);
@@ -1943,17 +1891,17 @@ int wv_train_up_backward(wv_train_up* h, const float* x, const float* g_ct, cons
     wv::launch_sum_parts(s, partial, h->scr, B, (size_t)M * 2);
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((M + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db, M, 1, 1.f);
     const NtPlan np_ = nt_plan(B, Tout, M, K);
-    T_LAUNCH(wv::launch_gemm_nt(s, dy, U, parts, 1.f, 0, B, M, K, Tout, np_.S, np_.TC));
+    WV_HIP_TRY(wv::launch_gemm_nt(s, dy, U, parts, 1.f, 0, B, M, K, Tout, np_.S, np_.TC));
     wv::launch_sum_parts(s, parts, h->dW, np_.S, (size_t)M * K);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(M), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, K);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     // du = W^T dy
     wv::PwDwArgs t{};
     t.X = dy; t.pw.M = K; t.pw.K = M; t.pw.Mp = h->KpT; t.pw.Kp = wv::round_up(M, wv::BK); t.pw.wq = h->wqT; t.pw.wt = h->wtT;
     t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = DU;
     t.B = B; t.Tin = Tout; t.Tout = Tout; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
     t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-    T_LAUNCH(wv::launch_pw_dw(t, s));
+    WV_HIP_TRY(wv::launch_pw_dw(t, s));
     // through the transposed conv and the activation
     {
         const bool al = (reinterpret_cast<uintptr_t>(DU) & 15) == 0;
@@ -1964,30 +1912,23 @@ int wv_train_up_backward(wv_train_up* h, const float* x, const float* g_ct, cons
     }
     wv::launch_sum_parts(s, partial, h->taps, B, (size_t)K * ks);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(K), dim3(256), 0, s, g_ct, v_ct, h->inv_ct, h->taps, dg_ct, dv_ct, ks);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- decoder tail ------------------------------------------------------------------------------------------------------------------
-struct wv_train_tail {
+struct wv_train_tail : wv::TrainHandle {
     int C = 0, ks = 0;
     float *w = nullptr, *inv = nullptr, *dwdb = nullptr, *taps = nullptr, *dbv = nullptr;
-    std::vector<void*> owned;
-    ~wv_train_tail() { for (void* p : owned) (void)hipFree(p); }
 };
 
 int wv_train_tail_create(int C, int ks, wv_train_tail** out) {
-    if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return tfail(WV_EINVAL, "bad channel count / kernel size");
+    if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size");
     auto* h = new wv_train_tail();
     h->C = C; h->ks = ks;
-    auto alloc = [&](float** p, size_t n) {
-        if (hipMalloc((void**)p, n * sizeof(float)) != hipSuccess) return false;
-        h->owned.push_back(*p);
-        return true;
-    };
-    if (!(alloc(&h->w, (size_t)C * ks) && alloc(&h->inv, 1) && alloc(&h->dwdb, (size_t)C * (ks + 1)) && alloc(&h->taps, (size_t)C * ks) && alloc(&h->dbv, C))) {
+    if (!((h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(1, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) && (h->taps = h->alloc((size_t)C * ks, false)) && (h->dbv = h->alloc(C, false)))) {
         delete h;
-        return tfail(WV_EHIP, "device allocation failed");
+        return fail(WV_EHIP, "device allocation failed");
     }
     *out = h;
     return WV_OK;
@@ -1997,19 +1938,19 @@ size_t wv_train_tail_workspace_bytes(const wv_train_tail* h, int B) { return (h 
 
 int wv_train_tail_forward(wv_train_tail* h, const float* x, const float* g, const float* v, const float* bias, float post, float wav_std,
                           float* delta, int B, int Tin, int T, void* stream) {
-    if (!h || !x || !g || !v || !delta || B < 1 || T < 1 || T > Tin) return tfail(WV_EINVAL, "null / bad argument");
+    if (!h || !x || !g || !v || !delta || B < 1 || T < 1 || T > Tin) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(1), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, 1, h->C * h->ks, 0, 0,
                        (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(wv::launch_tail(x, h->w, bias, nullptr, delta, B, h->C, Tin, T, h->ks, post, wav_std, s));
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(wv::launch_tail(x, h->w, bias, nullptr, delta, B, h->C, Tin, T, h->ks, post, wav_std, s));
     return WV_OK;
 }
 
 int wv_train_tail_backward(wv_train_tail* h, const float* x, const float* g, const float* v, float post, float wav_std, const float* delta,
                            const float* d_delta, float* dx, float* dg, float* dv, float* db, int B, int Tin, int T, void* ws, size_t ws_bytes, void* stream) {
-    if (!h || !x || !g || !v || !delta || !d_delta || !dx || !dg || !dv || !db) return tfail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || T > Tin || !ws || ws_bytes < wv_train_tail_workspace_bytes(h, B)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!h || !x || !g || !v || !delta || !d_delta || !dx || !dg || !dv || !db) return fail(WV_EINVAL, "null argument");
+    if (B < 1 || T < 1 || T > Tin || !ws || ws_bytes < wv_train_tail_workspace_bytes(h, B)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, ks = h->ks;
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(1), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, 1, C * ks, 0, 0,
@@ -2022,8 +1963,8 @@ int wv_train_tail_backward(wv_train_tail* h, const float* x, const float* g, con
     wv::launch_sum_parts(s, (const float*)ws, h->dwdb, B, (size_t)C * (ks + 1));
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((C + 255) / 256), dim3(256), 0, s, h->dwdb, h->taps, h->dbv, C, ks, 1.f);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(1), dim3(256), 0, s, g, v, h->inv, h->taps, dg, dv, C * ks);
-    T_LAUNCH(hipGetLastError());
-    T_LAUNCH(hipMemcpyAsync(db, h->dbv, sizeof(float), hipMemcpyDeviceToDevice, s));      // every channel row holds the same sum of dq
+    WV_HIP_TRY(hipGetLastError());
+    WV_HIP_TRY(hipMemcpyAsync(db, h->dbv, sizeof(float), hipMemcpyDeviceToDevice, s));      // every channel row holds the same sum of dq
     return WV_OK;
 }
 
@@ -2042,32 +1983,32 @@ static bool film_shape_ok(int B, int Dm, int E, int L, int S, int bands) {
 
 int wv_train_film_forward(const float* msg, const float* params, float* film, int B, int msg_dim, int E, int layers, int n_scales, int bands,
                           void* ws, size_t ws_bytes, void* stream) {
-    if (!msg || !params || !film || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return tfail(WV_EINVAL, "null / bad argument (E <= 256, layers <= 4)");
-    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!msg || !params || !film || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_EINVAL, "null / bad argument (E <= 256, layers <= 4)");
+    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_ENOMEM, "workspace too small");
     hipLaunchKernelGGL(wv::msg_film_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, msg, params, film, (float*)ws, msg_dim, E, layers, n_scales * bands * 2);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 /* `ws` must be the buffer forward used (it holds the MLP activations). */
 int wv_train_film_backward(const float* msg, const float* params, const float* dfilm, float* dparams, int B, int msg_dim, int E, int layers,
                            int n_scales, int bands, void* ws, size_t ws_bytes, void* stream) {
-    if (!msg || !params || !dfilm || !dparams || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return tfail(WV_ENOMEM, "workspace too small");
+    if (!msg || !params || !dfilm || !dparams || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t np = wv_train_film_param_count(msg_dim, E, layers, n_scales, bands);
     float* acts = (float*)ws;
     float* gpart = (float*)((char*)ws + al256((size_t)B * (layers + 1) * E * 4));
     hipLaunchKernelGGL(wv::msg_film_bwd_kernel, dim3(B), dim3(256), 0, s, msg, params, acts, dfilm, gpart, msg_dim, E, layers, n_scales * bands * 2, np);
     wv::launch_sum_parts(s, gpart, dparams, B, np);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_film_apply(const float* x, const float* film, float* y, int B, int C, int T, int bands, int n_scales, int scale, void* stream) {
-    if (!x || !film || !y || B < 1 || C < 1 || T < 1 || bands < 1 || C % bands || scale < 0 || scale >= n_scales) return tfail(WV_EINVAL, "null / bad argument");
+    if (!x || !film || !y || B < 1 || C < 1 || T < 1 || bands < 1 || C % bands || scale < 0 || scale >= n_scales) return fail(WV_EINVAL, "null / bad argument");
     hipLaunchKernelGGL(wv::film_apply_kernel, dim3(C, B), dim3(256), 0, (hipStream_t)stream, x, film, y, C, T, bands, n_scales * bands * 2, scale * bands * 2);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
@@ -2075,54 +2016,54 @@ int wv_train_film_apply(const float* x, const float* film, float* y, int B, int 
 int wv_train_film_apply_backward(const float* x, const float* film, const float* dy, float* dx, float* dfilm, int B, int C, int T, int bands,
                                  int n_scales, int scale, void* ws, size_t ws_bytes, void* stream) {
     if (!x || !film || !dy || !dx || !dfilm || B < 1 || C < 1 || T < 1 || bands < 1 || C % bands || scale < 0 || scale >= n_scales)
-        return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < (size_t)B * C * 2 * sizeof(float)) return tfail(WV_ENOMEM, "workspace too small");
+        return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < (size_t)B * C * 2 * sizeof(float)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int NF = n_scales * bands * 2, so = scale * bands * 2;
     hipLaunchKernelGGL(wv::film_apply_bwd_kernel, dim3(C, B), dim3(256), 0, s, x, film, dy, dx, (float*)ws, C, T, bands, NF, so);
     hipLaunchKernelGGL(wv::film_band_reduce_kernel, dim3((B * bands * 2 + 255) / 256), dim3(256), 0, s, (const float*)ws, dfilm, B, C, bands, NF, so);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_l1(const float* a, const float* b, float* loss, float* da, float grad_scale, size_t n, void* ws, size_t ws_bytes, void* stream) {
-    if (!a || !b || !loss || !n) return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return tfail(WV_ENOMEM, "workspace too small");
+    if (!a || !b || !loss || !n) return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(wv::l1_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, a, b, da, (float*)ws, grad_scale / (float)n, n);
     hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, (const float*)ws, wv::RED_BLOCKS, 1.f / (float)n, loss);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- gradient norm + AdamW over flat arenas ---------------------------------------------------------------------------------
 int wv_train_fold_weight(const float* g, const float* v, float* w, float* inv_norm, int M, int K, void* stream) {
-    if (!g || !v || !w || !inv_norm || M < 1 || K < 1) return tfail(WV_EINVAL, "null / bad argument");
+    if (!g || !v || !w || !inv_norm || M < 1 || K < 1) return fail(WV_EINVAL, "null / bad argument");
     hipLaunchKernelGGL(wv::wn_fold_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, g, v, w, inv_norm, (float*)nullptr,
                        (float*)nullptr, M, K, 0, 0, (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_sumsq(const float* g, size_t n, float* out, void* ws, size_t ws_bytes, void* stream) {
-    if (!g || !out || !n) return tfail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return tfail(WV_ENOMEM, "workspace too small");
+    if (!g || !out || !n) return fail(WV_EINVAL, "null / bad argument");
+    if (!ws || ws_bytes < wv_train_bce_workspace_bytes()) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(wv::sumsq_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, g, n, (float*)ws);
     hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, (const float*)ws, wv::RED_BLOCKS, 1.f, out);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 int wv_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
                    float weight_decay, int step, const float* grad_sumsq, float max_norm, void* stream) {
     if (!p || !g || !m || !v || !n || step < 1 || !(lr >= 0.f) || beta1 < 0.f || beta1 >= 1.f || beta2 < 0.f || beta2 >= 1.f)
-        return tfail(WV_EINVAL, "null / bad argument");
+        return fail(WV_EINVAL, "null / bad argument");
     const float bc1 = (float)(1.0 - std::pow((double)beta1, step));
     const float bc2s = (float)std::sqrt(1.0 - std::pow((double)beta2, step));
     hipLaunchKernelGGL(wv::adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, lr, beta1, beta2,
                        eps, weight_decay, bc1, bc2s, grad_sumsq, max_norm);
-    T_LAUNCH(hipGetLastError());
+    WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 

@@ -11,7 +11,7 @@
 
 #include <stdint.h>
 
-#include "../../include/waveverify_hip.h"
+#include "wv_host.h"
 
 namespace wv {
 
@@ -87,17 +87,22 @@ __global__ __launch_bounds__(WIN_NT) void session_advance_kernel(const float* __
 
 }  // namespace wv
 
-static int launched() { return hipGetLastError() == hipSuccess ? WV_OK : WV_EHIP; }
+using wv::fail;
+
+static int launched() {
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
 
 extern "C" int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream) {
-    if (!src || !offs || !dst || W < 1 || W > 65535 || L < 1 || n_src < L) return WV_EINVAL;
+    if (!src || !offs || !dst || W < 1 || W > 65535 || L < 1 || n_src < L) return fail(WV_EINVAL, "null pointer (src, offs, dst), W outside [1, 65535], L < 1 or n_src < L");
     hipLaunchKernelGGL(wv::window_gather_kernel, dim3((L + wv::WIN_TILE - 1) / wv::WIN_TILE, W), dim3(wv::WIN_NT), 0, (hipStream_t)stream, src, n_src,
                        offs, dst, L);
     return launched();
 }
 
 extern "C" int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream) {
-    if (!y || !desc || !out || W < 1 || W > 65535 || C < 1 || C > 65535 || L < 1 || n_out < 1) return WV_EINVAL;
+    if (!y || !desc || !out || W < 1 || W > 65535 || C < 1 || C > 65535 || L < 1 || n_out < 1) return fail(WV_EINVAL, "null pointer (y, desc, out), W or C outside [1, 65535], L or n_out < 1");
     hipLaunchKernelGGL(wv::window_scatter_kernel, dim3((L + wv::WIN_TILE - 1) / wv::WIN_TILE, C, W), dim3(wv::WIN_NT), 0, (hipStream_t)stream, y, desc,
                        out, n_out, C, L);
     return launched();
@@ -105,7 +110,7 @@ extern "C" int wv_window_scatter(const float* y, const int64_t* desc, float* out
 
 extern "C" int wv_window_reduce_mean(const float* psum, int n_rows, const int* ptr, const int* rows, const int64_t* lengths, float* mean_prob, int B,
                                      int nb, void* stream) {
-    if (!psum || !ptr || !rows || !lengths || !mean_prob || n_rows < 1 || B < 1 || nb < 1) return WV_EINVAL;
+    if (!psum || !ptr || !rows || !lengths || !mean_prob || n_rows < 1 || B < 1 || nb < 1) return fail(WV_EINVAL, "null pointer (psum, ptr, rows, lengths, mean_prob) or n_rows, B, nb < 1");
     hipLaunchKernelGGL(wv::window_mean_kernel, dim3((B * nb + wv::WIN_NT - 1) / wv::WIN_NT), dim3(wv::WIN_NT), 0, (hipStream_t)stream, psum, n_rows, ptr,
                        rows, lengths, mean_prob, B, nb);
     return launched();
@@ -113,8 +118,8 @@ extern "C" int wv_window_reduce_mean(const float* psum, int n_rows, const int* p
 
 extern "C" int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen, float* hist_out, int drop, int hv2,
                                   int S, void* stream) {
-    if (!hist || !hist_out || hist == hist_out || S < 1 || S > 65535 || hcap < 1 || hv < 0 || hv > hcap || n < 0 || (n > 0 && !x)) return WV_EINVAL;
-    if (wlen < 0 || wlen > hv + n || (wlen > 0 && !win) || drop < 0 || hv2 < 0 || hv2 > hcap || drop + hv2 != hv + n) return WV_EINVAL;
+    if (!hist || !hist_out || hist == hist_out || S < 1 || S > 65535 || hcap < 1 || hv < 0 || hv > hcap || n < 0 || (n > 0 && !x)) return fail(WV_EINVAL, "null hist / hist_out (or the same buffer), S outside [1, 65535], hcap < 1, hv outside [0, hcap], n < 0, or samples without x");
+    if (wlen < 0 || wlen > hv + n || (wlen > 0 && !win) || drop < 0 || hv2 < 0 || hv2 > hcap || drop + hv2 != hv + n) return fail(WV_EINVAL, "wlen outside [0, hv + n] (or a window without win), drop < 0, hv2 outside [0, hcap], or drop + hv2 != hv + n");
     const int m = wlen > hv2 ? wlen : hv2;
     if (m == 0) return WV_OK;
     hipLaunchKernelGGL(wv::session_advance_kernel, dim3((m + wv::WIN_NT - 1) / wv::WIN_NT, S), dim3(wv::WIN_NT), 0, (hipStream_t)stream, hist, hcap, hv,

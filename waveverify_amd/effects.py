@@ -18,7 +18,6 @@ library raise -- both are kept, not corrected.  The convolutions run in csrc/wv_
 from __future__ import annotations
 
 import collections
-import ctypes as C
 import math
 import random
 from fractions import Fraction
@@ -29,18 +28,10 @@ import torch
 
 from . import _lib
 
+_ON_GPU = "effects run on the GPU (no CPU fallback)"
+
 DEFAULT_SAMPLE_RATE = 16000
 EPSILON = 1e-5
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _dev(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError("effects run on the GPU (no CPU fallback)")
-    return t.float().contiguous()
 
 
 # ---- taps, as the libraries publish them ----------------------------------------------------------------------------------------
@@ -91,12 +82,11 @@ def _fir(x: torch.Tensor, taps: np.ndarray, half: int) -> torch.Tensor:
     """x [..., T] -> [n_filters, ..., T]: julius' replicate-padded 'same' convolution."""
     lib = _lib.load()
     shape = list(x.shape)
-    xr = _dev(x).reshape(-1, shape[-1])
+    xr = _lib.dev(x, _ON_GPU).reshape(-1, shape[-1])
     nf, L = taps.shape
     td = torch.from_numpy(np.ascontiguousarray(taps)).to(xr.device)
     y = torch.empty(xr.shape[0], nf, shape[-1], device=xr.device)
-    if lib.wv_fx_fir_bank(xr.data_ptr(), td.data_ptr(), y.data_ptr(), xr.shape[0], shape[-1], nf, L, 1, half, half, 1, 0, _stream()) != 0:
-        raise RuntimeError("wv_fx_fir_bank failed")
+    _lib.check(lib.wv_fx_fir_bank(xr.data_ptr(), td.data_ptr(), y.data_ptr(), xr.shape[0], shape[-1], nf, L, 1, half, half, 1, 0, _lib.stream()), "wv_fx_fir_bank")
     return y.permute(1, 0, 2).reshape([nf] + shape)
 
 
@@ -108,7 +98,7 @@ def lowpass(x: torch.Tensor, cutoff: float) -> torch.Tensor:
 
 def highpass(x: torch.Tensor, cutoff: float) -> torch.Tensor:
     """julius.highpass_filter(x, cutoff) = x - lowpass(x)."""
-    return _dev(x) - lowpass(x, cutoff)
+    return _lib.dev(x, _ON_GPU) - lowpass(x, cutoff)
 
 
 def bandpass(x: torch.Tensor, cutoff_low: float, cutoff_high: float) -> torch.Tensor:
@@ -129,17 +119,16 @@ def resampled_length(T: int, orig_freq: int, new_freq: int) -> int:
 def resample_waveform(x: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
     """torchaudio.transforms.Resample(orig_freq, new_freq)(x) on [..., T]."""
     if int(orig_freq) == int(new_freq):
-        return _dev(x)
+        return _lib.dev(x, _ON_GPU)
     lib = _lib.load()
     k, width, orig, new = resample_kernels(orig_freq, new_freq)
     shape = list(x.shape)
-    xr = _dev(x).reshape(-1, shape[-1])
+    xr = _lib.dev(x, _ON_GPU).reshape(-1, shape[-1])
     T = shape[-1]
     t_out = int(math.ceil(new * T / orig))
     kd = torch.from_numpy(np.ascontiguousarray(k)).to(xr.device)
     y = torch.empty(xr.shape[0], t_out, device=xr.device)
-    if lib.wv_fx_resample(xr.data_ptr(), kd.data_ptr(), y.data_ptr(), xr.shape[0], T, orig, new, k.shape[1], width, t_out, _stream()) != 0:
-        raise RuntimeError("wv_fx_resample failed")
+    _lib.check(lib.wv_fx_resample(xr.data_ptr(), kd.data_ptr(), y.data_ptr(), xr.shape[0], T, orig, new, k.shape[1], width, t_out, _lib.stream()), "wv_fx_resample")
     return y.reshape(shape[:-1] + [t_out])
 
 
@@ -153,15 +142,13 @@ def _fir_adjoint(dy: torch.Tensor, taps: np.ndarray, half: int) -> torch.Tensor:
     lib = _lib.load()
     shape = list(dy.shape)
     T = shape[-1]
-    dr = _dev(dy).reshape(-1, T)
+    dr = _lib.dev(dy, _ON_GPU).reshape(-1, T)
     L = taps.shape[1]
     rev = torch.from_numpy(np.ascontiguousarray(taps[:1, ::-1])).to(dr.device)
     dxp = torch.empty(dr.shape[0], 1, T + L - 1, device=dr.device)               # gradient towards the replicate-padded signal
-    if lib.wv_fx_fir_bank(dr.data_ptr(), rev.data_ptr(), dxp.data_ptr(), dr.shape[0], T, 1, L, 1, L - 1, L - 1, 0, 0, _stream()) != 0:
-        raise RuntimeError("wv_fx_fir_bank failed")
+    _lib.check(lib.wv_fx_fir_bank(dr.data_ptr(), rev.data_ptr(), dxp.data_ptr(), dr.shape[0], T, 1, L, 1, L - 1, L - 1, 0, 0, _lib.stream()), "wv_fx_fir_bank")
     dx = torch.empty_like(dr)
-    if lib.wv_fx_fold_replicate(dxp.data_ptr(), dx.data_ptr(), dr.shape[0], T, half, half, _stream()) != 0:
-        raise RuntimeError("wv_fx_fold_replicate failed")
+    _lib.check(lib.wv_fx_fold_replicate(dxp.data_ptr(), dx.data_ptr(), dr.shape[0], T, half, half, _lib.stream()), "wv_fx_fold_replicate")
     return dx.reshape(shape)
 
 
@@ -171,7 +158,7 @@ def lowpass_adjoint(dy: torch.Tensor, cutoff: float) -> torch.Tensor:
 
 
 def highpass_adjoint(dy: torch.Tensor, cutoff: float) -> torch.Tensor:
-    return _dev(dy) - lowpass_adjoint(dy, cutoff)
+    return _lib.dev(dy, _ON_GPU) - lowpass_adjoint(dy, cutoff)
 
 
 def bandpass_adjoint(dy: torch.Tensor, cutoff_low: float, cutoff_high: float) -> torch.Tensor:
@@ -182,15 +169,15 @@ def bandpass_adjoint(dy: torch.Tensor, cutoff_low: float, cutoff_high: float) ->
 def resample_waveform_adjoint(dy: torch.Tensor, orig_freq: int, new_freq: int, t_in: int) -> torch.Tensor:
     """Transpose of `resample_waveform(x [..., t_in], orig_freq, new_freq)`: dy [..., t_out] -> dx [..., t_in]."""
     if int(orig_freq) == int(new_freq):
-        return _dev(dy)
+        return _lib.dev(dy, _ON_GPU)
     lib = _lib.load()
     k, width, orig, new = resample_kernels(orig_freq, new_freq)
     shape = list(dy.shape)
-    dr = _dev(dy).reshape(-1, shape[-1])
+    dr = _lib.dev(dy, _ON_GPU).reshape(-1, shape[-1])
     kd = torch.from_numpy(np.ascontiguousarray(k)).to(dr.device)
     dx = torch.empty(dr.shape[0], t_in, device=dr.device)
-    if lib.wv_fx_resample_adjoint(dr.data_ptr(), kd.data_ptr(), dx.data_ptr(), dr.shape[0], t_in, orig, new, k.shape[1], width, shape[-1], _stream()) != 0:
-        raise RuntimeError("wv_fx_resample_adjoint failed")
+    _lib.check(lib.wv_fx_resample_adjoint(dr.data_ptr(), kd.data_ptr(), dx.data_ptr(), dr.shape[0], t_in, orig, new, k.shape[1], width, shape[-1],
+                                          _lib.stream()), "wv_fx_resample_adjoint")
     return dx.reshape(shape[:-1] + [t_in])
 
 
@@ -283,12 +270,7 @@ def speed_ratio(speed: float) -> Tuple[int, int]:
 
 
 def _rows(t: torch.Tensor) -> torch.Tensor:
-    return _dev(t).reshape(-1, t.shape[-1])
-
-
-def _ok(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed (code {rc})")
+    return _lib.dev(t, _ON_GPU).reshape(-1, t.shape[-1])
 
 
 def pointwise(x: torch.Tensor, op: int, a: float, noise: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -296,8 +278,8 @@ def pointwise(x: torch.Tensor, op: int, a: float, noise: Optional[torch.Tensor] 
     xr = _rows(x)
     nr = _rows(noise) if noise is not None else None
     y = torch.empty_like(xr)
-    _ok(_lib.load().wv_fx_pointwise(xr.data_ptr(), nr.data_ptr() if nr is not None else None, y.data_ptr(), xr.shape[0], xr.shape[1], op, float(a),
-                                    _stream()), "wv_fx_pointwise")
+    _lib.check(_lib.load().wv_fx_pointwise(xr.data_ptr(), _lib.ptr(nr), y.data_ptr(), xr.shape[0], xr.shape[1], op, float(a),
+                                           _lib.stream()), "wv_fx_pointwise")
     return y.reshape(x.shape)
 
 
@@ -305,7 +287,7 @@ def median(x: torch.Tensor, kernel_size: int) -> torch.Tensor:
     """scipy.signal.medfilt(x, kernel_size) along the last axis (zero padding; kernel_size odd, at most MEDIAN_MAX_K)."""
     xr = _rows(x)
     y = torch.empty_like(xr)
-    _ok(_lib.load().wv_fx_median(xr.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(kernel_size), _stream()), "wv_fx_median")
+    _lib.check(_lib.load().wv_fx_median(xr.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(kernel_size), _lib.stream()), "wv_fx_median")
     return y.reshape(x.shape)
 
 
@@ -315,8 +297,8 @@ def shush_forward(x: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None):
     mr = _rows(mask) if mask is not None else None
     y, keep = torch.empty_like(xr), torch.empty_like(xr)
     mo = torch.empty_like(xr) if mr is not None else None
-    _ok(_lib.load().wv_fx_shush(xr.data_ptr(), mr.data_ptr() if mr is not None else None, y.data_ptr(), keep.data_ptr(),
-                                mo.data_ptr() if mo is not None else None, xr.shape[0], xr.shape[1], int(k), _stream()), "wv_fx_shush")
+    _lib.check(_lib.load().wv_fx_shush(xr.data_ptr(), _lib.ptr(mr), y.data_ptr(), keep.data_ptr(),
+                                       _lib.ptr(mo), xr.shape[0], xr.shape[1], int(k), _lib.stream()), "wv_fx_shush")
     return y.reshape(x.shape), keep.reshape(x.shape), (mo.reshape(mask.shape) if mo is not None else None)
 
 
@@ -326,8 +308,8 @@ def echo_forward(x: torch.Tensor, n: int, volume: float):
     xr = _rows(x)
     rec = torch.empty(2, dtype=torch.int64, device=xr.device)
     y = torch.empty_like(xr)
-    _ok(lib.wv_fx_echo_peaks(xr.data_ptr(), rec.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume), _stream()), "wv_fx_echo_peaks")
-    _ok(lib.wv_fx_echo_apply(xr.data_ptr(), rec.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume), _stream()), "wv_fx_echo_apply")
+    _lib.check(lib.wv_fx_echo_peaks(xr.data_ptr(), rec.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume), _lib.stream()), "wv_fx_echo_peaks")
+    _lib.check(lib.wv_fx_echo_apply(xr.data_ptr(), rec.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume), _lib.stream()), "wv_fx_echo_apply")
     return y.reshape(x.shape), rec
 
 
@@ -338,8 +320,8 @@ def echo_backward(x: torch.Tensor, g: torch.Tensor, rec: torch.Tensor, n: int, v
     dx = torch.empty_like(xr)
     nbytes = int(lib.wv_fx_echo_backward_workspace_bytes())
     ws = _lib.scratch(nbytes, xr.device)
-    _ok(lib.wv_fx_echo_backward(xr.data_ptr(), gr.data_ptr(), rec.data_ptr(), dx.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume),
-                                ws.data_ptr(), nbytes, _stream()), "wv_fx_echo_backward")
+    _lib.check(lib.wv_fx_echo_backward(xr.data_ptr(), gr.data_ptr(), rec.data_ptr(), dx.data_ptr(), xr.shape[0], xr.shape[1], int(n), float(volume),
+                                       ws.data_ptr(), nbytes, _lib.stream()), "wv_fx_echo_backward")
     return dx.reshape(g.shape)
 
 
@@ -349,8 +331,8 @@ def smooth_forward(x: torch.Tensor, w: int, mask: Optional[torch.Tensor] = None,
     mr = _rows(mask) if mask is not None else None
     y = torch.empty_like(xr)
     mo = torch.empty_like(xr) if mr is not None else None
-    _ok(_lib.load().wv_fx_smooth(xr.data_ptr(), mr.data_ptr() if mr is not None else None, y.data_ptr(), mo.data_ptr() if mo is not None else None,
-                                 xr.shape[0], xr.shape[1], int(w), float(valid_threshold), _stream()), "wv_fx_smooth")
+    _lib.check(_lib.load().wv_fx_smooth(xr.data_ptr(), _lib.ptr(mr), y.data_ptr(), _lib.ptr(mo),
+                                        xr.shape[0], xr.shape[1], int(w), float(valid_threshold), _lib.stream()), "wv_fx_smooth")
     return y.reshape(x.shape), (mo.reshape(mask.shape) if mo is not None else None)
 
 
@@ -358,7 +340,7 @@ def smooth_backward(g: torch.Tensor, w: int) -> torch.Tensor:
     """Transpose of smooth_forward's audio path."""
     gr = _rows(g)
     dx = torch.empty_like(gr)
-    _ok(_lib.load().wv_fx_smooth_backward(gr.data_ptr(), dx.data_ptr(), gr.shape[0], gr.shape[1], int(w), _stream()), "wv_fx_smooth_backward")
+    _lib.check(_lib.load().wv_fx_smooth_backward(gr.data_ptr(), dx.data_ptr(), gr.shape[0], gr.shape[1], int(w), _lib.stream()), "wv_fx_smooth_backward")
     return dx.reshape(g.shape)
 
 
@@ -368,15 +350,15 @@ def scatter_zero(y: torch.Tensor, idx: torch.Tensor, mask: Optional[torch.Tensor
         if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == torch.float32):
             raise RuntimeError("scatter_zero works in place on contiguous float32 GPU tensors")
     T = y.shape[-1]
-    _ok(_lib.load().wv_fx_scatter_zero(y.data_ptr(), mask.data_ptr() if mask is not None else None, idx.data_ptr(), y.numel() // T, T, int(idx.shape[-1]),
-                                       _stream()), "wv_fx_scatter_zero")
+    _lib.check(_lib.load().wv_fx_scatter_zero(y.data_ptr(), _lib.ptr(mask), idx.data_ptr(), y.numel() // T, T, int(idx.shape[-1]),
+                                              _lib.stream()), "wv_fx_scatter_zero")
 
 
 def stretch_linear(x: torch.Tensor, t_out: int) -> torch.Tensor:
     """torch.nn.functional.interpolate(x, size=t_out, mode='linear', align_corners=False) along the last axis."""
     xr = _rows(x)
     y = torch.empty(xr.shape[0], int(t_out), device=xr.device)
-    _ok(_lib.load().wv_fx_stretch_linear(xr.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(t_out), _stream()), "wv_fx_stretch_linear")
+    _lib.check(_lib.load().wv_fx_stretch_linear(xr.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(t_out), _lib.stream()), "wv_fx_stretch_linear")
     return y.reshape(list(x.shape[:-1]) + [int(t_out)])
 
 
@@ -448,7 +430,7 @@ class AudioEffects:
         the reference's outputs.  Built as that chain: resample by the rational of 1 / s through the polyphase resampler (speed 0.8 ->
         4 : 5, T -> ceil(5 T / 4)), then the linear stretch back to T that _SoxEffectSTE(..., 'stretch') applies.  The mask comes back
         unchanged (adjust_mask_length to an equal length is the identity); the gradient is straight-through.  A tuple draws random.uniform."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if isinstance(speed, tuple):
                 speed = random.uniform(*speed)
@@ -463,7 +445,7 @@ class AudioEffects:
     def echo(tensor, volume_range=(0.1, 0.5), duration_range=(0.1, 0.5), sample_rate: int = DEFAULT_SAMPLE_RATE, mask=None, _tape=None, **kwargs):
         """The delayed copy comes BEFORE the sound (the reference correlates with [1, 0, .., 0, volume]); peak-normalised over the whole
         tensor; the last n - 1 samples are 0.  Too short a clip (T < 2) comes back unchanged, before anything is drawn."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         T = x.shape[-1]
         try:
             if T / sample_rate <= 0 or T < MIN_AUDIO_LENGTH:
@@ -481,7 +463,7 @@ class AudioEffects:
     def pink_noise(tensor, noise_std: float = 0.01, mask=None, _tape=None, **kwargs):
         """The noise comes from `pink_noise_host` (the reference's Python loop on numpy's global generator: the host loop is the cost);
         the device only computes tensor + noise * noise_std."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             noise = torch.from_numpy(pink_noise_host(x.numel())).reshape(x.shape).to(x.device)
             a = float(noise_std)
@@ -492,7 +474,7 @@ class AudioEffects:
     @staticmethod
     def median_filter(tensor, kernel_size: int = 3, mask=None, _tape=None, **kwargs):
         """scipy.signal.medfilt per row (ZERO padding, whatever the reference's comment says); an even kernel_size is bumped by 1."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if kernel_size < 1:
                 raise ValueError(f"Kernel size must be positive, got {kernel_size}")
@@ -505,7 +487,7 @@ class AudioEffects:
 
     @staticmethod
     def smooth(tensor, window_size_range=(2, 10), mask=None, valid_threshold: float = 0.5, _tape=None, **kwargs):
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         if mask is not None and mask.device != tensor.device:
             raise RuntimeError(f"Device mismatch in smooth effect: tensor on {tensor.device}, mask on {mask.device}")
         try:
@@ -521,7 +503,7 @@ class AudioEffects:
 
     @staticmethod
     def amplitude_scaling(tensor, scale: float = 1.0, mask=None, _tape=None, **kwargs):
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             a = float(scale)
         except (ValueError, TypeError):
@@ -533,7 +515,7 @@ class AudioEffects:
     @staticmethod
     def quantization(tensor, bit_depth: int = 16, mask=None, _tape=None, **kwargs):
         """(tensor * max_val).round() / max_val with max_val = 2^(bit_depth-1) - 1; bit_depth = 1 gives 0 / 0 = NaN, as in the reference."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if not 1 <= bit_depth <= 32:
                 raise ValueError(f"Bit depth must be between 1 and 32, got {bit_depth}")
@@ -546,7 +528,7 @@ class AudioEffects:
     def sample_suppression(tensor, suppression_percentage: float = 0.1, mask=None, _tape=None, **kwargs):
         """Zeroes int(T * pct) random samples per (b, c) in a copy of the audio and of the mask (the reference writes into the mask it is
         given, which its dispatcher has cloned; here the clone is made in place of the write)."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if not 0 <= suppression_percentage <= 1:
                 raise ValueError(f"Suppression percentage must be between 0 and 1, got {suppression_percentage}")
@@ -555,7 +537,7 @@ class AudioEffects:
         except (ValueError, TypeError):
             return tensor, mask
         y = x.clone()
-        m = _dev(mask).clone() if mask is not None else None
+        m = _lib.dev(mask, _ON_GPU).clone() if mask is not None else None
         idx_d = torch.from_numpy(idx).to(x.device)
         scatter_zero(y, idx_d, m)
         _note(_tape, idx=idx_d)
@@ -563,7 +545,7 @@ class AudioEffects:
 
     @staticmethod
     def _gaussian_noise(tensor, noise_std, mask):
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if noise_std < 0:
                 raise ValueError(f"Noise std must be non-negative, got {noise_std}")
@@ -583,7 +565,7 @@ class AudioEffects:
     @staticmethod
     def shush(tensor, fraction: float = 0.1, mask=None, _tape=None, **kwargs):
         """Zeroes the k = min(int(T * fraction), T - 1) quietest samples of each row; the mask is cleared where the OUTPUT is 0."""
-        x = _dev(tensor)
+        x = _lib.dev(tensor, _ON_GPU)
         try:
             if not 0 <= fraction <= 1:
                 raise ValueError(f"Fraction must be between 0 and 1, got {fraction}")
@@ -674,7 +656,7 @@ class EffectTape:
         if name == "shush" and "keep" in saved:
             return pointwise(d_out, OP_MUL, 0.0, saved["keep"])
         if name == "sample_suppression" and "idx" in saved:
-            d = _dev(d_out).clone()
+            d = _lib.dev(d_out, _ON_GPU).clone()
             scatter_zero(d, saved["idx"])
             return d
         if name == "echo" and "rec" in saved:

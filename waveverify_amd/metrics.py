@@ -21,6 +21,8 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
+from . import _lib
+
 
 class BER:
     def __init__(self, threshold: float = 0.5, eps: float = 1e-8):
@@ -65,18 +67,8 @@ class MIOU:
 
 
 # ---- per-clip metrics (the validation pass) --------------------------------------------------------------------------------------
-def _stream(t: torch.Tensor):
-    import ctypes as C
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
 def _f32(t: torch.Tensor) -> torch.Tensor:
     return t.detach().float().contiguous()
-
-
-def _ok(rc: int, what: str) -> None:
-    if rc != 0:
-        raise RuntimeError(f"{what} failed (code {rc})")
 
 
 def ber_per_clip(logits: torch.Tensor, bits: torch.Tensor, mask: Optional[torch.Tensor] = None, threshold: float = 0.5,
@@ -96,14 +88,14 @@ def ber_per_clip(logits: torch.Tensor, bits: torch.Tensor, mask: Optional[torch.
     z, g = _f32(logits), _f32(bits).to(logits.device)
     m = None if mask is None else _f32(mask).to(logits.device)
     if z.is_cuda:
-        from . import _lib
         lib = _lib.load()
         avg = torch.empty(B, W, dtype=torch.float32, device=z.device)
         errors = torch.empty(B, dtype=torch.int32, device=z.device)
         valid = torch.empty(B, dtype=torch.int32, device=z.device)
         ws = _lib.scratch(int(lib.wv_metrics_decode_workspace_bytes(B, W, T)), z.device)
-        _ok(lib.wv_metrics_decode(z.data_ptr(), g.data_ptr(), None if m is None else m.data_ptr(), float(threshold), float(eps), B, W, T,
-                                  avg.data_ptr(), errors.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(), _stream(z)), "wv_metrics_decode")
+        _lib.check(lib.wv_metrics_decode(z.data_ptr(), g.data_ptr(), _lib.ptr(m), float(threshold), float(eps), B, W, T,
+                                         avg.data_ptr(), errors.data_ptr(), valid.data_ptr(), ws.data_ptr(), ws.numel(),
+                                         _lib.stream(z.device)), "wv_metrics_decode")
         return errors, valid, avg
     p = torch.sigmoid(z.double())
     if m is not None:
@@ -128,11 +120,10 @@ def iou_counts(locator_out: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
     B, _, T = locator_out.shape
     p, g = _f32(locator_out), _f32(mask).to(locator_out.device)
     if p.is_cuda:
-        from . import _lib
         lib = _lib.load()
         counts = torch.empty(B, 4, dtype=torch.int32, device=p.device)
         ws = _lib.scratch(int(lib.wv_metrics_iou_workspace_bytes(B, T)), p.device)
-        _ok(lib.wv_metrics_iou(p.data_ptr(), g.data_ptr(), B, T, counts.data_ptr(), ws.data_ptr(), ws.numel(), _stream(p)), "wv_metrics_iou")
+        _lib.check(lib.wv_metrics_iou(p.data_ptr(), g.data_ptr(), B, T, counts.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream(p.device)), "wv_metrics_iou")
         return counts
     fg, g1, g0 = (p > 0.5)[:, 0], (g == 1)[:, 0], (g == 0)[:, 0]
     return torch.stack([(fg & g1).sum(1), (fg | g1).sum(1), (~fg & g0).sum(1), (~fg | g0).sum(1)], dim=1).to(torch.int32)
@@ -177,13 +168,12 @@ class SISNR:
         y = _f32(references)
         x = _f32(estimates).to(y.device)                        # the reference moves the estimate to the reference's device
         if y.is_cuda:
-            from . import _lib
             lib = _lib.load()
             out = torch.empty(B, dtype=torch.float64, device=y.device)
             mom = torch.empty(B, 5, dtype=torch.float64, device=y.device)
             ws = _lib.scratch(int(lib.wv_metrics_sisnr_workspace_bytes(B, T)), y.device)
-            _ok(lib.wv_metrics_sisnr(x.data_ptr(), y.data_ptr(), B, T, self.eps, out.data_ptr(), mom.data_ptr(), ws.data_ptr(), ws.numel(),
-                                     _stream(y)), "wv_metrics_sisnr")
+            _lib.check(lib.wv_metrics_sisnr(x.data_ptr(), y.data_ptr(), B, T, self.eps, out.data_ptr(), mom.data_ptr(), ws.data_ptr(), ws.numel(),
+                                            _lib.stream(y.device)), "wv_metrics_sisnr")
             self.last_moments = mom
             return out
         xd, yd = x.double()[:, 0], y.double()[:, 0]

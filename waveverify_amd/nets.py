@@ -142,10 +142,6 @@ class HipNet:
             raise ValueError(f"expected audio of shape [B,1,T], got {tuple(x.shape)}")
         return x.to(self.device, torch.float32).contiguous()
 
-    @staticmethod
-    def _stream() -> C.c_void_p:
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
     @property
     def hop_length(self) -> int:
         return self.cfg.hop_length
@@ -172,7 +168,7 @@ class HipNet:
             fn = self._lib.wv_generator_forward_f16 if precision == "f16" else self._lib.wv_generator_forward
             _lib.check(fn(
                 self._h, x.data_ptr(), msg.data_ptr(), msg.shape[0], out.data_ptr(),
-                int(add_input), B, T, ws.data_ptr(), ws.numel(), self._stream()),
+                int(add_input), B, T, ws.data_ptr(), ws.numel(), _lib.stream()),
                 "wv_generator_forward" + ("_f16" if precision == "f16" else ""))
         return out
 
@@ -191,12 +187,12 @@ class HipNet:
                 _lib.check(fn(
                     self._h, x.data_ptr(), logits.data_ptr() if want_logits else None,
                     mean.data_ptr() if want_mean else None, B, T, ws.data_ptr(), ws.numel(),
-                    self._stream()), "wv_detector_forward" + ("_f16" if precision == "f16" else ""))
+                    _lib.stream()), "wv_detector_forward" + ("_f16" if precision == "f16" else ""))
             elif self.cfg.kind == "locator":
                 fn = self._lib.wv_locator_forward_f16 if precision == "f16" else self._lib.wv_locator_forward
                 _lib.check(fn(
                     self._h, x.data_ptr(), logits.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
-                    self._stream()), "wv_locator_forward" + ("_f16" if precision == "f16" else ""))
+                    _lib.stream()), "wv_locator_forward" + ("_f16" if precision == "f16" else ""))
             else:
                 raise RuntimeError("generator has no detection head")
         return logits, mean
@@ -233,7 +229,7 @@ class HipNet:
             ws = self._workspace(W, L)
             fn = self._lib.wv_detector_forward_windowed_f16 if precision == "f16" else self._lib.wv_detector_forward_windowed
             _lib.check(fn(self._h, x.data_ptr(), lo.data_ptr(), hi.data_ptr(), psum.data_ptr(), W, L, ws.data_ptr(), ws.numel(),
-                          self._stream()), "wv_detector_forward_windowed" + ("_f16" if precision == "f16" else ""))
+                          _lib.stream()), "wv_detector_forward_windowed" + ("_f16" if precision == "f16" else ""))
         return psum
 
     def locator(self, x: torch.Tensor, precision: str = "f32") -> torch.Tensor:
@@ -255,7 +251,7 @@ class HipNet:
         with torch.cuda.device(self.device):
             ws = self._workspace(B, T)
             _lib.check(self._lib.wv_encoder_forward(self._h, x.data_ptr(), mp, rows, lat.data_ptr(),
-                                                    B, T, ws.data_ptr(), ws.numel(), self._stream()),
+                                                    B, T, ws.data_ptr(), ws.numel(), _lib.stream()),
                        "wv_encoder_forward")
         return lat
 
@@ -265,7 +261,7 @@ class HipNet:
                           device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.wv_model_film(self._h, msg.data_ptr(), msg.shape[0], out.data_ptr(),
-                                               B, self._stream()), "wv_model_film")
+                                               B, _lib.stream()), "wv_model_film")
         return out
 
     def __call__(self, *a, **kw):

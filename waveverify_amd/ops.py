@@ -4,7 +4,6 @@ Activations are CUDA tensors; weights are host arrays in the reference's layouts
 test handles — the nets in nets.py run the same kernels with weights packed once."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
 import numpy as np
@@ -25,18 +24,7 @@ def _hp(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data
 
 
-def _dp(t: Optional[torch.Tensor]):
-    return None if t is None else t.data_ptr()
-
-
-def _dev(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError("activations must live on the GPU")
-    return t.float().contiguous()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+_ON_GPU = "activations must live on the GPU"
 
 
 def _out(given: Optional[torch.Tensor], shape, dtype, device, what: str = "out") -> torch.Tensor:
@@ -55,20 +43,20 @@ def pw_dw(X, w_pw, w_dw, dw_bias=None, film=None, resid=None, stride=1, dilation
           pre_scale=1.0, pre_elu=True, out_scale=1.0, bands=1, act_scale: Optional[float] = None, out=None, out_act=None):
     """act_scale given: also returns the second output ELU(act_scale * y) -> (Y, Yact).  out / out_act: caller-owned outputs."""
     lib = _lib.load()
-    X = _dev(X)
+    X = _lib.dev(X, _ON_GPU)
     B, K, Tin = X.shape
     w_pw, w_dw, dw_bias = _w(w_pw), _w(w_dw), _w(dw_bias)
     M, ks = w_dw.shape[0], w_dw.shape[-1]
     w_pw = w_pw.reshape(M, K)
     Tout = -(-Tin // stride)
     Y = _out(out, (B, M, Tout), torch.float32, X.device)
-    film = None if film is None else _dev(film)
-    resid = None if resid is None else _dev(resid)
+    film = None if film is None else _lib.dev(film, _ON_GPU)
+    resid = None if resid is None else _lib.dev(resid, _ON_GPU)
     Yact = _out(out_act, Y.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_op_pw_dw(X.data_ptr(), _hp(w_pw), _hp(w_dw), _hp(dw_bias), _dp(film), _dp(resid),
+    _lib.check(lib.wv_op_pw_dw(X.data_ptr(), _hp(w_pw), _hp(w_dw), _hp(dw_bias), _lib.ptr(film), _lib.ptr(resid),
                                Y.data_ptr(), B, K, M, Tin, ks, stride, dilation, pre_scale,
-                               int(pre_elu), out_scale, bands, _dp(Yact), float(act_scale or 0.0),
-                               _stream()), "wv_op_pw_dw")
+                               int(pre_elu), out_scale, bands, _lib.ptr(Yact), float(act_scale or 0.0),
+                               _lib.stream()), "wv_op_pw_dw")
     return Y if act_scale is None else (Y, Yact)
 
 
@@ -77,14 +65,14 @@ def resblock(X, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_scale=1.0
     """Fused SEANetResnetBlock, raw in / raw out: y = X + out_scale * half2(half1(ELU(pre_scale * X))).
     -> Y, or (Y, Yact) with act_scale given, or Yact alone with want_raw=False."""
     lib = _lib.load()
-    X = _dev(X)
+    X = _lib.dev(X, _ON_GPU)
     B, Cc, T = X.shape
     ws = [_w(w_pw1).reshape(Cc, Cc), _w(w_dw1).reshape(Cc, -1), _w(b1), _w(w_pw2).reshape(Cc, Cc),
           _w(w_dw2).reshape(Cc, -1), _w(b2)]
     Y = _out(out, X.shape, torch.float32, X.device) if want_raw else None
     Yact = _out(out_act, X.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_op_resblock(X.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _dp(Y), _dp(Yact),
-                                  B, Cc, T, out_scale, float(act_scale or 0.0), _stream()), "wv_op_resblock")
+    _lib.check(lib.wv_op_resblock(X.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _lib.ptr(Y), _lib.ptr(Yact),
+                                  B, Cc, T, out_scale, float(act_scale or 0.0), _lib.stream()), "wv_op_resblock")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)
@@ -94,7 +82,7 @@ def dw_pw(X, w_pw, bias=None, w_dw=None, mode=0, ks_or_ratio=0, pre_scale=1.0, p
           l2norm=False, accumulate_into: Optional[torch.Tensor] = None, out_scale=1.0,
           act_scale: Optional[float] = None, out=None, out_act=None):
     lib = _lib.load()
-    X = _dev(X)
+    X = _lib.dev(X, _ON_GPU)
     B, K, Tin = X.shape
     w_pw, bias, w_dw = _w(w_pw), _w(bias), _w(w_dw)
     M = w_pw.shape[0]
@@ -108,20 +96,20 @@ def dw_pw(X, w_pw, bias=None, w_dw=None, mode=0, ks_or_ratio=0, pre_scale=1.0, p
     Yact = _out(out_act, Y.shape, torch.float32, X.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_op_dw_pw(X.data_ptr(), _hp(w_dw), _hp(w_pw), _hp(bias), Y.data_ptr(), B, K, M,
                                Tin, mode, ks_or_ratio, pre_scale, int(pre_elu), int(l2norm),
-                               int(accumulate_into is not None), out_scale, _dp(Yact),
-                               float(act_scale or 0.0), _stream()), "wv_op_dw_pw")
+                               int(accumulate_into is not None), out_scale, _lib.ptr(Yact),
+                               float(act_scale or 0.0), _lib.stream()), "wv_op_dw_pw")
     return Y if act_scale is None else (Y, Yact)
 
 
 def stft_logmag(wav, n_fft, hop, mean=0.0, std=1.0, basis=None, out=None) -> torch.Tensor:
     lib = _lib.load()
-    wav = _dev(wav)
+    wav = _lib.dev(wav, _ON_GPU)
     B, T = wav.shape[0], wav.shape[-1]
     Tf = -(-T // hop)
     P = _out(out, (B, n_fft // 2 + 1, Tf), torch.float32, wav.device)
     basis = _w(basis)
     _lib.check(lib.wv_op_stft_logmag(wav.data_ptr(), _hp(basis), P.data_ptr(), B, T, n_fft, hop, mean,
-                                     std, _stream()), "wv_op_stft_logmag")
+                                     std, _lib.stream()), "wv_op_stft_logmag")
     return P
 
 
@@ -129,14 +117,14 @@ def spec_block(wav, w_pw, x, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_s
                basis=None, out=None, out_act=None):
     """Whole SpecBlock in one launch: y = x + out_scale * (W @ logmag(STFT(wav))) -> Y, (Y, Yact) or Yact alone."""
     lib = _lib.load()
-    wav, x = _dev(wav), _dev(x)
+    wav, x = _lib.dev(wav, _ON_GPU), _lib.dev(x, _ON_GPU)
     B, T = wav.shape[0], wav.shape[-1]
     M = x.shape[1]
     w_pw = _w(w_pw).reshape(M, n_fft // 2 + 1)
     Y = _out(out, x.shape, torch.float32, x.device) if want_raw else None
     Yact = _out(out_act, x.shape, torch.float32, x.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_op_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x.data_ptr(), _dp(Y), _dp(Yact), B, T, n_fft, hop, M,
-                                    mean, std, out_scale, float(act_scale or 0.0), _stream()), "wv_op_spec_block")
+    _lib.check(lib.wv_op_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x.data_ptr(), _lib.ptr(Y), _lib.ptr(Yact), B, T, n_fft, hop, M,
+                                    mean, std, out_scale, float(act_scale or 0.0), _lib.stream()), "wv_op_spec_block")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)
@@ -144,34 +132,34 @@ def spec_block(wav, w_pw, x, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0, act_s
 
 def conv_pre(x, w, bias, in_scale, out=None) -> torch.Tensor:
     lib = _lib.load()
-    x = _dev(x)
+    x = _lib.dev(x, _ON_GPU)
     B, T = x.shape[0], x.shape[-1]
     w, bias = _w(w), _w(bias)
     Cc, ks = w.shape[0], w.shape[-1]
     Y = _out(out, (B, Cc, T), torch.float32, x.device)
     _lib.check(lib.wv_op_conv_pre(x.data_ptr(), _hp(w), _hp(bias), Y.data_ptr(), B, Cc, T, ks, in_scale,
-                                  _stream()), "wv_op_conv_pre")
+                                  _lib.stream()), "wv_op_conv_pre")
     return Y
 
 
 def tail(H, w, bias, x=None, T=None, pre_scale=1.0, out_scale=1.0, out=None) -> torch.Tensor:
     lib = _lib.load()
-    H = _dev(H)
+    H = _lib.dev(H, _ON_GPU)
     B, Cc, Tin = H.shape
     T = Tin if T is None else T
     w, bias = _w(w), _w(bias)
     ks = w.shape[-1]
-    x = None if x is None else _dev(x)
+    x = None if x is None else _lib.dev(x, _ON_GPU)
     out = _out(out, (B, 1, T), torch.float32, H.device)
-    _lib.check(lib.wv_op_tail(H.data_ptr(), _hp(w), _hp(bias), _dp(x), out.data_ptr(), B, Cc, Tin, T, ks,
-                              pre_scale, out_scale, _stream()), "wv_op_tail")
+    _lib.check(lib.wv_op_tail(H.data_ptr(), _hp(w), _hp(bias), _lib.ptr(x), out.data_ptr(), B, Cc, Tin, T, ks,
+                              pre_scale, out_scale, _lib.stream()), "wv_op_tail")
     return out
 
 
 def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True, out=None, out_mean=None):
     """-> (logits [B, nb, T] or None, mean probabilities [B, nb] or None); out / out_mean: caller-owned outputs."""
     lib = _lib.load()
-    Z = _dev(Z)
+    Z = _lib.dev(Z, _ON_GPU)
     B, D, Fr = Z.shape
     w_rev, b_rev, w_last, b_last = _w(w_rev), _w(b_rev), _w(w_last), _w(b_last)
     O, hop = w_rev.shape[1], w_rev.shape[2]
@@ -180,7 +168,7 @@ def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True, o
     logits = _out(out, (B, nb, T), torch.float32, Z.device) if want_logits else None
     mean = _out(out_mean, (B, nb), torch.float32, Z.device, "out_mean") if want_mean else None
     _lib.check(lib.wv_op_head(Z.data_ptr(), _hp(w_rev), _hp(b_rev), _hp(w_last), _hp(b_last),
-                              _dp(logits), _dp(mean), B, D, O, nb, hop, Fr, T, _stream()), "wv_op_head")
+                              _lib.ptr(logits), _lib.ptr(mean), B, D, O, nb, hop, Fr, T, _lib.stream()), "wv_op_head")
     return logits, mean
 
 
@@ -193,10 +181,10 @@ def _c8(t: torch.Tensor) -> torch.Tensor:
 
 def h16_from_f32(X, scale: float = 1.0, elu: bool = False, out=None) -> torch.Tensor:
     lib = _lib.load()
-    X = _dev(X)
+    X = _lib.dev(X, _ON_GPU)
     B, Cc, T = X.shape
     Y = _out(out, (B, (Cc + 15) // 16 * 2, T, 8), torch.float16, X.device)
-    _lib.check(lib.wv_h16_from_f32(X.data_ptr(), Y.data_ptr(), B, Cc, T, float(scale), int(elu), _stream()), "wv_h16_from_f32")
+    _lib.check(lib.wv_h16_from_f32(X.data_ptr(), Y.data_ptr(), B, Cc, T, float(scale), int(elu), _lib.stream()), "wv_h16_from_f32")
     return Y
 
 
@@ -207,18 +195,18 @@ def h16_to_f32(X16, channels: int, out=None) -> torch.Tensor:
     if (channels + 15) // 16 * 2 != G:
         raise ValueError("channel count does not match the tensor's groups")
     Y = _out(out, (B, channels, T), torch.float32, X16.device)
-    _lib.check(lib.wv_h16_to_f32(X16.data_ptr(), Y.data_ptr(), B, channels, T, _stream()), "wv_h16_to_f32")
+    _lib.check(lib.wv_h16_to_f32(X16.data_ptr(), Y.data_ptr(), B, channels, T, _lib.stream()), "wv_h16_to_f32")
     return Y
 
 
 def h16_conv_pre(x, w, bias, in_scale: float = 1.0, out=None) -> torch.Tensor:
     lib = _lib.load()
-    x = _dev(x)
+    x = _lib.dev(x, _ON_GPU)
     B, _, T = x.shape
     w, bias = _w(w), _w(bias)
     Cc, ks = w.shape[0], w.shape[-1]
     Y = _out(out, (B, Cc // 8, T, 8), torch.float16, x.device)
-    _lib.check(lib.wv_h16_conv_pre(x.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), Y.data_ptr(), B, Cc, T, ks, float(in_scale), _stream()),
+    _lib.check(lib.wv_h16_conv_pre(x.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), Y.data_ptr(), B, Cc, T, ks, float(in_scale), _lib.stream()),
                "wv_h16_conv_pre")
     return Y
 
@@ -232,8 +220,8 @@ def h16_resblock(X16, w_pw1, w_dw1, b1, w_pw2, w_dw2, b2, pre_scale=1.0, out_sca
     ws = [_w(w_pw1).reshape(Cc, Cc), _w(w_dw1).reshape(Cc, -1), _w(b1), _w(w_pw2).reshape(Cc, Cc), _w(w_dw2).reshape(Cc, -1), _w(b2)]
     Y = _out(out, X16.shape, torch.float16, X16.device) if want_raw else None
     Yact = _out(out_act, X16.shape, torch.float16, X16.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_h16_resblock(X16.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _dp(Y), _dp(Yact), B, Cc, T, float(out_scale),
-                                   float(act_scale or 0.0), _stream()), "wv_h16_resblock")
+    _lib.check(lib.wv_h16_resblock(X16.data_ptr(), float(pre_scale), *[_hp(w) for w in ws], _lib.ptr(Y), _lib.ptr(Yact), B, Cc, T, float(out_scale),
+                                   float(act_scale or 0.0), _lib.stream()), "wv_h16_resblock")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)
@@ -263,9 +251,9 @@ def h16_conv(X16, w_pw, w_dw=None, bias=None, resid16=None, K: Optional[int] = N
         res["f32"] = _out(out_f32, (B, M, Tout), torch.float32, X16.device, "out_f32")
     if resid16 is not None:
         _c8(resid16)
-    _lib.check(lib.wv_h16_conv(X16.data_ptr(), _hp(w_pw), _hp(None if w_dw is None else w_dw.reshape(M, ks)), _hp(bias), _dp(resid16),
-                               _dp(res.get("raw")), _dp(res.get("act")), _dp(res.get("f32")), B, K, M, Tin, ks, stride, pad, float(out_scale),
-                               float(act_scale or 0.0), _stream()), "wv_h16_conv")
+    _lib.check(lib.wv_h16_conv(X16.data_ptr(), _hp(w_pw), _hp(None if w_dw is None else w_dw.reshape(M, ks)), _hp(bias), _lib.ptr(resid16),
+                               _lib.ptr(res.get("raw")), _lib.ptr(res.get("act")), _lib.ptr(res.get("f32")), B, K, M, Tin, ks, stride, pad, float(out_scale),
+                               float(act_scale or 0.0), _lib.stream()), "wv_h16_conv")
     return res
 
 
@@ -273,14 +261,14 @@ def h16_spec_block(wav, w_pw, x16, n_fft, hop, mean=0.0, std=1.0, out_scale=1.0,
                    out=None, out_act=None):
     """Whole SpecBlock on the f16 pipe: y = x + out_scale * (W @ logmag(STFT(wav))) -> Y16, (Y16, Yact16) or Yact16 alone (c8 f16)."""
     lib = _lib.load()
-    wav, x16 = _dev(wav), _c8(x16)
+    wav, x16 = _lib.dev(wav, _ON_GPU), _c8(x16)
     B, T = wav.shape[0], wav.shape[-1]
     M = 8 * x16.shape[1]
     w_pw = _w(w_pw).reshape(M, n_fft // 2 + 1)
     Y = _out(out, x16.shape, torch.float16, x16.device) if want_raw else None
     Yact = _out(out_act, x16.shape, torch.float16, x16.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_h16_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x16.data_ptr(), _dp(Y), _dp(Yact), B, T, n_fft, hop, M,
-                                     mean, std, out_scale, float(act_scale or 0.0), _stream()), "wv_h16_spec_block")
+    _lib.check(lib.wv_h16_spec_block(wav.data_ptr(), _hp(_w(basis)), _hp(w_pw), x16.data_ptr(), _lib.ptr(Y), _lib.ptr(Yact), B, T, n_fft, hop, M,
+                                     mean, std, out_scale, float(act_scale or 0.0), _lib.stream()), "wv_h16_spec_block")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)
@@ -298,8 +286,8 @@ def h16_upsample(X16, w_ct, w_pw, bias, ratio: int, act_scale: Optional[float] =
     w_pw, w_ct = w_pw.reshape(M, K), w_ct.reshape(K, 2 * ratio)
     Y = _out(out, (B, M // 8, Tin * ratio, 8), torch.float16, X16.device) if want_raw else None
     Yact = _out(out_act, (B, M // 8, Tin * ratio, 8), torch.float16, X16.device, "out_act") if act_scale is not None else None
-    _lib.check(lib.wv_h16_upsample(X16.data_ptr(), _hp(w_ct), _hp(w_pw), _hp(bias), _dp(Y), _dp(Yact), B, K, M, Tin, int(ratio),
-                                   float(act_scale or 0.0), _stream()), "wv_h16_upsample")
+    _lib.check(lib.wv_h16_upsample(X16.data_ptr(), _hp(w_ct), _hp(w_pw), _hp(bias), _lib.ptr(Y), _lib.ptr(Yact), B, K, M, Tin, int(ratio),
+                                   float(act_scale or 0.0), _lib.stream()), "wv_h16_upsample")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)
@@ -314,19 +302,19 @@ def h16_tail(A16, w, bias, T: int, out_scale: float, x=None, out=None) -> torch.
     Cc, ks = w.shape[-2], w.shape[-1]
     if (Cc + 15) // 16 * 2 != G:
         raise ValueError("weight channels do not match the tensor's channel groups")
-    xd = _dev(x) if x is not None else None
+    xd = _lib.dev(x, _ON_GPU) if x is not None else None
     out = _out(out, (B, 1, T), torch.float32, A16.device)
-    _lib.check(lib.wv_h16_tail(A16.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), _dp(xd), out.data_ptr(), B, Cc, Tin, T, ks, float(out_scale), _stream()),
+    _lib.check(lib.wv_h16_tail(A16.data_ptr(), _hp(w.reshape(Cc, ks)), _hp(bias), _lib.ptr(xd), out.data_ptr(), B, Cc, Tin, T, ks, float(out_scale), _lib.stream()),
                "wv_h16_tail")
     return out
 
 
 def h16_l2norm(lat, out=None) -> torch.Tensor:
     lib = _lib.load()
-    lat = _dev(lat)
+    lat = _lib.dev(lat, _ON_GPU)
     B, D, Fr = lat.shape
     Y = _out(out, (B, (D + 15) // 16 * 2, Fr, 8), torch.float16, lat.device)
-    _lib.check(lib.wv_h16_l2norm(lat.data_ptr(), Y.data_ptr(), B, D, Fr, _stream()), "wv_h16_l2norm")
+    _lib.check(lib.wv_h16_l2norm(lat.data_ptr(), Y.data_ptr(), B, D, Fr, _lib.stream()), "wv_h16_l2norm")
     return Y
 
 
@@ -335,7 +323,7 @@ def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None, out=None) -> torch
     head weight (column bit * hop + j), bc [nb].  -> mean over t < T of sigmoid(logits) [B, nb]; with keep_lo / keep_hi ([B] ints) the
     windowed mode instead: the SUM over t in [keep_lo[b], keep_hi[b]) [B, nb]."""
     lib = _lib.load()
-    lat = _dev(lat)
+    lat = _lib.dev(lat, _ON_GPU)
     B, D, Fr = lat.shape
     wc, bc = _w(wc), _w(bc)
     nb = bc.shape[0]
@@ -352,7 +340,7 @@ def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None, out=None) -> torch
         if lo.numel() != B or hi.numel() != B:
             raise ValueError("keep_lo / keep_hi need one entry per clip")
     _lib.check(lib.wv_h16_head(lat.data_ptr(), _hp(wc), _hp(bc), None if lo is not None else out.data_ptr(), B, D, nb, hop, Fr, int(T),
-                               _dp(lo), _dp(hi), _dp(out) if lo is not None else None, _stream()), "wv_h16_head")
+                               _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(out) if lo is not None else None, _lib.stream()), "wv_h16_head")
     return out
 
 
@@ -360,7 +348,7 @@ def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optio
                   out_act=None):
     """wv_h16_conv with FiLM behind the conv: film [B, bands, 2] (gamma, beta) on the device."""
     lib = _lib.load()
-    X16, film = _c8(X16), _dev(film)
+    X16, film = _c8(X16), _lib.dev(film, _ON_GPU)
     B, G, Tin, _ = X16.shape
     w_pw, w_dw, bias = _w(w_pw), _w(w_dw), _w(bias)
     M = w_pw.shape[0]
@@ -370,7 +358,8 @@ def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optio
     Y = _out(out, (B, Gm, Tout, 8), torch.float16, X16.device) if want_raw else None
     Yact = _out(out_act, (B, Gm, Tout, 8), torch.float16, X16.device, "out_act") if act_scale is not None else None
     _lib.check(lib.wv_h16_conv_film(X16.data_ptr(), _hp(w_pw.reshape(M, K)), _hp(w_dw.reshape(M, ks) if w_dw is not None else None), _hp(bias), film.data_ptr(),
-                                    int(film.shape[1]), _dp(Y), _dp(Yact), B, K, M, Tin, ks, stride, pad, float(act_scale or 0.0), _stream()), "wv_h16_conv_film")
+                                    int(film.shape[1]), _lib.ptr(Y), _lib.ptr(Yact), B, K, M, Tin, ks, stride, pad, float(act_scale or 0.0), _lib.stream()),
+               "wv_h16_conv_film")
     if Y is None:
         return Yact
     return Y if act_scale is None else (Y, Yact)

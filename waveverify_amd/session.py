@@ -145,7 +145,7 @@ class _HipSession(StreamSession):
             _lib.check(self.net._lib.wv_session_advance(
                 hist.data_ptr(), hist.shape[1], t.hv, x.data_ptr() if x.numel() else None, x.shape[1],
                 win.data_ptr() if t.wlen else None, t.wlen, nxt.data_ptr(), t.drop, t.hv2, self.S,
-                self.net._stream()),
+                _lib.stream()),
                 "wv_session_advance")
         return win, nxt
 

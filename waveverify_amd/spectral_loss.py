@@ -133,8 +133,8 @@ class _Plan:
                 dwm = out
         ws = _lib.scratch(int(self._lib.wv_specloss_workspace_bytes(self._h, B, T)), wm.device)
         rc = self._lib.wv_specloss(self._h, wm.data_ptr(), x.data_ptr(), B, T, terms.data_ptr(), totals.data_ptr(),
-                                   None if dwm is None else dwm.data_ptr(), float(stft_scale), float(mel_scale), ws.data_ptr(), ws.numel(),
-                                   C.c_void_p(torch.cuda.current_stream(wm.device).cuda_stream))
+                                   _lib.ptr(dwm), float(stft_scale), float(mel_scale), ws.data_ptr(), ws.numel(),
+                                   _lib.stream(wm.device))
         _lib.check(rc, "wv_specloss")
         return terms, totals, dwm
 

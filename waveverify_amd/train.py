@@ -22,11 +22,7 @@ import torch
 
 from . import _lib
 
-
-def _f(t: torch.Tensor) -> torch.Tensor:
-    if not t.is_cuda:
-        raise RuntimeError("training tensors must live on the GPU")
-    return t.float().contiguous()
+_ON_GPU = "training tensors must live on the GPU"
 
 
 def _dst(into, key, like_shape, device):
@@ -43,124 +39,15 @@ def _dst(into, key, like_shape, device):
     return t
 
 
-class TrainHalf:
-    def __init__(self, channels: int):
-        self._lib = _lib.load()
-        self.C = int(channels)
-        self._h = C.c_void_p()
-        if self._lib.wv_train_half_create(self.C, C.byref(self._h)) != 0:
-            raise RuntimeError(f"wv_train_half_create: {self._lib.wv_train_last_error().decode()}")
-
-    @staticmethod
-    def _stream():
-        return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-    def _p(self, p: Dict[str, torch.Tensor]):
-        g_pw, v_pw = _f(p["g_pw"]).reshape(self.C), _f(p["v_pw"]).reshape(self.C, self.C)
-        g_dw, v_dw = _f(p["g_dw"]).reshape(self.C), _f(p["v_dw"]).reshape(self.C, 5)
-        return g_pw, v_pw, g_dw, v_dw, _f(p["b_dw"]).reshape(self.C)
-
-    def forward(self, x: torch.Tensor, p: Dict[str, torch.Tensor], pre_scale: float) -> torch.Tensor:
-        x = _f(x)
-        B, Cc, T = x.shape
-        g_pw, v_pw, g_dw, v_dw, b = self._p(p)
-        y = torch.empty_like(x)
-        rc = self._lib.wv_train_half_forward(self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(),
-                                             v_dw.data_ptr(), b.data_ptr(), float(pre_scale), y.data_ptr(), B, T,
-                                             self._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_half_forward: {self._lib.wv_train_last_error().decode()}")
-        return y
-
-    def backward(self, x: torch.Tensor, p: Dict[str, torch.Tensor], pre_scale: float, dy: torch.Tensor):
-        x, dy = _f(x), _f(dy)
-        B, Cc, T = x.shape
-        g_pw, v_pw, g_dw, v_dw, _ = self._p(p)
-        out = dict(dx=torch.empty_like(x), dg_pw=torch.empty_like(g_pw), dv_pw=torch.empty_like(v_pw),
-                   dg_dw=torch.empty_like(g_dw), dv_dw=torch.empty_like(v_dw), db_dw=torch.empty_like(g_dw))
-        ws = _lib.scratch(int(self._lib.wv_train_half_workspace_bytes(self._h, B, T)), x.device)
-        rc = self._lib.wv_train_half_backward(
-            self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), float(pre_scale),
-            dy.data_ptr(), out["dx"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(), out["dg_dw"].data_ptr(),
-            out["dv_dw"].data_ptr(), out["db_dw"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), self._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_half_backward: {self._lib.wv_train_last_error().decode()}")
-        return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self._lib.wv_train_half_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-
-class TrainUnit:
-    """The general trunk unit with live weight norm (wv_train_unit_*): act(pre_scale x) -> 1x1 [M,K] -> causal
-    depth-wise conv (ks, stride) + bias.  ks = 2r, stride = r, M = 2K is the encoder's Downsample unit
-    (/root/reference/modules/seanet.py:733-772).  params: g_pw [M], v_pw [M,K], g_dw [M], v_dw [M,ks], b_dw [M]."""
-
-    def __init__(self, k_in: int, m_out: int, ks: int, stride: int):
-        self._lib = _lib.load()
-        self.K, self.M, self.ks, self.stride = int(k_in), int(m_out), int(ks), int(stride)
-        self._h = C.c_void_p()
-        if self._lib.wv_train_unit_create(self.K, self.M, self.ks, self.stride, C.byref(self._h)) != 0:
-            raise RuntimeError(f"wv_train_unit_create: {self._lib.wv_train_last_error().decode()}")
-
-    def _p(self, p):
-        return (_f(p["g_pw"]).reshape(self.M), _f(p["v_pw"]).reshape(self.M, self.K), _f(p["g_dw"]).reshape(self.M),
-                _f(p["v_dw"]).reshape(self.M, self.ks), _f(p["b_dw"]).reshape(self.M))
-
-    def forward(self, x, p, pre_scale: float, pre_elu: bool = True):
-        x = _f(x)
-        B, _, T = x.shape
-        g_pw, v_pw, g_dw, v_dw, b = self._p(p)
-        y = torch.empty(B, self.M, -(-T // self.stride), device=x.device)
-        rc = self._lib.wv_train_unit_forward(self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(),
-                                             b.data_ptr(), float(pre_scale), int(pre_elu), y.data_ptr(), B, T, TrainHalf._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_unit_forward: {self._lib.wv_train_last_error().decode()}")
-        return y
-
-    def backward(self, x, p, pre_scale: float, dy, pre_elu: bool = True, need_dx: bool = True, into=None):
-        x, dy = _f(x), _f(dy)
-        B, _, T = x.shape
-        g_pw, v_pw, g_dw, v_dw, _ = self._p(p)
-        dev = x.device
-        out = dict(dx=_dst(into, "dx", x.shape, dev) if need_dx else None, dg_pw=_dst(into, "dg_pw", g_pw.shape, dev), dv_pw=_dst(into, "dv_pw", v_pw.shape, dev),
-                   dg_dw=_dst(into, "dg_dw", g_dw.shape, dev), dv_dw=_dst(into, "dv_dw", v_dw.shape, dev), db_dw=_dst(into, "db_dw", g_dw.shape, dev))
-        ws = _lib.scratch(int(self._lib.wv_train_unit_workspace_bytes(self._h, B, T)), x.device)
-        rc = self._lib.wv_train_unit_backward(
-            self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), float(pre_scale), int(pre_elu),
-            dy.data_ptr(), out["dx"].data_ptr() if need_dx else None, out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
-            out["dg_dw"].data_ptr(), out["dv_dw"].data_ptr(), out["db_dw"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_unit_backward: {self._lib.wv_train_last_error().decode()}")
-        return out
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self._lib.wv_train_unit_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
-
-
 class _Handle:
-    """Owner of one wv_train_* handle."""
+    """Owner of one library handle: create, status check, destroy."""
     _create = _destroy = ""
+    _check = staticmethod(_lib.check)
 
     def _open(self, *args):
         self._lib = _lib.load()
         self._h = C.c_void_p()
-        if getattr(self._lib, self._create)(*args, C.byref(self._h)) != 0:
-            raise RuntimeError(f"{self._create}: {self._lib.wv_train_last_error().decode()}")
-
-    def _check(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what}: {self._lib.wv_train_last_error().decode()}")
+        self._check(getattr(self._lib, self._create)(*args, C.byref(self._h)), self._create)
 
     def __del__(self):
         try:
@@ -169,6 +56,56 @@ class _Handle:
                 self._h = C.c_void_p()
         except Exception:
             pass
+
+
+class TrainUnit(_Handle):
+    """The general trunk unit with live weight norm (wv_train_unit_*): act(pre_scale x) -> 1x1 [M,K] -> causal
+    depth-wise conv (ks, stride) + bias.  ks = 2r, stride = r, M = 2K is the encoder's Downsample unit
+    (/root/reference/modules/seanet.py:733-772).  params: g_pw [M], v_pw [M,K], g_dw [M], v_dw [M,ks], b_dw [M]."""
+    _create, _destroy = "wv_train_unit_create", "wv_train_unit_destroy"
+
+    def __init__(self, k_in: int, m_out: int, ks: int, stride: int):
+        self.K, self.M, self.ks, self.stride = int(k_in), int(m_out), int(ks), int(stride)
+        self._open(self.K, self.M, self.ks, self.stride)
+
+    def _p(self, p):
+        return (_lib.dev(p["g_pw"], _ON_GPU).reshape(self.M), _lib.dev(p["v_pw"], _ON_GPU).reshape(self.M, self.K),
+                _lib.dev(p["g_dw"], _ON_GPU).reshape(self.M), _lib.dev(p["v_dw"], _ON_GPU).reshape(self.M, self.ks),
+                _lib.dev(p["b_dw"], _ON_GPU).reshape(self.M))
+
+    def forward(self, x, p, pre_scale: float, pre_elu: bool = True):
+        x = _lib.dev(x, _ON_GPU)
+        B, _, T = x.shape
+        g_pw, v_pw, g_dw, v_dw, b = self._p(p)
+        y = torch.empty(B, self.M, -(-T // self.stride), device=x.device)
+        self._check(self._lib.wv_train_unit_forward(self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(),
+                                                    b.data_ptr(), float(pre_scale), int(pre_elu), y.data_ptr(), B, T, _lib.stream()),
+                    "wv_train_unit_forward")
+        return y
+
+    def backward(self, x, p, pre_scale: float, dy, pre_elu: bool = True, need_dx: bool = True, into=None):
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
+        B, _, T = x.shape
+        g_pw, v_pw, g_dw, v_dw, _ = self._p(p)
+        dev = x.device
+        out = dict(dx=_dst(into, "dx", x.shape, dev) if need_dx else None, dg_pw=_dst(into, "dg_pw", g_pw.shape, dev), dv_pw=_dst(into, "dv_pw", v_pw.shape, dev),
+                   dg_dw=_dst(into, "dg_dw", g_dw.shape, dev), dv_dw=_dst(into, "dv_dw", v_dw.shape, dev), db_dw=_dst(into, "db_dw", g_dw.shape, dev))
+        ws = _lib.scratch(int(self._lib.wv_train_unit_workspace_bytes(self._h, B, T)), x.device)
+        self._check(self._lib.wv_train_unit_backward(
+            self._h, x.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), float(pre_scale), int(pre_elu),
+            dy.data_ptr(), _lib.ptr(out["dx"]), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
+            out["dg_dw"].data_ptr(), out["dv_dw"].data_ptr(), out["db_dw"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), _lib.stream()),
+            "wv_train_unit_backward")
+        return out
+
+
+class TrainHalf(TrainUnit):
+    """One half of a SEANetResnetBlock (/root/reference/modules/seanet.py:39-116): the unit with K = M = C, ks = 5, stride = 1, ELU on.
+    forward(x, p, pre_scale) and backward(x, p, pre_scale, dy) are the unit's."""
+
+    def __init__(self, channels: int):
+        super().__init__(channels, channels, 5, 1)
+        self.C = self.K
 
 
 OPT_KEY = "wv_amd_optimizers"        # checkpoint key of this library's flat AdamW moments (not the reference's `optimizers` schema)
@@ -183,51 +120,44 @@ class StftFeatures(_Handle):
         """basis: the `...spec.weight` tensor of a checkpoint ([2F, 1, n_fft], a learned one when the reference trained with
         spec_learnable: true, conf/base.yml) or None = the reference's windowed DFT basis (conv.py:1003-1026)."""
         self.n_fft, self.hop, self.mean, self.std = int(n_fft), int(hop), float(mean), float(std)
-        self._lib = _lib.load()
-        self._h = C.c_void_p()
         bp = None
         if basis is not None:
             b = np.ascontiguousarray(np.asarray(basis, dtype=np.float32).reshape(-1))
             if b.size != (self.n_fft + 2) * self.n_fft:
                 raise ValueError(f"spec.weight for n_fft={self.n_fft} must hold {(self.n_fft + 2) * self.n_fft} values, got {b.size}")
             bp = b.ctypes.data_as(C.c_void_p)
-        if self._lib.wv_stft_plan_create(self.n_fft, bp, C.byref(self._h)) != 0:
-            raise RuntimeError("wv_stft_plan_create failed")
+        self._open(self.n_fft, bp)
 
     def __call__(self, wav: torch.Tensor) -> torch.Tensor:
-        wav = _f(wav)
+        wav = _lib.dev(wav, _ON_GPU)
         B, T = wav.shape[0], wav.shape[-1]
         P = torch.empty(B, self.n_fft // 2 + 1, -(-T // self.hop), device=wav.device)
-        if self._lib.wv_stft_plan_logmag(self._h, wav.data_ptr(), P.data_ptr(), B, T, self.hop, self.mean, self.std, TrainHalf._stream()) != 0:
-            raise RuntimeError("wv_stft_plan_logmag failed")
+        _lib.check(self._lib.wv_stft_plan_logmag(self._h, wav.data_ptr(), P.data_ptr(), B, T, self.hop, self.mean, self.std, _lib.stream()), "wv_stft_plan_logmag")
         return P
 
     def backward(self, wav: torch.Tensor, dP: torch.Tensor, dwav: torch.Tensor, accumulate: bool = True) -> None:
         """dwav (+)= the gradient of <dP, features(wav)> towards the audio."""
-        wav, dP = _f(wav), _f(dP)
+        wav, dP = _lib.dev(wav, _ON_GPU), _lib.dev(dP, _ON_GPU)
         B, T = wav.shape[0], wav.shape[-1]
         ws = _lib.scratch(int(self._lib.wv_stft_plan_backward_workspace_bytes(self._h, B, T, self.hop)), wav.device)
-        if self._lib.wv_stft_plan_backward(self._h, wav.data_ptr(), dP.data_ptr(), dwav.data_ptr(), int(accumulate), B, T, self.hop, self.std,
-                                           ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
-            raise RuntimeError("wv_stft_plan_backward failed")
+        _lib.check(self._lib.wv_stft_plan_backward(self._h, wav.data_ptr(), dP.data_ptr(), dwav.data_ptr(), int(accumulate), B, T, self.hop, self.std,
+                                                   ws.data_ptr(), ws.numel(), _lib.stream()), "wv_stft_plan_backward")
 
     def basis_grad(self, wav: torch.Tensor, dP: torch.Tensor, dbasis: torch.Tensor) -> None:
         """dbasis ([2F, 1, n_fft] or [2F, n_fft], overwritten) = the gradient of <dP, features(wav)> towards the basis, all 2F rows."""
-        wav, dP = _f(wav), _f(dP)
+        wav, dP = _lib.dev(wav, _ON_GPU), _lib.dev(dP, _ON_GPU)
         B, T = wav.shape[0], wav.shape[-1]
         if dbasis.dtype != torch.float32 or not dbasis.is_contiguous() or dbasis.numel() != (self.n_fft + 2) * self.n_fft or dbasis.device != wav.device:
             raise ValueError(f"basis gradient for n_fft={self.n_fft}: need a contiguous float32 tensor of {(self.n_fft + 2) * self.n_fft} elements on {wav.device}")
         ws = _lib.scratch(int(self._lib.wv_stft_plan_basis_grad_workspace_bytes(self._h, B, T, self.hop)), wav.device)
-        if self._lib.wv_stft_plan_basis_grad(self._h, wav.data_ptr(), dP.data_ptr(), dbasis.data_ptr(), B, T, self.hop, self.std,
-                                             ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
-            raise RuntimeError("wv_stft_plan_basis_grad failed")
+        _lib.check(self._lib.wv_stft_plan_basis_grad(self._h, wav.data_ptr(), dP.data_ptr(), dbasis.data_ptr(), B, T, self.hop, self.std,
+                                                     ws.data_ptr(), ws.numel(), _lib.stream()), "wv_stft_plan_basis_grad")
 
     def set_basis_device(self, basis: torch.Tensor) -> None:
         """Run on `basis` from now on: a CUDA float32 tensor of (n_fft + 2) * n_fft values (e.g. the arena view an optimizer stepped)."""
         if not basis.is_cuda or basis.dtype != torch.float32 or not basis.is_contiguous() or basis.numel() != (self.n_fft + 2) * self.n_fft:
             raise ValueError(f"spec.weight for n_fft={self.n_fft}: need a contiguous float32 CUDA tensor of {(self.n_fft + 2) * self.n_fft} values")
-        if self._lib.wv_stft_plan_set_basis_device(self._h, basis.data_ptr(), TrainHalf._stream()) != 0:
-            raise RuntimeError("wv_stft_plan_set_basis_device failed")
+        _lib.check(self._lib.wv_stft_plan_set_basis_device(self._h, basis.data_ptr(), _lib.stream()), "wv_stft_plan_set_basis_device")
 
 
 class TrainConvPre(_Handle):
@@ -240,24 +170,24 @@ class TrainConvPre(_Handle):
         self._open(self.C, self.ks)
 
     def forward(self, x, p, in_scale: float):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, _, T = x.shape
-        g, v, b = _f(p["g"]).reshape(self.C), _f(p["v"]).reshape(self.C, self.ks), _f(p["b"]).reshape(self.C)
+        g, v, b = _lib.dev(p["g"], _ON_GPU).reshape(self.C), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.ks), _lib.dev(p["b"], _ON_GPU).reshape(self.C)
         y = torch.empty(B, self.C, T, device=x.device)
         self._check(self._lib.wv_train_convpre_forward(self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), b.data_ptr(), float(in_scale),
-                                                       y.data_ptr(), B, T, TrainHalf._stream()), "wv_train_convpre_forward")
+                                                       y.data_ptr(), B, T, _lib.stream()), "wv_train_convpre_forward")
         return y
 
     def backward(self, x, p, in_scale: float, dy, need_dx: bool = False, into=None):
-        x, dy = _f(x), _f(dy)
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, _, T = x.shape
-        g, v = _f(p["g"]).reshape(self.C), _f(p["v"]).reshape(self.C, self.ks)
+        g, v = _lib.dev(p["g"], _ON_GPU).reshape(self.C), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.ks)
         d = x.device
         out = dict(dx=torch.empty_like(x) if need_dx else None, dg=_dst(into, "dg", g.shape, d), dv=_dst(into, "dv", v.shape, d), db=_dst(into, "db", g.shape, d))
         ws = _lib.scratch(int(self._lib.wv_train_convpre_workspace_bytes(self._h, B, T)), x.device)
         self._check(self._lib.wv_train_convpre_backward(
             self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), float(in_scale), dy.data_ptr(), out["dx"].data_ptr() if need_dx else None,
-            out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream()),
+            out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), _lib.stream()),
             "wv_train_convpre_backward")
         return out
 
@@ -272,29 +202,29 @@ class TrainSpecAdd(_Handle):
         self._open(self.C, self.F)
 
     def forward(self, x, P, p, scale_param, res_scale: float):
-        x, P = _f(x), _f(P)
+        x, P = _lib.dev(x, _ON_GPU), _lib.dev(P, _ON_GPU)
         B, _, T = x.shape
-        g, v = _f(p["g"]).reshape(self.C), _f(p["v"]).reshape(self.C, self.F)
-        sp = None if scale_param is None else _f(scale_param).reshape(1)
+        g, v = _lib.dev(p["g"], _ON_GPU).reshape(self.C), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.F)
+        sp = None if scale_param is None else _lib.dev(scale_param, _ON_GPU).reshape(1)
         y = torch.empty_like(x)
         self._check(self._lib.wv_train_spec_forward(self._h, x.data_ptr(), P.data_ptr(), g.data_ptr(), v.data_ptr(),
-                                                    None if sp is None else sp.data_ptr(), float(res_scale), y.data_ptr(), B, T,
-                                                    TrainHalf._stream()), "wv_train_spec_forward")
+                                                    _lib.ptr(sp), float(res_scale), y.data_ptr(), B, T,
+                                                    _lib.stream()), "wv_train_spec_forward")
         return y
 
     def backward(self, P, p, scale_param, res_scale: float, dy, need_dP: bool = False, into=None):
-        P, dy = _f(P), _f(dy)
+        P, dy = _lib.dev(P, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, _, T = dy.shape
-        g, v = _f(p["g"]).reshape(self.C), _f(p["v"]).reshape(self.C, self.F)
-        sp = None if scale_param is None else _f(scale_param).reshape(1)
+        g, v = _lib.dev(p["g"], _ON_GPU).reshape(self.C), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.F)
+        sp = None if scale_param is None else _lib.dev(scale_param, _ON_GPU).reshape(1)
         out = dict(dg=_dst(into, "dg", g.shape, dy.device), dv=_dst(into, "dv", v.shape, dy.device),
                    d_scale_param=None if sp is None else _dst(into, "d_scale_param", (1,), dy.device),
                    dP=torch.empty_like(P) if need_dP else None)
         ws = _lib.scratch(int(self._lib.wv_train_spec_workspace_bytes(self._h, B, T)), dy.device)
         self._check(self._lib.wv_train_spec_backward(
-            self._h, P.data_ptr(), g.data_ptr(), v.data_ptr(), None if sp is None else sp.data_ptr(), float(res_scale), dy.data_ptr(),
+            self._h, P.data_ptr(), g.data_ptr(), v.data_ptr(), _lib.ptr(sp), float(res_scale), dy.data_ptr(),
             out["dg"].data_ptr(), out["dv"].data_ptr(), None if sp is None else out["d_scale_param"].data_ptr(),
-            out["dP"].data_ptr() if need_dP else None, B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream()), "wv_train_spec_backward")
+            out["dP"].data_ptr() if need_dP else None, B, T, ws.data_ptr(), ws.numel(), _lib.stream()), "wv_train_spec_backward")
         return out
 
 
@@ -308,21 +238,21 @@ class TrainConvPost(_Handle):
         self._open(self.C, self.D, self.ks)
 
     def _p(self, p):
-        return (_f(p["g_dw"]).reshape(self.C), _f(p["v_dw"]).reshape(self.C, self.ks), _f(p["g_pw"]).reshape(self.D),
-                _f(p["v_pw"]).reshape(self.D, self.C), _f(p["b"]).reshape(self.D))
+        return (_lib.dev(p["g_dw"], _ON_GPU).reshape(self.C), _lib.dev(p["v_dw"], _ON_GPU).reshape(self.C, self.ks), _lib.dev(p["g_pw"], _ON_GPU).reshape(self.D),
+                _lib.dev(p["v_pw"], _ON_GPU).reshape(self.D, self.C), _lib.dev(p["b"], _ON_GPU).reshape(self.D))
 
     def forward(self, x, p):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, _, T = x.shape
         g_dw, v_dw, g_pw, v_pw, b = self._p(p)
         y = torch.empty(B, self.D, T, device=x.device)
         self._check(self._lib.wv_train_convpost_forward(self._h, x.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(),
-                                                        b.data_ptr(), int(self.l2norm), y.data_ptr(), B, T, TrainHalf._stream()),
+                                                        b.data_ptr(), int(self.l2norm), y.data_ptr(), B, T, _lib.stream()),
                     "wv_train_convpost_forward")
         return y
 
     def backward(self, x, p, dy, into=None):
-        x, dy = _f(x), _f(dy)
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, _, T = x.shape
         g_dw, v_dw, g_pw, v_pw, b = self._p(p)
         d = x.device
@@ -332,7 +262,7 @@ class TrainConvPost(_Handle):
         self._check(self._lib.wv_train_convpost_backward(
             self._h, x.data_ptr(), g_dw.data_ptr(), v_dw.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), b.data_ptr(), int(self.l2norm), dy.data_ptr(),
             out["dx"].data_ptr(), out["dg_dw"].data_ptr(), out["dv_dw"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
-            out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream()), "wv_train_convpost_backward")
+            out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), _lib.stream()), "wv_train_convpost_backward")
         return out
 
 
@@ -346,25 +276,25 @@ class TrainHead(_Handle):
         self._open(self.D, self.O, self.nb, self.hop)
 
     def _p(self, p):
-        return (_f(p["w_rev"]).reshape(self.D, self.O, self.hop), _f(p["b_rev"]).reshape(self.O), _f(p["w_last"]).reshape(self.nb, self.O),
-                _f(p["b_last"]).reshape(self.nb))
+        return (_lib.dev(p["w_rev"], _ON_GPU).reshape(self.D, self.O, self.hop), _lib.dev(p["b_rev"], _ON_GPU).reshape(self.O),
+                _lib.dev(p["w_last"], _ON_GPU).reshape(self.nb, self.O), _lib.dev(p["b_last"], _ON_GPU).reshape(self.nb))
 
     def _ws(self, B, N, dev):
         return _lib.scratch(int(self._lib.wv_train_head_workspace_bytes(self._h, B, N)), dev)
 
     def forward(self, z, p, T: int):
-        z = _f(z)
+        z = _lib.dev(z, _ON_GPU)
         B, _, N = z.shape
         w_rev, b_rev, w_last, b_last = self._p(p)
         logits = torch.empty(B, self.nb, T, device=z.device)
         ws = self._ws(B, N, z.device)
         self._check(self._lib.wv_train_head_forward(self._h, z.data_ptr(), w_rev.data_ptr(), b_rev.data_ptr(), w_last.data_ptr(), b_last.data_ptr(),
-                                                    logits.data_ptr(), B, N, int(T), ws.data_ptr(), ws.numel(), TrainHalf._stream()),
+                                                    logits.data_ptr(), B, N, int(T), ws.data_ptr(), ws.numel(), _lib.stream()),
                     "wv_train_head_forward")
         return logits
 
     def backward(self, z, p, dlogits, into=None):
-        z, dl = _f(z), _f(dlogits)
+        z, dl = _lib.dev(z, _ON_GPU), _lib.dev(dlogits, _ON_GPU)
         B, _, N = z.shape
         w_rev, b_rev, w_last, _ = self._p(p)
         d = z.device
@@ -374,7 +304,7 @@ class TrainHead(_Handle):
         self._check(self._lib.wv_train_head_backward(
             self._h, z.data_ptr(), w_rev.data_ptr(), b_rev.data_ptr(), w_last.data_ptr(), dl.data_ptr(), out["dz"].data_ptr(),
             out["dw_rev"].data_ptr(), out["db_rev"].data_ptr(), out["dw_last"].data_ptr(), out["db_last"].data_ptr(), B, N, dl.shape[2],
-            ws.data_ptr(), ws.numel(), TrainHalf._stream()), "wv_train_head_backward")
+            ws.data_ptr(), ws.numel(), _lib.stream()), "wv_train_head_backward")
         return out
 
 
@@ -388,21 +318,21 @@ class TrainUp(_Handle):
         self._open(self.K, self.M, self.r)
 
     def _p(self, p):
-        return (_f(p["g_ct"]).reshape(self.K), _f(p["v_ct"]).reshape(self.K, 2 * self.r), _f(p["g_pw"]).reshape(self.M),
-                _f(p["v_pw"]).reshape(self.M, self.K), _f(p["b"]).reshape(self.M))
+        return (_lib.dev(p["g_ct"], _ON_GPU).reshape(self.K), _lib.dev(p["v_ct"], _ON_GPU).reshape(self.K, 2 * self.r), _lib.dev(p["g_pw"], _ON_GPU).reshape(self.M),
+                _lib.dev(p["v_pw"], _ON_GPU).reshape(self.M, self.K), _lib.dev(p["b"], _ON_GPU).reshape(self.M))
 
     def forward(self, x, p, pre_scale: float, pre_elu: bool = True):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, _, T = x.shape
         g_ct, v_ct, g_pw, v_pw, b = self._p(p)
         y = torch.empty(B, self.M, T * self.r, device=x.device)
         self._check(self._lib.wv_train_up_forward(self._h, x.data_ptr(), g_ct.data_ptr(), v_ct.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(),
-                                                  b.data_ptr(), float(pre_scale), int(pre_elu), y.data_ptr(), B, T, TrainHalf._stream()),
+                                                  b.data_ptr(), float(pre_scale), int(pre_elu), y.data_ptr(), B, T, _lib.stream()),
                     "wv_train_up_forward")
         return y
 
     def backward(self, x, p, pre_scale: float, dy, pre_elu: bool = True, into=None):
-        x, dy = _f(x), _f(dy)
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, _, T = x.shape
         g_ct, v_ct, g_pw, v_pw, b = self._p(p)
         d = x.device
@@ -412,7 +342,7 @@ class TrainUp(_Handle):
         self._check(self._lib.wv_train_up_backward(
             self._h, x.data_ptr(), g_ct.data_ptr(), v_ct.data_ptr(), g_pw.data_ptr(), v_pw.data_ptr(), float(pre_scale), int(pre_elu),
             dy.data_ptr(), out["dx"].data_ptr(), out["dg_ct"].data_ptr(), out["dv_ct"].data_ptr(), out["dg_pw"].data_ptr(), out["dv_pw"].data_ptr(),
-            out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), TrainHalf._stream()), "wv_train_up_backward")
+            out["db"].data_ptr(), B, T, ws.data_ptr(), ws.numel(), _lib.stream()), "wv_train_up_backward")
         return out
 
 
@@ -426,24 +356,24 @@ class TrainTail(_Handle):
         self._open(self.C, self.ks)
 
     def forward(self, x, p, post: float, wav_std: float, T: int):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, _, Tin = x.shape
-        g, v, b = _f(p["g"]).reshape(1), _f(p["v"]).reshape(self.C, self.ks), _f(p["b"]).reshape(1)
+        g, v, b = _lib.dev(p["g"], _ON_GPU).reshape(1), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.ks), _lib.dev(p["b"], _ON_GPU).reshape(1)
         delta = torch.empty(B, 1, T, device=x.device)
         self._check(self._lib.wv_train_tail_forward(self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), b.data_ptr(), float(post), float(wav_std),
-                                                    delta.data_ptr(), B, Tin, int(T), TrainHalf._stream()), "wv_train_tail_forward")
+                                                    delta.data_ptr(), B, Tin, int(T), _lib.stream()), "wv_train_tail_forward")
         return delta
 
     def backward(self, x, p, post: float, wav_std: float, delta, d_delta, into=None):
-        x, delta, dd = _f(x), _f(delta), _f(d_delta)
+        x, delta, dd = _lib.dev(x, _ON_GPU), _lib.dev(delta, _ON_GPU), _lib.dev(d_delta, _ON_GPU)
         B, _, Tin = x.shape
-        g, v = _f(p["g"]).reshape(1), _f(p["v"]).reshape(self.C, self.ks)
+        g, v = _lib.dev(p["g"], _ON_GPU).reshape(1), _lib.dev(p["v"], _ON_GPU).reshape(self.C, self.ks)
         d = x.device
         out = dict(dx=torch.empty_like(x), dg=_dst(into, "dg", g.shape, d), dv=_dst(into, "dv", v.shape, d), db=_dst(into, "db", (1,), d))
         ws = _lib.scratch(int(self._lib.wv_train_tail_workspace_bytes(self._h, B)), x.device)
         self._check(self._lib.wv_train_tail_backward(
             self._h, x.data_ptr(), g.data_ptr(), v.data_ptr(), float(post), float(wav_std), delta.data_ptr(), dd.data_ptr(), out["dx"].data_ptr(),
-            out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, Tin, delta.shape[-1], ws.data_ptr(), ws.numel(), TrainHalf._stream()),
+            out["dg"].data_ptr(), out["dv"].data_ptr(), out["db"].data_ptr(), B, Tin, delta.shape[-1], ws.data_ptr(), ws.numel(), _lib.stream()),
             "wv_train_tail_backward")
         return out
 
@@ -456,7 +386,7 @@ class _HalfGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dg_pw", "dv_pw", "dg_dw", "dv_dw", "db")]
 
 
-class TrainBlock:
+class TrainBlock(_Handle):
     """Whole SEANetResnetBlock (/root/reference/modules/seanet.py:245-281, identity shortcut):
     y = x + res_scale * res_scale_param * half2(half1(pre_scale * x)); `res_scale_param` is the trainable [1]
     tensor of zero_init blocks or None.
@@ -464,42 +394,38 @@ class TrainBlock:
     Contract: `backward(..., saved)` reuses the weight folds its `forward` left in the handle -- call it after THAT forward, with the
     same parameter tensors, before any optimizer step or other forward on this block (different tensors raise; changed values in the
     same tensors cannot be detected)."""
+    _create, _destroy = "wv_train_block_create", "wv_train_block_destroy"
 
     def __init__(self, channels: int):
-        self._lib = _lib.load()
         self.C = int(channels)
-        self._h = C.c_void_p()
-        if self._lib.wv_train_block_create(self.C, C.byref(self._h)) != 0:
-            raise RuntimeError(f"wv_train_block_create: {self._lib.wv_train_last_error().decode()}")
+        self._open(self.C)
 
     def _params(self, ps):
         keep, arr = [], (_HalfParams * 2)()
         for i, p in enumerate(ps):
-            t = [_f(p["g_pw"]).reshape(self.C), _f(p["v_pw"]).reshape(self.C, self.C), _f(p["g_dw"]).reshape(self.C),
-                 _f(p["v_dw"]).reshape(self.C, 5), _f(p["b_dw"]).reshape(self.C)]
+            t = [_lib.dev(p["g_pw"], _ON_GPU).reshape(self.C), _lib.dev(p["v_pw"], _ON_GPU).reshape(self.C, self.C), _lib.dev(p["g_dw"], _ON_GPU).reshape(self.C),
+                 _lib.dev(p["v_dw"], _ON_GPU).reshape(self.C, 5), _lib.dev(p["b_dw"], _ON_GPU).reshape(self.C)]
             keep.append(t)
             arr[i] = _HalfParams(*[x.data_ptr() for x in t])
         return arr, keep
 
     def forward(self, x, ps, res_scale_param, pre_scale: float, res_scale: float):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, _, T = x.shape
         arr, keep = self._params(ps)
-        rsp = None if res_scale_param is None else _f(res_scale_param).reshape(1)
+        rsp = None if res_scale_param is None else _lib.dev(res_scale_param, _ON_GPU).reshape(1)
         y = torch.empty_like(x)
         saved = _lib.scratch(int(self._lib.wv_train_block_saved_bytes(self._h, B, T)), x.device)
-        rc = self._lib.wv_train_block_forward(self._h, x.data_ptr(), arr, None if rsp is None else rsp.data_ptr(), float(pre_scale),
-                                              float(res_scale), y.data_ptr(), saved.data_ptr(), saved.numel(), B, T, TrainHalf._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_block_forward: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_block_forward(self._h, x.data_ptr(), arr, _lib.ptr(rsp), float(pre_scale),
+                                                    float(res_scale), y.data_ptr(), saved.data_ptr(), saved.numel(), B, T, _lib.stream()), "wv_train_block_forward")
         return y, saved
 
     def backward(self, x, ps, res_scale_param, pre_scale: float, res_scale: float, dy, saved, into=None):
         """into: optional dict(halves=[{dg_pw, dv_pw, dg_dw, dv_dw, db_dw} x 2], d_res_scale_param, dx) of destinations (see _dst)."""
-        x, dy = _f(x), _f(dy)
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, _, T = x.shape
         arr, keep = self._params(ps)
-        rsp = None if res_scale_param is None else _f(res_scale_param).reshape(1)
+        rsp = None if res_scale_param is None else _lib.dev(res_scale_param, _ON_GPU).reshape(1)
         dev = x.device
         grads, garr = [], (_HalfGrads * 2)()
         for i in range(2):
@@ -511,21 +437,11 @@ class TrainBlock:
         dx = _dst(into, "dx", x.shape, dev)
         drsp = None if rsp is None else _dst(into, "d_res_scale_param", (1,), dev)
         ws = _lib.scratch(int(self._lib.wv_train_block_workspace_bytes(self._h, B, T)), dev)
-        rc = self._lib.wv_train_block_backward(
-            self._h, x.data_ptr(), arr, None if rsp is None else rsp.data_ptr(), float(pre_scale), float(res_scale), dy.data_ptr(),
-            saved.data_ptr(), dx.data_ptr(), garr, None if drsp is None else drsp.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
-            TrainHalf._stream())
-        if rc != 0:
-            raise RuntimeError(f"wv_train_block_backward: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_block_backward(
+            self._h, x.data_ptr(), arr, _lib.ptr(rsp), float(pre_scale), float(res_scale), dy.data_ptr(),
+            saved.data_ptr(), dx.data_ptr(), garr, _lib.ptr(drsp), B, T, ws.data_ptr(), ws.numel(),
+            _lib.stream()), "wv_train_block_backward")
         return dict(dx=dx, halves=grads, d_res_scale_param=drsp)
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None) and self._h.value:
-                self._lib.wv_train_block_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
 
 def bce_logits(logits: torch.Tensor, mask=None, msg=None, grad_scale: float = 1.0, want_grad: bool = True):
@@ -542,17 +458,15 @@ def bce_logits(logits: torch.Tensor, mask=None, msg=None, grad_scale: float = 1.
     if msg is None and Cz != 1:
         raise ValueError("localization loss: logits and presence mask must have the same shape")
     lib = _lib.load()
-    z = _f(logits)
-    m = None if mask is None else _f(mask)
-    g = None if msg is None else _f(msg)
+    z = _lib.dev(logits, _ON_GPU)
+    m = None if mask is None else _lib.dev(mask, _ON_GPU)
+    g = None if msg is None else _lib.dev(msg, _ON_GPU)
     loss = torch.empty(1, device=z.device)
     dz = torch.empty_like(z) if want_grad else None
     ws = _lib.scratch(int(lib.wv_train_bce_workspace_bytes()), z.device)
-    rc = lib.wv_train_bce_logits(z.data_ptr(), None if m is None else m.data_ptr(), None if g is None else g.data_ptr(), loss.data_ptr(),
-                                 None if dz is None else dz.data_ptr(), float(grad_scale), B, Cz, T, ws.data_ptr(), ws.numel(),
-                                 TrainHalf._stream())
-    if rc != 0:
-        raise RuntimeError(f"wv_train_bce_logits: {lib.wv_train_last_error().decode()}")
+    _lib.check(lib.wv_train_bce_logits(z.data_ptr(), _lib.ptr(m), _lib.ptr(g), loss.data_ptr(),
+                                       _lib.ptr(dz), float(grad_scale), B, Cz, T, ws.data_ptr(), ws.numel(),
+                                       _lib.stream()), "wv_train_bce_logits")
     return loss, dz
 
 
@@ -581,19 +495,16 @@ class FlatAdamW:
             raise RuntimeError("FlatAdamW: contiguous float32 CUDA arenas required")
         if p.numel() != self.m.numel() or g.numel() != p.numel():
             raise ValueError("FlatAdamW: arena size mismatch")
-        st = TrainHalf._stream()
+        st = _lib.stream()
         norm = None
         if max_norm is not None:
-            if self._lib.wv_train_sumsq(g.data_ptr(), g.numel(), self._ss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st) != 0:
-                raise RuntimeError(f"wv_train_sumsq: {self._lib.wv_train_last_error().decode()}")
+            _lib.check(self._lib.wv_train_sumsq(g.data_ptr(), g.numel(), self._ss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), st), "wv_train_sumsq")
             norm = self._ss.sqrt()
         lr = self.lr
         self.t += 1
-        rc = self._lib.wv_train_adamw(p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), p.numel(), lr, self.betas[0],
-                                      self.betas[1], self.eps, self.weight_decay, self.t,
-                                      self._ss.data_ptr() if max_norm is not None else None, float(max_norm or 0.0), st)
-        if rc != 0:
-            raise RuntimeError(f"wv_train_adamw: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_adamw(p.data_ptr(), g.data_ptr(), self.m.data_ptr(), self.v.data_ptr(), p.numel(), lr, self.betas[0],
+                                            self.betas[1], self.eps, self.weight_decay, self.t,
+                                            self._ss.data_ptr() if max_norm is not None else None, float(max_norm or 0.0), st), "wv_train_adamw")
         return norm
 
 
@@ -671,34 +582,32 @@ class FilmMlp:
 
     def forward(self, msg: torch.Tensor, params, packed: Optional[torch.Tensor] = None) -> torch.Tensor:
         """packed: the parameters already laid out in `self.keys` order (a slice of a flat arena), else they are gathered here."""
-        msg = _f(msg)
+        msg = _lib.dev(msg, _ON_GPU)
         B = msg.shape[0]
         self._packed, self._msg = (self.pack(params) if packed is None else packed), msg
         if self._packed.numel() != self.np or not self._packed.is_contiguous():
             raise ValueError("FilmMlp: packed parameter block of the wrong size / layout")
         film = torch.empty(B, self.NF, device=msg.device)
         self._ws = _lib.scratch(int(self._lib.wv_train_film_workspace_bytes(B, self.Dm, self.E, self.L, self.S, self.bands)), msg.device)
-        if self._lib.wv_train_film_forward(msg.data_ptr(), self._packed.data_ptr(), film.data_ptr(), B, self.Dm, self.E, self.L, self.S, self.bands,
-                                           self._ws.data_ptr(), self._ws.numel(), TrainHalf._stream()) != 0:
-            raise RuntimeError(f"wv_train_film_forward: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_film_forward(msg.data_ptr(), self._packed.data_ptr(), film.data_ptr(), B, self.Dm, self.E, self.L, self.S, self.bands,
+                                                   self._ws.data_ptr(), self._ws.numel(), _lib.stream()), "wv_train_film_forward")
         return film
 
     def apply(self, x, film, scale: int):
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         B, Cc, T = x.shape
         y = torch.empty_like(x)
-        if self._lib.wv_train_film_apply(x.data_ptr(), film.data_ptr(), y.data_ptr(), B, Cc, T, self.bands, self.S, scale, TrainHalf._stream()) != 0:
-            raise RuntimeError(f"wv_train_film_apply: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_film_apply(x.data_ptr(), film.data_ptr(), y.data_ptr(), B, Cc, T, self.bands, self.S, scale, _lib.stream()),
+                   "wv_train_film_apply")
         return y
 
     def apply_backward(self, x, film, dy, dfilm, scale: int):
-        x, dy = _f(x), _f(dy)
+        x, dy = _lib.dev(x, _ON_GPU), _lib.dev(dy, _ON_GPU)
         B, Cc, T = x.shape
         dx = torch.empty_like(x)
         ws = torch.empty(B * Cc * 2, device=x.device)
-        if self._lib.wv_train_film_apply_backward(x.data_ptr(), film.data_ptr(), dy.data_ptr(), dx.data_ptr(), dfilm.data_ptr(), B, Cc, T, self.bands,
-                                                  self.S, scale, ws.data_ptr(), ws.numel() * 4, TrainHalf._stream()) != 0:
-            raise RuntimeError(f"wv_train_film_apply_backward: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_film_apply_backward(x.data_ptr(), film.data_ptr(), dy.data_ptr(), dx.data_ptr(), dfilm.data_ptr(), B, Cc, T, self.bands,
+                                                          self.S, scale, ws.data_ptr(), ws.numel() * 4, _lib.stream()), "wv_train_film_apply_backward")
         return dx
 
     def backward(self, dfilm, gviews, dp: Optional[torch.Tensor] = None) -> None:
@@ -710,9 +619,8 @@ class FilmMlp:
             dp = torch.empty(self.np, device=dfilm.device)
         elif dp.numel() != self.np or not dp.is_contiguous() or dp.dtype != torch.float32:
             raise ValueError("FilmMlp: gradient block of the wrong size / layout")
-        if self._lib.wv_train_film_backward(self._msg.data_ptr(), self._packed.data_ptr(), dfilm.data_ptr(), dp.data_ptr(), B, self.Dm, self.E, self.L,
-                                            self.S, self.bands, self._ws.data_ptr(), self._ws.numel(), TrainHalf._stream()) != 0:
-            raise RuntimeError(f"wv_train_film_backward: {self._lib.wv_train_last_error().decode()}")
+        _lib.check(self._lib.wv_train_film_backward(self._msg.data_ptr(), self._packed.data_ptr(), dfilm.data_ptr(), dp.data_ptr(), B, self.Dm, self.E, self.L,
+                                                    self.S, self.bands, self._ws.data_ptr(), self._ws.numel(), _lib.stream()), "wv_train_film_backward")
         off = 0
         for k in (self.keys if scatter else ()):
             n = gviews[k].numel()
@@ -860,8 +768,7 @@ class _NetTrainer:
         lib = _lib.load()
         M, K = int(v.shape[0]), int(v.numel() // v.shape[0])
         w, inv = torch.empty_like(v), torch.empty(M, device=v.device)
-        if lib.wv_train_fold_weight(g.data_ptr(), v.data_ptr(), w.data_ptr(), inv.data_ptr(), M, K, TrainHalf._stream()) != 0:
-            raise RuntimeError(f"wv_train_fold_weight: {lib.wv_train_last_error().decode()}")
+        _lib.check(lib.wv_train_fold_weight(g.data_ptr(), v.data_ptr(), w.data_ptr(), inv.data_ptr(), M, K, _lib.stream()), "wv_train_fold_weight")
         return w
 
     def optimizer_state(self) -> Dict[str, object]:
@@ -935,7 +842,7 @@ class _NetTrainer:
         cfg, rs = self.cfg, self.cfg.res_scale_enc
         sv = dict(x=x, scales=[], film=None)
         if self.with_msg:
-            msg = _f(msg)
+            msg = _lib.dev(msg, _ON_GPU)
             if msg.shape[0] != x.shape[0]:                                         # one message for the batch (watermarking.py:320-329)
                 msg = msg.repeat(-(-x.shape[0] // msg.shape[0]), 1)[: x.shape[0]].contiguous()
             sv["film"] = self.film.forward(msg, self.params, self._film_p)
@@ -1052,7 +959,7 @@ class EncoderNetTrainer(_NetTrainer):
                     w_last=self.params["last_layer.weight"], b_last=self.params["last_layer.bias"])
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         self._z = self.encoder_forward(x, None)
         return self.head.forward(self._z, self._head_p(), x.shape[-1])
 
@@ -1118,7 +1025,7 @@ class GeneratorTrainer(_NetTrainer):
 
     def forward(self, x: torch.Tensor, msg: torch.Tensor) -> torch.Tensor:
         cfg, rs = self.cfg, self.cfg.res_scale_dec
-        x = _f(x)
+        x = _lib.dev(x, _ON_GPU)
         z = self.encoder_forward(x, msg)
         sv = dict(z=z, ups=[])
         h = self.dec_in.forward(z, self._in_p(), 1.0, False)
@@ -1141,7 +1048,7 @@ class GeneratorTrainer(_NetTrainer):
         cfg, rs, sv = self.cfg, self.cfg.res_scale_dec, self._dec
         if sv is None:
             raise RuntimeError("backward before forward")
-        d_wm = _f(d_wm)
+        d_wm = _lib.dev(d_wm, _ON_GPU)
         g0, g1 = self._gwn(f"decoder.model.{self.i_last}")
         g = self.tail.backward(sv["tail_in"], self._tail_p(), self.post, cfg.wav_std, sv["delta"], d_wm,
                                dict(dg=g0, dv=g1, db=self.gviews[f"decoder.model.{self.i_last}.conv.conv.bias"]))
@@ -1172,16 +1079,15 @@ class GeneratorTrainer(_NetTrainer):
 
 def l1_loss(a: torch.Tensor, b: torch.Tensor, grad_scale: float = 1.0, want_grad: bool = True):
     """mean |a - b| (the reference's waveform loss, scripts/train.py:1322) -> (loss [1], grad_scale * dloss/da or None)."""
-    a, b = _f(a), _f(b)
+    a, b = _lib.dev(a, _ON_GPU), _lib.dev(b, _ON_GPU)
     if a.shape != b.shape:
         raise ValueError(f"shape mismatch: {tuple(a.shape)} vs {tuple(b.shape)}")
     lib = _lib.load()
     loss = torch.empty(1, device=a.device)
     da = torch.empty_like(a) if want_grad else None
     ws = _lib.scratch(int(lib.wv_train_bce_workspace_bytes()), a.device)
-    if lib.wv_train_l1(a.data_ptr(), b.data_ptr(), loss.data_ptr(), None if da is None else da.data_ptr(), float(grad_scale), a.numel(),
-                       ws.data_ptr(), ws.numel(), TrainHalf._stream()) != 0:
-        raise RuntimeError(f"wv_train_l1: {lib.wv_train_last_error().decode()}")
+    _lib.check(lib.wv_train_l1(a.data_ptr(), b.data_ptr(), loss.data_ptr(), _lib.ptr(da), float(grad_scale), a.numel(),
+                               ws.data_ptr(), ws.numel(), _lib.stream()), "wv_train_l1")
     return loss, da
 
 
@@ -1304,7 +1210,7 @@ class WatermarkTrainer:
             self.effect_update_count += 1
 
     def step(self, x: torch.Tensor, msg: torch.Tensor, extra_d_wm: Optional[torch.Tensor] = None, augment: bool = True):
-        x, msg = _f(x), _f(msg)
+        x, msg = _lib.dev(x, _ON_GPU), _lib.dev(msg, _ON_GPU)
         if msg.dim() == 1:
             msg = msg[None]
         if msg.shape[0] != x.shape[0]:                                 # one (or a shorter list of) message(s) for the batch: repeated as the
@@ -1346,7 +1252,7 @@ class WatermarkTrainer:
             if self.spectral is not None:                                 # d_wm += 10 dSTFT/dwm + 20 dmel/dwm, in place
                 stft, mel, d_wm = self.spectral(wm, x, stft_grad_scale=lam["stft/loss"], mel_grad_scale=lam["mel/loss"], out=d_wm)
             if extra_d_wm is not None:
-                d_wm = d_wm + _f(extra_d_wm)
+                d_wm = d_wm + _lib.dev(extra_d_wm, _ON_GPU)
             self.G.begin_reduce()
             self.G.backward(d_wm)
         except BaseException:
@@ -1403,7 +1309,7 @@ class WatermarkTrainer:
             if name in fx.REFUSED or name.startswith("_") or getattr(fx.AudioEffects, name, None) is None:
                 why = f" (needs {fx.REFUSED[name]})" if name in fx.REFUSED else ""
                 raise NotImplementedError(f"effect '{name}' is not available on the GPU path{why}")
-        x, msg = _f(x), _f(msg)
+        x, msg = _lib.dev(x, _ON_GPU), _lib.dev(msg, _ON_GPU)
         if msg.dim() == 1:
             msg = msg[None]
         if msg.shape[0] != x.shape[0]:

@@ -10,11 +10,11 @@ are written back.  The result equals the whole-clip forward up to f32 summation 
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import List, Sequence
 
+from . import _lib
 from .config import NetConfig
 
 
@@ -148,24 +148,14 @@ def _unpack(out, lengths, bases, as_batch, C_=1):
     return [out[C_ * b0: C_ * b0 + C_ * T].view(C_, T) if C_ > 1 else out[b0: b0 + T] for b0, T in zip(bases, lengths)]
 
 
-def _check(rc, what):
-    from . import _lib
-    _lib.check(rc, what)
-
-
-def _stream():
-    torch = _torch()
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
 def gather(net, packed, wins: Sequence[Window], bases):
     """[W, 1, L] window batch from the packed clips (wv_window_gather)."""
     torch = _torch()
     W, L = len(wins), wins[0].length
     offs = torch.tensor([bases[w.clip] + w.start for w in wins], dtype=torch.int64).to(packed.device)
     xw = torch.empty((W, 1, L), dtype=torch.float32, device=packed.device)
-    _check(net._lib.wv_window_gather(packed.data_ptr(), packed.numel(), offs.data_ptr(), xw.data_ptr(), W, L, _stream()),
-           "wv_window_gather")
+    _lib.check(net._lib.wv_window_gather(packed.data_ptr(), packed.numel(), offs.data_ptr(), xw.data_ptr(), W, L, _lib.stream()),
+               "wv_window_gather")
     return xw
 
 
@@ -176,8 +166,8 @@ def scatter(net, y, wins: Sequence[Window], bases, lengths, out, C_=1):
     desc = torch.tensor([[C_ * bases[w.clip] + w.start, lengths[w.clip], w.keep_lo - w.start, w.keep_hi - w.start] for w in wins],
                         dtype=torch.int64).to(y.device)
     y = y.contiguous()
-    _check(net._lib.wv_window_scatter(y.data_ptr(), desc.data_ptr(), out.data_ptr(), out.numel(), W, C_, L, _stream()),
-           "wv_window_scatter")
+    _lib.check(net._lib.wv_window_scatter(y.data_ptr(), desc.data_ptr(), out.data_ptr(), out.numel(), W, C_, L, _lib.stream()),
+               "wv_window_scatter")
 
 
 def _run(net, clips, window, max_windows, fwd, C_=1):
@@ -242,6 +232,6 @@ def windowed_detector_mean_prob(net, clips, window: int = 480000, precision: str
         rows_t = torch.tensor(rows, dtype=torch.int32).to(net.device)
         len_t = torch.tensor(lengths, dtype=torch.int64).to(net.device)
         mean = torch.empty((len(lengths), nb), dtype=torch.float32, device=net.device)
-        _check(net._lib.wv_window_reduce_mean(psum.data_ptr(), n_rows, ptr_t.data_ptr(), rows_t.data_ptr(), len_t.data_ptr(),
-                                              mean.data_ptr(), len(lengths), nb, _stream()), "wv_window_reduce_mean")
+        _lib.check(net._lib.wv_window_reduce_mean(psum.data_ptr(), n_rows, ptr_t.data_ptr(), rows_t.data_ptr(), len_t.data_ptr(),
+                                                  mean.data_ptr(), len(lengths), nb, _lib.stream()), "wv_window_reduce_mean")
         return mean
