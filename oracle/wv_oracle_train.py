@@ -13,6 +13,16 @@ from __future__ import annotations
 import numpy as np
 
 
+def _apply(W, a):
+    """"mk,bkt->bmt" as a BLAS matmul (einsum's own loop took seconds at the training fuzz's shapes; same sums to ~1e-13)."""
+    return np.matmul(W, a)
+
+
+def _outer(dh, a):
+    """"bmt,bkt->mk": sum over clips and time of dh a^T."""
+    return np.matmul(dh, a.transpose(0, 2, 1)).sum(0)
+
+
 def fold(g: np.ndarray, v: np.ndarray) -> np.ndarray:
     """w = g * v / ||v||, norm over all dims but 0 (conv.py:73-74)."""
     n = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(1)).reshape((-1,) + (1,) * (v.ndim - 1))
@@ -35,7 +45,7 @@ def half_forward(x, s, g_pw, v_pw, g_dw, v_dw, b):
     a = np.where(z > 0, z, np.expm1(z))
     W = fold(g_pw.astype(np.float64), v_pw.astype(np.float64))[:, :, 0]          # [M, K]
     w = fold(g_dw.astype(np.float64), v_dw.astype(np.float64))[:, 0, :]          # [M, ks]
-    h = np.einsum("mk,bkt->bmt", W, a)
+    h = _apply(W, a)
     ks = w.shape[1]
     hp = np.pad(h, ((0, 0), (0, 0), (ks - 1, 0)))
     T = x.shape[2]
@@ -54,8 +64,8 @@ def half_backward(x, s, g_pw, v_pw, g_dw, v_dw, b, dy):
     dw = np.stack([(dy * hp[:, :, i:i + T]).sum((0, 2)) for i in range(ks)], 1)            # [M, ks]
     dyp = np.pad(dy, ((0, 0), (0, 0), (0, ks - 1)))
     dh = sum(w[None, :, i, None] * dyp[:, :, ks - 1 - i:ks - 1 - i + T] for i in range(ks))  # dh[t] = sum_i w[i] dy[t + 4 - i]
-    dW = np.einsum("bmt,bkt->mk", dh, a)
-    da = np.einsum("mk,bmt->bkt", W, dh)
+    dW = _outer(dh, a)
+    da = _apply(W.T, dh)
     dx = da * np.where(z > 0, 1.0, np.exp(z)) * s
     dg_pw, dv_pw = fold_backward(g_pw.astype(np.float64), v_pw.astype(np.float64), dW[:, :, None])
     dg_dw, dv_dw = fold_backward(g_dw.astype(np.float64), v_dw.astype(np.float64), dw[:, None, :])
@@ -102,7 +112,7 @@ def unit_forward(x, s, g_pw, v_pw, g_dw, v_dw, b, stride=1, elu=True):
     a = np.where(z > 0, z, np.expm1(z)) if elu else z
     W = fold(g_pw.astype(np.float64), v_pw.astype(np.float64))[:, :, 0]
     w = fold(g_dw.astype(np.float64), v_dw.astype(np.float64))[:, 0, :]
-    h = np.einsum("mk,bkt->bmt", W, a)
+    h = _apply(W, a)
     ks, T = w.shape[1], x.shape[2]
     Tout, pad = -(-T // stride), ks - stride
     hp = np.pad(h, ((0, 0), (0, 0), (pad, (Tout - 1) * stride + ks - pad - T)))
@@ -121,8 +131,8 @@ def unit_backward(x, s, g_pw, v_pw, g_dw, v_dw, b, dy, stride=1, elu=True):
     for i in range(ks):
         dhp[:, :, sl(i)] += w[None, :, i, None] * dy
     dh = dhp[:, :, pad:pad + T]
-    dW = np.einsum("bmt,bkt->mk", dh, a)
-    da = np.einsum("mk,bmt->bkt", W, dh)
+    dW = _outer(dh, a)
+    da = _apply(W.T, dh)
     dx = da * (np.where(z > 0, 1.0, np.exp(z)) if elu else 1.0) * s
     dg_pw, dv_pw = fold_backward(g_pw.astype(np.float64), v_pw.astype(np.float64), dW[:, :, None])
     dg_dw, dv_dw = fold_backward(g_dw.astype(np.float64), v_dw.astype(np.float64), dw[:, None, :])
@@ -150,8 +160,8 @@ def spec_add_backward(x, P, g, v, scale_param, res_scale, dy):
     dy = dy.astype(np.float64)
     W = fold(g.astype(np.float64), v.astype(np.float64))[:, :, 0]
     sp = 1.0 if scale_param is None else float(np.asarray(scale_param).reshape(-1)[0])
-    z = np.einsum("cf,bft->bct", W, P)
-    G = np.einsum("bct,bft->cf", dy, P)
+    z = _apply(W, P)
+    G = _outer(dy, P)
     dg, dv = fold_backward(g.astype(np.float64), v.astype(np.float64), (res_scale * sp * G)[:, :, None])
     return dict(y=x.astype(np.float64) + res_scale * sp * z, dg=dg, dv=dv, d_scale_param=res_scale * float((dy * z).sum()))
 

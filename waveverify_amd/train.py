@@ -635,6 +635,8 @@ class _NetTrainer:
     def _build(self, cfg, state_dict, with_msg: bool, lr: float, max_norm: float, device, spec_learnable: bool = False):
         if cfg.dilation_base != 1:
             raise NotImplementedError("training units: dilation_base = 1 only")
+        if cfg.residual_kernel_size != 5:
+            raise NotImplementedError("training units: residual_kernel_size = 5 only")
         self.cfg, self.max_norm, self.with_msg, self.spec_learnable = cfg, float(max_norm), with_msg, bool(spec_learnable)
         skip = () if with_msg else ("encoder.msg_embedding.", "encoder.film_layers.")
         items = [(k, np.asarray(v, dtype=np.float32)) for k, v in state_dict.items()
