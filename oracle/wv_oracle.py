@@ -11,7 +11,9 @@ with a test-side `audiotools` stub) and committed as tests/golden/*.npz.
 tests/test_oracle_golden.py asserts oracle == golden to <= 2e-5 on every tensor.
 
 Every function cites the reference lines it follows (paths relative to /root/reference).
-All arithmetic is float32 like the reference; tensors are [B, C, T], time innermost.
+All arithmetic is float32 like the reference; tensors are [B, C, T], time innermost.  The forward units also take
+`dtype=np.float64` (a _Net carries its own): the same statements in float64, the yardstick of tests/test_gpu_infer_fuzz.py.
+The float32 evaluation is the one pinned to the golden outputs; tests/test_infer_fuzz_cases_cpu.py ties the float64 one to it.
 """
 from __future__ import annotations
 
@@ -23,17 +25,23 @@ import numpy as np
 F32 = np.float32
 
 
+def _in(a, dtype):
+    """An operand in the evaluation's dtype.  float32 (the default everywhere) leaves the caller's array as it is, so that the float32
+    evaluation stays bit for bit what it was before the functions took a dtype."""
+    return a if dtype is F32 or a is None else np.asarray(a, dtype)
+
+
 # --------------------------------------------------------------------------- weights
-def fold_weight_norm(g: np.ndarray, v: np.ndarray) -> np.ndarray:
+def fold_weight_norm(g: np.ndarray, v: np.ndarray, dtype=F32) -> np.ndarray:
     """w = g * v / ||v||, norm over every dim but 0 (modules/conv.py:73-74 ->
     torch.nn.utils.parametrizations.weight_norm, dim=0)."""
-    v = np.asarray(v, F32)
-    nrm = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(axis=1, dtype=F32)).astype(F32)
-    scale = (np.asarray(g, F32).reshape(-1) / nrm).astype(F32)
-    return (v * scale.reshape((-1,) + (1,) * (v.ndim - 1))).astype(F32)
+    v = np.asarray(v, dtype)
+    nrm = np.sqrt((v.reshape(v.shape[0], -1) ** 2).sum(axis=1, dtype=dtype)).astype(dtype)
+    scale = (np.asarray(g, dtype).reshape(-1) / nrm).astype(dtype)
+    return (v * scale.reshape((-1,) + (1,) * (v.ndim - 1))).astype(dtype)
 
 
-def fold_state_dict(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+def fold_state_dict(sd: Dict[str, np.ndarray], dtype=F32) -> Dict[str, np.ndarray]:
     """Turn `...parametrizations.weight.original0/1` pairs into plain `...weight` keys, the
     layout checkpoints are saved in (scripts/train.py:1624-1629)."""
     out: Dict[str, np.ndarray] = {}
@@ -42,16 +50,17 @@ def fold_state_dict(sd: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
         if tag in k:
             if k.endswith("original0"):
                 base = k[: -len("parametrizations.weight.original0")]
-                out[base + "weight"] = fold_weight_norm(val, sd[base + tag + "1"])
+                out[base + "weight"] = fold_weight_norm(val, sd[base + tag + "1"], dtype)
         else:
-            out[k] = np.asarray(val, F32)
+            out[k] = np.asarray(val, dtype)
     return out
 
 
 # --------------------------------------------------------------------------- elementwise
-def elu(x: np.ndarray) -> np.ndarray:
+def elu(x: np.ndarray, dtype=F32) -> np.ndarray:
     """nn.ELU(alpha=1): x if x > 0 else exp(x) - 1."""
-    return np.where(x > 0, x, np.expm1(np.minimum(x, 0))).astype(F32)
+    x = _in(x, dtype)
+    return np.where(x > 0, x, np.expm1(np.minimum(x, 0))).astype(dtype)
 
 
 def sigmoid(x: np.ndarray) -> np.ndarray:
@@ -67,9 +76,10 @@ def extra_padding_for_conv1d(length: int, kernel_size: int, stride: int, padding
 
 
 def sconv1d(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray], stride: int = 1,
-            dilation: int = 1, groups: int = 1) -> np.ndarray:
+            dilation: int = 1, groups: int = 1, dtype=F32) -> np.ndarray:
     """Causal SConv1d.forward (modules/conv.py:715-763): left pad (k-1)*d-(s-1), right pad
     `extra` so the last frame is complete, then a plain conv1d."""
+    x, w, b = _in(x, dtype), _in(w, dtype), _in(b, dtype)
     B, Cin, T = x.shape
     Cout, Cin_g, k = w.shape
     pad_total = (k - 1) * dilation - (stride - 1)
@@ -81,26 +91,27 @@ def sconv1d(x: np.ndarray, w: np.ndarray, b: Optional[np.ndarray], stride: int =
         Tout = (xp.shape[-1] - dilation * (k - 1) - 1) // stride + 1
         span = (Tout - 1) * stride + 1
         if groups == Cin and Cin_g == 1 and Cout == Cin:          # depth-wise
-            y = np.zeros((B, Cout, Tout), F32)
+            y = np.zeros((B, Cout, Tout), dtype)
             for i in range(k):
                 y += w[None, :, 0, i, None] * xp[:, :, i * dilation: i * dilation + span: stride]
         elif groups == 1:                                         # dense k-tap conv
-            y = np.zeros((B, Cout, Tout), F32)
+            y = np.zeros((B, Cout, Tout), dtype)
             for i in range(k):
                 y += np.matmul(w[:, :, i], xp[:, :, i * dilation: i * dilation + span: stride])
         else:
             raise NotImplementedError("only pointwise, depth-wise and dense convs occur")
     if b is not None:
         y = y + b[None, :, None]
-    return y.astype(F32)
+    return y.astype(dtype)
 
 
-def sconvtr1d_depthwise(x: np.ndarray, w: np.ndarray, stride: int) -> np.ndarray:
+def sconvtr1d_depthwise(x: np.ndarray, w: np.ndarray, stride: int, dtype=F32) -> np.ndarray:
     """Causal depth-wise SConvTranspose1d.forward (modules/conv.py:838-881): conv_transpose1d
     then drop the last k - s samples (trim_right_ratio = 1)."""
+    x, w = _in(x, dtype), _in(w, dtype)
     B, C, L = x.shape
     k = w.shape[-1]
-    full = np.zeros((B, C, (L - 1) * stride + k), F32)
+    full = np.zeros((B, C, (L - 1) * stride + k), dtype)
     for i in range(k):
         full[:, :, i: i + (L - 1) * stride + 1: stride] += x * w[None, :, 0, i, None]
     trim = k - stride
@@ -126,13 +137,14 @@ def dft_basis(n_fft: int) -> np.ndarray:
 
 
 def causal_stft_mag(wav: np.ndarray, n_fft: int, hop: int, basis: Optional[np.ndarray] = None,
-                    eps: float = 1e-12) -> np.ndarray:
+                    eps: float = 1e-12, dtype=F32) -> np.ndarray:
     """CausalSTFT.forward (modules/conv.py:1036-1080): left-pad n_fft-1 zeros, strided conv
     with the DFT basis, sqrt(max(re^2+im^2, eps)).  wav [B,1,T] -> [B,F,ceil(T/hop)]."""
     if basis is None:
-        basis = dft_basis(n_fft)
+        basis = dft_basis(n_fft)                                    # the reference's float32 buffer in every dtype: it is data, like a weight
+    basis = _in(basis, dtype)
     B, _, T = wav.shape
-    xp = np.pad(wav[:, 0, :], ((0, 0), (n_fft - 1, 0))).astype(F32)
+    xp = np.pad(wav[:, 0, :], ((0, 0), (n_fft - 1, 0))).astype(dtype)
     n_frames = (xp.shape[-1] - n_fft) // hop + 1
     st = xp.strides
     frames = np.lib.stride_tricks.as_strided(
@@ -140,16 +152,17 @@ def causal_stft_mag(wav: np.ndarray, n_fft: int, hop: int, basis: Optional[np.nd
     c = np.matmul(basis, frames)                                  # [B, 2F, n_frames]
     Fq = n_fft // 2 + 1
     p = c[:, :Fq] ** 2 + c[:, Fq:] ** 2
-    return np.sqrt(np.maximum(p, F32(eps))).astype(F32)
+    return np.sqrt(np.maximum(p, dtype(eps))).astype(dtype)
 
 
 # --------------------------------------------------------------------------- blocks
 class _Net:
     """Weights + hyper-parameters; `cfg` is a waveverify_amd.config.NetConfig-like object."""
 
-    def __init__(self, cfg, sd: Dict[str, np.ndarray]):
+    def __init__(self, cfg, sd: Dict[str, np.ndarray], dtype=F32):
         self.cfg = cfg
-        self.sd = fold_state_dict({k: np.asarray(v) for k, v in sd.items()})
+        self.dtype = dtype                                          # every function that takes a net evaluates in the net's dtype
+        self.sd = fold_state_dict({k: np.asarray(v) for k, v in sd.items()}, dtype)
 
     def w(self, key: str) -> np.ndarray:
         return self.sd[key]
@@ -162,49 +175,53 @@ def resnet_block(net: _Net, prefix: str, x: np.ndarray, idx: int, res_scale: flo
                  dilations: List[int]) -> np.ndarray:
     """SEANetResnetBlock.forward with skip='identity' (modules/seanet.py:245-281) over
     dws_conv_block x2 (seanet.py:39-116): [ELU, 1x1 (no bias), DW k (bias)] twice."""
-    pre_scale = F32((1 + idx * res_scale ** 2) ** -0.5)             # seanet.py:183
+    D = net.dtype
+    x = _in(x, D)
+    pre_scale = D((1 + idx * res_scale ** 2) ** -0.5)               # seanet.py:183
     y = x * pre_scale
     for (pw, dw), dil in zip(((1, 2), (4, 5)), dilations):
-        y = elu(y)
-        y = sconv1d(y, net.w(f"{prefix}.block.{pw}.conv.conv.weight"), None)
+        y = elu(y, D)
+        y = sconv1d(y, net.w(f"{prefix}.block.{pw}.conv.conv.weight"), None, dtype=D)
         wd = net.w(f"{prefix}.block.{dw}.conv.conv.weight")
         y = sconv1d(y, wd, net.w(f"{prefix}.block.{dw}.conv.conv.bias"), dilation=dil,
-                    groups=wd.shape[0])
-    scale = F32(res_scale)
+                    groups=wd.shape[0], dtype=D)
+    scale = D(res_scale)
     p = net.opt(f"{prefix}.res_scale_param")
     if p is not None:
-        scale = F32(scale * p.reshape(-1)[0])                       # seanet.py:272-274
-    return (y * scale + x).astype(F32)                               # seanet.py:277
+        scale = D(scale * p.reshape(-1)[0])                         # seanet.py:272-274
+    return (y * scale + x).astype(D)                                 # seanet.py:277
 
 
 def spec_block(net: _Net, prefix: str, x: np.ndarray, wav: np.ndarray, n_fft: int, hop: int,
                mean: float, std: float, res_scale: float) -> np.ndarray:
     """SpecBlock.forward (modules/seanet.py:463-511)."""
+    D = net.dtype
+    x = _in(x, D)
     basis = net.opt(f"{prefix}.spec.weight")
     if basis is not None:
         basis = basis[:, 0, :]
-    y = causal_stft_mag(wav, n_fft, hop, basis)
-    y = np.log(np.maximum(y, F32(1e-5))).astype(F32)                # :484
-    y = ((y - F32(mean)) / F32(std)).astype(F32)                    # :494
-    y = sconv1d(y, net.w(f"{prefix}.layer.conv.conv.weight"), None)
-    scale = F32(res_scale)
+    y = causal_stft_mag(wav, n_fft, hop, basis, dtype=D)
+    y = np.log(np.maximum(y, D(1e-5))).astype(D)                    # :484
+    y = ((y - D(mean)) / D(std)).astype(D)                          # :494
+    y = sconv1d(y, net.w(f"{prefix}.layer.conv.conv.weight"), None, dtype=D)
+    scale = D(res_scale)
     p = net.opt(f"{prefix}.scale_param")
     if p is not None:
-        scale = F32(p.reshape(-1)[0] * scale)                       # :500-502
-    return (x + y * scale).astype(F32)                               # :505
+        scale = D(p.reshape(-1)[0] * scale)                         # :500-502
+    return (x + y * scale).astype(D)                                 # :505
 
 
 def msg_embedding(net: _Net, msg: np.ndarray) -> np.ndarray:
     """encoder.msg_embedding = [Linear, (Linear, ReLU) x embedding_layers]
     (modules/seanet.py:831-839): note no ReLU after the first Linear."""
     cfg = net.cfg
-    h = msg.astype(F32)
+    h = msg.astype(net.dtype)
     h = h @ net.w("encoder.msg_embedding.0.weight").T + net.w("encoder.msg_embedding.0.bias")
     for i in range(cfg.embedding_layers):
         j = 1 + 2 * i
         h = h @ net.w(f"encoder.msg_embedding.{j}.weight").T + net.w(f"encoder.msg_embedding.{j}.bias")
         h = np.maximum(h, 0)
-    return h.astype(F32)
+    return h.astype(net.dtype)
 
 
 def film_params(net: _Net, emb: np.ndarray) -> np.ndarray:
@@ -212,7 +229,8 @@ def film_params(net: _Net, emb: np.ndarray) -> np.ndarray:
     returns [B, n_scales, freq_bands, 2] with [..., 0] = gamma, [..., 1] = beta."""
     cfg = net.cfg
     S = len(cfg.strides)
-    out = np.zeros((emb.shape[0], S, cfg.freq_bands, 2), F32)
+    emb = _in(emb, net.dtype)
+    out = np.zeros((emb.shape[0], S, cfg.freq_bands, 2), net.dtype)
     for s in range(S):
         for b in range(cfg.freq_bands):
             for j, nm in enumerate(("gamma", "beta")):
@@ -226,12 +244,14 @@ def encoder_forward(net: _Net, x: np.ndarray, msg: Optional[np.ndarray],
                     taps: Optional[dict] = None) -> np.ndarray:
     """SEANetEncoder.forward (modules/seanet.py:883-976)."""
     cfg = net.cfg
+    D = net.dtype
     rs = cfg.res_scale_enc
+    x = _in(x, D)
     wav = x
     # conv_pre: Scale(1/wav_std) then SConv1d(1 -> C0, k)          (seanet.py:657-664)
-    h = sconv1d((x * F32(1.0 / cfg.wav_std)).astype(F32),
+    h = sconv1d((x * D(1.0 / cfg.wav_std)).astype(D),
                 net.w("encoder.conv_pre.1.conv.conv.weight"),
-                net.w("encoder.conv_pre.1.conv.conv.bias"))
+                net.w("encoder.conv_pre.1.conv.conv.bias"), dtype=D)
     if taps is not None:
         taps["conv_pre"] = h
     film = None
@@ -255,11 +275,11 @@ def encoder_forward(net: _Net, x: np.ndarray, msg: Optional[np.ndarray],
             taps[f"enc_scale{s}_pre_down"] = h
         stride *= ratio
         # downsample: Scale -> ELU -> 1x1 (C->2C) -> DW strided (k=2r, s=r)   (seanet.py:733-772)
-        h = elu(h * F32((1 + cfg.n_residual_enc * rs ** 2) ** -0.5))
-        h = sconv1d(h, net.w(f"encoder.downsample.{s}.2.conv.conv.weight"), None)
+        h = elu(h * D((1 + cfg.n_residual_enc * rs ** 2) ** -0.5), D)
+        h = sconv1d(h, net.w(f"encoder.downsample.{s}.2.conv.conv.weight"), None, dtype=D)
         wd = net.w(f"encoder.downsample.{s}.3.conv.conv.weight")
         h = sconv1d(h, wd, net.w(f"encoder.downsample.{s}.3.conv.conv.bias"), stride=ratio,
-                    groups=wd.shape[0])
+                    groups=wd.shape[0], dtype=D)
         if taps is not None:
             taps[f"enc_scale{s}_down"] = h
         if film is not None:                                        # seanet.py:928-966
@@ -267,21 +287,21 @@ def encoder_forward(net: _Net, x: np.ndarray, msg: Optional[np.ndarray],
             bw = C // cfg.freq_bands
             g = np.repeat(film[:, s, :, 0], bw, axis=1)[:, :, None]
             bt = np.repeat(film[:, s, :, 1], bw, axis=1)[:, :, None]
-            h = (h * g + bt).astype(F32)
+            h = (h * g + bt).astype(D)
         if taps is not None:
             taps[f"enc_scale{s}_out"] = h
         mult *= 2
     h = spec_block(net, "encoder.spec_post", h, wav, mult * cfg.n_fft_base, stride,
                    cfg.spec_means[-1], cfg.spec_stds[-1], rs)           # seanet.py:789-790: [-1]
     # conv_post: ELU -> DW k (no bias) -> 1x1 (bias) -> L2Norm      (seanet.py:797-823)
-    h = elu(h)
+    h = elu(h, D)
     wd = net.w("encoder.conv_post.1.conv.conv.weight")
-    h = sconv1d(h, wd, None, groups=wd.shape[0])
+    h = sconv1d(h, wd, None, groups=wd.shape[0], dtype=D)
     h = sconv1d(h, net.w("encoder.conv_post.2.conv.conv.weight"),
-                net.w("encoder.conv_post.2.conv.conv.bias"))
+                net.w("encoder.conv_post.2.conv.conv.bias"), dtype=D)
     # L2Norm (seanet.py:288-318): F.normalize(dim=1, eps=1e-12) * sqrt(C)
-    nrm = np.sqrt((h ** 2).sum(axis=1, keepdims=True, dtype=F32))
-    h = (h / np.maximum(nrm, F32(1e-12)) * F32(h.shape[1] ** 0.5)).astype(F32)
+    nrm = np.sqrt((h ** 2).sum(axis=1, keepdims=True, dtype=D))
+    h = (h / np.maximum(nrm, D(1e-12)) * D(h.shape[1] ** 0.5)).astype(D)
     if taps is not None:
         taps["latent"] = h
     return h
@@ -305,36 +325,38 @@ def decoder_layout(cfg):
 def decoder_forward(net: _Net, z: np.ndarray, taps: Optional[dict] = None) -> np.ndarray:
     """SEANetDecoder.forward (modules/seanet.py:1212-1226; layers built :1067-1204)."""
     cfg = net.cfg
+    D = net.dtype
     rs = cfg.res_scale_dec
     i_pw0, i_dw0, ups, i_last = decoder_layout(cfg)
-    h = sconv1d(z, net.w(f"decoder.model.{i_pw0}.conv.conv.weight"), None)
+    h = sconv1d(z, net.w(f"decoder.model.{i_pw0}.conv.conv.weight"), None, dtype=D)
     wd = net.w(f"decoder.model.{i_dw0}.conv.conv.weight")
-    h = sconv1d(h, wd, net.w(f"decoder.model.{i_dw0}.conv.conv.bias"), groups=wd.shape[0])
-    post = F32((1 + cfg.n_residual_dec * rs ** 2) ** -0.5)
+    h = sconv1d(h, wd, net.w(f"decoder.model.{i_dw0}.conv.conv.bias"), groups=wd.shape[0], dtype=D)
+    post = D((1 + cfg.n_residual_dec * rs ** 2) ** -0.5)
     for i, (ct, pw, res, r, C) in enumerate(ups):
         if i > 0:
             h = h * post                                             # seanet.py:1098-1107
-        h = elu(h)
-        h = sconvtr1d_depthwise(h, net.w(f"decoder.model.{ct}.convtr.convtr.weight"), r)
+        h = elu(h, D)
+        h = sconvtr1d_depthwise(h, net.w(f"decoder.model.{ct}.convtr.convtr.weight"), r, dtype=D)
         h = sconv1d(h, net.w(f"decoder.model.{pw}.conv.conv.weight"),
-                    net.w(f"decoder.model.{pw}.conv.conv.bias"))
+                    net.w(f"decoder.model.{pw}.conv.conv.bias"), dtype=D)
         for j, ri in enumerate(res):                                 # idx = j (seanet.py:1159)
             h = resnet_block(net, f"decoder.model.{ri}", h, j, rs, [cfg.dilation_base ** j, 1])
         if taps is not None:
             taps[f"dec_scale{i}_out"] = h
-    h = elu(h * post)                                                # seanet.py:1177-1179
+    h = elu(h * post, D)                                             # seanet.py:1177-1179
     h = sconv1d(h, net.w(f"decoder.model.{i_last}.conv.conv.weight"),
-                net.w(f"decoder.model.{i_last}.conv.conv.bias"))
-    return np.tanh(h * F32(cfg.wav_std)).astype(F32)                 # :1193, final Tanh
+                net.w(f"decoder.model.{i_last}.conv.conv.bias"), dtype=D)
+    return np.tanh(h * D(cfg.wav_std)).astype(D)                     # :1193, final Tanh
 
 
 # --------------------------------------------------------------------------- nets
-def generator_forward(cfg, sd, x: np.ndarray, msg: np.ndarray, taps: Optional[dict] = None
+def generator_forward(cfg, sd, x: np.ndarray, msg: np.ndarray, taps: Optional[dict] = None, dtype=F32
                       ) -> np.ndarray:
-    """Generator.forward (model/generator.py:360-423): delta = decode(encode(x, msg))[..., :T]."""
-    net = sd if isinstance(sd, _Net) else _Net(cfg, sd)
+    """Generator.forward (model/generator.py:360-423): delta = decode(encode(x, msg))[..., :T].
+    dtype: the arithmetic of the whole evaluation (a given _Net carries its own)."""
+    net = sd if isinstance(sd, _Net) else _Net(cfg, sd, dtype)
     T = x.shape[-1]
-    z = encoder_forward(net, x.astype(F32), msg, taps)
+    z = encoder_forward(net, x.astype(net.dtype), msg, taps)
     return decoder_forward(net, z, taps)[..., :T]
 
 
@@ -348,24 +370,25 @@ def head_forward(net: _Net, z: np.ndarray, T: int) -> np.ndarray:
     (model/detector.py:300-310, model/locator.py:247-258)."""
     W1 = net.w("reverse_convolution.weight")                         # [D, O, hop]
     b1 = net.w("reverse_convolution.bias")
+    z = _in(z, net.dtype)
     B, D, Fr = z.shape
     O, hop = W1.shape[1], W1.shape[2]
     up = np.einsum("bdf,doj->bofj", z, W1, optimize=True).reshape(B, O, Fr * hop)
-    up = (up + b1[None, :, None]).astype(F32)[:, :, :T]
+    up = (up + b1[None, :, None]).astype(net.dtype)[:, :, :T]
     W2 = net.w("last_layer.weight")[:, :, 0]
-    return (np.matmul(W2, up) + net.w("last_layer.bias")[None, :, None]).astype(F32)
+    return (np.matmul(W2, up) + net.w("last_layer.bias")[None, :, None]).astype(net.dtype)
 
 
-def detector_forward(cfg, sd, x: np.ndarray, taps: Optional[dict] = None) -> np.ndarray:
+def detector_forward(cfg, sd, x: np.ndarray, taps: Optional[dict] = None, dtype=F32) -> np.ndarray:
     """Detector.forward (model/detector.py:366-391): logits [B, nbits, T]."""
-    net = sd if isinstance(sd, _Net) else _Net(cfg, sd)
-    z = encoder_forward(net, x.astype(F32), None, taps)
+    net = sd if isinstance(sd, _Net) else _Net(cfg, sd, dtype)
+    z = encoder_forward(net, x.astype(net.dtype), None, taps)
     return head_forward(net, z, x.shape[-1])
 
 
-def locator_forward(cfg, sd, x: np.ndarray, taps: Optional[dict] = None) -> np.ndarray:
+def locator_forward(cfg, sd, x: np.ndarray, taps: Optional[dict] = None, dtype=F32) -> np.ndarray:
     """Locator.forward (model/locator.py:268-299): logits [B, 1, T]."""
-    return detector_forward(cfg, sd, x, taps)
+    return detector_forward(cfg, sd, x, taps, dtype)
 
 
 # --------------------------------------------------------------------------- decisions
