@@ -142,6 +142,18 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
                              float* out, int add_input, int B, int T,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* Localized detection: the detector in its gated per-FRAME form (frame f = samples [f*hop, min((f+1)*hop, T)), Fr = ceil(T/hop)).
+ * x [B,1,T]; gate [B,T] f32 DEVICE or NULL; sample t of clip b is gated iff gate == NULL || gate[b][t] > gate_thr (strict, as the
+ * reference's locator_out > 0.5).  Locator LOGITS go in as they are with gate_thr = log(p / (1 - p)), a 0/1 mask with gate_thr = 0.5.
+ * fsum [B, nbits + 1, Fr] f32: row bit < nbits, frame f = the sum over the gated samples of the frame of sigmoid(logit[bit][t]); row
+ * nbits = the number of gated samples of the frame (an exact integer).  Every element is written, zeros included; no logits are stored;
+ * the summation order is fixed, so two runs agree bit for bit.  Workspace and routing of wv_detector_forward (_f16: of
+ * wv_detector_forward_f16 with logits == NULL; where its f16 head does not apply, the exact frames kernel runs on the f32 tail). */
+int wv_detector_forward_frames(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum,
+                               int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+int wv_detector_forward_frames_f16(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum,
+                                   int B, int T, void* workspace, size_t workspace_bytes, void* stream);
+
 /* message MLP + all FiLM gammas/betas (seanet.py:831-846,905-912): msg [rows,msg_dim] ->
  * film [B,n_scales,bands,2]; uses the model's parameters. */
 int wv_model_film(wv_model* m, const float* msg, int msg_rows, float* film, int B, void* stream);
@@ -171,6 +183,11 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          of wv_detector_forward for (W, L); the _f16 twin runs the f16-operand mode.
  *   wv_window_reduce_mean  mean_prob [B,nbits] = (sum over psum rows rows[ptr[b] .. ptr[b+1]) in that order, in f64) / lengths[b];
  *                          ptr [B+1] / rows int32, lengths [B] int64, all device.
+ *   wv_frames_reduce       fsum [B, nb + 1, Fr_stride] (wv_detector_forward_frames) -> per segment seg [n_seg][3] int32 device = {clip,
+ *                          f_lo, f_hi}: S[bit] and N = the sums over frames f_lo .. f_hi - 1, in that order, in f64, of row bit and of the
+ *                          count row; prob [n_seg, nb] f32 = S / (float(N) + eps) (the eps add in f32, as wv_metrics_decode makes it, the
+ *                          quotient rounded once), count [n_seg] f64 = N.  N == 0 gives prob = 0: "no watermark found" is the host's
+ *                          to report.  A segment reaching outside the tensor counts as empty.  Segments may overlap.
  *   wv_session_advance     one tick of S lockstep sessions: stream s's samples are cat(hist[s][0 .. hv), x[s][0 .. n)) with
  *                          hist [S,hcap], x [S,n]; win [S,1,wlen] = their first wlen samples (wlen may be 0), hist_out [S,hcap] =
  *                          their samples [drop, drop + hv2); drop + hv2 == hv + n, hist_out != hist. */
@@ -182,6 +199,8 @@ int wv_detector_forward_windowed_f16(wv_model* m, const float* x, const int* kee
                                      int W, int L, void* workspace, size_t workspace_bytes, void* stream);
 int wv_window_reduce_mean(const float* psum, int n_rows, const int* ptr, const int* rows, const int64_t* lengths,
                           float* mean_prob, int B, int nb, void* stream);
+int wv_frames_reduce(const float* fsum, int B, int nb, int Fr_stride, const int* seg, int n_seg, float eps, float* prob, double* count,
+                     void* stream);
 int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen,
                        float* hist_out, int drop, int hv2, int S, void* stream);
 
@@ -265,6 +284,11 @@ int wv_op_head(const float* Z, const float* w_rev, const float* b_rev,
                const float* w_last, const float* b_last, float* logits, float* mean_prob,
                int B, int D, int O, int nb, int hop, int Fr, int T, void* stream);
 
+/* the same head in the gated per-frame form of wv_detector_forward_frames: gate [B,T] DEVICE or NULL, fsum [B, nb + 1, Fr] DEVICE;
+ * Fr must be ceil(T / hop). */
+int wv_op_head_frames(const float* Z, const float* w_rev, const float* b_rev, const float* w_last, const float* b_last,
+                      const float* gate, float gate_thr, float* fsum, int B, int D, int O, int nb, int hop, int Fr, int T, void* stream);
+
 /* ---- f16-operand / f32-accumulate mode (BASELINE.json configs[4] "MFMA linears fp16"; csrc/wv_h16.hip): a throughput mode of the
  * detector next to the exact-f32 path.  Activations are f16 in the "c8" layout [B][roundup(C,16)/8][T][8] (channel groups of eight,
  * time-major inside a group = the B operand of v_mfma_f32_32x32x16_f16 as it lies in memory); accumulation, stencils, ELU, bias and
@@ -309,6 +333,9 @@ int wv_op_head(const float* Z, const float* w_rev, const float* b_rev,
  *                     mean_prob [B,nb] = the mean, or -- keep_lo / keep_hi [B] int32 DEVICE, psum [B,nb] -- psum = the sum over
  *                     t in [keep_lo[b], keep_hi[b]) (mean_prob NULL).  Fr = ceil(T / hop); D % 16 == 0, D <= 128, nb % 4 == 0,
  *                     nb <= 32, hop % 32 == 0, else WV_EINVAL
+ *   wv_h16_head_frames  wv_h16_head in the gated per-frame form of wv_detector_forward_frames_f16: gate [B,T] DEVICE or NULL, fsum
+ *                     [B, nb + 1, Fr] DEVICE; a frame's sum is taken by the lane that owns it plus one cross-half add.  wv_h16_head's
+ *                     limits and hop <= 2016, else WV_EINVAL
  *   wv_h16_conv_film  wv_h16_conv with FiLM behind it (film [B, bands, 2] DEVICE: gamma, beta per clip and band of M / bands rows) */
 int wv_h16_round_host(const float* in, uint16_t* out, int64_t n);   /* HOST pointers: the weight packers' f32 -> f16 rounding (nearest even) */
 int wv_h16_from_f32(const float* X, void* Y16, int B, int C, int T, float scale, int elu, void* stream);
@@ -327,6 +354,8 @@ int wv_h16_tail(const void* A16, const float* w, const float* bias, const float*
 int wv_h16_l2norm(const float* lat, void* Y16, int B, int D, int Fr, void* stream);
 int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T,
                 const int* keep_lo, const int* keep_hi, float* psum, void* stream);
+int wv_h16_head_frames(const float* lat, const float* wc, const float* bc, const float* gate, float gate_thr, float* fsum, int B, int D, int nb,
+                       int hop, int Fr, int T, void* stream);
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
                      int B, int K, int M, int Tin, int ks, int stride, int pad, float act_scale, void* stream);
 

@@ -55,6 +55,8 @@ SIGNATURES = {
     "wv_encoder_forward": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP,
                                      C.c_size_t, _VP]),
     "wv_detector_forward_f16": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_detector_forward_frames": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
+    "wv_detector_forward_frames_f16": (C.c_int, [_VP, _VP, _VP, C.c_float, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_locator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_generator_forward_f16": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_model_film": (C.c_int, [_VP, _VP, C.c_int, _VP, C.c_int, _VP]),
@@ -68,6 +70,7 @@ SIGNATURES = {
     "wv_detector_forward_windowed": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_detector_forward_windowed_f16": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP, C.c_size_t, _VP]),
     "wv_window_reduce_mean": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, C.c_int, C.c_int, _VP]),
+    "wv_frames_reduce": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int, C.c_float, _VP, _VP, _VP]),
     "wv_session_advance": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_op_pw_dw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
@@ -84,6 +87,7 @@ SIGNATURES = {
                              C.c_float, C.c_float, _VP]),
     "wv_op_head": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int,
                              C.c_int, C.c_int, C.c_int, _VP]),
+    "wv_op_head_frames": (C.c_int, [_VP] * 6 + [C.c_float, _VP] + [C.c_int] * 7 + [_VP]),
     "wv_h16_round_host": (C.c_int, [_VP, _VP, C.c_int64]),
     "wv_h16_from_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _VP]),
     "wv_h16_to_f32": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
@@ -95,6 +99,7 @@ SIGNATURES = {
     "wv_h16_tail": (C.c_int, [_VP] * 5 + [C.c_int] * 5 + [C.c_float, _VP]),
     "wv_h16_l2norm": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_h16_head": (C.c_int, [_VP] * 4 + [C.c_int] * 6 + [_VP] * 4),
+    "wv_h16_head_frames": (C.c_int, [_VP] * 4 + [C.c_float, _VP] + [C.c_int] * 6 + [_VP]),
     "wv_h16_conv_film": (C.c_int, [_VP] * 5 + [C.c_int] + [_VP] * 2 + [C.c_int] * 7 + [C.c_float, _VP]),
     "wv_stft_plan_create": (C.c_int, [C.c_int, _VP, C.POINTER(_VP)]),
     "wv_stft_plan_destroy": (None, [_VP]),

@@ -12,15 +12,16 @@ import logging
 import math
 from pathlib import Path
 from types import SimpleNamespace
-from typing import Dict, Mapping, Optional, Tuple, Union
+from typing import Dict, List, Mapping, Optional, Tuple, Union
 
 import numpy as np
 import torch
 
-from . import session, window
+from . import localize, ops, session, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
+from .localize import Segment
 from .nets import HipNet
 from .utils import load_audio, message_to_tensor, save_audio, tensor_to_message
 from .watermark_id import WatermarkID
@@ -116,6 +117,65 @@ class WaveVerify:
         """-> sigmoid(locator logits) [B, T]."""
         return torch.sigmoid(self._need("locator").locator(audio, precision=self.locator_precision)).squeeze(1)
 
+    # ------------------------------------------------------------------ localized detection (NOT in the reference's package API)
+    def _gate(self, audio, threshold: float, gate):
+        """-> (gate tensor, gate_thr) for the frames kernels: a caller's 0/1 mask with 0.5, else the locator's LOGITS with the logit of
+        `threshold` (sigmoid(logit) > threshold, strict, without writing a gate tensor of its own)."""
+        if gate is not None:
+            return gate, 0.5
+        return self._need("locator").locator(audio, precision=self.locator_precision), localize.gate_threshold(threshold)
+
+    def _segments(self, fsum, lengths, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int) -> List[List[Segment]]:
+        """Per-clip frame sums (a list of [nb + 1, Fr_b], or [B, nb + 1, Fr]) -> per clip its Segments: runs of on frames from the count
+        row, then ONE wv_frames_reduce over all of them."""
+        per_clip = list(fsum) if not isinstance(fsum, torch.Tensor) else [fsum[b] for b in range(fsum.shape[0])]
+        nb = per_clip[0].shape[0] - 1
+        Frs = [int(f.shape[1]) for f in per_clip]
+        stride = max(Frs)
+        flat = torch.zeros((len(per_clip), nb + 1, stride), dtype=torch.float32, device=per_clip[0].device)
+        for b, f in enumerate(per_clip):
+            flat[b, :, :Frs[b]] = f
+        counts = flat[:, nb, :].cpu().numpy()
+        segs = []
+        for b, T in enumerate(lengths):
+            for lo, hi in localize.segments_from_counts(counts[b, :Frs[b]], localize.frame_valid(T, hop), min_on, min_gap_frames, min_len_frames):
+                segs.append((b, lo, hi))
+        out: List[List[Segment]] = [[] for _ in lengths]
+        if not segs:
+            return out
+        prob, count = ops.frames_reduce(flat, segs)
+        prob, count = prob.cpu(), count.cpu().numpy()
+        for i, (b, lo, hi) in enumerate(segs):
+            n = min(hi * hop, lengths[b]) - lo * hop
+            out[b].append(Segment(lo * hop / self.sample_rate, min(hi * hop, lengths[b]) / self.sample_rate,
+                                  WatermarkID.custom(tensor_to_message(prob[i])), float(prob[i].mean()), float(count[i]) / n,
+                                  prob[i].numpy(), (lo, hi)))
+        return out
+
+    @torch.no_grad()
+    def detect_localized_batch(self, audio: torch.Tensor, threshold: float = 0.5,
+                               gate: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """Decode only where the watermark is: -> (bits [B,16] int32, prob [B,16], coverage [B] float64).  prob is the mean of
+        sigmoid(detector logit) over the samples the locator marks (sigmoid(locator logit) > threshold), the reference's masked BER
+        decode (scripts/evaluate.py:442-516), without storing any logits; bits = prob >= 0.5; coverage = marked samples / T.
+        gate [B,T] (0/1) replaces the locator.  A clip with coverage 0 has no watermark found: its prob and bits are 0."""
+        det = self._need("detector")
+        g, thr = self._gate(audio, threshold, gate)
+        fsum = det.detector_frame_sums(audio, g, thr, self.detector_precision)
+        B, _, Fr = fsum.shape
+        prob, count = ops.frames_reduce(fsum, [(b, 0, Fr) for b in range(B)])
+        return (prob >= 0.5).to(torch.int32), prob, count / torch.full_like(count, float(audio.shape[-1]))   # a true division, element by element
+
+    @torch.no_grad()
+    def detect_segments_batch(self, audio: torch.Tensor, threshold: float = 0.5, gate: Optional[torch.Tensor] = None, min_on: float = 0.5,
+                              min_gap_frames: int = 2, min_len_frames: int = 5) -> List[List[Segment]]:
+        """Per clip the list of watermarked Segments (localize.segments_from_counts on the gated sample counts per detector frame), each
+        decoded over its own gated samples: a clip spliced from differently marked sources gives one Segment per source."""
+        det = self._need("detector")
+        g, thr = self._gate(audio, threshold, gate)
+        fsum = det.detector_frame_sums(audio, g, thr, self.detector_precision)
+        return self._segments(fsum, [int(audio.shape[-1])] * fsum.shape[0], det.hop_length, min_on, min_gap_frames, min_len_frames)
+
     # ------------------------------------------------------------------ windowed: variable-length clips, live sessions (NOT in the reference)
     def _window_samples(self, window_seconds: float) -> int:
         """window_seconds -> samples, rounded up to the lcm of the nets' hops so one plan suits embed, detect and locate."""
@@ -138,12 +198,39 @@ class WaveVerify:
         return window.windowed_generator(self._need("generator"), clips, self._messages(watermark_ids),
                                          self._window_samples(window_seconds), self.generator_precision)
 
+    def _clip_frame_sums(self, clips, window_seconds: float, threshold: float):
+        """-> (per-clip frame sums, lengths): the locator windowed, its logits the gate of the windowed frames kernel."""
+        W = self._window_samples(window_seconds)
+        logits = window.windowed_locator(self._need("locator"), clips, W, self.locator_precision)
+        fsum = window.windowed_detector_frame_sums(self._need("detector"), clips, logits, localize.gate_threshold(threshold), W,
+                                                   self.detector_precision)
+        lengths = [int(clips.shape[-1])] * clips.shape[0] if isinstance(clips, torch.Tensor) else [int(c.numel()) for c in clips]
+        return fsum, lengths
+
     @torch.no_grad()
-    def detect_clips(self, clips, window_seconds: float = 30.0) -> Tuple[torch.Tensor, torch.Tensor]:
-        """-> (bits [B,16] int32, mean_prob [B,16]) for clips of any lengths, windowed."""
+    def detect_clips(self, clips, window_seconds: float = 30.0, localized: bool = False, threshold: float = 0.5):
+        """-> (bits [B,16] int32, mean_prob [B,16]) for clips of any lengths, windowed.  localized=True: the masked decode of
+        detect_localized_batch instead, -> (bits, prob, coverage [B] float64)."""
+        if localized:
+            fsum, lengths = self._clip_frame_sums(clips, window_seconds, threshold)
+            per_clip = list(fsum) if not isinstance(fsum, torch.Tensor) else [fsum[b] for b in range(fsum.shape[0])]
+            probs, counts = [], []
+            for f in per_clip:                                  # one [1, nb + 1, Fr_b] tensor per clip: the clips' Fr differ
+                p, c = ops.frames_reduce(f.unsqueeze(0), [(0, 0, f.shape[1])])
+                probs.append(p)
+                counts.append(c)
+            prob, count = torch.cat(probs), torch.cat(counts)
+            return (prob >= 0.5).to(torch.int32), prob, count / torch.tensor(lengths, dtype=torch.float64, device=count.device)
         mp = window.windowed_detector_mean_prob(self._need("detector"), clips, self._window_samples(window_seconds),
                                                 self.detector_precision)
         return (mp >= 0.5).to(torch.int32), mp
+
+    @torch.no_grad()
+    def detect_segments_clips(self, clips, window_seconds: float = 30.0, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2,
+                              min_len_frames: int = 5) -> List[List[Segment]]:
+        """detect_segments_batch for clips of any lengths, windowed."""
+        fsum, lengths = self._clip_frame_sums(clips, window_seconds, threshold)
+        return self._segments(fsum, lengths, self._need("detector").hop_length, min_on, min_gap_frames, min_len_frames)
 
     @torch.no_grad()
     def locate_clips(self, clips, window_seconds: float = 30.0):
@@ -183,10 +270,16 @@ class WaveVerify:
             logger.error(f"Embedding failed: {str(e)}")
             raise RuntimeError(f"Failed to embed watermark: {str(e)}") from e
 
-    def detect(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> Tuple[WatermarkID, float]:
+    def detect(self, audio_path: Union[str, Path], localized: bool = False, *, window_seconds: Optional[float] = None) -> Tuple[WatermarkID, float]:
+        """localized (NOT in the reference): decode only over the samples the locator marks (detect_localized_batch); where it marks
+        none, the all-zero id comes back with confidence 0."""
         try:
             audio, _ = load_audio(audio_path, self.sample_rate)
-            if window_seconds is None:
+            if localized and window_seconds is None:
+                _, mp, _ = self.detect_localized_batch(audio.unsqueeze(0))
+            elif localized:
+                _, mp, _ = self.detect_clips(audio.unsqueeze(0), window_seconds, localized=True)
+            elif window_seconds is None:
                 _, mp = self.detect_batch(audio.unsqueeze(0))
             else:
                 _, mp = self.detect_clips(audio.unsqueeze(0), window_seconds)
@@ -196,6 +289,18 @@ class WaveVerify:
         except Exception as e:
             logger.error(f"Detection failed: {str(e)}")
             raise RuntimeError(f"Failed to detect watermark: {str(e)}") from e
+
+    def segments(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> List[Segment]:
+        """NOT in the reference: the file's watermarked Segments (start_s, end_s, watermark, confidence, coverage), each decoded over its
+        own marked samples; an empty list where the locator marks nothing."""
+        try:
+            audio, _ = load_audio(audio_path, self.sample_rate)
+            if window_seconds is None:
+                return self.detect_segments_batch(audio.unsqueeze(0))[0]
+            return self.detect_segments_clips(audio.unsqueeze(0), window_seconds)[0]
+        except Exception as e:
+            logger.error(f"Segment detection failed: {str(e)}")
+            raise RuntimeError(f"Failed to detect watermark segments: {str(e)}") from e
 
     def locate(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> np.ndarray:
         try:
@@ -214,10 +319,10 @@ class WaveVerify:
             raise RuntimeError(f"Failed to locate watermark: {str(e)}") from e
 
     def verify(self, audio_path: Union[str, Path],
-               expected_watermark: Union[WatermarkID, str, int]) -> bool:
+               expected_watermark: Union[WatermarkID, str, int], localized: bool = False) -> bool:
         try:
             expected = self._validate_watermark_id(expected_watermark)
-            detected, _ = self.detect(audio_path)
+            detected, _ = self.detect(audio_path, localized)
             return detected == expected
         except Exception as e:
             logger.error(f"Verification failed: {str(e)}")

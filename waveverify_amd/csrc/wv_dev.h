@@ -19,6 +19,8 @@ __device__ __forceinline__ float act(float x, float scale, int elu) {
     return elu ? elu1(x) : x;
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+// the localized heads' gate: sample t of a clip's gate row counts iff there is no gate or gate[t] > thr (strict, as locator_out > 0.5)
+__device__ __forceinline__ bool head_gated(const float* gate_row, float thr, long long t) { return !gate_row || gate_row[t] > thr; }
 
 // B operand for the k-inner core: a thread owns a 2(k) x 4(time) micro-tile -- two 16-byte row
 // loads, exactly the coalescing of a plain row copy -- and scatters it as four 8-byte halves of

@@ -1275,6 +1275,31 @@ hipError_t conv16u_launch(const Conv16Args& a, hipStream_t s) {
 // are skipped and the SUM goes to psum[b][bit]; WIN = false is the whole-clip launch, unchanged.
 struct Head16Args { const float* Y; H16Weight w; const float* bc; float* mean_prob; int B, D, nb, hop, Fr, T; const int* keep_lo; const int* keep_hi; float* psum; };
 
+// The L2-normalised f16 z tile of frames f0 .. f0 + 63 of one clip's latent Yb [D][Fr], in LDS as c8 [D/8][64][8] (frames past Fr: zero);
+// shared by head16_kernel and head16_frames_kernel.  Called by all 256 threads; barriers inside, the tile is staged on return.
+__device__ __forceinline__ void head16_stage_tile(const float* __restrict__ Yb, int D, int Fr, int f0, int tid, float* ys, h16* zs, float* inv) {
+    __syncthreads();
+    for (int i = tid; i < D * 64; i += 256) {
+        const int m = i >> 6, c = i & 63;
+        ys[i] = f0 + c < Fr ? Yb[(size_t)m * Fr + f0 + c] : 0.f;
+    }
+    __syncthreads();
+    if (tid < 64) {
+        float ss = 0.f;
+        for (int m = 0; m < D; ++m) ss = fmaf(ys[m * 64 + tid], ys[m * 64 + tid], ss);
+        inv[tid] = sqrtf((float)D) / fmaxf(sqrtf(ss), 1e-12f);
+    }
+    __syncthreads();
+    for (int i = tid; i < (D / 8) * 64; i += 256) {
+        const int g = i >> 6, c = i & 63;
+        h16x8 o;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] = (h16)(ys[(8 * g + j) * 64 + c] * inv[c]);
+        *reinterpret_cast<h16x8*>(zs + (size_t)i * 8) = o;
+    }
+    __syncthreads();
+}
+
 template <bool WIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void head16_kernel(Head16Args p) {
     __shared__ __attribute__((aligned(16))) float ys[128 * 64];       // y tile [D][64] f32
@@ -1292,26 +1317,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int i = 0; i < 8; ++i) total[i] = 0.f;
     const int lo = WIN ? p.keep_lo[b] : 0, hi = WIN ? p.keep_hi[b] : p.T;
     for (int f0 = WIN ? (lo / p.hop) / 64 * 64 : 0; f0 < Fr; f0 += 64) {
-        __syncthreads();
-        for (int i = tid; i < D * 64; i += 256) {
-            const int m = i >> 6, c = i & 63;
-            ys[i] = f0 + c < Fr ? Yb[(size_t)m * Fr + f0 + c] : 0.f;
-        }
-        __syncthreads();
-        if (tid < 64) {
-            float ss = 0.f;
-            for (int m = 0; m < D; ++m) ss = fmaf(ys[m * 64 + tid], ys[m * 64 + tid], ss);
-            inv[tid] = sqrtf((float)D) / fmaxf(sqrtf(ss), 1e-12f);
-        }
-        __syncthreads();
-        for (int i = tid; i < (D / 8) * 64; i += 256) {
-            const int g = i >> 6, c = i & 63;
-            h16x8 o;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (h16)(ys[(8 * g + j) * 64 + c] * inv[c]);
-            *reinterpret_cast<h16x8*>(zs + (size_t)i * 8) = o;
-        }
-        __syncthreads();
+        head16_stage_tile(Yb, D, Fr, f0, tid, ys, zs, inv);
         h16x8 bf[8][2];                                          // B fragments: chunk c, frame tile e (D <= 128)
 #pragma unroll
         for (int c = 0; c < 8; ++c)
@@ -1369,6 +1375,90 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
                 if (WIN) p.psum[(size_t)b * p.nb + wave * bpw + i] = v;
                 else p.mean_prob[(size_t)b * p.nb + wave * bpw + i] = v / (float)p.T;
             }
+        }
+    }
+}
+
+// The same head in its gated per-frame form (localized detection): fsum[b][bit][f] = the sum over the gated samples t < T of frame f of
+// sigmoid(logit[bit][t]), fsum[b][nb][f] = their number; sample t is gated iff gate == null || gate[b][t] > gate_thr.  One workgroup per
+// (64-frame tile, clip).  A lane already owns a frame (f = f0 + 32 e + r, the halves h hold its samples), so a frame's sum is lane-local
+// over (mt, i) in that order plus ONE cross-half add: fixed order, no atomics.  The tile's gate bits are built once with coalesced reads
+// (64 * hop consecutive samples, one ballot per 64) into gw[64][hop / 32] and serve every bit; the count row is their popcount.
+struct Head16FramesArgs { const float* Y; H16Weight w; const float* bc; const float* gate; float gate_thr; float* fsum; int B, D, nb, hop, Fr, T; };
+
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void head16_frames_kernel(Head16FramesArgs p) {
+    __shared__ __attribute__((aligned(16))) float ys[128 * 64];       // y tile [D][64] f32
+    __shared__ __attribute__((aligned(16))) h16 zs[16 * 64 * 8];       // z tile, c8 [D/8][64][8]
+    __shared__ float inv[64];
+    extern __shared__ uint32_t gw[];                                  // gate bits [64 frames][hop / 32]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5, r = lane & 31;
+    const int b = blockIdx.y, f0 = blockIdx.x * 64, D = p.D, Fr = p.Fr, NC = D / 16, bpw = p.nb / 4, mtb = p.hop / 32;
+    const float* Yb = p.Y + (size_t)b * D * Fr;
+    const float* gb = p.gate ? p.gate + (size_t)b * p.T : nullptr;
+    float* fb = p.fsum + (size_t)b * (p.nb + 1) * Fr;
+    const __amdgpu_buffer_rsrc_t rW = uniform_rsrc(p.w.wq, p.w.nchunks * p.w.Mp * 32);
+    const int Mp = p.w.Mp;
+    const long long tbase = (long long)f0 * p.hop;
+    for (int s0 = wave * 64; s0 < 64 * p.hop; s0 += 256) {       // hop % 32 == 0: a 32-bit word never straddles two frames
+        const long long t = tbase + s0 + lane;
+        const bool on = t < p.T && head_gated(gb, p.gate_thr, t);
+        const unsigned long long m = __ballot(on);
+        if (lane == 0) { gw[s0 >> 5] = (uint32_t)m; gw[(s0 >> 5) + 1] = (uint32_t)(m >> 32); }
+    }
+    head16_stage_tile(Yb, D, Fr, f0, tid, ys, zs, inv);          // its barriers publish gw as well
+    if (tid < 64 && f0 + tid < Fr) {
+        int c = 0;
+        for (int mt = 0; mt < mtb; ++mt) c += __popc(gw[tid * mtb + mt]);
+        fb[(size_t)p.nb * Fr + f0 + tid] = (float)c;
+    }
+    h16x8 bf[8][2];                                              // B fragments: chunk c, frame tile e (D <= 128)
+#pragma unroll
+    for (int c = 0; c < 8; ++c)
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+            if (c < NC) bf[c][e] = *reinterpret_cast<const h16x8*>(zs + (size_t)((2 * c + h) * 64 + 32 * e + r) * 8);
+    for (int bi = 0; bi < bpw; ++bi) {
+        const int bit = wave * bpw + bi;
+        const float bcv = p.bc[bit];
+        float s[2] = {0.f, 0.f};
+        for (int mt = 0; mt < mtb; ++mt) {
+            const int m0 = bit * p.hop + 32 * mt;
+            const int avoff = ((m0 + r) * 2 + h) * 16;
+            h16x8 a[8];
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                const int so = c * Mp * 32;
+                if (c < NC) a[c] = __builtin_bit_cast(h16x8, __builtin_amdgcn_raw_buffer_load_b128(rW, avoff, so, 0));
+            }
+            f32x16 acc[2];
+#pragma unroll
+            for (int e = 0; e < 2; ++e)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[e][i] = 0.f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (c < NC) {
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) acc[e] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[c], bf[c][e], acc[e], 0, 0, 0);
+                }
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const uint32_t word = gw[(32 * e + r) * mtb + mt];        // samples 32 mt .. 32 mt + 31 of frame f0 + 32 e + r
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const int j = 8 * (i >> 2) + 4 * h + (i & 3);
+                    const float sg = __builtin_amdgcn_rcpf(1.f + __expf(-(acc[e][i] + bcv)));   // head16_kernel's sigmoid
+                    s[e] += (word >> j) & 1u ? sg : 0.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float v = s[e] + __shfl_xor(s[e], 32);
+            const int f = f0 + 32 * e + r;
+            if (h == 0 && f < Fr) fb[(size_t)bit * Fr + f] = v;
         }
     }
 }
@@ -1617,6 +1707,17 @@ hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, fl
     Head16Args a{Y, w, bc, mean_prob, B, D, nb, hop, Fr, T, keep_lo, keep_hi, psum};
     if (win) hipLaunchKernelGGL(head16_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, a);
     else hipLaunchKernelGGL(head16_kernel<false>, dim3((unsigned)B), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_head16_frames(const float* Y, const H16Weight& w, const float* bc, const float* gate, float gate_thr, float* fsum, int B, int D, int nb, int hop,
+                                int Fr, int T, hipStream_t s) {
+    if (!Y || !w.wq || !bc || !fsum || B < 1 || B > 65535 || Fr < 1 || T < 1 || hop < 1) return hipErrorInvalidValue;
+    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return hipErrorInvalidValue;                    // Fr = ceil(T / hop)
+    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || hop > 2016 || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
+    prof::Scope ps(s, "head16_frames", 2.0 * B * D * (double)nb * hop * Fr, (double)B * (4.0 * D * Fr + 4.0 * (nb + 1) * Fr + (gate ? 4.0 * T : 0.0)));
+    Head16FramesArgs a{Y, w, bc, gate, gate_thr, fsum, B, D, nb, hop, Fr, T};
+    hipLaunchKernelGGL(head16_frames_kernel, dim3((unsigned)((Fr + 63) / 64), (unsigned)B), dim3(256), (size_t)(hop / 32) * 64 * sizeof(uint32_t), s, a);
     return hipGetLastError();
 }
 

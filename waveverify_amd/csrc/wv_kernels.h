@@ -258,6 +258,10 @@ inline void pack_stft16(const float* basis, int n_fft, std::vector<uint16_t> (&q
 // fragments), sigmoid, mean over time.  hipErrorNotSupported outside D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0.
 hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s,
                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr);
+// the same head in the gated per-frame form of HeadFramesArgs: fsum [B][nb + 1][Fr], gate [B][T] or null.  launch_head16's limits, and
+// hop <= 2016 (the gate bits of a 64-frame tile lie in LDS beside the latent tile).
+hipError_t launch_head16_frames(const float* Y, const H16Weight& w, const float* bc, const float* gate, float gate_thr, float* fsum, int B, int D, int nb, int hop,
+                                int Fr, int T, hipStream_t s);
 hipError_t launch_conv_pre16(const float* x, const float* w, const float* bias, void* Y, int B, int C, int T, int ks, float in_scale, hipStream_t s);
 hipError_t launch_f32_to_c8(const float* X, void* Y, int B, int C, int T, float scale, int elu, hipStream_t s);
 // L2Norm over channels (seanet.py:288-318: y / max(||y||, 1e-12) * sqrt(D)) of a latent [B][D][Fr] f32 -> c8 f16 (the f16 decoder's input)
@@ -365,6 +369,19 @@ struct HeadArgs {
     float* psum = nullptr;
 };
 hipError_t launch_head(const HeadArgs& a, hipStream_t s);
+// the gated per-frame form (localized detection): sample t of clip b is gated iff gate == nullptr || gate[b][t] > gate_thr (strict);
+// fsum[b][bit][f] = sum over the gated t < T of frame f of sigmoid(logit[bit][t]), fsum[b][nb][f] = the number of gated samples of
+// frame f.  Every element of fsum is written; no logits are stored; fixed summation order.  Fr == ceil(T / hop).
+struct HeadFramesArgs {
+    const float* Z;       // [B, D, Fr]
+    const float* wc;
+    const float* bc;
+    const float* gate;    // [B, T] or null
+    float gate_thr;
+    float* fsum;          // [B, nb + 1, Fr]
+    int B, D, nb, hop, Fr, T;
+};
+hipError_t launch_head_frames(const HeadFramesArgs& a, hipStream_t s);
 
 // ---- K7: message MLP + FiLM parameters ------------------------------------------------------
 struct FilmArgs {

@@ -970,6 +970,67 @@ __global__ __launch_bounds__(NT_) void head_kernel(HeadArgs p) {
     }
 }
 
+// K6f  the head's gated per-frame form (localized detection).  Same GEMM and workgroup = (bit, clip) as head_kernel, but the sigmoids
+// are summed per FRAME (a row of the accumulator tile) over the samples the gate passes, and nothing is reduced across frames:
+// fsum[b][bit][f] = sum over t in frame f, t < T, gated(t), of sigmoid(logit[bit][t]).  Fixed order per row: a lane's columns, then a
+// five-step xor tree over the 32 lanes of its half-wave, then the WN waves in order through LDS, then the j0 tiles in order.
+// Workgroup x == nb writes the count row instead, fsum[b][nb][f] = the number of gated samples of the frame (an integer sum: exact).
+template <class T>
+__global__ __launch_bounds__(NT_) void head_frames_kernel(HeadFramesArgs p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    const int bit = blockIdx.x, b = blockIdx.y;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float* gb = p.gate ? p.gate + (size_t)b * p.T : nullptr;
+    float* out = p.fsum + ((size_t)b * (p.nb + 1) + bit) * p.Fr;
+    if (bit == p.nb) {                                       // one wave per frame
+        for (int f = wave; f < p.Fr; f += NT_ / 64) {
+            const int t0 = f * p.hop, n = min(p.hop, p.T - t0);
+            int c = 0;
+            for (int j = lane; j < n; j += 64) c += head_gated(gb, p.gate_thr, t0 + j) ? 1 : 0;
+            for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+            if (lane == 0) out[f] = (float)c;
+        }
+        return;
+    }
+    const float bc = p.bc[bit];
+    const int nchunks = (p.D + BK - 1) / BK;
+    const int wm = wave / T::WN, wn = wave % T::WN;
+    float* red = smem;                                       // [WN][BM]: the stages are free after the mainloop's last barrier
+    for (int f0 = 0; f0 < p.Fr; f0 += T::BM) {
+        float rowacc = 0.f;                                  // thread tid < BM owns frame f0 + tid
+        for (int j0 = 0; j0 < p.hop; j0 += T::BN) {
+            f32x16 acc[T::MT][T::NT];
+            zero_acc<T>(acc);
+            ZLoader la{p.Z + (size_t)b * p.D * p.Fr, p.D, p.Fr, f0};
+            RowLoader lb{p.wc + (size_t)bit * p.hop, p.D, p.nb * p.hop, p.hop, j0, 1.f, 0,
+                         nullptr, 0, false, false};
+            gemm_mainloop<T>(acc, la, lb, nchunks, smem);
+#pragma unroll
+            for (int i = 0; i < T::MT; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int row = wm * T::MT * 32 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const int f = f0 + row;
+                    float rs = 0.f;
+#pragma unroll
+                    for (int j = 0; j < T::NT; ++j) {
+                        const int jj = j0 + wn * T::NT * 32 + j * 32 + (lane & 31);
+                        const int t = f * p.hop + jj;
+                        const bool on = f < p.Fr && jj < p.hop && t < p.T && head_gated(gb, p.gate_thr, t);
+                        rs += on ? sigmoidf_(acc[i][j][r] + bc) : 0.f;
+                    }
+                    for (int off = 16; off > 0; off >>= 1) rs += __shfl_xor(rs, off);
+                    if ((lane & 31) == 0) red[wn * T::BM + row] = rs;
+                }
+            __syncthreads();
+            if ((int)threadIdx.x < T::BM)
+                for (int w = 0; w < T::WN; ++w) rowacc += red[w * T::BM + threadIdx.x];
+            __syncthreads();                                 // red is read before the next mainloop stages over it
+        }
+        if ((int)threadIdx.x < T::BM && f0 + (int)threadIdx.x < p.Fr) out[f0 + threadIdx.x] = rowacc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // K7  message MLP + FiLM gammas/betas (seanet.py:831-846, 905-912).  One workgroup per clip.
 // ------------------------------------------------------------------------------------------
@@ -1367,6 +1428,17 @@ hipError_t launch_head(const HeadArgs& a, hipStream_t s) {
     } else {
         hipLaunchKernelGGL((head_kernel<T, false>), grid, dim3(NT_), stage_bytes<T>(), s, a);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_head_frames(const HeadFramesArgs& a, hipStream_t s) {
+    using T = Tile<64, 64, 2, 2>;
+    if (!a.Z || !a.wc || !a.bc || !a.fsum || a.B < 1 || a.B > 65535 || a.D < 1 || a.nb < 1 || a.hop < 1 || a.Fr < 1 || a.T < 1) return hipErrorInvalidValue;
+    if ((long long)(a.Fr - 1) * a.hop >= a.T || (long long)a.Fr * a.hop < a.T) return hipErrorInvalidValue;       // Fr = ceil(T / hop)
+    static const std::string name = tile_name<T>("head_frames");
+    prof::Scope ps(s, name.c_str(), 2.0 * a.B * a.D * (double)a.nb * a.hop * a.Fr,
+                   4.0 * a.B * ((double)a.D * a.Fr + (a.nb + 1.0) * a.Fr + (a.gate ? (double)(a.nb + 1) * a.T : 0.0)));
+    hipLaunchKernelGGL((head_frames_kernel<T>), dim3(a.nb + 1, a.B), dim3(NT_), stage_bytes<T>(), s, a);
     return hipGetLastError();
 }
 

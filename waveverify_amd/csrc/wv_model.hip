@@ -1133,13 +1133,15 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
 }
 
 // keep_lo / keep_hi / psum: the windowed mean-probability mode (wv_detector_forward_windowed); all null otherwise.
+// fsum (with gate, gate_thr): the gated per-frame mode (wv_detector_forward_frames) instead of any other output.
 static int run_head_model(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,
                           void* ws, size_t ws_bytes, void* stream, bool f16 = false,
-                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr) {
+                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr,
+                          const float* gate = nullptr, float gate_thr = 0.f, float* fsum = nullptr) {
     WsLayout L;
     int rc = check_common(m, B, T, ws, ws_bytes, &L);
     if (rc) return rc;
-    if (!x || (!logits && !mean_prob && !psum)) return fail(WV_EINVAL, "null tensor");
+    if (!x || (!logits && !mean_prob && !psum && !fsum)) return fail(WV_EINVAL, "null tensor");
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)ws;
     float* latent = (float*)(w + L.off_lat);
@@ -1150,10 +1152,16 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
         // mean probabilities only: conv_post and the head run on the f16 pipe as well (L2Norm + composed head GEMM + sigmoid + time mean)
         const wv_config& c = m->cfg;
         const int D = c.dimension, hop = hop_of(c);
-        const bool head16 = !logits && (int)m->h16.size() > c.n_strides && m->h16.back().head.wq && D % 16 == 0 && D <= 128 && m->head_nb % 4 == 0 && m->head_nb <= 32 && hop % 32 == 0;
+        const bool head16 = !logits && (int)m->h16.size() > c.n_strides && m->h16.back().head.wq && D % 16 == 0 && D <= 128 && m->head_nb % 4 == 0 && m->head_nb <= 32 && hop % 32 == 0 && (!fsum || hop <= 2016);
         bool latent_done = false;
         rc = run_encoder_stages_f16(m, x, nullptr, B, T, w, L, st, head16 ? H16_TAIL_LATENT : H16_TAIL_F32, &post_done, &latent_done, &Fr);
         if (rc) return rc;
+        if (latent_done && fsum) {
+            wv::prof::set_role("head16");
+            const hipError_t e2 = wv::launch_head16_frames(latent, m->h16.back().head, m->head_bc, gate, gate_thr, fsum, B, D, m->head_nb, hop, Fr, T, st);
+            if (e2 != hipSuccess) return fail(WV_EHIP, std::string("launch_head16_frames: ") + hipGetErrorString(e2));
+            return WV_OK;
+        }
         if (latent_done) {
             wv::prof::set_role("head16");
             const hipError_t e2 = wv::launch_head16(latent, m->h16.back().head, m->head_bc, mean_prob, B, D, m->head_nb, hop, Fr, T, st,
@@ -1165,6 +1173,13 @@ static int run_head_model(wv_model* m, const float* x, float* logits, float* mea
     rc = run_encoder(m, x, nullptr, 0, latent, B, T, w, L, st, &Fr, f16 ? m->cfg.n_strides : 0, post_done);
     if (rc) return rc;
     wv::prof::set_role("head");
+    if (fsum) {
+        wv::HeadFramesArgs q{};
+        q.Z = latent; q.wc = m->head_wc; q.bc = m->head_bc; q.gate = gate; q.gate_thr = gate_thr; q.fsum = fsum;
+        q.B = B; q.D = m->cfg.dimension; q.nb = m->head_nb; q.hop = hop_of(m->cfg); q.Fr = Fr; q.T = T;
+        WV_HIP_TRY(wv::launch_head_frames(q, st));
+        return WV_OK;
+    }
     wv::HeadArgs h{};
     h.Z = latent; h.wc = m->head_wc; h.bc = m->head_bc; h.logits = logits; h.mean_prob = mean_prob;
     h.B = B; h.D = m->cfg.dimension; h.nb = m->head_nb; h.hop = hop_of(m->cfg); h.Fr = Fr; h.T = T;
@@ -1185,6 +1200,20 @@ int wv_detector_forward_windowed_f16(wv_model* m, const float* x, const int* kee
     if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
     if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
     return run_head_model(m, x, nullptr, nullptr, W, L, ws, ws_bytes, stream, true, keep_lo, keep_hi, psum);
+}
+
+int wv_detector_forward_frames(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum, int B, int T,
+                               void* ws, size_t ws_bytes, void* stream) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!fsum) return fail(WV_EINVAL, "null tensor");
+    return run_head_model(m, x, nullptr, nullptr, B, T, ws, ws_bytes, stream, false, nullptr, nullptr, nullptr, gate, gate_thr, fsum);
+}
+
+int wv_detector_forward_frames_f16(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum, int B, int T,
+                                   void* ws, size_t ws_bytes, void* stream) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!fsum) return fail(WV_EINVAL, "null tensor");
+    return run_head_model(m, x, nullptr, nullptr, B, T, ws, ws_bytes, stream, true, nullptr, nullptr, nullptr, gate, gate_thr, fsum);
 }
 
 int wv_detector_forward(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,

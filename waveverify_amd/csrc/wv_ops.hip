@@ -76,6 +76,25 @@ int done(Tmp& t, hipError_t e, hipStream_t s) {
     return WV_OK;
 }
 
+// the head's composed weight wc[D][nb * hop] and bias bc[nb] (wv_kernels.h, K6) from the reference's two layers
+void compose_head(const float* w_rev, const float* b_rev, const float* w_last, const float* b_last, int D, int O, int nb, int hop,
+                  std::vector<float>& wc, std::vector<float>& bc) {
+    wc.assign((size_t)D * nb * hop, 0.f);
+    bc.assign(nb, 0.f);
+    for (int d = 0; d < D; ++d)
+        for (int n = 0; n < nb; ++n)
+            for (int j = 0; j < hop; ++j) {
+                double acc = 0;
+                for (int o = 0; o < O; ++o) acc += (double)w_last[(size_t)n * O + o] * w_rev[((size_t)d * O + o) * hop + j];
+                wc[((size_t)d * nb + n) * hop + j] = (float)acc;
+            }
+    for (int n = 0; n < nb; ++n) {
+        double acc = b_last[n];
+        for (int o = 0; o < O; ++o) acc += (double)w_last[(size_t)n * O + o] * b_rev[o];
+        bc[n] = (float)acc;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,6 +313,19 @@ int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_
     w.wq = t.upb(q.data(), q.size() * sizeof(uint16_t));
     const hipError_t e = wv::launch_head16(lat, w, t.up(bc, nb), mean_prob, B, D, nb, hop, Fr, T, (hipStream_t)stream, keep_lo, keep_hi, psum);
     if (e == hipErrorNotSupported) return unsupported("D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, and a weight pack of exactly that shape");
+    return done(t, e, (hipStream_t)stream);
+}
+int wv_h16_head_frames(const float* lat, const float* wc, const float* bc, const float* gate, float gate_thr, float* fsum, int B, int D, int nb, int hop,
+                       int Fr, int T, void* stream) {
+    if (!lat || !wc || !bc || !fsum || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return fail(WV_EINVAL, "null pointer (lat, wc, bc, fsum) or B, D, nb, hop, Fr, T < 1");
+    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return fail(WV_EINVAL, "Fr is not ceil(T / hop)");
+    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || hop > 2016) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, hop <= 2016");   // launch_head16_frames' gate
+    Tmp t;
+    wv::H16Weight w;
+    const std::vector<uint16_t> q = wv::pack_head16(wc, D, nb, hop, &w);
+    w.wq = t.upb(q.data(), q.size() * sizeof(uint16_t));
+    const hipError_t e = wv::launch_head16_frames(lat, w, t.up(bc, nb), gate, gate_thr, fsum, B, D, nb, hop, Fr, T, (hipStream_t)stream);
+    if (e == hipErrorNotSupported) return unsupported("D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, hop <= 2016, and a weight pack of exactly that shape");
     return done(t, e, (hipStream_t)stream);
 }
 int wv_h16_conv_film(const void* X16, const float* w_pw, const float* w_dw, const float* bias, const float* film, int bands, void* Y16, void* Yact16,
@@ -526,24 +558,26 @@ int wv_op_head(const float* Z, const float* w_rev, const float* b_rev, const flo
                int hop, int Fr, int T, void* stream) {
     if (!Z || !w_rev || !b_rev || !w_last || !b_last || (!logits && !mean_prob)) return fail(WV_EINVAL, "null pointer (Z, a weight or bias, or both logits and mean_prob)");
     if (T > Fr * hop) return fail(WV_EINVAL, "T > Fr * hop");
-    std::vector<float> wc((size_t)D * nb * hop), bc(nb);
-    for (int d = 0; d < D; ++d)
-        for (int n = 0; n < nb; ++n)
-            for (int j = 0; j < hop; ++j) {
-                double acc = 0;
-                for (int o = 0; o < O; ++o) acc += (double)w_last[(size_t)n * O + o] * w_rev[((size_t)d * O + o) * hop + j];
-                wc[((size_t)d * nb + n) * hop + j] = (float)acc;
-            }
-    for (int n = 0; n < nb; ++n) {
-        double acc = b_last[n];
-        for (int o = 0; o < O; ++o) acc += (double)w_last[(size_t)n * O + o] * b_rev[o];
-        bc[n] = (float)acc;
-    }
+    std::vector<float> wc, bc;
+    compose_head(w_rev, b_rev, w_last, b_last, D, O, nb, hop, wc, bc);
     Tmp t;
     wv::HeadArgs a{};
     a.Z = Z; a.wc = t.upv(wc); a.bc = t.upv(bc); a.logits = logits; a.mean_prob = mean_prob;
     a.B = B; a.D = D; a.nb = nb; a.hop = hop; a.Fr = Fr; a.T = T;
     return done(t, wv::launch_head(a, (hipStream_t)stream), (hipStream_t)stream);
+}
+
+int wv_op_head_frames(const float* Z, const float* w_rev, const float* b_rev, const float* w_last, const float* b_last, const float* gate,
+                      float gate_thr, float* fsum, int B, int D, int O, int nb, int hop, int Fr, int T, void* stream) {
+    if (!Z || !w_rev || !b_rev || !w_last || !b_last || !fsum || B < 1 || D < 1 || O < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return fail(WV_EINVAL, "null pointer (Z, a weight or bias, fsum) or B, D, O, nb, hop, Fr, T < 1");
+    if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return fail(WV_EINVAL, "Fr is not ceil(T / hop)");
+    std::vector<float> wc, bc;
+    compose_head(w_rev, b_rev, w_last, b_last, D, O, nb, hop, wc, bc);
+    Tmp t;
+    wv::HeadFramesArgs a{};
+    a.Z = Z; a.wc = t.upv(wc); a.bc = t.upv(bc); a.gate = gate; a.gate_thr = gate_thr; a.fsum = fsum;
+    a.B = B; a.D = D; a.nb = nb; a.hop = hop; a.Fr = Fr; a.T = T;
+    return done(t, wv::launch_head_frames(a, (hipStream_t)stream), (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 //   window_scatter_kernel  kept columns of [W, C, L] window outputs -> each clip's [C, T] output
 //   window_mean_kernel     per-window sigmoid sums psum[W, nb] (head_kernel / head16_kernel in their windowed mode) -> mean_prob[B, nb],
 //                          windows of a clip added in a fixed order in f64: deterministic, no drift with length
+//   frames_reduce_kernel   the localized heads' per-frame sums fsum[B, nb + 1, Fr] -> per SEGMENT {clip, f_lo, f_hi} the masked mean probability
+//                          of every bit and the gated sample count, frames added in order in f64
 //   session_advance_kernel a live session's tick: [S, H] history + [S, n] new samples -> the tick's window and the next history
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
 #include <hip/hip_runtime.h>
@@ -71,6 +73,29 @@ __global__ __launch_bounds__(WIN_NT) void window_mean_kernel(const float* __rest
     mean[i] = len[b] > 0 ? (float)(acc / (double)len[b]) : 0.f;
 }
 
+// one thread per (segment, bit): S = sum over f in [f_lo, f_hi) of fsum[clip][bit][f] and N = the same sum of the count row, both in that
+// order in f64; prob = S / (float(N) + eps), the eps add in f32 as metrics_decode_finish_kernel makes it, the quotient rounded once;
+// N == 0 (an empty or wholly ungated segment) gives prob = 0.  A segment outside the tensor is treated as empty.
+__global__ __launch_bounds__(WIN_NT) void frames_reduce_kernel(const float* __restrict__ fsum, int B, int nb, int Fr, const int* __restrict__ seg, int n_seg,
+                                                               float eps, float* __restrict__ prob, double* __restrict__ count) {
+    const int i = blockIdx.x * WIN_NT + threadIdx.x;
+    if (i >= n_seg * nb) return;
+    const int sg = i / nb, k = i % nb;
+    const int clip = seg[3 * sg], lo = seg[3 * sg + 1], hi = seg[3 * sg + 2];
+    double acc = 0.0, cnt = 0.0;
+    if (clip >= 0 && clip < B && lo >= 0 && hi <= Fr) {
+        const float* row = fsum + ((size_t)clip * (nb + 1) + k) * Fr;
+        const float* crow = fsum + ((size_t)clip * (nb + 1) + nb) * Fr;
+        for (int f = lo; f < hi; ++f) {
+            acc += (double)row[f];
+            cnt += (double)crow[f];
+        }
+    }
+    const float d = (float)cnt + eps;
+    prob[i] = cnt > 0.0 ? (float)(acc / (double)d) : 0.f;
+    if (k == 0) count[sg] = cnt;
+}
+
 // grid (ceil(max(wlen, hv2) / WIN_NT), S).  Stream s's samples are cat(hist[s][0 .. hv), x[s][0 .. n)); the window is that sequence's
 // first wlen samples, the next history its samples [drop, drop + hv2).
 __global__ __launch_bounds__(WIN_NT) void session_advance_kernel(const float* __restrict__ hist, int hcap, int hv, const float* __restrict__ x, int n,
@@ -113,6 +138,14 @@ extern "C" int wv_window_reduce_mean(const float* psum, int n_rows, const int* p
     if (!psum || !ptr || !rows || !lengths || !mean_prob || n_rows < 1 || B < 1 || nb < 1) return fail(WV_EINVAL, "null pointer (psum, ptr, rows, lengths, mean_prob) or n_rows, B, nb < 1");
     hipLaunchKernelGGL(wv::window_mean_kernel, dim3((B * nb + wv::WIN_NT - 1) / wv::WIN_NT), dim3(wv::WIN_NT), 0, (hipStream_t)stream, psum, n_rows, ptr,
                        rows, lengths, mean_prob, B, nb);
+    return launched();
+}
+
+extern "C" int wv_frames_reduce(const float* fsum, int B, int nb, int Fr_stride, const int* seg, int n_seg, float eps, float* prob, double* count,
+                                void* stream) {
+    if (!fsum || !seg || !prob || !count || B < 1 || nb < 1 || Fr_stride < 1 || n_seg < 1 || (long long)n_seg * nb > 0x7fffffffLL) return fail(WV_EINVAL, "null pointer (fsum, seg, prob, count), B, nb, Fr_stride or n_seg < 1, or n_seg * nb beyond 2^31");
+    hipLaunchKernelGGL(wv::frames_reduce_kernel, dim3((n_seg * nb + wv::WIN_NT - 1) / wv::WIN_NT), dim3(wv::WIN_NT), 0, (hipStream_t)stream, fsum, B, nb,
+                       Fr_stride, seg, n_seg, eps, prob, count);
     return launched();
 }
 

@@ -232,6 +232,34 @@ class HipNet:
                           _lib.stream()), "wv_detector_forward_windowed" + ("_f16" if precision == "f16" else ""))
         return psum
 
+    def detector_frame_sums(self, x: torch.Tensor, gate: Optional[torch.Tensor] = None, gate_thr: float = 0.0, precision: str = "f32",
+                            out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Localized detection's kernel output, fsum [B, nbits + 1, Fr] with Fr = ceil(T / hop): row bit = per frame the sum of
+        sigmoid(logit) over the samples whose gate [B, T] (or [B,1,T]) value is > gate_thr (every sample without a gate), row nbits = the
+        number of those samples.  Locator logits go in as the gate with gate_thr = log(p / (1 - p)); a 0/1 mask with gate_thr = 0.5.
+        No logits are stored; two runs agree bit for bit."""
+        if self.cfg.kind != "detector":
+            raise RuntimeError("not a detector")
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16'")
+        x = self._prep(x)
+        B, _, T = x.shape
+        nb, Fr = self.cfg.head_bits, -(-T // self.hop_length)
+        if gate is not None:
+            gate = gate.to(self.device, torch.float32).contiguous()
+            if gate.numel() != B * T:
+                raise ValueError(f"gate must hold [B, T] = [{B}, {T}] values, got {tuple(gate.shape)}")
+        if out is None:
+            out = torch.empty((B, nb + 1, Fr), dtype=torch.float32, device=self.device)
+        if tuple(out.shape) != (B, nb + 1, Fr) or not out.is_contiguous() or out.dtype != torch.float32:
+            raise ValueError(f"out must be a contiguous float32 [{B},{nb + 1},{Fr}] tensor")
+        with torch.cuda.device(self.device):
+            ws = self._workspace(B, T)
+            fn = self._lib.wv_detector_forward_frames_f16 if precision == "f16" else self._lib.wv_detector_forward_frames
+            _lib.check(fn(self._h, x.data_ptr(), _lib.ptr(gate), float(gate_thr), out.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
+                          _lib.stream()), "wv_detector_forward_frames" + ("_f16" if precision == "f16" else ""))
+        return out
+
     def locator(self, x: torch.Tensor, precision: str = "f32") -> torch.Tensor:
         """Locator.forward: logits [B, 1, T].  precision="f16": the f16-operand / f32-accumulate throughput mode."""
         if self.cfg.kind != "locator":

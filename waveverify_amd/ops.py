@@ -172,6 +172,47 @@ def head(Z, w_rev, b_rev, w_last, b_last, T, want_logits=True, want_mean=True, o
     return logits, mean
 
 
+def _gate(gate, B, T, device):
+    if gate is None:
+        return None
+    gate = _lib.dev(gate, _ON_GPU)
+    if gate.numel() != B * T:
+        raise ValueError(f"gate must hold [B, T] = [{B}, {T}] values, got {tuple(gate.shape)}")
+    return gate
+
+
+def head_frames(Z, w_rev, b_rev, w_last, b_last, T, gate=None, gate_thr=0.0, out=None) -> torch.Tensor:
+    """The head's gated per-frame form (head_frames_kernel): -> fsum [B, nb + 1, Fr]; row bit = per frame the sum of sigmoid(logit)
+    over the samples with gate > gate_thr (all samples without a gate), row nb = their number."""
+    lib = _lib.load()
+    Z = _lib.dev(Z, _ON_GPU)
+    B, D, Fr = Z.shape
+    w_rev, b_rev, w_last, b_last = _w(w_rev), _w(b_rev), _w(w_last), _w(b_last)
+    O, hop = w_rev.shape[1], w_rev.shape[2]
+    nb = w_last.shape[0]
+    w_last = w_last.reshape(nb, O)
+    gate = _gate(gate, B, int(T), Z.device)
+    fsum = _out(out, (B, nb + 1, Fr), torch.float32, Z.device)
+    _lib.check(lib.wv_op_head_frames(Z.data_ptr(), _hp(w_rev), _hp(b_rev), _hp(w_last), _hp(b_last), _lib.ptr(gate), float(gate_thr),
+                                     fsum.data_ptr(), B, D, O, nb, hop, Fr, int(T), _lib.stream()), "wv_op_head_frames")
+    return fsum
+
+
+def frames_reduce(fsum, segments, eps: float = 1e-8):
+    """wv_frames_reduce: fsum [B, nb + 1, Fr], segments [n, 3] ints {clip, f_lo, f_hi} -> (prob [n, nb] float32, count [n] float64)."""
+    lib = _lib.load()
+    fsum = _lib.dev(fsum, _ON_GPU)
+    B, nb1, Fr = fsum.shape
+    seg = torch.as_tensor(segments, dtype=torch.int32).reshape(-1, 3).contiguous().to(fsum.device)
+    n = seg.shape[0]
+    prob = torch.empty((n, nb1 - 1), dtype=torch.float32, device=fsum.device)
+    count = torch.empty(n, dtype=torch.float64, device=fsum.device)
+    if n:
+        _lib.check(lib.wv_frames_reduce(fsum.data_ptr(), B, nb1 - 1, Fr, seg.data_ptr(), n, float(eps), prob.data_ptr(), count.data_ptr(),
+                                        _lib.stream()), "wv_frames_reduce")
+    return prob, count
+
+
 # ---- the f16 mode's units (csrc/wv_h16.hip).  A "c8" tensor is torch.float16 [B, roundup(C,16)/8, T, 8] --------------------------
 def _c8(t: torch.Tensor) -> torch.Tensor:
     if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 4 and t.shape[-1] == 8 and t.is_contiguous()):
@@ -342,6 +383,23 @@ def h16_head(lat, wc, bc, T: int, keep_lo=None, keep_hi=None, out=None) -> torch
     _lib.check(lib.wv_h16_head(lat.data_ptr(), _hp(wc), _hp(bc), None if lo is not None else out.data_ptr(), B, D, nb, hop, Fr, int(T),
                                _lib.ptr(lo), _lib.ptr(hi), _lib.ptr(out) if lo is not None else None, _lib.stream()), "wv_h16_head")
     return out
+
+
+def h16_head_frames(lat, wc, bc, T: int, gate=None, gate_thr=0.0, out=None) -> torch.Tensor:
+    """h16_head in the gated per-frame form (head16_frames_kernel): -> fsum [B, nb + 1, Fr], as ops.head_frames."""
+    lib = _lib.load()
+    lat = _lib.dev(lat, _ON_GPU)
+    B, D, Fr = lat.shape
+    wc, bc = _w(wc), _w(bc)
+    nb = bc.shape[0]
+    hop = wc.shape[-1] // nb
+    if wc.shape != (D, nb * hop):
+        raise ValueError(f"wc must be [D, nb * hop] = [{D}, {nb} * hop], got {wc.shape}")
+    gate = _gate(gate, B, int(T), lat.device)
+    fsum = _out(out, (B, nb + 1, Fr), torch.float32, lat.device)
+    _lib.check(lib.wv_h16_head_frames(lat.data_ptr(), _hp(wc), _hp(bc), _lib.ptr(gate), float(gate_thr), fsum.data_ptr(), B, D, nb, hop, Fr,
+                                      int(T), _lib.stream()), "wv_h16_head_frames")
+    return fsum
 
 
 def h16_conv_film(X16, w_pw, w_dw, bias, film, ks, stride, pad, act_scale: Optional[float] = None, want_raw: bool = True, out=None,

@@ -235,3 +235,51 @@ def windowed_detector_mean_prob(net, clips, window: int = 480000, precision: str
         _lib.check(net._lib.wv_window_reduce_mean(psum.data_ptr(), n_rows, ptr_t.data_ptr(), rows_t.data_ptr(), len_t.data_ptr(),
                                                   mean.data_ptr(), len(lengths), nb, _lib.stream()), "wv_window_reduce_mean")
         return mean
+
+
+# --------------------------------------------------------------------------- localized detection: per-frame sums, windowed
+def frame_scatter_desc(wins: Sequence[Window], frame_bases: Sequence[int], frames: Sequence[int], hop: int, C_: int) -> List[List[int]]:
+    """wv_window_scatter descriptors in FRAME units for window outputs [W, C_, ceil(L / hop)]: per window {offset of its frame 0 in the
+    packed [C_, Fr] clip outputs, the clip's Fr, kept frames lo, hi} (relative to the window).  Window starts and keep edges are hop
+    multiples, so kept frames are whole; only a clip's last frame is partial (keep_hi == T there, rounded up).  Pure Python."""
+    desc = []
+    for w in wins:
+        if w.start % hop or w.keep_lo % hop:
+            raise ValueError("window start and keep edge must be hop multiples")
+        desc.append([C_ * frame_bases[w.clip] + w.start // hop, frames[w.clip], (w.keep_lo - w.start) // hop, -(-(w.keep_hi - w.start) // hop)])
+    return desc
+
+
+def windowed_detector_frame_sums(net, clips, gates=None, gate_thr: float = 0.0, window: int = 480000, precision: str = "f32",
+                                 max_windows: int = 64):
+    """HipNet.detector_frame_sums of every clip, windowed: a list of [nbits + 1, Fr_b] tensors, or [B, nbits + 1, Fr] for a [B,1,T] input.
+    gates: None, or the clips' gates in the same form as `clips` (per clip one value per sample).  Gate windows are gathered from the
+    packed gates with the audio's own offsets, the frames kernel runs on the window batch and the kept frames are scattered in frame
+    units, so no logits and no separate gate tensor are written."""
+    torch = _torch()
+    nb1, hop = net.cfg.head_bits + 1, net.cfg.hop_length
+    with torch.cuda.device(net.device):
+        packed, lengths, bases, as_batch = _pack(clips, net.device)
+        gpacked = None
+        if gates is not None:
+            if isinstance(gates, torch.Tensor) and gates.dim() == 2:
+                gates = gates.unsqueeze(1)
+            gpacked, glen, _, _ = _pack(gates, net.device)
+            if glen != lengths:
+                raise ValueError("every clip's gate must have the clip's length")
+        frames = [-(-T // hop) for T in lengths]
+        fbases = [0]
+        for n in frames[:-1]:
+            fbases.append(fbases[-1] + n)
+        out = torch.empty(nb1 * sum(frames), dtype=torch.float32, device=net.device)
+        for wins in plan(lengths, window, net.cfg, max_windows):
+            W, L = len(wins), wins[0].length
+            xw = gather(net, packed, wins, bases)
+            gw = None if gpacked is None else gather(net, gpacked, wins, bases).view(W, L)
+            fs = net.detector_frame_sums(xw, gw, gate_thr, precision)
+            desc = torch.tensor(frame_scatter_desc(wins, fbases, frames, hop, nb1), dtype=torch.int64).to(net.device)
+            _lib.check(net._lib.wv_window_scatter(fs.data_ptr(), desc.data_ptr(), out.data_ptr(), out.numel(), W, nb1, fs.shape[2], _lib.stream()),
+                       "wv_window_scatter")
+        if as_batch:
+            return out.view(len(lengths), nb1, frames[0])
+        return [out[nb1 * f0: nb1 * (f0 + n)].view(nb1, n) for f0, n in zip(fbases, frames)]
