@@ -590,6 +590,23 @@ size_t wv_metrics_sisnr_workspace_bytes(int B, int T);
 int wv_metrics_sisnr(const float* estimate, const float* reference, int B, int T, double eps, double* sisnr, double* moments, void* workspace,
                      size_t workspace_bytes, void* stream);
 
+/* ==== csrc/wv_stoi.hip: STOI per clip (Taal et al. 2011, non-extended; the algorithm and its constants in waveverify_amd/stoi.py) ----
+ * reference (the CLEAN clip: the silent frames are its, and the measure is not symmetric) and estimate [B,1,T], device pointers on any
+ * 4-byte boundary.  Both go to 10 kHz through wv_fx_resample with `kernels` [up][L] (orig = down, nw = up, L, width as documented there;
+ * stoi.resample_kernels builds the table of Octave's `resample` filter); kernels = NULL with up == down means the clips are at 10 kHz.
+ * basis: [256][512] float followed by 256 window samples (stoi.dft_basis: bins 7..218 of the 512-point DFT, re / im interleaved, the Hann
+ * window folded in, zero rows behind), built on the host in float64 and kept by the caller.  Outputs, every element written:
+ *   stoi     [B] double, 8-byte aligned: d, or 1e-5 where fewer than 30 frames are left
+ *   frames   [B][2] int32: frames kept, frames of the 10 kHz clip (F = ceil((ceil(T up / down) - 256) / 128), 0 under 257 samples)
+ *   kept_idx optional [B][F] int32: the kept frames' indices ascending, then -1
+ *   tob      optional [B][2][15][F - 1] float: third-octave magnitudes of reference and estimate, zeros behind a clip's kept - 1 frames
+ * NULL = not written.  Sums run in fixed orders without atomics (frame energies, band sums and the correlation in f64; the DFT as an
+ * f32 fmaf chain on the matrix pipe): two runs are bit-equal and a clip's numbers do not depend on its batch.  B <= 65535. */
+size_t wv_metrics_stoi_workspace_bytes(int B, int T, int up, int down, int L, int width);
+int wv_metrics_stoi(const float* reference, const float* estimate, int B, int T, const float* kernels, int up, int down, int L, int width,
+                    const float* basis, double* stoi, int* frames, int* kept_idx, float* tob, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* ==== csrc/wv_aug.hip: temporal augmentations of the training step ------------------------------------
  * One bandwidth-bound pass that replaces the reference's per-clip / per-segment Python loops and its GPU->CPU->GPU
  * hop (model/watermarking.py:487-519,540).  All pointers are DEVICE pointers, tensors [B,C,T] contiguous f32.

@@ -178,6 +178,8 @@ SIGNATURES = {
     "wv_metrics_iou": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_size_t, _VP]),
     "wv_metrics_sisnr_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "wv_metrics_sisnr": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "wv_metrics_stoi_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
+    "wv_metrics_stoi": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP] + [C.c_int] * 4 + [_VP] * 6 + [C.c_size_t, _VP]),
     "wv_aug_localize_sequence": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                            _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_aug_backward": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),

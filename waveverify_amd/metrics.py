@@ -10,6 +10,7 @@ Per-clip forms for a validation pass, fused on the GPU (csrc/wv_metrics.hip), on
     errors, valid, avg = ber_per_clip(logits, bits, mask)      # BER of the batch = errors.sum() / valid.sum()
     miou = miou_per_clip(locator_out, mask)                    # [B] float64, from iou_counts(...) -> [B,4] int32
     sisnr = SISNR()(estimate, reference)                       # [B] float64 dB; SISNR().mean(...) is the reference's scalar
+    stoi = STOI()(estimate, reference, sample_rate=16000)      # [B] float64 (csrc/wv_stoi.hip; the algorithm in stoi.py)
 
 Device tensors go through the kernels; CPU tensors take a torch route with the same arithmetic (f64 sums, then the reference's f32
 finish for the bit decision), so host-only callers need no GPU.  `BER` and `MIOU` above stay the reference's own formulation.
@@ -197,3 +198,55 @@ class SISNR:
 
     def mean(self, estimates: torch.Tensor, references: torch.Tensor) -> torch.Tensor:
         return self(estimates, references).mean()
+
+
+class STOI:
+    """Short-time objective intelligibility (Taal et al. 2011), per clip, the third number next to BER / mIoU and SI-SNR the reference
+    reports on a validation batch (scripts/evaluate.py:65-144, there through the pystoi package, clip by clip on the host).  The
+    algorithm, its constants and the frame-range switch are in waveverify_amd/stoi.py; parity with an installed `pystoi` stays unpinned.
+
+        STOI()(estimates, references, sample_rate=16000) -> [B] float64 on the inputs' device
+
+    in the reference's own argument order: the REFERENCE clip is the algorithm's x (its silent frames are the ones dropped) and the
+    measure is not symmetric.  `.mean(...)` is the scalar the reference's module returns; `.last_frames` ([B,2] int32) holds the frames
+    kept and the frames of each clip.  A clip left with fewer than 30 frames gives 1e-5, pystoi's answer; the CPU route also raises pystoi's
+    RuntimeWarning, the device route does not (it would cost a trip to the host: `last_frames` says which clips, and validate() warns
+    from the copy it makes anyway).  Device tensors go through csrc/wv_stoi.hip (one call; tables cached per sample rate and device),
+    CPU tensors through the float64 numpy route."""
+
+    def __init__(self, extended: bool = False):
+        if extended:
+            raise NotImplementedError("extended STOI is not implemented")
+        self.last_frames: Optional[torch.Tensor] = None
+
+    def __call__(self, estimates: torch.Tensor, references: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        import warnings
+        from . import stoi as S
+        if estimates.shape != references.shape or estimates.dim() != 3 or estimates.shape[1] != 1:
+            raise ValueError(f"estimates and references must both be [B, 1, T], got {tuple(estimates.shape)} and {tuple(references.shape)}")
+        if int(sample_rate) < 1:
+            raise ValueError(f"sample_rate must be positive, got {sample_rate}")
+        B, _, T = estimates.shape
+        x = _f32(references)
+        y = _f32(estimates).to(x.device)
+        if x.is_cuda:
+            lib = _lib.load()
+            kern, up, down, L, width, basis = S.device_tables(sample_rate, x.device)
+            out = torch.empty(B, dtype=torch.float64, device=x.device)
+            frames = torch.empty(B, 2, dtype=torch.int32, device=x.device)
+            ws = _lib.scratch(int(lib.wv_metrics_stoi_workspace_bytes(B, T, up, down, L, width)), x.device)
+            _lib.check(lib.wv_metrics_stoi(x.data_ptr(), y.data_ptr(), B, T, _lib.ptr(kern), up, down, L, width, basis.data_ptr(), out.data_ptr(),
+                                           frames.data_ptr(), None, None, ws.data_ptr(), ws.numel(), _lib.stream(x.device)), "wv_metrics_stoi")
+            self.last_frames = frames
+            short = None                                        # known on the device only: no trip to the host for a warning
+        else:
+            res = [S.stoi_numpy(x[b, 0].numpy(), y[b, 0].numpy(), int(sample_rate)) for b in range(B)]
+            out = torch.tensor([r[0] for r in res], dtype=torch.float64)
+            self.last_frames = torch.tensor([[r[1], r[2]] for r in res], dtype=torch.int32).reshape(B, 2)
+            short = any(r[1] - 1 < S.N_SEG for r in res)
+        if short:
+            warnings.warn(S.SHORT_MESSAGE, RuntimeWarning)
+        return out
+
+    def mean(self, estimates: torch.Tensor, references: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        return self(estimates, references, sample_rate).mean()

@@ -1278,7 +1278,7 @@ class WatermarkTrainer:
             out["stft/loss"], out["mel/loss"] = stft, mel
         return out
 
-    def validate(self, x: torch.Tensor, msg: torch.Tensor, eval_effects=None, augment: bool = True, seed: int = 0):
+    def validate(self, x: torch.Tensor, msg: torch.Tensor, eval_effects=None, augment: bool = True, seed: int = 0, stoi: bool = False):
         """The reference's validation pass for the terms that live on this path (model/watermarking.py:443-483 `_forward_valid`,
         :755-809 `_evaluate_single_effect`, scripts/train.py:956-1091 `val_loop`), without a gradient:
 
@@ -1292,8 +1292,13 @@ class WatermarkTrainer:
         counts); "per_clip": {"effects": names, "errors", "valid": [E,B] int, "ber", "miou": [E,B] float64 (BER nan where a clip
         has no valid bit), "sisnr": [B] float64}}.  Losses are device tensors like step()'s; the metrics are host numbers.
 
-        Absent on purpose: STOI and PESQ, which the reference takes from the pystoi and pesq packages (arithmetic this project does
-        not have), and the adversarial terms (no discriminator on this path).
+        With stoi=True the result gains "STOI", the batch mean of metrics.STOI of the watermarked clips against the originals at the
+        augmenter's sample rate (the reference's other imperceptibility number, scripts/train.py:1081), and per_clip gains "stoi": [B]
+        float64; a clip too short for it gives pystoi's 1e-5 and RuntimeWarning.  The default leaves the result key for key as it was.
+
+        Absent on purpose: PESQ, which the reference takes from the pesq package (ITU arithmetic this project does not restate), and
+        the adversarial terms (no discriminator on this path).  STOI is this project's restatement of the published algorithm (stoi.py):
+        parity with an installed `pystoi` stays unpinned.
 
         The trainer is left as it was found: no gradient, all-reduce or optimizer step; the effect scheduler is neither asked nor
         told; the augmentation is drawn by an augmenter of validate's own, and the random streams the draws and the noise effects
@@ -1350,8 +1355,16 @@ class WatermarkTrainer:
             if self.spectral is not None:
                 out["stft/loss"], out["mel/loss"], _ = self.spectral(wm, x, want_grad=False)
             sisnr = SISNR()(wm, x)
+            stoi_d = stoi_frames = None
+            if stoi:
+                from .metrics import STOI
+                stoi_metric = STOI()
+                stoi_d = stoi_metric(wm, x, sample_rate=self.aug.sample_rate)
+                stoi_frames = stoi_metric.last_frames
             # one trip to the host for every count of the pass
             errors, valid, counts, sisnr = (t.cpu().numpy() for t in (torch.stack(errors), torch.stack(valid), torch.stack(counts), sisnr))
+            if stoi:
+                stoi_d, stoi_frames = stoi_d.cpu().numpy(), stoi_frames.cpu().numpy()
         finally:
             np.random.set_state(rng[0])
             _random.setstate(rng[1])
@@ -1376,4 +1389,11 @@ class WatermarkTrainer:
         with np.errstate(invalid="ignore", divide="ignore"):
             ber = np.where(valid > 0, errors / np.where(valid > 0, valid, 1), np.nan)
         out["per_clip"] = {"effects": [n for n, _ in plan], "errors": errors, "valid": valid, "ber": ber, "miou": miou, "sisnr": sisnr}
+        if stoi:
+            from . import stoi as _stoi
+            if (stoi_frames[:, 0] - 1 < _stoi.N_SEG).any():
+                import warnings
+                warnings.warn(_stoi.SHORT_MESSAGE, RuntimeWarning)
+            out["STOI"] = float(stoi_d.mean())
+            out["per_clip"]["stoi"] = stoi_d
         return out
