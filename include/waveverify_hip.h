@@ -661,6 +661,24 @@ int wv_fx_resample_adjoint(const float* dy, const float* kernels, float* dx, int
  * Any 1 <= Tout <= (ceil(T / orig) + 1) * nw is served (the same formula, continued or cut short); a longer one is refused. */
 int wv_fx_resample(const float* x, const float* kernels, float* y, int rows, int T, int orig, int nw, int L, int width, int Tout, void* stream);
 
+/* ==== csrc/wv_native.hip: the two ends of the native-rate embed route ---------------------------------------------
+ * A file of C channels at its own rate goes to the model's 16 kHz mono, and the model's 16 kHz residual comes back onto every channel,
+ * one kernel each.  The resampler is wv_fx_resample's (orig : nw divided by their gcd, L = 2*width + orig, output m = n*nw + f reads inputs
+ * n*orig - width + j, j < L, zero outside the signal; one fmaf chain per output in ascending j from +0), but the table arrives TRANSPOSED:
+ * kernels_t [L][nw], kernels_t[j][f] = kernels[f][j].  orig = nw = L = 1, width = 0, kernels_t = {1} is the identity resampler.
+ * Planar device tensors on any 4-byte boundary.  Refused with nothing launched and nothing written: a null pointer, B outside [1, 65535],
+ * C outside [1, 64], a length, orig, nw or L below 1, width < 0, an output longer than (ceil(T_in / orig) + 1) * nw (T_in = Tn for the front
+ * end, T16 for the back end), or a ratio whose 256-output tile reads more than 64 KB of input: ((nw + 254) / nw) * orig + L > 16384 floats.
+ *   front end: x [B][C][Tn] -> y [B][Tout];  mono[s] = (x[b][0][s] + x[b][1][s] + ...) / (float)C, summed left to right in f32 and divided
+ *              exactly, formed on the way into the kernel's LDS window (no mono tensor is written);  y[b][m] = the chain over mono.
+ *   back end:  delta [B][T16], x and out [B][C][Tn];  u[b][m] = the chain over delta, once per m < Tn;  out[b][c][m] = x[b][c][m] +
+ *              gain * u[b][m] with both roundings kept (gain = 1 gives x + u).  out may be x: each element is read, then written, by the
+ *              same thread. */
+int wv_native_downmix_resample(const float* x, const float* kernels_t, float* y, int B, int C, int Tn, int orig, int nw, int L, int width, int Tout,
+                               void* stream);
+int wv_native_upsample_add(const float* x, const float* delta, const float* kernels_t, float* out, int B, int C, int T16, int Tn, int orig, int nw, int L,
+                           int width, float gain, void* stream);
+
 /* ==== csrc/wv_fx_time.hip: plain-arithmetic time-domain effects ----------------------------------------------------------------
  * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
  * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding

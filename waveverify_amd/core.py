@@ -17,13 +17,13 @@ from typing import Dict, List, Mapping, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import localize, ops, session, window
+from . import localize, native, ops, session, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
 from .localize import Segment
 from .nets import HipNet
-from .utils import load_audio, message_to_tensor, save_audio, tensor_to_message
+from .utils import load_audio, load_audio_native, message_to_tensor, save_audio, tensor_to_message
 from .watermark_id import WatermarkID
 
 logger = logging.getLogger(__name__)
@@ -116,6 +116,29 @@ class WaveVerify:
     def locate_batch(self, audio: torch.Tensor) -> torch.Tensor:
         """-> sigmoid(locator logits) [B, T]."""
         return torch.sigmoid(self._need("locator").locator(audio, precision=self.locator_precision)).squeeze(1)
+
+    # ------------------------------------------------------------------ native rate and channel count (NOT in the reference)
+    @torch.no_grad()
+    def to_model_rate(self, audio: torch.Tensor, sample_rate: int) -> torch.Tensor:
+        """audio [B,C,Tn] (or [C,Tn]) at `sample_rate` -> the model's input [B,1,T16]: the channel mean at 16 kHz, one kernel
+        (native.downmix_resample).  For one or two channels these are the bits load_audio gives for the same file."""
+        return native.downmix_resample(audio.to(self.device), sample_rate)
+
+    @torch.no_grad()
+    def embed_native_batch(self, audio: torch.Tensor, sample_rate: int, message: torch.Tensor, strength: float = 1.0,
+                           window_seconds: Optional[float] = None) -> torch.Tensor:
+        """audio [B,C,Tn] (or [C,Tn]) at `sample_rate`; message [B,16] or [1,16] -> watermarked [B,C,Tn] at the same rate: the generator
+        runs on to_model_rate(audio), its residual alone is resampled back to `sample_rate` and strength times it is added to every
+        channel (native.upsample_add).  window_seconds: run the 16 kHz copy as windows of that length.  What a detector later sees is
+        x16 + down(up(residual)), not x16 + residual: DESIGN.md section 7d-3."""
+        gen = self._need("generator")
+        audio = audio.to(self.device)
+        x16 = self.to_model_rate(audio, sample_rate)
+        if window_seconds is None:
+            delta = gen.generator(x16, message, add_input=False, precision=self.generator_precision)
+        else:
+            delta = window.windowed_generator(gen, x16, message, self._window_samples(window_seconds), self.generator_precision, add_input=False)
+        return native.upsample_add(audio, delta, sample_rate, strength)
 
     # ------------------------------------------------------------------ localized detection (NOT in the reference's package API)
     def _gate(self, audio, threshold: float, gate):
@@ -252,11 +275,23 @@ class WaveVerify:
 
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],
-              output_path: Optional[Union[str, Path]] = None, *,
+              output_path: Optional[Union[str, Path]] = None, *, native: bool = False, strength: float = 1.0,
               window_seconds: Optional[float] = None) -> Tuple[np.ndarray, int, WatermarkID]:
-        """window_seconds (NOT in the reference): run the clip as windows of that length; None = one whole-clip forward."""
+        """window_seconds (NOT in the reference): run the clip as windows of that length; None = one whole-clip forward.
+        native (NOT in the reference): keep the file's own sample rate and channels (embed_native_batch) -> (array [C, Tn], or [Tn] for a
+        mono file; the file's sample rate; id), every channel saved at that rate.  strength scales the residual; it needs native."""
+        if not native and strength != 1.0:
+            raise ValueError("strength other than 1.0 needs native=True (the reference's route adds the residual as it is)")
         try:
             watermark_id = self._validate_watermark_id(watermark_id)
+            if native:
+                audio, sr = load_audio_native(audio_path)                           # [C, Tn] at the file's rate
+                msg = message_to_tensor(watermark_id.to_bits(), self.watermark_bits)
+                wm = self.embed_native_batch(audio.unsqueeze(0), sr, msg, strength, window_seconds).squeeze(0)
+                if output_path:
+                    save_audio(wm, output_path, sr)
+                out = wm.cpu().numpy()
+                return (out[0] if out.shape[0] == 1 else out), sr, watermark_id
             audio, _ = load_audio(audio_path, self.sample_rate)
             msg = message_to_tensor(watermark_id.to_bits(), self.watermark_bits)
             if window_seconds is None:

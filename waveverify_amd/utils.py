@@ -62,9 +62,8 @@ def _read_wav(path: Path) -> Tuple[np.ndarray, int]:
     return x[: n * ch].reshape(n, ch).T.copy(), sr            # [channels, samples]
 
 
-def load_audio(audio_path: Union[str, Path], target_sr: int = DEFAULT_SAMPLE_RATE
-               ) -> Tuple[torch.Tensor, int]:
-    """-> (waveform [1, T] float32, sample_rate); mono mix-down, resample to target_sr."""
+def _decode(audio_path: Union[str, Path]) -> Tuple[torch.Tensor, int]:
+    """-> (waveform [C, T] as the container holds it, sample_rate): the decoding and the errors load_audio and load_audio_native share."""
     audio_path = Path(audio_path)
     if not audio_path.exists():
         raise FileNotFoundError(f"Audio file not found: {audio_path}")
@@ -81,6 +80,20 @@ def load_audio(audio_path: Union[str, Path], target_sr: int = DEFAULT_SAMPLE_RAT
             waveform, sr = torchaudio.load(str(audio_path))
     except Exception as e:
         raise RuntimeError(f"Cannot load audio file: {str(e)}")
+    return waveform, sr
+
+
+def load_audio_native(audio_path: Union[str, Path]) -> Tuple[torch.Tensor, int]:
+    """NOT in the reference: -> (waveform [C, Tn] float32, the file's own sample_rate); load_audio's decoding and errors without the
+    mix-down and without the resample (the native-rate embed route does both on the GPU, waveverify_amd/native.py)."""
+    waveform, sr = _decode(audio_path)
+    return waveform.float(), int(sr)
+
+
+def load_audio(audio_path: Union[str, Path], target_sr: int = DEFAULT_SAMPLE_RATE
+               ) -> Tuple[torch.Tensor, int]:
+    """-> (waveform [1, T] float32, sample_rate); mono mix-down, resample to target_sr."""
+    waveform, sr = _decode(audio_path)
     if waveform.shape[0] > 1:
         waveform = torch.mean(waveform, dim=0, keepdim=True)
     if sr != target_sr:

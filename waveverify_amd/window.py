@@ -180,9 +180,10 @@ def _run(net, clips, window, max_windows, fwd, C_=1):
         return _unpack(out, lengths, bases, as_batch, C_)
 
 
-def windowed_generator(net, clips, msg, window: int = 480000, precision: str = "f32", max_windows: int = 64):
+def windowed_generator(net, clips, msg, window: int = 480000, precision: str = "f32", max_windows: int = 64, add_input: bool = True):
     """Watermarked audio G(x, msg) + x of every clip, windowed.  clips: a list of 1-D device tensors of any lengths (-> a list
-    of 1-D tensors) or [B,1,T] (-> [B,1,T]); msg [B|1, 16]: each window uses its clip's row."""
+    of 1-D tensors) or [B,1,T] (-> [B,1,T]); msg [B|1, 16]: each window uses its clip's row.  add_input=False: the residual
+    G(x, msg) alone (what the native-rate route brings back up to the file's rate)."""
     torch = _torch()
     msg = msg.to(net.device).float()
     if msg.dim() == 1:
@@ -190,7 +191,7 @@ def windowed_generator(net, clips, msg, window: int = 480000, precision: str = "
 
     def fwd(xw, wins):
         rows = torch.tensor([w.clip % msg.shape[0] for w in wins], dtype=torch.int64, device=net.device)
-        return net.generator(xw, msg.index_select(0, rows).contiguous(), add_input=True, precision=precision)
+        return net.generator(xw, msg.index_select(0, rows).contiguous(), add_input=add_input, precision=precision)
     return _run(net, clips, window, max_windows, fwd)
 
 
