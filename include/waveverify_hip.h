@@ -302,27 +302,31 @@ int wv_op_head_frames(const float* Z, const float* w_rev, const float* b_rev, co
  *                     Yf32 [B,M,Tout] f32 row-major (any of them NULL).
  *   wv_h16_spec_block whole SpecBlock in one launch (seanet.py:463-511): the STFT on the f16 pipe with the waveform split in two f16 terms,
  *                     log-magnitude, the 1x1 and the add; the spectrogram stays in LDS.  Every row of the basis is applied (sin_0 and
- *                     sin_{F-1} in f32 beside the matrix product).  (n_fft, hop) in {(64,1),(128,2),(256,8),(512,40),(1024,320)} with
- *                     M = n_fft (generator / detector scales) or {(64,1),(128,4),(256,32)} with M = n_fft / 2 (the locator's), else
- *                     WV_EINVAL; x16 / Y16 / Yact16 c8 f16 [B, M/8, ceil(T/hop), 8]
+ *                     sin_{F-1} in f32 beside the matrix product).  (n_fft, hop, M) a row of WV_SPEC16_ROWS (csrc/wv_kernels.h):
+ *                     (64,1),(128,2),(256,8),(512,40),(1024,320) with M = n_fft (generator / detector scales), (64,1),(128,4),(256,32)
+ *                     with M = n_fft / 2 (the locator's), else WV_EINVAL; x16 / Y16 / Yact16 c8 f16 [B, M/8, ceil(T/hop), 8]
+ *   The three forwards below walk a plan that wv_model_finalize decides once from the coverage predicates of csrc/wv_kernels.h: a plan
+ *   exists when k = 5, dilation 1, every encoder stage is whole 8-channel groups and its ResnetBlocks an rh16_width (else WV_ESTATE);
+ *   a SpecBlock / spec_post runs in one launch where spec16_scale holds (a row of WV_SPEC16_ROWS; spec_post: one marked `post`), else,
+ *   or when the launcher refuses a limit of the call, as the exact STFT kernel + the 1x1 on the f16 pipe.
  *   wv_detector_forward_f16   Detector.forward (model/detector.py:366-391) in this mode: conv_pre, the ResnetBlocks, the SpecBlocks
  *                     (STFT as a split-f16 matrix product) incl. spec_post and the downsample units on the f16 pipe; with logits == NULL
- *                     (mean probabilities only) conv_post and the head as well, otherwise those two by the exact path's f32 kernels.
- *                     Same arguments and workspace as wv_detector_forward; WV_ESTATE for a model without an f16 plan.
+ *                     (mean probabilities only) and head16_covers(dimension, nbits, hop) conv_post and the head as well, otherwise
+ *                     those two by the exact path's f32 kernels.  Same arguments and workspace as wv_detector_forward.
  *   wv_locator_forward_f16    Locator.forward (model/locator.py:268-299) in this mode: the encoder stages on the f16 pipe (32- and
  *                     64-channel ResnetBlocks, composed downsample convs).  Its SpecBlocks (n_fft = 2 C at every scale) and spec_post
  *                     (256 points, hop 32, 128 channels) each run as ONE fused launch on the f16 pipe: the STFT as a split-f16
  *                     matrix product, NOT the exact path's f32 STFT kernel, with the basis rows sin_0 and sin_{F-1} applied in f32
- *                     beside it; a scale the fused kernel does not serve falls back to the exact STFT kernel + the 1x1 on the f16
- *                     pipe.  conv_post and the head run on the exact f32 kernels (the locator always returns logits).  Arguments of
- *                     wv_locator_forward.
+ *                     beside it; a scale outside WV_SPEC16_ROWS runs the exact STFT kernel + the 1x1 on the f16 pipe.  conv_post
+ *                     and the head run on the exact f32 kernels (the locator always returns logits).  Arguments of wv_locator_forward.
  *   wv_generator_forward_f16  Generator.forward (model/generator.py:360-423; modules/seanet.py:883-976, 1067-1226) in this mode: the
  *                     encoder as above with FiLM in the downsample convs' epilogues, conv_post as one composed conv, L2Norm, then
  *                     the decoder: first conv pair as one composed conv, every upsample unit (ELU -> depth-wise ConvTranspose1d ->
  *                     1x1, seanet.py:1147-1170) as ONE two-tap conv over (phase, channel) rows, ResnetBlocks of 768 / 384 / 192 / 96
  *                     channels in one launch each, the tail (f32 sums, tanh, + x) on the c8 stream.  Message MLP / FiLM scalars in f32.
- *                     Arguments and workspace of wv_generator_forward; WV_ESTATE for a model without an f16 plan; B <= 65535 (the tail's
- *                     launch grid, wv_h16_tail's limit too).
+ *                     Arguments and workspace of wv_generator_forward; WV_ESTATE also without a decoder plan (dimension % 16 == 0,
+ *                     tail16_taps(last_kernel_size), stages of whole 16-channel group pairs and, with ResnetBlocks, an rh16_width);
+ *                     B <= 65535 (the tail's launch grid, wv_h16_tail's limit too).
  *   wv_h16_upsample   the decoder's upsample unit as that conv: x16 = the PRE-ACTIVATED input c8 [B, K/8, Tin, 8]; w_ct [K,1,2r], w_pw
  *                     [M,K,1], bias [M] HOST; Y16 / Yact16 c8 [B, M/8, Tin*r, 8] (either may be NULL)
  *   wv_h16_tail       decoder tail on the pre-activated c8 stream: out[B,1,T] = tanh(out_scale * (b + Conv1d(C -> 1, ks)(a16))) (+ x)
@@ -331,8 +335,8 @@ int wv_op_head_frames(const float* Z, const float* w_rev, const float* b_rev, co
  *                     composed head GEMM against f16(wc) (wc [D][nb*hop] HOST, column bit*hop + j; bc [nb] HOST: the exact path's
  *                     ConvTranspose1d(k = s = hop) -> Conv1d(O -> nb, 1) composition), sigmoid, and over t < T (t = frame*hop + j) either
  *                     mean_prob [B,nb] = the mean, or -- keep_lo / keep_hi [B] int32 DEVICE, psum [B,nb] -- psum = the sum over
- *                     t in [keep_lo[b], keep_hi[b]) (mean_prob NULL).  Fr = ceil(T / hop); D % 16 == 0, D <= 128, nb % 4 == 0,
- *                     nb <= 32, hop % 32 == 0, else WV_EINVAL
+ *                     t in [keep_lo[b], keep_hi[b]) (mean_prob NULL).  Fr = ceil(T / hop); head16_covers: D % 16 == 0, D <= 128,
+ *                     nb % 4 == 0, nb <= 32, hop % 32 == 0, else WV_EINVAL
  *   wv_h16_head_frames  wv_h16_head in the gated per-frame form of wv_detector_forward_frames_f16: gate [B,T] DEVICE or NULL, fsum
  *                     [B, nb + 1, Fr] DEVICE; a frame's sum is taken by the lane that owns it plus one cross-half add.  wv_h16_head's
  *                     limits and hop <= 2016, else WV_EINVAL

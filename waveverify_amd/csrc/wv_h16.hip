@@ -1570,7 +1570,7 @@ __global__ __launch_bounds__(256) void tail16_kernel(const h16* __restrict__ A, 
 }  // namespace
 
 bool rh_supported(const RhArgs& a) {
-    if (!(a.C == 32 || a.C == 64 || a.C == 96 || a.C == 128 || a.C == 192 || a.C == 256 || a.C == 384 || a.C == 512 || a.C == 768)) return false;
+    if (!rh16_width(a.C)) return false;
     if (!a.X || (!a.Y && !a.Yact) || a.T < 1 || a.B < 1 || !a.w1.wq || !a.w2.wq || !a.tab1 || !a.tab2) return false;
     if (a.w1.M != a.C || a.w1.K != a.C || a.w2.M != a.C || a.w2.K != a.C || a.w1.Mp != a.C || a.w2.Mp != a.C || a.w1.Kp != a.C || a.w2.Kp != a.C) return false;
     if ((long long)a.C * a.T * 2 >= H_OOB) return false;
@@ -1679,21 +1679,13 @@ hipError_t launch_conv16(const Conv16Args& a, hipStream_t s) {
 hipError_t launch_spec16(const Spec16Args& a, hipStream_t s) {
     if (!a.wav || !a.side || !a.resid || (!a.Y && !a.Yact && !a.Yf32) || !a.cosw.wq || !a.sinw.wq || !a.cosl.wq || !a.sinl.wq || !a.pw.wq || a.B < 1 || a.T < 1) return hipErrorInvalidValue;
     const int N = a.n_fft, M = a.pw.M;
-    if (a.Tf != (a.T + a.hop - 1) / a.hop || (M != N && 2 * M != N) || a.pw.K != N / 2 + 1 || a.pw.Mp != M || a.pw.Kp != N / 2 + 16 || a.cosw.M != N / 2 || a.cosw.K != N ||
+    if (a.Tf != (a.T + a.hop - 1) / a.hop || a.pw.K != N / 2 + 1 || a.pw.Mp != M || a.pw.Kp != N / 2 + 16 || a.cosw.M != N / 2 || a.cosw.K != N ||
         a.sinw.M != N / 2 || a.sinw.K != N || a.cosw.Mp != N / 2 || a.sinw.Mp != N / 2 || a.cosw.nchunks < N / 16 || a.sinw.nchunks < N / 16 || a.cosl.nchunks < N / 16 || a.sinl.nchunks < N / 16)
         return hipErrorNotSupported;
     if ((long long)M * a.Tf * 2 >= H_OOB || !al16(a.resid) || (a.Y && !al16(a.Y)) || (a.Yact && !al16(a.Yact))) return hipErrorNotSupported;
-    if (M == N) {                                               // generator / detector scales
-        if (N == 64 && a.hop == 1) return spec16_launch<SP<64, 1>>(a, s);
-        if (N == 128 && a.hop == 2) return spec16_launch<SP<128, 2>>(a, s);
-        if (N == 256 && a.hop == 8) return spec16_launch<SP<256, 8>>(a, s);
-        if (N == 512 && a.hop == 40) return spec16_launch<SP<512, 40>>(a, s);
-        if (N == 1024 && a.hop == 320) return spec16_launch<SP<1024, 320>>(a, s);
-    } else {                                                    // the locator's: half as many channels as DFT points
-        if (N == 64 && a.hop == 1) return spec16_launch<SP<64, 1, 32>>(a, s);
-        if (N == 128 && a.hop == 4) return spec16_launch<SP<128, 4, 64>>(a, s);
-        if (N == 256 && a.hop == 32) return spec16_launch<SP<256, 32, 128>>(a, s);
-    }
+#define WV_SPEC16_GO(N_, H_, M_, P_) if (N == N_ && a.hop == H_ && M == M_) return spec16_launch<SP<N_, H_, M_>>(a, s);
+    WV_SPEC16_ROWS(WV_SPEC16_GO)
+#undef WV_SPEC16_GO
     return hipErrorNotSupported;
 }
 
@@ -1702,7 +1694,7 @@ hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, fl
     const bool win = keep_lo || keep_hi || psum;
     if (win && (!keep_lo || !keep_hi || !psum || mean_prob)) return hipErrorInvalidValue;
     if (!Y || !w.wq || !bc || (!mean_prob && !win) || B < 1 || Fr < 1 || T < 1) return hipErrorInvalidValue;
-    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
+    if (!head16_covers(D, nb, hop, false) || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
     prof::Scope ps(s, "head16", 2.0 * B * D * (double)nb * hop * Fr, (double)B * (4.0 * D * Fr + 4.0 * nb));
     Head16Args a{Y, w, bc, mean_prob, B, D, nb, hop, Fr, T, keep_lo, keep_hi, psum};
     if (win) hipLaunchKernelGGL(head16_kernel<true>, dim3((unsigned)B), dim3(256), 0, s, a);
@@ -1714,7 +1706,7 @@ hipError_t launch_head16_frames(const float* Y, const H16Weight& w, const float*
                                 int Fr, int T, hipStream_t s) {
     if (!Y || !w.wq || !bc || !fsum || B < 1 || B > 65535 || Fr < 1 || T < 1 || hop < 1) return hipErrorInvalidValue;
     if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return hipErrorInvalidValue;                    // Fr = ceil(T / hop)
-    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || hop > 2016 || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
+    if (!head16_covers(D, nb, hop, true) || w.M != nb * hop || w.K != D || w.Kp != D || w.Mp != nb * hop || w.nchunks < D / 16) return hipErrorNotSupported;
     prof::Scope ps(s, "head16_frames", 2.0 * B * D * (double)nb * hop * Fr, (double)B * (4.0 * D * Fr + 4.0 * (nb + 1) * Fr + (gate ? 4.0 * T : 0.0)));
     Head16FramesArgs a{Y, w, bc, gate, gate_thr, fsum, B, D, nb, hop, Fr, T};
     hipLaunchKernelGGL(head16_frames_kernel, dim3((unsigned)((Fr + 63) / 64), (unsigned)B), dim3(256), (size_t)(hop / 32) * 64 * sizeof(uint32_t), s, a);
@@ -1749,7 +1741,7 @@ hipError_t launch_l2norm_c8(const float* X, void* Y, int B, int D, int Fr, hipSt
 hipError_t launch_tail16(const void* A16, const float* w, const float* bias, const float* x, float* out, int B, int C, int Tin, int T, int ks, float out_scale,
                          hipStream_t s) {
     if (!A16 || !w || !out || B < 1 || B > 65535 || C < 8 || (C % 8) || Tin < 1 || T < 1 || T > Tin) return hipErrorInvalidValue;
-    if (ks != 5 && ks != 7 && ks != 3) return hipErrorNotSupported;
+    if (!tail16_taps(ks)) return hipErrorNotSupported;
     prof::Scope ps(s, "tail16", 2.0 * B * C * ks * (double)T, (double)B * (2.0 * C * Tin + 8.0 * T));
     const dim3 grid((T + 255) / 256, B);
     const h16* A = reinterpret_cast<const h16*>(A16);

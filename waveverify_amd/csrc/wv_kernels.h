@@ -148,7 +148,7 @@ inline std::vector<uint16_t> pack_head16(const float* wc, int D, int nb, int hop
         for (int r = 0; r < rows; ++r) wt[(size_t)r * D + d] = wc[(size_t)d * rows + r];
     return pack_h16(wt.data(), nullptr, rows, D, 1, out);
 }
-// whole ResnetBlock, c8 f16 in / out (C in {32, 64, 96, 128, 192, 256, 384, 512, 768}, k = 5, dilation 1).  The kernel keeps both
+// whole ResnetBlock, c8 f16 in / out (C in rh16_width, k = 5, dilation 1).  The kernel keeps both
 // activations times log2(e) (one instruction less per ELU, wv_h16.hip elu_l2), so the operands arrive pre-scaled -- pack_rh_pw /
 // pack_rh_table: w1, w2 = the 1x1 weights DIVIDED by log2(e); tab1 = the first stencil's taps and bias TIMES log2(e)
 // (pack_rh_table(.., RH_LOG2E)); tab2 plain (pack_rh_table(.., 1.0)); both tables in the kernel's channel-pair layout.
@@ -173,6 +173,7 @@ inline std::vector<float> pack_rh_table(const float* dw_w, const float* dw_b, in
     }
     return t;
 }
+inline bool rh16_width(int C) { return C == 32 || C == 64 || C == 96 || C == 128 || C == 192 || C == 256 || C == 384 || C == 512 || C == 768; }   // the widths rh_kernel is built for
 bool rh_supported(const RhArgs& a);
 hipError_t launch_resblock16(const RhArgs& a, hipStream_t s);
 struct Conv16Args {           // y = out_scale * (bias + conv(x)) + resid; x, resid, Y, Yact c8 f16; Yf32 [B][M][Tout] f32 row-major
@@ -217,8 +218,18 @@ hipError_t launch_conv16(const Conv16Args& a, hipStream_t s);
 // whole SpecBlock (STFT on the f16 pipe with a two-term split of the waveform -> log-magnitude -> 1x1 -> + x), the spectrogram stays in LDS.
 // cosw / sinw: the basis' cos rows f = 0 .. n_fft/2 - 1 and sin rows (row 0 = the Nyquist bin's cos row) as A fragments (pack_stft16);
 // side: the two sin rows that leaves out, sin_0 and sin_{F-1}, f32 [2][n_fft] (as StftArgs::side / pack_stft_basis), applied in f32.
-// pw: the 1x1 [M][F] with K padded to n_fft/2 + 16.  (n_fft, hop, M) in {(64,1), (128,2), (256,8), (512,40), (1024,320)} with M = n_fft and
-// {(64,1), (128,4), (256,32)} with M = n_fft / 2, else hipErrorNotSupported.
+// pw: the 1x1 [M][F] with K padded to n_fft/2 + 16.  The geometries are the rows of WV_SPEC16_ROWS, else hipErrorNotSupported.
+// X(n_fft, hop, channels, post): one spec16_kernel instantiation per row -- the default generator's / detector's five scales (as many
+// channels as DFT points) and the default locator's three (half as many).  post = 1: the row may also serve spec_post (its f32 / ELU(x')
+// outputs; the two default nets' last scales, the only ones the tests pin in that role).
+#define WV_SPEC16_ROWS(X) \
+    X(64, 1, 64, 0) X(128, 2, 128, 0) X(256, 8, 256, 0) X(512, 40, 512, 0) X(1024, 320, 1024, 1) X(64, 1, 32, 0) X(128, 4, 64, 0) X(256, 32, 128, 1)
+inline bool spec16_scale(int n_fft, int hop, int C, bool post) {   // is (n_fft, hop, C) one of launch_spec16's, for a stage or for spec_post?
+#define WV_SPEC16_HIT(N, H, M, P) if (n_fft == N && hop == H && C == M) return P || !post;
+    WV_SPEC16_ROWS(WV_SPEC16_HIT)
+#undef WV_SPEC16_HIT
+    return false;
+}
 struct Spec16Args {
     const float* wav; H16Weight cosw, sinw, cosl, sinl, pw; const void* resid; void* Y; void* Yact;   // cosl / sinl: (basis - f16(basis)) * 2^11
     const float* side;    // [2][n_fft] f32: sin_0 row, sin_{F-1} row
@@ -255,11 +266,15 @@ inline void pack_stft16(const float* basis, int n_fft, std::vector<uint16_t> (&q
     for (int k = 0; k < 4; ++k) q[k] = pack_h16(m[k].data(), nullptr, R, n_fft, 1, &w[k]);
 }
 // detector head, mean-probability output only: L2Norm over channels of Y [B][D][Fr] (f32), composed head GEMM (w: [nb * hop][D] as A
-// fragments), sigmoid, mean over time.  hipErrorNotSupported outside D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0.
+// fragments), sigmoid, mean over time.  hipErrorNotSupported outside head16_covers(D, nb, hop, false).
+// The head's shape limits; frames: the gated per-frame form, whose gate bits of a 64-frame tile lie in LDS beside the latent tile.
+// oracle/wv_oracle_h16.py head16_gate restates this for the tests: keep the two in step.
+inline bool head16_covers(int D, int nb, int hop, bool frames) {
+    return D % 16 == 0 && D <= 128 && nb % 4 == 0 && nb <= 32 && hop % 32 == 0 && (!frames || hop <= 2016);
+}
 hipError_t launch_head16(const float* Y, const H16Weight& w, const float* bc, float* mean_prob, int B, int D, int nb, int hop, int Fr, int T, hipStream_t s,
                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr);
-// the same head in the gated per-frame form of HeadFramesArgs: fsum [B][nb + 1][Fr], gate [B][T] or null.  launch_head16's limits, and
-// hop <= 2016 (the gate bits of a 64-frame tile lie in LDS beside the latent tile).
+// the same head in the gated per-frame form of HeadFramesArgs: fsum [B][nb + 1][Fr], gate [B][T] or null.  head16_covers(D, nb, hop, true).
 hipError_t launch_head16_frames(const float* Y, const H16Weight& w, const float* bc, const float* gate, float gate_thr, float* fsum, int B, int D, int nb, int hop,
                                 int Fr, int T, hipStream_t s);
 hipError_t launch_conv_pre16(const float* x, const float* w, const float* bias, void* Y, int B, int C, int T, int ks, float in_scale, hipStream_t s);
@@ -267,6 +282,7 @@ hipError_t launch_f32_to_c8(const float* X, void* Y, int B, int C, int T, float 
 // L2Norm over channels (seanet.py:288-318: y / max(||y||, 1e-12) * sqrt(D)) of a latent [B][D][Fr] f32 -> c8 f16 (the f16 decoder's input)
 hipError_t launch_l2norm_c8(const float* X, void* Y, int B, int D, int Fr, hipStream_t s);
 // decoder tail on a PRE-ACTIVATED c8 f16 input: out = tanh(out_scale * (b + conv_{C -> 1, ks}(a))) (+ x), first T samples (seanet.py:1177-1202)
+inline bool tail16_taps(int ks) { return ks == 3 || ks == 5 || ks == 7; }   // the kernel sizes tail16_kernel is built for, else hipErrorNotSupported
 hipError_t launch_tail16(const void* A16, const float* w, const float* bias, const float* x, float* out, int B, int C, int Tin, int T, int ks, float out_scale, hipStream_t s);
 hipError_t launch_c8_to_f32(const void* X, float* Y, int B, int C, int T, hipStream_t s);
 

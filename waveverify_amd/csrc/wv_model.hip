@@ -85,9 +85,19 @@ struct wv_model {
     // depth-wise conv composed into one [M][2r][K] conv -- and per decoder stage: the upsample unit as one 2-tap conv over (phase, channel)
     // rows (pack_up16) and its ResnetBlocks; the decoder's first conv pair as one composed conv
     struct H16Block { wv::H16Weight w1, w2; const float *tab1 = nullptr, *tab2 = nullptr; };
-    struct H16Stage { std::vector<H16Block> blocks; wv::H16Weight spec, down, cosw, sinw, cosl, sinl, post, head; };   // post / head: the last entry only (conv_post as one composed conv, the head GEMM)
+    // The plan is decided once, in pack_model, from the kernels' coverage predicates (wv_kernels.h); the forward calls read it.  The SpecBlock
+    // route of a stage or of spec_post: spec16 in one launch, or the exact STFT kernel, an f16 copy and the 1x1 + add as a k = 1 conv16.
+    // A launcher may still refuse a limit that depends on the call (buffer bytes, alignment): the walk then steps down one route, and
+    // spec_post, behind the second, hands over to the exact path.
+    enum SpecRoute { SPEC_ONE_LAUNCH, SPEC_STFT_1X1 };
+    struct H16Stage {
+        std::vector<H16Block> blocks;
+        wv::H16Weight spec, down, cosw, sinw, cosl, sinl, post, head;   // cos / sin: SPEC_ONE_LAUNCH only; post / head: the last entry only
+        SpecRoute route = SPEC_STFT_1X1;
+        bool head16 = false, head16_frames = false;   // last entry: head16_covers the net and `head` is packed (the frames form too)
+    };
     struct H16Up { wv::H16Weight up; int mb = 0; std::vector<H16Block> blocks; };
-    std::vector<H16Stage> h16;                    // n_strides stages; one more when spec_post runs on the f16 pipe too (only its spec / cos / sin / post / head members)
+    std::vector<H16Stage> h16;                    // empty = no f16 plan; else n_strides stages and one entry for spec_post -> conv_post -> head
     wv::H16Weight h16_dec_head;
     std::vector<H16Up> h16_ups;                   // generator only; empty = no f16 decoder plan
 
@@ -98,6 +108,9 @@ namespace {
 
 int hop_of(const wv_config& c) { int h = 1; for (int i = 0; i < c.n_strides; ++i) h *= c.strides[i]; return h; }
 int ratio_enc(const wv_config& c, int s) { return c.strides[c.n_strides - 1 - s]; }   // seanet.py:646
+std::string spec_prefix(const wv_config& c, int s) {                                  // SpecBlock of stage s; s == n_strides: spec_post
+    return s == c.n_strides ? std::string("encoder.spec_post") : "encoder.spec_blocks." + std::to_string(s);
+}
 
 void add(wv_model* m, const std::string& name, std::vector<int64_t> shape, bool wn, bool optional = false) {
     Param p; p.name = name; p.shape = std::move(shape); p.wn = wn; p.optional = optional;
@@ -214,9 +227,9 @@ struct Uploader {
         }
         return static_cast<const float*>(d);
     }
-    wv::H16Weight h16(const std::vector<float>& pw, const float* dw, int M, int K, int ks) {
+    wv::H16Weight h16(const std::vector<float>& pw, const float* dw, int M, int K, int ks, bool dw_by_k = false) {
         wv::H16Weight w;
-        const std::vector<uint16_t> q = wv::pack_h16(pw.data(), dw, M, K, ks, &w);
+        const std::vector<uint16_t> q = wv::pack_h16(pw.data(), dw, M, K, ks, &w, dw_by_k);
         return h16_up(q, w);
     }
     wv_model::H16Block h16_block(const std::string& pre, int C) {
@@ -227,6 +240,19 @@ struct Uploader {
         b.tab1 = up(wv::pack_rh_table(host(pre + ".block.2.conv.conv.weight").data(), host(pre + ".block.2.conv.conv.bias").data(), C, wv::RH_LOG2E));
         b.tab2 = up(wv::pack_rh_table(host(pre + ".block.5.conv.conv.weight").data(), host(pre + ".block.5.conv.conv.bias").data(), C, 1.0));
         return b;
+    }
+    // the four A-fragment matrices of launch_spec16 (cos / sin, high and low halves) from a basis [2F][n_fft]
+    void h16_stft(wv_model::H16Stage& st, const std::vector<float>& basis, int n_fft) {
+        std::vector<uint16_t> q4[4];
+        wv::H16Weight w4[4];
+        wv::pack_stft16(basis.data(), n_fft, q4, w4);
+        st.cosw = h16_up(q4[0], w4[0]); st.sinw = h16_up(q4[1], w4[1]); st.cosl = h16_up(q4[2], w4[2]); st.sinl = h16_up(q4[3], w4[3]);
+    }
+    // [M][5] = (0,0,0,0,1): the identity stencil of a K1 launch that only wants its 1x1
+    const float* id_taps(int M) {
+        std::vector<float> taps((size_t)M * 5, 0.f);
+        for (int mm = 0; mm < M; ++mm) taps[(size_t)mm * 5 + 4] = 1.f;
+        return up(taps);
     }
     wv::H16Weight h16_up(const std::vector<uint16_t>& q, wv::H16Weight w) {
         if (err != WV_OK) return w;
@@ -290,6 +316,11 @@ std::vector<float> make_basis(int n_fft) {
     }
     return w;
 }
+// the basis in force for a SpecBlock: the one given under `key` through wv_model_set_stft_basis, else the analytic one
+std::vector<float> basis_for(const wv_model* m, const std::string& key, int n_fft) {
+    auto ov = m->stft_override.find(key);
+    return ov != m->stft_override.end() ? ov->second : make_basis(n_fft);
+}
 
 // [2F][n_fft] reference layout -> basis_t[Kp][Mp] with column 2f = cos row f, 2f+1 = sin row f
 const float* pack_basis(Uploader& U, const std::vector<float>& basis, int n_fft, int* Mp_out, const float** side_out,
@@ -334,7 +365,7 @@ int pack_model(wv_model* m) {
     int mult = 1, stride = 1;
     for (int s = 0; s <= S; ++s) {
         const bool post = s == S;
-        const std::string pre = post ? "encoder.spec_post" : "encoder.spec_blocks." + std::to_string(s);
+        const std::string pre = spec_prefix(c, s);
         if (!post) {
             std::vector<ResBlock> blocks;
             for (int j = 1; j <= c.n_residual_enc; ++j)                    // idx = j (seanet.py:684)
@@ -344,20 +375,13 @@ int pack_model(wv_model* m) {
         }
         SpecLayer sp{};
         sp.n_fft = mult * c.n_fft_base; sp.hop = stride; sp.F = sp.n_fft / 2 + 1;
-        auto ov = m->stft_override.find(pre + ".spec.weight");
-        sp.basis_t = pack_basis(U, ov != m->stft_override.end() ? ov->second : make_basis(sp.n_fft),
-                                sp.n_fft, &sp.Mp, &sp.side, &sp.basis_q);
+        sp.basis_t = pack_basis(U, basis_for(m, pre + ".spec.weight", sp.n_fft), sp.n_fft, &sp.Mp, &sp.side, &sp.basis_q);
         const int mi = post ? WV_MAX_STRIDES : s;                           // spec_post uses [-1]
-        sp.mean = post ? c.spec_means[WV_MAX_STRIDES] : c.spec_means[s];
-        sp.inv_std = 1.f / (post ? c.spec_stds[WV_MAX_STRIDES] : c.spec_stds[s]);
-        (void)mi;
+        sp.mean = c.spec_means[mi];
+        sp.inv_std = 1.f / c.spec_stds[mi];
         sp.pw = U.pw(pre + ".layer.conv.conv.weight");
         sp.scale = U.scalar_or(pre + ".scale_param", 1.f) * rs;            // seanet.py:500-502
-        {
-            std::vector<float> taps((size_t)sp.pw.M * 5, 0.f);
-            for (int mm = 0; mm < sp.pw.M; ++mm) taps[(size_t)mm * 5 + 4] = 1.f;
-            sp.id_taps = U.up(taps);
-        }
+        sp.id_taps = U.id_taps(sp.pw.M);
         m->specs.push_back(sp);
         if (!post) {
             DownLayer d{};
@@ -375,12 +399,10 @@ int pack_model(wv_model* m) {
     m->post_dw_w = U.plain("encoder.conv_post.1.conv.conv.weight");
     m->post_pw = U.pw("encoder.conv_post.2.conv.conv.weight");
     m->post_b = U.plain("encoder.conv_post.2.conv.conv.bias");
-    (void)C0;
 
     // message MLP + FiLM (only when the tensors were provided; mandatory for the generator)
     m->has_film = m->params[m->index["encoder.msg_embedding.0.weight"]].set;
     if (m->has_film) {
-        const int E = c.embedding_dim;
         m->f_w0 = U.plain("encoder.msg_embedding.0.weight");
         m->f_b0 = U.plain("encoder.msg_embedding.0.bias");
         std::vector<float> wl, bl, wf, bf;
@@ -398,7 +420,6 @@ int pack_model(wv_model* m) {
                     wf.insert(wf.end(), w.begin(), w.end()); bf.push_back(bb[0]);
                 }
         m->f_wl = U.up(wl); m->f_bl = U.up(bl); m->f_wf = U.up(wf); m->f_bf = U.up(bf);
-        (void)E;
     }
 
     if (c.kind == WV_KIND_GENERATOR) {
@@ -414,13 +435,8 @@ int pack_model(wv_model* m) {
             u.ct_w = U.plain("decoder.model." + std::to_string(n + 2) + ".convtr.convtr.weight");
             u.pw = U.pw("decoder.model." + std::to_string(n + 3) + ".conv.conv.weight");
             u.pw_b = U.plain("decoder.model." + std::to_string(n + 3) + ".conv.conv.bias");
-            {
-                std::vector<float> taps((size_t)u.pw.M * 5, 0.f);
-                for (int mm = 0; mm < u.pw.M; ++mm) taps[(size_t)mm * 5 + 4] = 1.f;
-                u.id_taps = U.up(taps);
-                const std::vector<float>& cw = U.host("decoder.model." + std::to_string(n + 2) + ".convtr.convtr.weight");
-                u.ct_wt = U.up(wv::pack_ct_wt(cw.data(), u.pw.K, u.pw.Kp, u.ratio));
-            }
+            u.id_taps = U.id_taps(u.pw.M);
+            u.ct_wt = U.up(wv::pack_ct_wt(U.host("decoder.model." + std::to_string(n + 2) + ".convtr.convtr.weight").data(), u.pw.K, u.pw.Kp, u.ratio));
             u.pre_scale = i > 0 ? m->dec_post : 1.f;
             for (int j = 0; j < c.n_residual_dec; ++j)                     // idx = j (seanet.py:1159)
                 u.res.push_back(pack_resblock(U, "decoder.model." + std::to_string(n + 4 + j), j, rd,
@@ -454,58 +470,39 @@ int pack_model(wv_model* m) {
         m->head_wc = U.up(wc); m->head_bc = U.up(bc); m->head_nb = nb;
         head_wc_host = wc;
     }
-    // f16 mode: only for layer shapes the f16 kernels cover (else the *_forward_f16 entry points report WV_ESTATE)
-    auto rh_c = [](int C) { return C == 32 || C == 64 || C == 96 || C == 128 || C == 192 || C == 256 || C == 384 || C == 512 || C == 768; };
+    // f16 mode: only for layer shapes the f16 kernels cover (else the *_forward_f16 entry points report WV_ESTATE).  The SpecBlock route of
+    // every scale: one launch where (n_fft, hop, channels) is a row of spec16's table, else the exact STFT kernel and the 1x1 on the f16 pipe.
+    std::vector<wv_model::SpecRoute> route;
+    for (int s = 0, C = C0; s <= S; ++s, C *= 2)
+        route.push_back(wv::spec16_scale(m->specs[s].n_fft, m->specs[s].hop, C, s == S) ? wv_model::SPEC_ONE_LAUNCH : wv_model::SPEC_STFT_1X1);
     bool h16_ok = c.residual_kernel_size == 5 && c.dilation_base == 1 && c.kernel_size <= 16 && c.last_kernel_size <= 16;
     for (int s = 0, C = C0; s < S && h16_ok; ++s, C *= 2) {
-        h16_ok = rh_c(C) || m->enc_blocks[s].empty();
-        // a scale the one-launch SpecBlock does not take stages its f16 spectrogram (roundup(F, 16) rows) in the intermediate buffer of C rows of f32
-        if (C != m->specs[s].n_fft && round_up_int(m->specs[s].F, 16) > 2 * C) h16_ok = false;
-        if (C % 8) h16_ok = false;
+        // whole channel groups of eight at every stage (so the top width, behind n_strides >= 1 doublings, is whole 16-channel group pairs)
+        h16_ok = (wv::rh16_width(C) || m->enc_blocks[s].empty()) && C % 8 == 0;
+        // the STFT + 1x1 route stages its f16 spectrogram (roundup(F, 16) rows) in the intermediate buffer of C rows of f32
+        if (route[s] == wv_model::SPEC_STFT_1X1 && round_up_int(m->specs[s].F, 16) > 2 * C) h16_ok = false;
     }
     if (h16_ok) {
-        int C = C0;
-        for (int s = 0; s < S && U.err == WV_OK; ++s, C *= 2) {
+        for (int s = 0, C = C0; s <= S && U.err == WV_OK; ++s, C *= 2) {
             wv_model::H16Stage st;
-            for (int j = 0; j < c.n_residual_enc; ++j)
-                st.blocks.push_back(U.h16_block("encoder.blocks." + std::to_string(s) + "." + std::to_string(j), C));
-            const int F = m->specs[s].F, r = ratio_enc(c, s);
-            st.spec = U.h16(U.host("encoder.spec_blocks." + std::to_string(s) + ".layer.conv.conv.weight"), nullptr, C, F, 1);
-            const std::string dp = "encoder.downsample." + std::to_string(s);
-            st.down = U.h16(U.host(dp + ".2.conv.conv.weight"), U.host(dp + ".3.conv.conv.weight").data(), 2 * C, C, 2 * r);
-            {
-                const int n_fft = m->specs[s].n_fft;
-                auto ov = m->stft_override.find("encoder.spec_blocks." + std::to_string(s) + ".spec.weight");
-                const std::vector<float> basis = ov != m->stft_override.end() ? ov->second : make_basis(n_fft);
-                std::vector<uint16_t> q4[4];
-                wv::H16Weight w4[4];
-                wv::pack_stft16(basis.data(), n_fft, q4, w4);
-                st.cosw = U.h16_up(q4[0], w4[0]); st.sinw = U.h16_up(q4[1], w4[1]); st.cosl = U.h16_up(q4[2], w4[2]); st.sinl = U.h16_up(q4[3], w4[3]);
-            }
-            m->h16.push_back(std::move(st));
-        }
-        if (U.err == WV_OK && C % 16 == 0) {
-            // spec_post on the f16 pipe as well: in one launch where the scale is one of spec16's (the default generator / detector: 1024 points,
-            // hop 320; the default locator: 256 points, hop 32, 128 channels), else the exact STFT kernel + the 1x1 on the f16 pipe
-            wv_model::H16Stage st;
-            const int n_fft = m->specs[S].n_fft;
-            st.spec = U.h16(U.host("encoder.spec_post.layer.conv.conv.weight"), nullptr, C, m->specs[S].F, 1);
-            if ((C == n_fft && C == 1024 && m->specs[S].hop == 320) || (2 * C == n_fft && C == 128 && m->specs[S].hop == 32)) {
-                auto ov = m->stft_override.find("encoder.spec_post.spec.weight");
-                const std::vector<float> basis = ov != m->stft_override.end() ? ov->second : make_basis(n_fft);
-                std::vector<uint16_t> q4[4];
-                wv::H16Weight w4[4];
-                wv::pack_stft16(basis.data(), n_fft, q4, w4);
-                st.cosw = U.h16_up(q4[0], w4[0]); st.sinw = U.h16_up(q4[1], w4[1]); st.cosl = U.h16_up(q4[2], w4[2]); st.sinl = U.h16_up(q4[3], w4[3]);
-            }
-            // conv_post (ELU -> depth-wise k -> 1x1 + bias, seanet.py:797-823) as one dense conv: W[m][i][k] = pw[m][k] * dw[k][i];
-            // the head's composed weight wc[D][nb * hop] transposed into A fragments [nb * hop][D]
-            {
-                wv::H16Weight w;
-                const std::vector<uint16_t> q = wv::pack_h16(U.host("encoder.conv_post.2.conv.conv.weight").data(), U.host("encoder.conv_post.1.conv.conv.weight").data(),
-                                                             c.dimension, C, c.last_kernel_size, &w, true);
-                st.post = U.h16_up(q, w);
-                if (c.kind != WV_KIND_GENERATOR) {
+            const SpecLayer& sp = m->specs[s];
+            const std::string pre = spec_prefix(c, s);
+            st.route = route[s];
+            st.spec = U.h16(U.host(pre + ".layer.conv.conv.weight"), nullptr, C, sp.F, 1);
+            if (st.route == wv_model::SPEC_ONE_LAUNCH) U.h16_stft(st, basis_for(m, pre + ".spec.weight", sp.n_fft), sp.n_fft);
+            if (s < S) {
+                for (int j = 0; j < c.n_residual_enc; ++j)
+                    st.blocks.push_back(U.h16_block("encoder.blocks." + std::to_string(s) + "." + std::to_string(j), C));
+                const std::string dp = "encoder.downsample." + std::to_string(s);
+                st.down = U.h16(U.host(dp + ".2.conv.conv.weight"), U.host(dp + ".3.conv.conv.weight").data(), 2 * C, C, 2 * ratio_enc(c, s));
+            } else {
+                // conv_post (ELU -> depth-wise k -> 1x1 + bias, seanet.py:797-823) as one dense conv: W[m][i][k] = pw[m][k] * dw[k][i];
+                // the head's composed weight wc[D][nb * hop] transposed into A fragments [nb * hop][D]
+                st.post = U.h16(U.host("encoder.conv_post.2.conv.conv.weight"), U.host("encoder.conv_post.1.conv.conv.weight").data(), c.dimension, C,
+                                c.last_kernel_size, true);
+                st.head16 = c.kind != WV_KIND_GENERATOR && wv::head16_covers(c.dimension, m->head_nb, hop_of(c), false);
+                st.head16_frames = st.head16 && wv::head16_covers(c.dimension, m->head_nb, hop_of(c), true);
+                if (st.head16) {
                     wv::H16Weight wh;
                     const std::vector<uint16_t> qh = wv::pack_head16(head_wc_host.data(), c.dimension, m->head_nb, hop_of(c), &wh);
                     st.head = U.h16_up(qh, wh);
@@ -513,9 +510,10 @@ int pack_model(wv_model* m) {
             }
             m->h16.push_back(std::move(st));
         }
-        // the generator's decoder (seanet.py:1067-1226): needs the latent from the f16 conv_post above
-        bool dec_ok = c.kind == WV_KIND_GENERATOR && (int)m->h16.size() > S && c.dimension % 16 == 0 && (c.last_kernel_size == 3 || c.last_kernel_size == 5 || c.last_kernel_size == 7);
-        for (size_t i = 0; i < m->ups.size() && dec_ok; ++i) dec_ok = (m->ups[i].res.empty() || rh_c(m->ups[i].pw.M)) && m->ups[i].pw.M % 16 == 0 && m->ups[i].pw.K % 16 == 0;
+        // the generator's decoder (seanet.py:1067-1226), from the latent of the f16 conv_post above
+        bool dec_ok = c.kind == WV_KIND_GENERATOR && c.dimension % 16 == 0 && wv::tail16_taps(c.last_kernel_size);
+        for (size_t i = 0; i < m->ups.size() && dec_ok; ++i)
+            dec_ok = (m->ups[i].res.empty() || wv::rh16_width(m->ups[i].pw.M)) && m->ups[i].pw.M % 16 == 0 && m->ups[i].pw.K % 16 == 0;
         if (dec_ok && U.err == WV_OK) {
             // decoder.model.0 (1x1, D -> C) and .1 (depth-wise k) as one composed conv: W[m][i][k] = dw[m][i] * pw[m][k]
             m->h16_dec_head = U.h16(U.host("decoder.model.0.conv.conv.weight"), U.host("decoder.model.1.conv.conv.weight").data(), m->dec_pw0.M, c.dimension, c.kernel_size);
@@ -664,6 +662,15 @@ Stream make_stream(char* ws, const WsLayout& L) {
     return st;
 }
 
+// the STFT of SpecBlock `sp` over the waveform x [B][T], log-magnitudes to P
+wv::StftArgs stft_args(const SpecLayer& sp, const float* x, float* P, int B, int T) {
+    wv::StftArgs sa{};
+    sa.wav = x; sa.basis_t = sp.basis_t; sa.basis_q = sp.basis_q; sa.side = sp.side; sa.P = P; sa.B = B; sa.T = T;
+    sa.Tf = (T + sp.hop - 1) / sp.hop; sa.n_fft = sp.n_fft; sa.hop = sp.hop; sa.F = sp.F; sa.Mp = sp.Mp;
+    sa.mean = sp.mean; sa.inv_std = sp.inv_std;
+    return sa;
+}
+
 // SEANetEncoder.forward (modules/seanet.py:883-976). Result in `latent` [B, dimension, Fr].
 // first_stage > 0: the stages before it ran elsewhere (the f16 mode); their raw output [B, C, Tl] is in the stream's buffer r[0];
 // post_spec_done: so did spec_post (only conv_post is left).
@@ -705,10 +712,7 @@ int run_encoder(wv_model* m, const float* x, const float* msg, int msg_rows, flo
         if (post && post_spec_done) break;
         wv::prof::set_role("enc.spec");
         const SpecLayer& sp = m->specs[s];
-        wv::StftArgs sa{};
-        sa.wav = x; sa.basis_t = sp.basis_t; sa.basis_q = sp.basis_q; sa.side = sp.side; sa.P = P; sa.B = B; sa.T = T;
-        sa.Tf = (T + sp.hop - 1) / sp.hop; sa.n_fft = sp.n_fft; sa.hop = sp.hop; sa.F = sp.F; sa.Mp = sp.Mp;
-        sa.mean = sp.mean; sa.inv_std = sp.inv_std;
+        const wv::StftArgs sa = stft_args(sp, x, P, B, T);
         if (sa.Tf != Tl) return fail(WV_EINVAL, "internal: STFT frame count != feature length");
         bool fused_spec = false;
         {
@@ -898,8 +902,7 @@ int wv_model_set_stft_basis(wv_model* m, const char* name, const float* data, in
     const std::string n(name);
     int mult = 1; bool ok = false;
     for (int s = 0; s <= m->cfg.n_strides; ++s) {
-        const std::string key = (s == m->cfg.n_strides ? std::string("encoder.spec_post")
-                                                       : "encoder.spec_blocks." + std::to_string(s)) + ".spec.weight";
+        const std::string key = spec_prefix(m->cfg, s) + ".spec.weight";
         const int n_fft = mult * m->cfg.n_fft_base;
         if (key == n) {
             if (numel != (int64_t)(n_fft + 2) * n_fft) return fail(WV_EINVAL, "size mismatch for " + n);
@@ -1006,24 +1009,61 @@ int wv_generator_forward(wv_model* m, const float* x, const float* msg, int msg_
     return WV_OK;
 }
 
-// The encoder stages of the f16 mode (wv_h16.hip): conv_pre, then per stage the ResnetBlocks (one launch each), the SpecBlock (one launch
-// where the scale is one of spec16's, else the exact path's STFT kernel and the 1x1 + add on the f16 pipe) and the downsample unit (one
-// composed conv; FiLM in its epilogue when `film` is given: the generator).  What happens behind the last stage:
-//   tail = H16_TAIL_F32      the last downsample (or spec_post, when it runs on the f16 pipe: *post_done) writes f32 [B, C, Tl] into the stream
-//                            buffer r[0], where run_encoder(first_stage = n_strides) picks up (logits outputs: conv_post and the head exact)
-//   tail = H16_TAIL_LATENT   spec_post -> ELU -> conv_post as one composed conv on the f16 pipe, the latent BEFORE its L2Norm as f32
-//                            [B, D, Fr] at the workspace's latent slot; *latent_done (falls back to H16_TAIL_F32 when that plan is missing)
-enum { H16_TAIL_F32 = 0, H16_TAIL_LATENT = 1 };
-static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film, int B, int T, char* ws, const WsLayout& L, hipStream_t st, int tail,
-                                  bool* post_done, bool* latent_done, int* Fr_out) {
+// What an f16 launcher answered, under the launcher's name: a shape it does not cover is WV_ESTATE, a HIP error WV_EHIP.
+static int h16_fail(const char* launcher, hipError_t e) {
+    return fail(e == hipErrorNotSupported ? WV_ESTATE : WV_EHIP, std::string(launcher) + ": " + hipGetErrorString(e));
+}
+
+// One SpecBlock of the f16 walk, of stage s or (s == n_strides) spec_post (seanet.py:500-502, 781-795): x' = x + scale * (W @ P) from the c8
+// stream `resid` [B, C, Tl], out as ELU(act_scale * x') in c8 (Yact) and / or as f32 [B, C, Tl] (Yf32).  The planned route first; behind a
+// one-launch route whose launcher refuses a limit of this call, and for every other scale, the exact path's STFT kernel -> P in HBM ->
+// f16 copy -> the 1x1 + add as a k = 1 conv.  *ran = false, nothing launched: the spectrogram does not fit its staging buffer.
+static int spec_step_f16(const wv_model* m, int s, const float* x, const void* resid, void* Yact, float act_scale, float* Yf32, int B, int T, int Tl, int C,
+                         char* ws, const WsLayout& L, hipStream_t st, bool* ran) {
+    const SpecLayer& sp = m->specs[s];
+    const wv_model::H16Stage& hs = m->h16[s];
+    float* P = (float*)(ws + L.off_p);
+    void* P16 = ws + L.off_u;
+    const wv::StftArgs sa = stft_args(sp, x, P, B, T);
+    if (sa.Tf != Tl) return fail(WV_EINVAL, "internal: STFT frame count != feature length");
+    *ran = true;
+    if (hs.route == wv_model::SPEC_ONE_LAUNCH) {
+        wv::Spec16Args f{};
+        f.wav = x; f.side = sp.side; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = resid; f.Y = nullptr;
+        f.Yact = Yact; f.Yf32 = Yf32;
+        f.out_scale = sp.scale; f.act_scale = act_scale; f.c1 = 0.5f * 0.6931471805599453f * sp.inv_std; f.c0 = -sp.mean * sp.inv_std;
+        f.B = B; f.T = T; f.Tf = Tl; f.n_fft = sp.n_fft; f.hop = sp.hop;
+        const hipError_t fe = wv::launch_spec16(f, st);
+        if (fe == hipSuccess) return WV_OK;
+        if (fe != hipErrorNotSupported) return h16_fail(s == m->cfg.n_strides ? "launch_spec16 (post)" : "launch_spec16", fe);
+    }
+    if ((size_t)B * round_up_int(sp.F, 16) * Tl * 2 > L.act * 4 || (size_t)B * sp.F * Tl > L.spec) { *ran = false; return WV_OK; }
+    WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
+    WV_HIP_TRY(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
+    wv::Conv16Args q{};
+    q.X = P16; q.w = hs.spec; q.bias = nullptr; q.resid = resid; q.Y = nullptr; q.Yact = Yact; q.Yf32 = Yf32;
+    q.out_scale = sp.scale; q.act_scale = act_scale; q.B = B; q.M = C; q.Tin = Tl; q.Tout = Tl; q.ks = 1; q.stride = 1; q.pad = 0;
+    WV_HIP_TRY(wv::launch_conv16(q, st));
+    return WV_OK;
+}
+
+// The encoder of the f16 mode (wv_h16.hip): conv_pre, then per stage the ResnetBlocks (one launch each), the SpecBlock (spec_step_f16) and the
+// downsample unit (one composed conv; FiLM in its epilogue when `film` is given: the generator), then spec_post.  Where it leaves the stream:
+//   H16_END_LATENT      (want_latent) spec_post -> ELU -> conv_post as one composed conv on the f16 pipe: the latent BEFORE its L2Norm as f32
+//                       [B, D, Fr] at the workspace's latent slot
+//   H16_END_SPEC_POST   (else) spec_post wrote f32 [B, C, Tl] into the stream buffer r[0]: run_encoder(first_stage = n_strides,
+//                       post_spec_done) picks up (logits outputs: conv_post and the head exact)
+//   H16_END_STAGES      spec_post could not run here: the last stage's output as f32 in r[0], run_encoder(first_stage = n_strides) picks up
+enum H16End { H16_END_STAGES, H16_END_SPEC_POST, H16_END_LATENT };
+static int run_encoder_f16(wv_model* m, const float* x, const float* film, int B, int T, char* ws, const WsLayout& L, hipStream_t st, bool want_latent,
+                           H16End* end, int* Fr_out) {
     const wv_config& c = m->cfg;
     const int S = c.n_strides;
     void* R[2] = {ws + L.off_r0, ws + L.off_r1};
     void* A0 = ws + L.off_a0;
-    float* P = (float*)(ws + L.off_p);
-    void* P16 = ws + L.off_u;
     int cur = 0, Tl = T, C = c.channels_enc;
     const int film_stride = c.n_strides * c.freq_bands * 2;
+    bool ran = false;
     wv::prof::set_role("enc16.conv_pre");
     WV_HIP_TRY(wv::launch_conv_pre16(x, m->pre_w, m->pre_b, R[0], B, C, T, c.kernel_size, 1.f / c.wav_std, st));
     for (int s = 0; s < S; ++s) {
@@ -1035,39 +1075,18 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
             a.X = R[cur]; a.pre_scale = r.pre_scale; a.w1 = hs.blocks[j].w1; a.w2 = hs.blocks[j].w2; a.tab1 = hs.blocks[j].tab1; a.tab2 = hs.blocks[j].tab2;
             a.Y = R[cur ^ 1]; a.Yact = nullptr; a.out_scale = r.out_scale; a.act_scale = 0.f; a.B = B; a.C = C; a.T = Tl;
             const hipError_t e = wv::launch_resblock16(a, st);
-            if (e != hipSuccess) return fail(e == hipErrorNotSupported ? WV_ESTATE : WV_EHIP, std::string("launch_resblock16: ") + hipGetErrorString(e));
+            if (e != hipSuccess) return h16_fail("launch_resblock16", e);
             cur ^= 1;
         }
+        // only ELU(c * x') is consumed, by the downsample unit
         wv::prof::set_role("enc16.spec");
-        const SpecLayer& sp = m->specs[s];
-        wv::StftArgs sa{};
-        sa.wav = x; sa.basis_t = sp.basis_t; sa.basis_q = sp.basis_q; sa.side = sp.side; sa.P = P; sa.B = B; sa.T = T;
-        sa.Tf = (T + sp.hop - 1) / sp.hop; sa.n_fft = sp.n_fft; sa.hop = sp.hop; sa.F = sp.F; sa.Mp = sp.Mp;
-        sa.mean = sp.mean; sa.inv_std = sp.inv_std;
-        if (sa.Tf != Tl) return fail(WV_EINVAL, "internal: STFT frame count != feature length");
         const DownLayer& d = m->downs[s];
-        // x' = x + scale * (W @ P); only ELU(c * x') is consumed.  One launch where the scale is one of the fused kernel's (the default
-        // detector's / generator's four), else the exact path's STFT kernel -> P in HBM -> f16 copy -> the 1x1 + add as a k = 1 conv
-        wv::Spec16Args f{};
-        f.wav = x; f.side = sp.side; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr; f.Yact = A0;
-        f.out_scale = sp.scale; f.act_scale = d.pre_scale; f.c1 = 0.5f * 0.6931471805599453f * sp.inv_std; f.c0 = -sp.mean * sp.inv_std;
-        f.B = B; f.T = T; f.Tf = Tl; f.n_fft = sp.n_fft; f.hop = sp.hop;
-        const hipError_t fe = (C == sp.n_fft || 2 * C == sp.n_fft) ? wv::launch_spec16(f, st) : hipErrorNotSupported;
-        if (fe != hipSuccess && fe != hipErrorNotSupported) return fail(WV_EHIP, std::string("launch_spec16: ") + hipGetErrorString(fe));
-        if (fe == hipErrorNotSupported) {
-            if ((size_t)B * round_up_int(sp.F, 16) * Tl * 2 > L.act * 4) return fail(WV_ESTATE, "f16 mode: the spectrogram of this scale does not fit its staging buffer");
-            WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
-            WV_HIP_TRY(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
-            wv::Conv16Args q{};
-            q.X = P16; q.w = hs.spec; q.bias = nullptr; q.resid = R[cur]; q.Y = nullptr; q.Yact = A0; q.Yf32 = nullptr;
-            q.out_scale = sp.scale; q.act_scale = d.pre_scale; q.B = B; q.M = C; q.Tin = Tl; q.Tout = Tl; q.ks = 1; q.stride = 1; q.pad = 0;
-            WV_HIP_TRY(wv::launch_conv16(q, st));
-        }
+        int rc = spec_step_f16(m, s, x, R[cur], A0, d.pre_scale, nullptr, B, T, Tl, C, ws, L, st, &ran);
+        if (rc) return rc;
+        if (!ran) return fail(WV_ESTATE, "f16 mode: the spectrogram of this scale does not fit its staging buffer");
         wv::prof::set_role(film ? "enc16.down_film" : "enc16.down");
-        const bool last = s + 1 == S, post16 = (int)m->h16.size() > S;
         wv::Conv16Args g{};
-        g.X = A0; g.w = hs.down; g.bias = d.dw_b; g.resid = nullptr; g.Y = (last && !post16) ? nullptr : R[cur ^ 1]; g.Yact = nullptr;
-        g.Yf32 = (last && !post16) ? (float*)R[0] : nullptr; g.out_scale = 1.f; g.act_scale = 0.f;
+        g.X = A0; g.w = hs.down; g.bias = d.dw_b; g.resid = nullptr; g.Y = R[cur ^ 1]; g.Yact = nullptr; g.Yf32 = nullptr; g.out_scale = 1.f; g.act_scale = 0.f;
         g.B = B; g.M = 2 * C; g.Tin = Tl; g.Tout = (Tl + d.ratio - 1) / d.ratio; g.ks = 2 * d.ratio; g.stride = d.ratio; g.pad = d.ratio;
         if (film) {
             if ((2 * C) % c.freq_bands) return fail(WV_EINVAL, "channels not divisible by freq_bands");
@@ -1076,168 +1095,138 @@ static int run_encoder_stages_f16(wv_model* m, const float* x, const float* film
         WV_HIP_TRY(wv::launch_conv16(g, st));
         cur ^= 1; Tl = g.Tout; C *= 2;
     }
-    *post_done = false; *latent_done = false; *Fr_out = Tl;
-    if ((int)m->h16.size() > S) {
-        // spec_post (seanet.py:781-795) on the f16 pipe as well: x' = x + scale * (W @ P) from the c8 buffer R[cur], out as ELU(x') in c8 (for
-        // the composed conv_post) or as f32 [B, C, Tl] in the stream buffer r[0] (for the exact conv_post; when x sits in R[0] the f32
-        // result, twice the bytes, goes through R[1] and is copied over).
-        wv::prof::set_role("enc16.spec_post");
-        const SpecLayer& sp = m->specs[S];
-        const wv_model::H16Stage& hs = m->h16[S];
-        if ((T + sp.hop - 1) / sp.hop != Tl) return fail(WV_EINVAL, "internal: STFT frame count != feature length");
-        const bool latent = tail == H16_TAIL_LATENT && hs.post.wq && c.last_kernel_size <= 16;
-        float* f32out = latent ? nullptr : (float*)R[cur ^ 1];
-        bool done = false;
-        if (hs.cosw.wq) {
-            wv::Spec16Args f{};
-            f.wav = x; f.side = sp.side; f.cosw = hs.cosw; f.sinw = hs.sinw; f.cosl = hs.cosl; f.sinl = hs.sinl; f.pw = hs.spec; f.resid = R[cur]; f.Y = nullptr;
-            f.Yact = latent ? A0 : nullptr; f.Yf32 = f32out;
-            f.out_scale = sp.scale; f.act_scale = latent ? 1.f : 0.f; f.c1 = 0.5f * 0.6931471805599453f * sp.inv_std; f.c0 = -sp.mean * sp.inv_std;
-            f.B = B; f.T = T; f.Tf = Tl; f.n_fft = sp.n_fft; f.hop = sp.hop;
-            const hipError_t fe = wv::launch_spec16(f, st);
-            if (fe == hipSuccess) done = true;
-            else if (fe != hipErrorNotSupported) return fail(WV_EHIP, std::string("launch_spec16 (post): ") + hipGetErrorString(fe));
-        }
-        if (!done && (size_t)B * round_up_int(sp.F, 16) * Tl * 2 <= L.act * 4 && (size_t)B * sp.F * Tl <= L.spec) {
-            // any other scale: the exact path's STFT kernel -> P in HBM -> f16 copy -> the 1x1 + add as a k = 1 conv
-            wv::StftArgs sa{};
-            sa.wav = x; sa.basis_t = sp.basis_t; sa.basis_q = sp.basis_q; sa.side = sp.side; sa.P = P; sa.B = B; sa.T = T;
-            sa.Tf = Tl; sa.n_fft = sp.n_fft; sa.hop = sp.hop; sa.F = sp.F; sa.Mp = sp.Mp; sa.mean = sp.mean; sa.inv_std = sp.inv_std;
-            WV_HIP_TRY(wv::launch_stft_logmag(sa, st));
-            WV_HIP_TRY(wv::launch_f32_to_c8(P, P16, B, sp.F, Tl, 1.f, 0, st));
-            wv::Conv16Args q{};
-            q.X = P16; q.w = hs.spec; q.bias = nullptr; q.resid = R[cur]; q.Y = nullptr; q.Yact = latent ? A0 : nullptr; q.Yf32 = f32out;
-            q.out_scale = sp.scale; q.act_scale = latent ? 1.f : 0.f; q.B = B; q.M = C; q.Tin = Tl; q.Tout = Tl; q.ks = 1; q.stride = 1; q.pad = 0;
-            WV_HIP_TRY(wv::launch_conv16(q, st));
-            done = true;
-        }
-        if (done && latent) {
-            wv::prof::set_role("enc16.conv_post");
-            wv::Conv16Args g{};
-            g.X = A0; g.w = hs.post; g.bias = m->post_b; g.resid = nullptr; g.Y = nullptr; g.Yact = nullptr; g.Yf32 = (float*)(ws + L.off_lat);
-            g.out_scale = 1.f; g.act_scale = 0.f; g.B = B; g.M = c.dimension; g.Tin = Tl; g.Tout = Tl; g.ks = c.last_kernel_size; g.stride = 1;
-            g.pad = c.last_kernel_size - 1;
-            WV_HIP_TRY(wv::launch_conv16(g, st));
-            *post_done = true; *latent_done = true;
-            return WV_OK;
-        }
-        if (done) {
-            if ((cur ^ 1) != 0) WV_HIP_TRY(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
-            *post_done = true;
-            return WV_OK;
-        }
-        WV_HIP_TRY(wv::launch_c8_to_f32(R[cur], (float*)R[cur ^ 1], B, C, Tl, st));     // the exact path's spec_post takes it from here
-        if ((cur ^ 1) != 0) WV_HIP_TRY(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
+    *Fr_out = Tl;
+    // spec_post from the c8 buffer R[cur]: out as ELU(x') in c8 (for the composed conv_post), or as f32 [B, C, Tl] for the exact conv_post --
+    // twice the bytes, so it goes to the other buffer, and from R[1] is copied over to the stream buffer r[0]
+    wv::prof::set_role("enc16.spec_post");
+    int rc = spec_step_f16(m, S, x, R[cur], want_latent ? A0 : nullptr, want_latent ? 1.f : 0.f, want_latent ? nullptr : (float*)R[cur ^ 1], B, T, Tl, C, ws, L,
+                           st, &ran);
+    if (rc) return rc;
+    if (ran && want_latent) {
+        wv::prof::set_role("enc16.conv_post");
+        wv::Conv16Args g{};
+        g.X = A0; g.w = m->h16[S].post; g.bias = m->post_b; g.resid = nullptr; g.Y = nullptr; g.Yact = nullptr; g.Yf32 = (float*)(ws + L.off_lat);
+        g.out_scale = 1.f; g.act_scale = 0.f; g.B = B; g.M = c.dimension; g.Tin = Tl; g.Tout = Tl; g.ks = c.last_kernel_size; g.stride = 1;
+        g.pad = c.last_kernel_size - 1;
+        WV_HIP_TRY(wv::launch_conv16(g, st));
+        *end = H16_END_LATENT;
+        return WV_OK;
     }
+    *end = ran ? H16_END_SPEC_POST : H16_END_STAGES;
+    if (!ran) WV_HIP_TRY(wv::launch_c8_to_f32(R[cur], (float*)R[cur ^ 1], B, C, Tl, st));     // the exact path's spec_post takes it from here
+    if ((cur ^ 1) != 0) WV_HIP_TRY(hipMemcpyAsync(R[0], R[1], (size_t)B * C * Tl * sizeof(float), hipMemcpyDeviceToDevice, st));
     return WV_OK;
 }
 
-// keep_lo / keep_hi / psum: the windowed mean-probability mode (wv_detector_forward_windowed); all null otherwise.
-// fsum (with gate, gate_thr): the gated per-frame mode (wv_detector_forward_frames) instead of any other output.
-static int run_head_model(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,
-                          void* ws, size_t ws_bytes, void* stream, bool f16 = false,
-                          const int* keep_lo = nullptr, const int* keep_hi = nullptr, float* psum = nullptr,
-                          const float* gate = nullptr, float gate_thr = 0.f, float* fsum = nullptr) {
+// What a call of the detector's / locator's head wants.  Outputs (at least one): logits [B, nb, T], mean_prob [B, nb]; psum with keep_lo /
+// keep_hi: the windowed mean-probability mode (wv_detector_forward_windowed); fsum (with gate, gate_thr): the gated per-frame mode
+// (wv_detector_forward_frames) instead of any other output.  f16: the f16-operand mode.
+struct HeadCall {
+    float* logits = nullptr; float* mean_prob = nullptr;
+    const int* keep_lo = nullptr; const int* keep_hi = nullptr; float* psum = nullptr;
+    const float* gate = nullptr; float gate_thr = 0.f; float* fsum = nullptr;
+    bool f16 = false;
+};
+static int run_head_model(wv_model* m, const float* x, int B, int T, void* ws, size_t ws_bytes, void* stream, const HeadCall& o) {
     WsLayout L;
     int rc = check_common(m, B, T, ws, ws_bytes, &L);
     if (rc) return rc;
-    if (!x || (!logits && !mean_prob && !psum && !fsum)) return fail(WV_EINVAL, "null tensor");
+    if (!x || (!o.logits && !o.mean_prob && !o.psum && !o.fsum)) return fail(WV_EINVAL, "null tensor");
     hipStream_t st = (hipStream_t)stream;
+    const wv_config& c = m->cfg;
     char* w = (char*)ws;
     float* latent = (float*)(w + L.off_lat);
     int Fr = 0;
-    bool post_done = false;
-    if (f16) {
+    H16End end = H16_END_STAGES;
+    if (o.f16) {
         if (m->h16.empty()) return fail(WV_ESTATE, "this model has no f16 plan (ResnetBlock stages of 32 ... 768 channels, k = 5, dilation 1)");
         // mean probabilities only: conv_post and the head run on the f16 pipe as well (L2Norm + composed head GEMM + sigmoid + time mean)
-        const wv_config& c = m->cfg;
-        const int D = c.dimension, hop = hop_of(c);
-        const bool head16 = !logits && (int)m->h16.size() > c.n_strides && m->h16.back().head.wq && D % 16 == 0 && D <= 128 && m->head_nb % 4 == 0 && m->head_nb <= 32 && hop % 32 == 0 && (!fsum || hop <= 2016);
-        bool latent_done = false;
-        rc = run_encoder_stages_f16(m, x, nullptr, B, T, w, L, st, head16 ? H16_TAIL_LATENT : H16_TAIL_F32, &post_done, &latent_done, &Fr);
+        const wv_model::H16Stage& top = m->h16.back();
+        const bool head16 = !o.logits && (o.fsum ? top.head16_frames : top.head16);
+        rc = run_encoder_f16(m, x, nullptr, B, T, w, L, st, head16, &end, &Fr);
         if (rc) return rc;
-        if (latent_done && fsum) {
+        if (end == H16_END_LATENT) {
             wv::prof::set_role("head16");
-            const hipError_t e2 = wv::launch_head16_frames(latent, m->h16.back().head, m->head_bc, gate, gate_thr, fsum, B, D, m->head_nb, hop, Fr, T, st);
-            if (e2 != hipSuccess) return fail(WV_EHIP, std::string("launch_head16_frames: ") + hipGetErrorString(e2));
-            return WV_OK;
-        }
-        if (latent_done) {
-            wv::prof::set_role("head16");
-            const hipError_t e2 = wv::launch_head16(latent, m->h16.back().head, m->head_bc, mean_prob, B, D, m->head_nb, hop, Fr, T, st,
-                                                    keep_lo, keep_hi, psum);
-            if (e2 != hipSuccess) return fail(WV_EHIP, std::string("launch_head16: ") + hipGetErrorString(e2));
-            return WV_OK;
+            const hipError_t e2 = o.fsum ? wv::launch_head16_frames(latent, top.head, m->head_bc, o.gate, o.gate_thr, o.fsum, B, c.dimension, m->head_nb, hop_of(c), Fr, T, st)
+                                         : wv::launch_head16(latent, top.head, m->head_bc, o.mean_prob, B, c.dimension, m->head_nb, hop_of(c), Fr, T, st,
+                                                             o.keep_lo, o.keep_hi, o.psum);
+            return e2 == hipSuccess ? WV_OK : h16_fail(o.fsum ? "launch_head16_frames" : "launch_head16", e2);
         }
     }
-    rc = run_encoder(m, x, nullptr, 0, latent, B, T, w, L, st, &Fr, f16 ? m->cfg.n_strides : 0, post_done);
+    rc = run_encoder(m, x, nullptr, 0, latent, B, T, w, L, st, &Fr, o.f16 ? c.n_strides : 0, end == H16_END_SPEC_POST);
     if (rc) return rc;
     wv::prof::set_role("head");
-    if (fsum) {
+    if (o.fsum) {
         wv::HeadFramesArgs q{};
-        q.Z = latent; q.wc = m->head_wc; q.bc = m->head_bc; q.gate = gate; q.gate_thr = gate_thr; q.fsum = fsum;
-        q.B = B; q.D = m->cfg.dimension; q.nb = m->head_nb; q.hop = hop_of(m->cfg); q.Fr = Fr; q.T = T;
+        q.Z = latent; q.wc = m->head_wc; q.bc = m->head_bc; q.gate = o.gate; q.gate_thr = o.gate_thr; q.fsum = o.fsum;
+        q.B = B; q.D = c.dimension; q.nb = m->head_nb; q.hop = hop_of(c); q.Fr = Fr; q.T = T;
         WV_HIP_TRY(wv::launch_head_frames(q, st));
         return WV_OK;
     }
     wv::HeadArgs h{};
-    h.Z = latent; h.wc = m->head_wc; h.bc = m->head_bc; h.logits = logits; h.mean_prob = mean_prob;
-    h.B = B; h.D = m->cfg.dimension; h.nb = m->head_nb; h.hop = hop_of(m->cfg); h.Fr = Fr; h.T = T;
-    h.keep_lo = keep_lo; h.keep_hi = keep_hi; h.psum = psum;
+    h.Z = latent; h.wc = m->head_wc; h.bc = m->head_bc; h.logits = o.logits; h.mean_prob = o.mean_prob;
+    h.B = B; h.D = c.dimension; h.nb = m->head_nb; h.hop = hop_of(c); h.Fr = Fr; h.T = T;
+    h.keep_lo = o.keep_lo; h.keep_hi = o.keep_hi; h.psum = o.psum;
     WV_HIP_TRY(wv::launch_head(h, st));
     return WV_OK;
 }
 
+static int detector_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum, int W, int L, void* ws, size_t ws_bytes,
+                             void* stream, bool f16) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
+    HeadCall o;
+    o.keep_lo = keep_lo; o.keep_hi = keep_hi; o.psum = psum; o.f16 = f16;
+    return run_head_model(m, x, W, L, ws, ws_bytes, stream, o);
+}
 int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum, int W, int L,
                                  void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
-    return run_head_model(m, x, nullptr, nullptr, W, L, ws, ws_bytes, stream, false, keep_lo, keep_hi, psum);
+    return detector_windowed(m, x, keep_lo, keep_hi, psum, W, L, ws, ws_bytes, stream, false);
 }
-
 int wv_detector_forward_windowed_f16(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum, int W, int L,
                                      void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    if (!keep_lo || !keep_hi || !psum) return fail(WV_EINVAL, "null tensor");
-    return run_head_model(m, x, nullptr, nullptr, W, L, ws, ws_bytes, stream, true, keep_lo, keep_hi, psum);
+    return detector_windowed(m, x, keep_lo, keep_hi, psum, W, L, ws, ws_bytes, stream, true);
 }
 
+static int detector_frames(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum, int B, int T, void* ws, size_t ws_bytes,
+                           void* stream, bool f16) {
+    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
+    if (!fsum) return fail(WV_EINVAL, "null tensor");
+    HeadCall o;
+    o.gate = gate; o.gate_thr = gate_thr; o.fsum = fsum; o.f16 = f16;
+    return run_head_model(m, x, B, T, ws, ws_bytes, stream, o);
+}
 int wv_detector_forward_frames(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum, int B, int T,
                                void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    if (!fsum) return fail(WV_EINVAL, "null tensor");
-    return run_head_model(m, x, nullptr, nullptr, B, T, ws, ws_bytes, stream, false, nullptr, nullptr, nullptr, gate, gate_thr, fsum);
+    return detector_frames(m, x, gate, gate_thr, fsum, B, T, ws, ws_bytes, stream, false);
 }
-
 int wv_detector_forward_frames_f16(wv_model* m, const float* x, const float* gate, float gate_thr, float* fsum, int B, int T,
                                    void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    if (!fsum) return fail(WV_EINVAL, "null tensor");
-    return run_head_model(m, x, nullptr, nullptr, B, T, ws, ws_bytes, stream, true, nullptr, nullptr, nullptr, gate, gate_thr, fsum);
+    return detector_frames(m, x, gate, gate_thr, fsum, B, T, ws, ws_bytes, stream, true);
 }
 
+// Detector.forward / Locator.forward: `kind`'s net, logits and / or mean probabilities
+static int head_forward(wv_model* m, int kind, const float* x, float* logits, float* mean_prob, int B, int T, void* ws, size_t ws_bytes, void* stream, bool f16) {
+    if (m && m->cfg.kind != kind) return fail(WV_ESTATE, kind == WV_KIND_DETECTOR ? "not a detector model" : "not a locator model");
+    HeadCall o;
+    o.logits = logits; o.mean_prob = mean_prob; o.f16 = f16;
+    return run_head_model(m, x, B, T, ws, ws_bytes, stream, o);
+}
 int wv_detector_forward(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,
                         void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    return run_head_model(m, x, logits, mean_prob, B, T, ws, ws_bytes, stream);
+    return head_forward(m, WV_KIND_DETECTOR, x, logits, mean_prob, B, T, ws, ws_bytes, stream, false);
 }
-
 int wv_detector_forward_f16(wv_model* m, const float* x, float* logits, float* mean_prob, int B, int T,
                             void* ws, size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_DETECTOR) return fail(WV_ESTATE, "not a detector model");
-    return run_head_model(m, x, logits, mean_prob, B, T, ws, ws_bytes, stream, true);
+    return head_forward(m, WV_KIND_DETECTOR, x, logits, mean_prob, B, T, ws, ws_bytes, stream, true);
 }
-
 int wv_locator_forward(wv_model* m, const float* x, float* logits, int B, int T, void* ws,
                        size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_LOCATOR) return fail(WV_ESTATE, "not a locator model");
-    return run_head_model(m, x, logits, nullptr, B, T, ws, ws_bytes, stream);
+    return head_forward(m, WV_KIND_LOCATOR, x, logits, nullptr, B, T, ws, ws_bytes, stream, false);
 }
-
 int wv_locator_forward_f16(wv_model* m, const float* x, float* logits, int B, int T, void* ws,
                            size_t ws_bytes, void* stream) {
-    if (m && m->cfg.kind != WV_KIND_LOCATOR) return fail(WV_ESTATE, "not a locator model");
-    return run_head_model(m, x, logits, nullptr, B, T, ws, ws_bytes, stream, true);
+    return head_forward(m, WV_KIND_LOCATOR, x, logits, nullptr, B, T, ws, ws_bytes, stream, true);
 }
 
 // Generator.forward in the f16-operand mode (generator.py:360-423; seanet.py:883-976, 1067-1226): the encoder stages above with FiLM in
@@ -1260,10 +1249,10 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
     rc = run_film(m, msg, msg_rows, film, B, st);
     if (rc) return rc;
     int Fr = 0;
-    bool post_done = false, latent_done = false;
-    rc = run_encoder_stages_f16(m, x, film, B, T, w, L, st, H16_TAIL_LATENT, &post_done, &latent_done, &Fr);
+    H16End end = H16_END_STAGES;
+    rc = run_encoder_f16(m, x, film, B, T, w, L, st, true, &end, &Fr);
     if (rc) return rc;
-    if (!latent_done) return fail(WV_ESTATE, "f16 generator: spec_post / conv_post are not on the f16 pipe for this configuration");
+    if (end != H16_END_LATENT) return fail(WV_ESTATE, "f16 generator: spec_post / conv_post are not on the f16 pipe for this configuration");
     void* R[2] = {w + L.off_r0, w + L.off_r1};
     void* A0 = w + L.off_a0;
     wv::prof::set_role("dec16.l2norm");
@@ -1305,7 +1294,7 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
             a.Y = last ? nullptr : dst; a.Yact = last ? dst : nullptr; a.out_scale = r.out_scale; a.act_scale = last ? stage_next : 0.f;
             a.B = B; a.C = u.pw.M; a.T = Tl;
             const hipError_t e = wv::launch_resblock16(a, st);
-            if (e != hipSuccess) return fail(e == hipErrorNotSupported ? WV_ESTATE : WV_EHIP, std::string("launch_resblock16 (decoder): ") + hipGetErrorString(e));
+            if (e != hipSuccess) return h16_fail("launch_resblock16 (decoder)", e);
             curb = dst;
         }
         act = curb;
@@ -1313,7 +1302,7 @@ int wv_generator_forward_f16(wv_model* m, const float* x, const float* msg, int 
     wv::prof::set_role("dec16.tail");
     {
         const hipError_t e = wv::launch_tail16(act, m->last_w, m->last_b, add_input ? x : nullptr, out, B, c.channels_dec, Tl, T, c.last_kernel_size, c.wav_std, st);
-        if (e != hipSuccess) return fail(e == hipErrorNotSupported ? WV_ESTATE : WV_EHIP, std::string("launch_tail16: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return h16_fail("launch_tail16", e);
     }
     return WV_OK;
 }

@@ -306,7 +306,7 @@ int wv_h16_head(const float* lat, const float* wc, const float* bc, float* mean_
                 const int* keep_lo, const int* keep_hi, float* psum, void* stream) {
     if (!lat || !wc || !bc || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return fail(WV_EINVAL, "null pointer (lat, wc, bc) or B, D, nb, hop, Fr, T < 1");
     if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return fail(WV_EINVAL, "Fr is not ceil(T / hop)");      // Fr = ceil(T / hop), as the nets' latents have
-    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0");               // launch_head16's gate
+    if (!wv::head16_covers(D, nb, hop, false)) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0");               // launch_head16's gate
     Tmp t;
     wv::H16Weight w;
     const std::vector<uint16_t> q = wv::pack_head16(wc, D, nb, hop, &w);
@@ -319,7 +319,7 @@ int wv_h16_head_frames(const float* lat, const float* wc, const float* bc, const
                        int Fr, int T, void* stream) {
     if (!lat || !wc || !bc || !fsum || B < 1 || D < 1 || nb < 1 || hop < 1 || Fr < 1 || T < 1) return fail(WV_EINVAL, "null pointer (lat, wc, bc, fsum) or B, D, nb, hop, Fr, T < 1");
     if ((long long)(Fr - 1) * hop >= T || (long long)Fr * hop < T) return fail(WV_EINVAL, "Fr is not ceil(T / hop)");
-    if (D % 16 || D > 128 || nb % 4 || nb > 32 || hop % 32 || hop > 2016) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, hop <= 2016");   // launch_head16_frames' gate
+    if (!wv::head16_covers(D, nb, hop, true)) return fail(WV_EINVAL, "head limits: D % 16 == 0, D <= 128, nb % 4 == 0, nb <= 32, hop % 32 == 0, hop <= 2016");   // launch_head16_frames' gate
     Tmp t;
     wv::H16Weight w;
     const std::vector<uint16_t> q = wv::pack_head16(wc, D, nb, hop, &w);

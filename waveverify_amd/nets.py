@@ -147,13 +147,19 @@ class HipNet:
         return self.cfg.hop_length
 
     # ------------------------------------------------------------------ forward passes
+    def _entry(self, base: str, precision: str):
+        """The library's entry point `base` in the given precision mode -> (function, its name for error messages)."""
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16'")
+        name = base + ("_f16" if precision == "f16" else "")
+        return getattr(self._lib, name), name
+
     def generator(self, x: torch.Tensor, msg: torch.Tensor, add_input: bool = False, precision: str = "f32") -> torch.Tensor:
         """delta = G(x, msg) [B,1,T]; with add_input the watermarked audio delta + x
         (model/watermarking.py:423-441).  precision="f16": the f16-operand / f32-accumulate throughput mode (csrc/wv_h16.hip)."""
         if self.cfg.kind != "generator":
             raise RuntimeError("not a generator")
-        if precision not in ("f32", "f16"):
-            raise ValueError("precision must be 'f32' or 'f16'")
+        fn, name = self._entry("wv_generator_forward", precision)
         x = self._prep(x)
         B, _, T = x.shape
         msg = msg.to(self.device).float().contiguous()          # seanet.py:909 casts to float
@@ -165,11 +171,9 @@ class HipNet:
         out = torch.empty_like(x)
         with torch.cuda.device(self.device):
             ws = self._workspace(B, T)
-            fn = self._lib.wv_generator_forward_f16 if precision == "f16" else self._lib.wv_generator_forward
             _lib.check(fn(
                 self._h, x.data_ptr(), msg.data_ptr(), msg.shape[0], out.data_ptr(),
-                int(add_input), B, T, ws.data_ptr(), ws.numel(), _lib.stream()),
-                "wv_generator_forward" + ("_f16" if precision == "f16" else ""))
+                int(add_input), B, T, ws.data_ptr(), ws.numel(), _lib.stream()), name)
         return out
 
     def _head(self, x, want_logits: bool, want_mean: bool, precision: str = "f32"):
@@ -180,19 +184,16 @@ class HipNet:
         mean = torch.empty((B, nb), dtype=torch.float32, device=self.device) if want_mean else None
         with torch.cuda.device(self.device):
             ws = self._workspace(B, T)
-            if precision not in ("f32", "f16"):
-                raise ValueError("precision must be 'f32' or 'f16'")
+            fn, name = self._entry(f"wv_{self.cfg.kind}_forward", precision)
             if self.cfg.kind == "detector":
-                fn = self._lib.wv_detector_forward_f16 if precision == "f16" else self._lib.wv_detector_forward
                 _lib.check(fn(
                     self._h, x.data_ptr(), logits.data_ptr() if want_logits else None,
                     mean.data_ptr() if want_mean else None, B, T, ws.data_ptr(), ws.numel(),
-                    _lib.stream()), "wv_detector_forward" + ("_f16" if precision == "f16" else ""))
+                    _lib.stream()), name)
             elif self.cfg.kind == "locator":
-                fn = self._lib.wv_locator_forward_f16 if precision == "f16" else self._lib.wv_locator_forward
                 _lib.check(fn(
                     self._h, x.data_ptr(), logits.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
-                    _lib.stream()), "wv_locator_forward" + ("_f16" if precision == "f16" else ""))
+                    _lib.stream()), name)
             else:
                 raise RuntimeError("generator has no detection head")
         return logits, mean
@@ -213,8 +214,7 @@ class HipNet:
         -> psum [W, nbits] = sum over t in [keep_lo, keep_hi) of sigmoid(logit); written into `psum` when given."""
         if self.cfg.kind != "detector":
             raise RuntimeError("not a detector")
-        if precision not in ("f32", "f16"):
-            raise ValueError("precision must be 'f32' or 'f16'")
+        fn, name = self._entry("wv_detector_forward_windowed", precision)
         x = self._prep(x)
         W, _, L = x.shape
         lo = torch.as_tensor(keep_lo, dtype=torch.int32).reshape(-1).to(self.device)
@@ -227,9 +227,8 @@ class HipNet:
             raise ValueError(f"psum must be a contiguous float32 [{W},{self.cfg.head_bits}] tensor")
         with torch.cuda.device(self.device):
             ws = self._workspace(W, L)
-            fn = self._lib.wv_detector_forward_windowed_f16 if precision == "f16" else self._lib.wv_detector_forward_windowed
             _lib.check(fn(self._h, x.data_ptr(), lo.data_ptr(), hi.data_ptr(), psum.data_ptr(), W, L, ws.data_ptr(), ws.numel(),
-                          _lib.stream()), "wv_detector_forward_windowed" + ("_f16" if precision == "f16" else ""))
+                          _lib.stream()), name)
         return psum
 
     def detector_frame_sums(self, x: torch.Tensor, gate: Optional[torch.Tensor] = None, gate_thr: float = 0.0, precision: str = "f32",
@@ -240,8 +239,7 @@ class HipNet:
         No logits are stored; two runs agree bit for bit."""
         if self.cfg.kind != "detector":
             raise RuntimeError("not a detector")
-        if precision not in ("f32", "f16"):
-            raise ValueError("precision must be 'f32' or 'f16'")
+        fn, name = self._entry("wv_detector_forward_frames", precision)
         x = self._prep(x)
         B, _, T = x.shape
         nb, Fr = self.cfg.head_bits, -(-T // self.hop_length)
@@ -255,9 +253,8 @@ class HipNet:
             raise ValueError(f"out must be a contiguous float32 [{B},{nb + 1},{Fr}] tensor")
         with torch.cuda.device(self.device):
             ws = self._workspace(B, T)
-            fn = self._lib.wv_detector_forward_frames_f16 if precision == "f16" else self._lib.wv_detector_forward_frames
             _lib.check(fn(self._h, x.data_ptr(), _lib.ptr(gate), float(gate_thr), out.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
-                          _lib.stream()), "wv_detector_forward_frames" + ("_f16" if precision == "f16" else ""))
+                          _lib.stream()), name)
         return out
 
     def locator(self, x: torch.Tensor, precision: str = "f32") -> torch.Tensor:
