@@ -14,6 +14,9 @@
  *   wv_locator_forward    Locator.forward              model/locator.py:268-299
  *   wv_window_* / wv_session_advance / wv_detector_forward_windowed
  *                         not in the reference: windowed long-form and live-session execution
+ *   wv_loudness / wv_pool_sample
+ *                         the data path of scripts/train.py:440-475 (audiotools' AudioDataset: a random excerpt,
+ *                         re-drawn until its BS.1770 loudness exceeds the cutoff), as a restatement of the standard
  *   wv_model_set_param*   nn.Module.load_state_dict on the stripped / parametrized key layouts
  *                         waveverify/core.py:324-426, scripts/train.py:1589-1676
  *   wv_op_*               the fused units of modules/seanet.py + modules/conv.py, exported one by
@@ -610,6 +613,38 @@ size_t wv_metrics_stoi_workspace_bytes(int B, int T, int up, int down, int L, in
 int wv_metrics_stoi(const float* reference, const float* estimate, int B, int T, const float* kernels, int up, int down, int L, int width,
                     const float* basis, double* stoi, int* frames, int* kept_idx, float* tob, void* workspace, size_t workspace_bytes,
                     void* stream);
+
+/* ==== csrc/wv_loudness.hip: ITU-R BS.1770-4 gated loudness of windows of one arena, and the loudness-gated batch draw ---------
+ * Not the reference's own arithmetic (it measures through audiotools / pyloudnorm, scripts/train.py:440-475): a restatement of the
+ * published standard; the constants and the float64 statement are in waveverify_amd/loudness.py.  One channel.
+ *
+ * wv_loudness measures N windows of T samples that live anywhere in the f32 arena `pool` (they may overlap; a plain batch [B,1,T] is
+ * starts[b] = b T).  Device pointers:
+ *   starts  [N] int64: sample offset of a window in pool
+ *   lens    [N] int32: its valid samples, clamped to [0, T]; the rest of the window counts as zeros, and nothing at or past
+ *           pool + starts + lens is read
+ *   table   12 doubles from loudness.device_table(fs): the K-weighting as 2 x 6 [b0 b1 b2 1 a1 a2] (shelf, then high-pass; scipy's sos
+ *           layout), computed on the host in float64
+ * fs % 10 == 0, 4 (fs / 10) <= T <= 2^30.  The filter state is zero at every window's first sample.  Outputs:
+ *   lufs     [N] double: -0.691 + 10 log10(mean z of the blocks past both gates), -70.0 where no block passes the absolute gate
+ *   sub      [N][T / (fs / 10)] double: sum of squares of the K-weighted signal over each whole 100 ms sub-block; block j is
+ *            sub-blocks j..j+3, z_j their sum / (4 fs / 10)
+ *   filtered optional [N][T] float: the K-weighted signal (f64 rounded once); NULL = not written
+ * starts, table, lufs and sub on 8-byte boundaries.  A lane per window runs the recurrence sample by sample in f64 in scipy.signal.sosfilt's
+ * order of operations (the nearly double high-pass pole makes every other order differ from it by 1e-11 .. 4e-10 where only the filter
+ * rings); the lanes of a wave share coalesced loads through LDS in chunks of wv_loudness_chunk() samples.  Sums in sample and block order,
+ * no atomics: runs are bit-equal and a window's numbers depend neither on N nor on its row.  The kernel keeps its intermediates in LDS;
+ * the workspace is reserved (its query gives 0 for a refused shape), and one shorter than the query is a bad argument like the others:
+ * WV_EINVAL, nothing written.
+ *
+ * wv_pool_sample: starts, lens [B][tries], lufs [B][tries] double or NULL.  choice[b] = the first try k with lufs[b][k] > cutoff, else
+ * tries - 1 (lufs == NULL: 0); out [B,1,T] float = window (b, choice[b]) copied, zeros past its length.  One launch; B <= 65535. */
+int wv_loudness_chunk(void);
+size_t wv_loudness_workspace_bytes(int N, int T, int fs);
+int wv_loudness(const float* pool, const int64_t* starts, const int32_t* lens, int N, int T, int fs, const double* table, double* lufs,
+                double* sub, float* filtered, void* workspace, size_t workspace_bytes, void* stream);
+int wv_pool_sample(const float* pool, const int64_t* starts, const int32_t* lens, const double* lufs, int B, int tries, int T, double cutoff,
+                   float* out, int32_t* choice, void* stream);
 
 /* ==== csrc/wv_aug.hip: temporal augmentations of the training step ------------------------------------
  * One bandwidth-bound pass that replaces the reference's per-clip / per-segment Python loops and its GPU->CPU->GPU

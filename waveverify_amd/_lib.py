@@ -180,6 +180,10 @@ SIGNATURES = {
     "wv_metrics_sisnr": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP, C.c_size_t, _VP]),
     "wv_metrics_stoi_workspace_bytes": (C.c_size_t, [C.c_int] * 6),
     "wv_metrics_stoi": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP] + [C.c_int] * 4 + [_VP] * 6 + [C.c_size_t, _VP]),
+    "wv_loudness_chunk": (C.c_int, []),
+    "wv_loudness_workspace_bytes": (C.c_size_t, [C.c_int] * 3),
+    "wv_loudness": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_size_t, _VP]),
+    "wv_pool_sample": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, _VP, _VP, _VP]),
     "wv_aug_localize_sequence": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP,
                                            _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_aug_backward": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),

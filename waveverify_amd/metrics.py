@@ -11,6 +11,7 @@ Per-clip forms for a validation pass, fused on the GPU (csrc/wv_metrics.hip), on
     miou = miou_per_clip(locator_out, mask)                    # [B] float64, from iou_counts(...) -> [B,4] int32
     sisnr = SISNR()(estimate, reference)                       # [B] float64 dB; SISNR().mean(...) is the reference's scalar
     stoi = STOI()(estimate, reference, sample_rate=16000)      # [B] float64 (csrc/wv_stoi.hip; the algorithm in stoi.py)
+    lufs = Loudness()(x, sample_rate=16000)                    # [B] float64 LUFS (csrc/wv_loudness.hip; the algorithm in loudness.py)
 
 Device tensors go through the kernels; CPU tensors take a torch route with the same arithmetic (f64 sums, then the reference's f32
 finish for the bit decision), so host-only callers need no GPU.  `BER` and `MIOU` above stay the reference's own formulation.
@@ -250,3 +251,64 @@ class STOI:
 
     def mean(self, estimates: torch.Tensor, references: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
         return self(estimates, references, sample_rate).mean()
+
+
+def loudness_windows(arena: torch.Tensor, starts: torch.Tensor, lens: torch.Tensor, T: int, sample_rate: int,
+                     want_filtered: bool = False):
+    """wv_loudness on N windows of T samples of one flat float32 device arena -> (lufs [N] float64, sub [N, T // (fs / 10)] float64,
+    filtered [N, T] float32 or None).  starts [N] int64 sample offsets, lens [N] int32 valid samples (the rest of a window counts as
+    zeros and is not read), both on the arena's device."""
+    from . import loudness as L
+    lib = _lib.load()
+    N, T, fs = int(starts.numel()), int(T), int(sample_rate)
+    h = L.sub_block(fs)
+    if T < L.BLOCK_SUBS * h:
+        raise ValueError(f"loudness: {T} samples at {fs} Hz are fewer than one gating block of {L.BLOCK_SUBS} sub-blocks ({L.BLOCK_SUBS * h})")
+    if not (arena.is_cuda and arena.dtype == torch.float32 and arena.is_contiguous() and starts.dtype == torch.int64 and lens.dtype == torch.int32
+            and starts.device == arena.device and lens.device == arena.device and lens.numel() == N and starts.is_contiguous() and lens.is_contiguous()):
+        raise ValueError("loudness_windows: a contiguous float32 device arena with int64 starts and int32 lens [N] on its device is required")
+    table = L.device_table(fs, arena.device)
+    lufs = torch.empty(N, dtype=torch.float64, device=arena.device)
+    sub = torch.empty(N, T // h, dtype=torch.float64, device=arena.device)
+    filtered = torch.empty(N, T, dtype=torch.float32, device=arena.device) if want_filtered else None
+    ws = _lib.scratch(int(lib.wv_loudness_workspace_bytes(N, T, fs)), arena.device)
+    _lib.check(lib.wv_loudness(arena.data_ptr(), starts.data_ptr(), lens.data_ptr(), N, T, fs, table.data_ptr(), lufs.data_ptr(), sub.data_ptr(),
+                               _lib.ptr(filtered), ws.data_ptr(), ws.numel(), _lib.stream(arena.device)), "wv_loudness")
+    return lufs, sub, filtered
+
+
+class Loudness:
+    """Gated loudness of every clip in LUFS per ITU-R BS.1770-4 (one channel): K-weighting, 400 ms blocks at 75 % overlap, the
+    absolute gate at -70 LUFS and the relative gate 10 LU under the gated mean; loudness.MIN_LOUDNESS (-70.0) where nothing passes the
+    absolute gate.  It is the level measure next to SI-SNR and STOI -- how much did embed() change a file's level -- and the gate of
+    data.ClipPool.sample.  The constants and the algorithm are in waveverify_amd/loudness.py: a restatement of the published standard,
+    parity with audiotools' `Meter` (what the reference's data loader measures with) stays unpinned.
+
+        Loudness()(x, sample_rate=16000) -> [B] float64 on x's device,  x [B, 1, T], T >= 0.4 s, sample_rate % 10 == 0
+
+    Device tensors go through csrc/wv_loudness.hip (one launch; the table cached per sample rate and device), CPU tensors through the
+    float64 host route.  `.last_sub` holds the [B, T // (fs / 10)] sub-block energies."""
+
+    def __init__(self):
+        self.last_sub: Optional[torch.Tensor] = None
+
+    def __call__(self, x: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        from . import loudness as L
+        if x.dim() != 3 or x.shape[1] != 1:
+            raise ValueError(f"x must be [B, 1, T], got {tuple(x.shape)}")
+        B, _, T = x.shape
+        h = L.sub_block(sample_rate)
+        if T < L.BLOCK_SUBS * h:
+            raise ValueError(f"loudness: {T} samples at {sample_rate} Hz are fewer than one gating block of {L.BLOCK_SUBS} sub-blocks ({L.BLOCK_SUBS * h})")
+        x = _f32(x)
+        if x.is_cuda:
+            starts = torch.arange(B, dtype=torch.int64, device=x.device) * T
+            lens = torch.full((B,), T, dtype=torch.int32, device=x.device)
+            out, self.last_sub, _ = loudness_windows(x.reshape(-1), starts, lens, T, sample_rate)
+            return out
+        sub = L.sub_block_energies(L.k_filter(x[:, 0].numpy(), int(sample_rate)), int(sample_rate))
+        self.last_sub = torch.from_numpy(sub)
+        return torch.tensor([L.gate(s, int(sample_rate)) for s in sub], dtype=torch.float64)
+
+    def mean(self, x: torch.Tensor, sample_rate: int = 16000) -> torch.Tensor:
+        return self(x, sample_rate).mean()

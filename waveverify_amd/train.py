@@ -1278,7 +1278,23 @@ class WatermarkTrainer:
             out["stft/loss"], out["mel/loss"] = stft, mel
         return out
 
-    def validate(self, x: torch.Tensor, msg: torch.Tensor, eval_effects=None, augment: bool = True, seed: int = 0, stoi: bool = False):
+    def fit(self, pool, steps: int, batch: int, seed: int = 0, duration: float = 1.0, **sample_kwargs):
+        """`steps` training steps on batches drawn from a data.ClipPool -> the list of step() outputs.  Per step: pool.sample(batch,
+        duration, rng, **sample_kwargs) with ONE numpy generator seeded with `seed` for the whole run, the messages [batch,
+        msg_dimension] as torch.randint(0, 2, ...) from ONE CPU torch.Generator seeded with `seed`, then the unchanged step()."""
+        if pool.sample_rate != self.aug.sample_rate:
+            raise ValueError(f"fit: the pool is at {pool.sample_rate} Hz, the trainer at {self.aug.sample_rate} Hz")
+        rng = np.random.default_rng(seed)
+        gen = torch.Generator().manual_seed(int(seed))
+        outs = []
+        for _ in range(int(steps)):
+            x, _ = pool.sample(batch, duration, rng=rng, **sample_kwargs)
+            msg = torch.randint(0, 2, (int(batch), self.G.cfg.msg_dimension), generator=gen).float()
+            outs.append(self.step(x, msg.to(x.device)))
+        return outs
+
+    def validate(self, x: torch.Tensor, msg: torch.Tensor, eval_effects=None, augment: bool = True, seed: int = 0, stoi: bool = False,
+                 loudness: bool = False):
         """The reference's validation pass for the terms that live on this path (model/watermarking.py:443-483 `_forward_valid`,
         :755-809 `_evaluate_single_effect`, scripts/train.py:956-1091 `val_loop`), without a gradient:
 
@@ -1295,6 +1311,10 @@ class WatermarkTrainer:
         With stoi=True the result gains "STOI", the batch mean of metrics.STOI of the watermarked clips against the originals at the
         augmenter's sample rate (the reference's other imperceptibility number, scripts/train.py:1081), and per_clip gains "stoi": [B]
         float64; a clip too short for it gives pystoi's 1e-5 and RuntimeWarning.  The default leaves the result key for key as it was.
+
+        With loudness=True the result gains "LUFS delta", the batch mean of lufs(wm) - lufs(x) by metrics.Loudness at the augmenter's
+        sample rate (ITU-R BS.1770-4 gated loudness: how much embedding changed the level), and per_clip gains "lufs_in" and "lufs_wm":
+        [B] float64.  Clips under 0.4 s raise ValueError.  A restatement of the standard: parity with audiotools' `Meter` stays unpinned.
 
         Absent on purpose: PESQ, which the reference takes from the pesq package (ITU arithmetic this project does not restate), and
         the adversarial terms (no discriminator on this path).  STOI is this project's restatement of the published algorithm (stoi.py):
@@ -1361,10 +1381,16 @@ class WatermarkTrainer:
                 stoi_metric = STOI()
                 stoi_d = stoi_metric(wm, x, sample_rate=self.aug.sample_rate)
                 stoi_frames = stoi_metric.last_frames
+            lufs_in = lufs_wm = None
+            if loudness:
+                from .metrics import Loudness
+                lufs_in, lufs_wm = Loudness()(x, self.aug.sample_rate), Loudness()(wm, self.aug.sample_rate)
             # one trip to the host for every count of the pass
             errors, valid, counts, sisnr = (t.cpu().numpy() for t in (torch.stack(errors), torch.stack(valid), torch.stack(counts), sisnr))
             if stoi:
                 stoi_d, stoi_frames = stoi_d.cpu().numpy(), stoi_frames.cpu().numpy()
+            if loudness:
+                lufs_in, lufs_wm = lufs_in.cpu().numpy(), lufs_wm.cpu().numpy()
         finally:
             np.random.set_state(rng[0])
             _random.setstate(rng[1])
@@ -1396,4 +1422,7 @@ class WatermarkTrainer:
                 warnings.warn(_stoi.SHORT_MESSAGE, RuntimeWarning)
             out["STOI"] = float(stoi_d.mean())
             out["per_clip"]["stoi"] = stoi_d
+        if loudness:
+            out["LUFS delta"] = float((lufs_wm - lufs_in).mean())
+            out["per_clip"]["lufs_in"], out["per_clip"]["lufs_wm"] = lufs_in, lufs_wm
         return out
