@@ -663,9 +663,20 @@ def test_window_gather_and_scatter_contracts():
 # ================================================================== whole-test reuse under poisoned workspaces
 # The package allocates every workspace and saved buffer through waveverify_amd._lib.scratch; under the `poison` fixture each one is an
 # exact-size 0xFF arena between guards, checked when the test ends.  These run existing tests (their oracles, their bars) that way.
+def _fresh_nets(fn, *args):
+    """test_gpu_window_fuzz keeps its nets from test to test; here they are built anew, so that their workspaces come from the fixture."""
+    import test_gpu_window_fuzz as TF
+    TF._net.cache_clear()
+    try:
+        fn(*args)
+    finally:
+        TF._net.cache_clear()
+
+
 def _reuse():
     import test_gpu_train as TT
     import test_gpu_window as TW
+    import test_gpu_window_fuzz as TF
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     cases = [
         ("half", lambda: TT.test_half_block_gradients_vs_oracle(5, 96, 36)),
@@ -684,6 +695,8 @@ def _reuse():
         ("window detect session", lambda: TW.test_detect_session({k: TW._net(k) for k in TW.KINDS})),
         ("window f16 detect", lambda: TW.test_windowed_f16_detect_vs_the_oracle({k: TW._net(k) for k in TW.KINDS})),
     ]
+    cases += [("window small net", lambda: _fresh_nets(TF.test_windowed_forwards_vs_float64, next(c for c in TF.EXACT if c[0] == "x14.detector"))),
+              ("window small-net session", lambda: _fresh_nets(TF.test_sessions_vs_float64, next(c for c in TF.EXACT if c[0] == "x6.generator")))]
     for args in [(4, 64, 128, 16000, 4, 2, True), (3, 128, 256, 8000, 8, 4, True), (2, 256, 512, 2000, 10, 5, True),
                  (2, 512, 1024, 400, 16, 8, True), (3, 96, 64, 404, 5, 1, False), (2, 64, 128, 36, 7, 3, True), (3, 32, 32, 50, 5, 1, True),
                  (2, 32, 64, 1001, 16, 8, True), (2, 24, 40, 7, 5, 1, False)]:
