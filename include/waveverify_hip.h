@@ -718,6 +718,28 @@ int wv_native_downmix_resample(const float* x, const float* kernels_t, float* y,
 int wv_native_upsample_add(const float* x, const float* delta, const float* kernels_t, float* out, int B, int C, int T16, int Tn, int orig, int nw, int L,
                            int width, float gain, void* stream);
 
+/* ---- the same two ends for live sessions: S streams in lockstep, one launch per end and push, the state on the device.
+ * A stage's sequence is cat(history[s][0 .. hv), new[s][0 .. n)), never materialised.  Output 0 of a call is phase 0 of the first phase group the
+ * stream has not emitted yet, and its first tap is sequence sample -pad (0 <= pad <= width; pad > 0 only while the stream's start lies inside the
+ * filter): output m = g * nw + f is the file kernels' fmaf chain over sequence samples g * orig - pad + j, j < L, zero outside the sequence.  The
+ * caller (waveverify_amd/native_session.py) asks only for outputs all of whose taps have arrived, or, at flush, for the rest with zeros past the end.
+ * Next-state buffers are second buffers, never their sources; a next state is the sequence's last samples: drop + hv2 == hv + n.  Any of n, n_out,
+ * nr, k, hv2, rv2 may be 0 (its pointer may then be null); with nothing to write nothing is launched.
+ *   front:  hist, hist_out [S][hcap] hold channel MEANS; x [S][C][n] new planar samples, whose mean is formed as wv_native_downmix_resample forms
+ *           it; y [S][n_out]; hist_out[s][0 .. hv2) = sequence samples [drop, drop + hv2).
+ *   back:   rhist, rhist_out [S][rcap] and r [S][nr] the 16 kHz residual (rhist_out = its samples [rdrop, rdrop + rv2), rdrop + rv2 == rv + nr);
+ *           pend, pend_out [S][C][pcap] the delay line of original samples not yet emitted and x [S][C][n] the new ones;
+ *           out[s][c][i] = cat(pend[s][c][0 .. pv), x[s][c])[i] + gain * u[s][i] for i < k <= pv + n, both roundings kept; pend_out[s][c] = that
+ *           sequence's samples [k, pv + n), at most pcap of them.
+ * Refused with WV_EINVAL, nothing launched or written: a null pointer that is needed, a next-state buffer equal to its source, S outside [1, 65535],
+ * C outside [1, 64], orig, nw or L < 1, width < 0, pad outside [0, width], a valid or next length outside [0, capacity], a negative count, more
+ * outputs than (ceil((pad + sequence) / orig) + 1) * nw, k > pv + n, or a 256-output tile whose input window passes 64 KB of LDS. */
+int wv_native_session_down(const float* hist, int hcap, int hv, const float* x, int n, const float* kernels_t, float* y, int n_out, int pad,
+                           float* hist_out, int drop, int hv2, int S, int C, int orig, int nw, int L, int width, void* stream);
+int wv_native_session_up_add(const float* rhist, int rcap, int rv, const float* r, int nr, const float* kernels_t, const float* pend, int pcap, int pv,
+                             const float* x, int n, float* out, int k, int pad, float gain, float* pend_out, float* rhist_out, int rdrop, int rv2,
+                             int S, int C, int orig, int nw, int L, int width, void* stream);
+
 /* ==== csrc/wv_fx_time.hip: plain-arithmetic time-domain effects ----------------------------------------------------------------
  * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
  * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding

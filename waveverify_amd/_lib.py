@@ -195,6 +195,9 @@ SIGNATURES = {
     "wv_fx_resample": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_native_downmix_resample": (C.c_int, [_VP, _VP, _VP] + [C.c_int] * 8 + [_VP]),
     "wv_native_upsample_add": (C.c_int, [_VP, _VP, _VP, _VP] + [C.c_int] * 8 + [C.c_float, _VP]),
+    "wv_native_session_down": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP] + [C.c_int] * 8 + [_VP]),
+    "wv_native_session_up_add": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int,
+                                           C.c_float, _VP, _VP] + [C.c_int] * 8 + [_VP]),
     "wv_fx_pointwise": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
     "wv_fx_median": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_shush": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),

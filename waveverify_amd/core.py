@@ -17,7 +17,7 @@ from typing import Dict, List, Mapping, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import localize, native, ops, session, window
+from . import localize, native, native_session, ops, session, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
@@ -263,15 +263,27 @@ class WaveVerify:
             return torch.sigmoid(out).squeeze(1)
         return [torch.sigmoid(o) for o in out]
 
-    def open_embed_session(self, watermark_ids) -> session.EmbedSession:
-        """Live watermarking of len(watermark_ids) streams in lockstep (session.py)."""
-        return session.EmbedSession(self._need("generator"), self._messages(watermark_ids), self.generator_precision)
+    def open_embed_session(self, watermark_ids, sample_rate: int = 16000, channels: int = 1, strength: float = 1.0):
+        """Live watermarking of len(watermark_ids) streams in lockstep.  With the defaults: session.EmbedSession, 16 kHz mono, push(x [S, n]).
+        Any other sample_rate, channels or strength: native_session.NativeEmbedSession, push(x [S, C, n]) -> [S, C, k] at the stream's own rate
+        and channel count, the arithmetic of embed_native_batch; a rate is refused as embed(native=True) refuses it."""
+        gen, msg = self._need("generator"), self._messages(watermark_ids)
+        if (int(sample_rate), int(channels), float(strength)) == (self.sample_rate, 1, 1.0):
+            return session.EmbedSession(gen, msg, self.generator_precision)
+        return native_session.NativeEmbedSession(gen, msg, sample_rate, channels, strength, self.generator_precision)
 
-    def open_detect_session(self, n: int = 1) -> session.DetectSession:
-        return session.DetectSession(self._need("detector"), n, self.detector_precision)
+    def open_detect_session(self, n: int = 1, sample_rate: int = 16000, channels: int = 1):
+        """session.DetectSession, or for another rate or channel count native_session.NativeDetectSession (push(x [n, C, k]))."""
+        if (int(sample_rate), int(channels)) == (self.sample_rate, 1):
+            return session.DetectSession(self._need("detector"), n, self.detector_precision)
+        return native_session.NativeDetectSession(self._need("detector"), n, sample_rate, channels, self.detector_precision)
 
-    def open_locate_session(self, n: int = 1) -> session.LocateSession:
-        return session.LocateSession(self._need("locator"), n, self.locator_precision)
+    def open_locate_session(self, n: int = 1, sample_rate: int = 16000, channels: int = 1):
+        """session.LocateSession, or for another rate or channel count native_session.NativeLocateSession, whose logits stay on the 16 kHz
+        time line."""
+        if (int(sample_rate), int(channels)) == (self.sample_rate, 1):
+            return session.LocateSession(self._need("locator"), n, self.locator_precision)
+        return native_session.NativeLocateSession(self._need("locator"), n, sample_rate, channels, self.locator_precision)
 
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],

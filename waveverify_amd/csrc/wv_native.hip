@@ -117,3 +117,147 @@ extern "C" int wv_native_upsample_add(const float* x, const float* delta, const 
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
+
+// ---- live sessions ---------------------------------------------------------------------------------------------------
+// The same two ends for a stream that arrives in pushes.  A stage's sequence is cat(history[0 .. hv), new[0 .. n)), never materialised: sample
+// p is read from the history when p < hv, else from the new buffer.  Output 0 of a call is phase 0 of the first phase group not yet emitted;
+// its first tap is sequence sample -pad (pad > 0 only while the stream's own start is still inside the filter), so output m = g * nw + f reads
+// sequence samples g * orig - pad + j, zero outside [0, hv + n): the chain of the file kernels over the same values.  One workgroup is one
+// stream x 256 outputs as above; the workgroups past the last tile write the next state into second buffers.
+namespace wv {
+
+// The front stage's sequence: the history holds channel MEANS, the new samples are C planar channels whose mean is formed as the file kernel
+// forms it.
+struct SessionMono {
+    const float* h;
+    const float* xs;
+    int hv, C;
+    long long n;
+    __device__ float operator()(long long p) const {
+        if (p < 0 || p >= hv + n) return 0.f;
+        if (p < hv) return h[(size_t)p];
+        const size_t q = (size_t)(p - hv);
+        float v = xs[q];
+        for (int c = 1; c < C; ++c) v += xs[(size_t)c * (size_t)n + q];
+        return v / (float)C;
+    }
+};
+
+__global__ __launch_bounds__(256) void native_session_down_kernel(const float* __restrict__ hist, int hcap, int hv, const float* __restrict__ x, int n,
+                                                                   const float* __restrict__ Kt, float* __restrict__ y, int n_out, int pad,
+                                                                   float* __restrict__ hist_out, int drop, int hv2, int tiles, int C, int orig, int nw,
+                                                                   int L) {
+    extern __shared__ float win[];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const SessionMono seq{hist + (size_t)s * hcap, x + (size_t)s * C * (size_t)n, hv, C, (long long)n};
+    if ((int)blockIdx.x >= tiles) {                                    // the next history: sequence samples [drop, drop + hv2)
+        const int j = ((int)blockIdx.x - tiles) * NATIVE_TILE + tid;
+        if (j < hv2) hist_out[(size_t)s * hcap + j] = seq((long long)drop + j);
+        return;
+    }
+    const int m0 = blockIdx.x * NATIVE_TILE;
+    const int n_lo = m0 / nw, cnt = min(NATIVE_TILE, n_out - m0), n_hi = (m0 + cnt - 1) / nw;
+    const long long p_base = (long long)n_lo * orig - pad;
+    const int wlen = (n_hi - n_lo) * orig + L;
+    for (int i = tid; i < wlen; i += 256) win[i] = seq(p_base + i);
+    __syncthreads();
+    if (tid < cnt) y[(size_t)s * n_out + m0 + tid] = native_chain(Kt, win, m0 + tid, n_lo, orig, nw, L);
+}
+
+__global__ __launch_bounds__(256) void native_session_up_add_kernel(const float* __restrict__ rhist, int rcap, int rv, const float* __restrict__ r, int nr,
+                                                                     const float* __restrict__ Kt, const float* __restrict__ pend, int pcap, int pv,
+                                                                     const float* __restrict__ x, int n, float* __restrict__ out, int k, int pad, float gain,
+                                                                     float* __restrict__ pend_out, int pv2, float* __restrict__ rhist_out, int rdrop, int rv2,
+                                                                     int tiles, int rblocks, int C, int orig, int nw, int L) {
+    extern __shared__ float win[];
+    const int s = blockIdx.y, tid = threadIdx.x, bx = blockIdx.x;
+    const float* rh = rhist + (size_t)s * rcap;
+    const float* rs = r + (size_t)s * (size_t)nr;
+    const long long r_end = (long long)rv + nr;
+    auto resid = [&](long long p) -> float { return (p < 0 || p >= r_end) ? 0.f : p < rv ? rh[(size_t)p] : rs[(size_t)(p - rv)]; };
+    // sample i of channel c of cat(pending[0 .. pv), x[0 .. n))
+    auto orig_ch = [&](int c, long long i) -> float {
+        const size_t row = (size_t)s * C + c;
+        return i < pv ? pend[row * pcap + (size_t)i] : x[row * (size_t)n + (size_t)(i - pv)];
+    };
+    if (bx >= tiles + rblocks) {                                       // the next delay line: the originals not yet emitted, [k, k + pv2)
+        const int j = (bx - tiles - rblocks) * NATIVE_TILE + tid;
+        if (j < pv2)
+            for (int c = 0; c < C; ++c) pend_out[((size_t)s * C + c) * pcap + j] = orig_ch(c, (long long)k + j);
+        return;
+    }
+    if (bx >= tiles) {                                                 // the next residual history
+        const int j = (bx - tiles) * NATIVE_TILE + tid;
+        if (j < rv2) rhist_out[(size_t)s * rcap + j] = resid((long long)rdrop + j);
+        return;
+    }
+    const int m0 = bx * NATIVE_TILE;
+    const int n_lo = m0 / nw, cnt = min(NATIVE_TILE, k - m0), n_hi = (m0 + cnt - 1) / nw;
+    const long long p_base = (long long)n_lo * orig - pad;
+    const int wlen = (n_hi - n_lo) * orig + L;
+    for (int i = tid; i < wlen; i += 256) win[i] = resid(p_base + i);
+    __syncthreads();
+    if (tid >= cnt) return;
+    const int m = m0 + tid;
+    const float gu = gain * native_chain(Kt, win, m, n_lo, orig, nw, L);
+    for (int c = 0; c < C; ++c) out[((size_t)s * C + c) * (size_t)k + m] = orig_ch(c, m) + gu;
+}
+
+}  // namespace wv
+
+// The refusals both session calls share.  seq = the resampler's sequence length (history + new), n_out what it is asked for.
+static int native_session_check(const char* who, int S, int C, int orig, int nw, int L, int width, int pad, long long seq, int n_out, size_t* smem) {
+    const std::string w(who);
+    if (S < 1 || S > 65535) return fail(WV_EINVAL, w + ": S outside [1, 65535]");
+    if (C < 1 || C > 64) return fail(WV_EINVAL, w + ": C outside [1, 64]");
+    if (orig < 1 || nw < 1 || L < 1 || width < 0) return fail(WV_EINVAL, w + ": orig, nw or L < 1, or width < 0");
+    if (pad < 0 || pad > width) return fail(WV_EINVAL, w + ": pad outside [0, width]");
+    if (n_out < 0 || (long long)n_out > ((seq + pad + orig - 1) / orig + 1) * nw) return fail(WV_EINVAL, w + ": outputs < 0 or more than (ceil((pad + history + new) / orig) + 1) * nw");
+    const long long bytes = wv::native_window(orig, nw, L) * (long long)sizeof(float);
+    if (bytes > (long long)wv::NATIVE_LDS_BYTES) return fail(WV_EINVAL, w + ": the input window of a 256-output tile (" + std::to_string(bytes) + " bytes) exceeds 64 KB of LDS");
+    *smem = (size_t)bytes;
+    return WV_OK;
+}
+
+// ceil(v / 256) for any int v >= 0, without the overflow of v + 255.
+static int tiles_of(int v) { return v / wv::NATIVE_TILE + (v % wv::NATIVE_TILE != 0); }
+
+// 0 <= valid <= cap, and the next state a suffix of the sequence that fits: drop + next == valid + fresh.
+static bool session_roll_ok(int cap, int valid, int fresh, int drop, int next) {
+    return cap >= 1 && valid >= 0 && valid <= cap && fresh >= 0 && drop >= 0 && next >= 0 && next <= cap && (long long)drop + next == (long long)valid + fresh;
+}
+
+extern "C" int wv_native_session_down(const float* hist, int hcap, int hv, const float* x, int n, const float* kernels_t, float* y, int n_out, int pad,
+                                      float* hist_out, int drop, int hv2, int S, int C, int orig, int nw, int L, int width, void* stream) {
+    const char* who = "wv_native_session_down";
+    if (!hist || !hist_out || hist == hist_out || !kernels_t || (n > 0 && !x) || (n_out > 0 && !y)) return fail(WV_EINVAL, std::string(who) + ": null pointer (hist, hist_out, kernels_t; x with n > 0; y with n_out > 0), or hist_out == hist");
+    if (!session_roll_ok(hcap, hv, n, drop, hv2)) return fail(WV_EINVAL, std::string(who) + ": hcap < 1, hv or hv2 outside [0, hcap], n or drop < 0, or drop + hv2 != hv + n");
+    size_t smem = 0;
+    if (int rc = native_session_check(who, S, C, orig, nw, L, width, pad, (long long)hv + n, n_out, &smem)) return rc;
+    const int tiles = tiles_of(n_out), blocks = tiles + tiles_of(hv2);
+    if (blocks == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::native_session_down_kernel, dim3(blocks, S), dim3(256), smem, (hipStream_t)stream, hist, hcap, hv, x, n, kernels_t, y, n_out, pad,
+                       hist_out, drop, hv2, tiles, C, orig, nw, L);
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
+
+extern "C" int wv_native_session_up_add(const float* rhist, int rcap, int rv, const float* r, int nr, const float* kernels_t, const float* pend, int pcap, int pv,
+                                        const float* x, int n, float* out, int k, int pad, float gain, float* pend_out, float* rhist_out, int rdrop, int rv2,
+                                        int S, int C, int orig, int nw, int L, int width, void* stream) {
+    const char* who = "wv_native_session_up_add";
+    if (!rhist || !rhist_out || rhist == rhist_out || !pend || !pend_out || pend == pend_out || !kernels_t || (nr > 0 && !r) || (n > 0 && !x) || (k > 0 && !out))
+        return fail(WV_EINVAL, std::string(who) + ": null pointer (rhist, rhist_out, pend, pend_out, kernels_t; r with nr > 0; x with n > 0; out with k > 0), or a next-state buffer that is its source");
+    if (!session_roll_ok(rcap, rv, nr, rdrop, rv2)) return fail(WV_EINVAL, std::string(who) + ": rcap < 1, rv or rv2 outside [0, rcap], nr or rdrop < 0, or rdrop + rv2 != rv + nr");
+    const long long pv2 = (long long)pv + n - k;
+    if (pcap < 1 || pv < 0 || pv > pcap || n < 0 || k < 0 || pv2 < 0 || pv2 > pcap) return fail(WV_EINVAL, std::string(who) + ": pcap < 1, pv outside [0, pcap], n or k < 0, or pv + n - k outside [0, pcap]");
+    size_t smem = 0;
+    if (int rc = native_session_check(who, S, C, orig, nw, L, width, pad, (long long)rv + nr, k, &smem)) return rc;
+    const int tiles = tiles_of(k), rblocks = tiles_of(rv2);
+    const int blocks = tiles + rblocks + tiles_of((int)pv2);
+    if (blocks == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::native_session_up_add_kernel, dim3(blocks, S), dim3(256), smem, (hipStream_t)stream, rhist, rcap, rv, r, nr, kernels_t, pend, pcap,
+                       pv, x, n, out, k, pad, gain, pend_out, (int)pv2, rhist_out, rdrop, rv2, tiles, rblocks, C, orig, nw, L);
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}

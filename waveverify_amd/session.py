@@ -151,18 +151,19 @@ class _HipSession(StreamSession):
 
 
 class EmbedSession(_HipSession):
-    """Watermark S live streams: push(x [S, n]) -> watermarked samples of the frames completed by this push [S, 1, k]."""
+    """Watermark S live streams: push(x [S, n]) -> watermarked samples of the frames completed by this push [S, 1, k].
+    add_input=False: the generator's residual alone (what native_session.py brings back to a stream's own rate)."""
 
-    def __init__(self, net, msg, precision: str = "f32"):
+    def __init__(self, net, msg, precision: str = "f32", add_input: bool = True):
         import torch
         msg = torch.as_tensor(msg).to(net.device).float()
         if msg.dim() == 1:
             msg = msg.unsqueeze(0)
-        self.msg = msg.contiguous()
+        self.msg, self.add_input = msg.contiguous(), bool(add_input)
         super().__init__(net, msg.shape[0], precision)
 
     def _net_forward(self, win, keep):
-        return self.net.generator(win, self.msg, add_input=True, precision=self.precision)[:, :, keep:].contiguous()
+        return self.net.generator(win, self.msg, add_input=self.add_input, precision=self.precision)[:, :, keep:].contiguous()
 
     def _no_output(self):
         return self._torch.zeros((self.S, 1, 0), dtype=self._torch.float32, device=self.net.device)
