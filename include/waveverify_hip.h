@@ -772,8 +772,11 @@ int wv_fx_shush(const float* x, const float* mask_in, float* y, float* keep, flo
  * when both are > 0; the last n - 1 samples of each row are 0.  Two launches: the peaks call fills the record (WV_FX_ECHO_RECORD_BYTES,
  * 8-byte aligned: two 64-bit words, (bits of the maximum) << 32 | ~(flat position), for x then for c), the apply call reads it.
  * The backward is the reference's autograd through the correlation and both maxima; it needs x, the record of the forward and a
- * workspace of the stated size (any contents), and sums g * c in a fixed order.  Ties for a maximum are outside the contract: the
- * forward does not depend on which of two equal peaks is recorded, the backward sends the peak's gradient to the earliest. */
+ * workspace of wv_fx_echo_backward_workspace_bytes() (any contents: partial sums of g * c and partial counts of the tied peaks),
+ * and sums g * c in a fixed order.  Ties for a maximum are inside the contract: the forward does not depend on which of several equal
+ * peaks is recorded (the earliest), and the backward shares each maximum's gradient evenly among ALL positions whose magnitude equals
+ * it, as torch's autograd of a full-reduction max does (clipped audio has many); it reads only the magnitudes of the record, not the
+ * positions.  With one peak each the result is that of the recorded positions. */
 #define WV_FX_ECHO_RECORD_BYTES 16
 int wv_fx_echo_peaks(const float* x, void* rec, int rows, int T, int n, float volume, void* stream);
 int wv_fx_echo_apply(const float* x, const void* rec, float* y, int rows, int T, int n, float volume, void* stream);
@@ -790,7 +793,8 @@ int wv_fx_smooth_backward(const float* g, float* dx, int rows, int T, int w, voi
  * skipped.  sample_suppression's forward (on a copy of the input) and, on the gradient, its backward. */
 int wv_fx_scatter_zero(float* y, float* mask, const int* idx, int rows, int T, int num, void* stream);
 /* torch.nn.functional.interpolate(mode='linear', align_corners=False) from Tin to Tout samples: source coordinate
- * max(0, (m + 0.5) * Tin / Tout - 0.5) with the scale in f32 (AudioProcessor.adjust_audio_length(mode='stretch')). */
+ * max(0, (m + 0.5) * Tin / Tout - 0.5) with the scale in f32 and the multiply-add rounded once (fused), as torch's CPU kernel
+ * evaluates it (AudioProcessor.adjust_audio_length(mode='stretch')); i0 = min(int(coordinate), Tin - 1), the blend in f32. */
 int wv_fx_stretch_linear(const float* x, float* y, int rows, int Tin, int Tout, void* stream);
 
 #ifdef __cplusplus

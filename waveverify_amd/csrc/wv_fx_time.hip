@@ -2,7 +2,9 @@
 // Functions, :1504-1681 echo / pink_noise, :1873-2132 median_filter .. random_noise, :2338-2404 white_noise / shush, :190-209 the
 // linear stretch).  Unlike the sinc filters of wv_fx.hip these are pinned to the reference itself (tests/golden/effects_time.npz):
 // the pointwise ops, the median, shush and scatter-zero bit for bit, echo / smooth / stretch to the filter bar (float sums whose
-// order is not the CPU's).  This file is compiled with -ffp-contract=off: a mul followed by an add stays two roundings, as in torch.
+// order is not the CPU's), and case by case to a float64 oracle of each operation (oracle/wv_oracle_fx_time.py, tests/test_gpu_fx_time_fuzz.py).
+// This file is compiled with -ffp-contract=off: a mul followed by an add stays two roundings, as in torch; the one fused multiply-add,
+// the stretch's source coordinate, is written out as fmaf because torch's CPU kernel fuses it.
 // All kernels are bandwidth-class: [rows][T] contiguous f32 in, the same out, 16-byte accesses where the placement allows them
 // (the pointwise pass; the windowed kernels read a tile through LDS, whose fill is coalesced dwords because tiles start at any
 // sample), one launch each except echo (whole-tensor maxima first, then the apply).
@@ -244,63 +246,101 @@ __global__ __launch_bounds__(256) void echo_apply_kernel(const float* __restrict
     }
 }
 
-// Echo backward (the reference's autograd crosses the correlation and both maxima).  With s = mo / mr and S = sum(g * c) / mr over the
-// valid samples:  dx[u] = s * (g[u] + volume * g[u - n + 1])  -  S * s * sign(c[j*]) * (e_j* + volume * e_(j* + n - 1))  +  S * sign(x[i*]) * e_i*.
-// Pass 1: ECHO_PARTS partial sums of g * c, each summed in a fixed order; pass 2 adds them in index order (every workgroup, the same
-// way) and writes dx.  Without the normalisation (a maximum of 0) only the first term is left, with s = 1.
+// Echo backward (the reference's autograd crosses the correlation and both maxima).  With s = mo / mr, S = sum(g * c) / mr over the
+// valid samples, I the positions with |x| == mo and J the valid positions with |c| == mr (torch's full-reduction max shares its
+// gradient evenly among tied positions):
+//     dx[u] = s * (g[u] + volume * g[u - n + 1])  -  S * s / |J| * sum_{j in J} sign(c[j]) * (e_j + volume * e_(j + n - 1))  +  S / |I| * sum_{i in I} sign(x[i]) * e_i.
+// Pass 1: ECHO_PARTS partial sums of g * c, each summed in a fixed order, and beside them the partial counts of I and J (c is formed
+// as the forward formed it, so `==` against the record's magnitudes finds exactly the samples the forward's maxima saw); pass 2 adds
+// them in index order (every workgroup, the same way) and writes dx, testing each sample against the two magnitudes.  With one peak
+// each the divisions are by 1 and the result is what the recorded positions alone would give.  Without the normalisation (a maximum
+// of 0) only the first term is left, with s = 1.  Workspace: float parts[ECHO_PARTS], then uint32 |I| and |J| partials of the same length.
 constexpr int ECHO_PARTS = 256;
 
-__global__ __launch_bounds__(256) void echo_dot_kernel(const float* __restrict__ x, const float* __restrict__ g, float* __restrict__ parts, size_t N, int T, int n,
-                                                        float volume) {
+__global__ __launch_bounds__(256) void echo_dot_kernel(const float* __restrict__ x, const float* __restrict__ g, const unsigned long long* __restrict__ rec,
+                                                        float* __restrict__ parts, size_t N, int T, int n, float volume) {
     __shared__ float red[256];
+    __shared__ uint32_t redx[256], redc[256];
     const int tid = threadIdx.x;
+    const uint32_t bo = (uint32_t)(rec[0] >> 32), br = (uint32_t)(rec[1] >> 32);
     float acc = 0.f;
+    uint32_t nx = 0, nc = 0;
     for (size_t i = (size_t)blockIdx.x * 256 + tid; i < N; i += (size_t)gridDim.x * 256) {
         const int t = (int)(i % (size_t)T);
+        const float v = x[i];
+        nx += abs_bits(v) == bo ? 1u : 0u;
         if (t < T - n + 1) {
             const float d = volume * x[i + n - 1];
-            acc += g[i] * (x[i] + d);
+            const float c = v + d;
+            acc += g[i] * c;
+            nc += abs_bits(c) == br ? 1u : 0u;
         }
     }
     red[tid] = acc;
+    redx[tid] = nx;
+    redc[tid] = nc;
     __syncthreads();
     for (int off = 128; off > 0; off >>= 1) {
-        if (tid < off) red[tid] += red[tid + off];
+        if (tid < off) {
+            red[tid] += red[tid + off];
+            redx[tid] += redx[tid + off];
+            redc[tid] += redc[tid + off];
+        }
         __syncthreads();
     }
-    if (tid == 0) parts[blockIdx.x] = red[0];
+    if (tid == 0) {
+        uint32_t* counts = reinterpret_cast<uint32_t*>(parts + ECHO_PARTS);
+        parts[blockIdx.x] = red[0];
+        counts[blockIdx.x] = redx[0];
+        counts[ECHO_PARTS + blockIdx.x] = redc[0];
+    }
 }
 
 __global__ __launch_bounds__(256) void echo_backward_kernel(const float* __restrict__ x, const float* __restrict__ g, const unsigned long long* __restrict__ rec,
                                                              const float* __restrict__ parts, int nparts, float* __restrict__ dx, size_t N, int T, int n,
                                                              float volume) {
-    __shared__ float s_S;
+    __shared__ float s_S, s_nx, s_nc;
     const float mo = peak_value(rec[0]), mr = peak_value(rec[1]);
+    const uint32_t bo = (uint32_t)(rec[0] >> 32), br = (uint32_t)(rec[1] >> 32);
     const bool norm = mr > 0.f && mo > 0.f;
     if (threadIdx.x == 0) {
+        const uint32_t* counts = reinterpret_cast<const uint32_t*>(parts + ECHO_PARTS);
         double sum = 0.0;
-        for (int p = 0; p < nparts; ++p) sum += (double)parts[p];
+        uint32_t nx = 0, nc = 0;
+        for (int p = 0; p < nparts; ++p) {
+            sum += (double)parts[p];
+            nx += counts[p];
+            nc += counts[ECHO_PARTS + p];
+        }
         s_S = norm ? (float)(sum / (double)mr) : 0.f;
+        s_nx = (float)(nx > 0 ? nx : 1u);
+        s_nc = (float)(nc > 0 ? nc : 1u);
     }
     __syncthreads();
-    const float S = s_S, s = norm ? mo / mr : 1.f;
-    const size_t ip = peak_index(rec[0]), jp = peak_index(rec[1]);
-    float sx = 0.f, sc = 0.f;
-    if (norm) {
-        sx = x[ip] < 0.f ? -1.f : 1.f;
-        const float d = volume * x[jp + n - 1];
-        sc = (x[jp] + d) < 0.f ? -1.f : 1.f;
-    }
+    const float S = s_S, s = norm ? mo / mr : 1.f, fnx = s_nx, fnc = s_nc;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < N; i += (size_t)gridDim.x * 256) {
         const int t = (int)(i % (size_t)T);
+        const float v = x[i];
         float dc0 = 0.f, dc1 = 0.f;                                    // dL/dc at t and at t - n + 1
-        if (t < T - n + 1) dc0 = s * g[i] - ((norm && i == jp) ? S * s * sc : 0.f);
+        if (t < T - n + 1) {
+            dc0 = s * g[i];
+            if (norm) {
+                const float d = volume * x[i + n - 1];
+                const float c = v + d;
+                if (abs_bits(c) == br) dc0 -= S * s * (c < 0.f ? -1.f : 1.f) / fnc;
+            }
+        }
         if (t - n + 1 >= 0) {
             const size_t j = i - (size_t)(n - 1);
-            dc1 = s * g[j] - ((norm && j == jp) ? S * s * sc : 0.f);
+            dc1 = s * g[j];
+            if (norm) {
+                const float d = volume * v;
+                const float c = x[j] + d;
+                if (abs_bits(c) == br) dc1 -= S * s * (c < 0.f ? -1.f : 1.f) / fnc;
+            }
         }
         float o = dc0 + volume * dc1;
-        if (norm && i == ip) o += S * sx;
+        if (norm && abs_bits(v) == bo) o += S * (v < 0.f ? -1.f : 1.f) / fnx;
         dx[i] = o;
     }
 }
@@ -367,12 +407,13 @@ __global__ __launch_bounds__(256) void scatter_zero_kernel(float* __restrict__ y
 }
 
 // torch.nn.functional.interpolate(mode='linear', align_corners=False): scale = Tin / Tout in f32, source coordinate
-// max(0, scale * (m + 0.5) - 0.5), the two neighbours weighted 1 - l and l.
+// max(0, scale * (m + 0.5) - 0.5) rounded ONCE (a fused multiply-add: rounding the product first moves the coordinate by up to an ulp
+// of m, 1e-4 of the peak on a one-second clip), the two neighbours weighted 1 - l and l.
 __global__ __launch_bounds__(256) void stretch_kernel(const float* __restrict__ x, float* __restrict__ y, int Tin, int Tout) {
     const int row = blockIdx.y, m = blockIdx.x * 256 + threadIdx.x;
     if (m >= Tout) return;
     const float scale = (float)Tin / (float)Tout;
-    float src = scale * ((float)m + 0.5f) - 0.5f;
+    float src = fmaf(scale, (float)m + 0.5f, -0.5f);                   // ONE rounding, as torch's CPU kernel is compiled; the file's other products stay unfused
     src = src < 0.f ? 0.f : src;
     const int i0 = min((int)src, Tin - 1), i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
     const float l1 = src - (float)i0, l0 = 1.f - l1;
@@ -445,7 +486,7 @@ extern "C" int wv_fx_echo_apply(const float* x, const void* rec, float* y, int r
     return launched();
 }
 
-extern "C" size_t wv_fx_echo_backward_workspace_bytes(void) { return (size_t)wv::ECHO_PARTS * sizeof(float); }
+extern "C" size_t wv_fx_echo_backward_workspace_bytes(void) { return (size_t)wv::ECHO_PARTS * (sizeof(float) + 2 * sizeof(uint32_t)); }
 
 extern "C" int wv_fx_echo_backward(const float* x, const float* g, const void* rec, float* dx, int rows, int T, int n, float volume, void* workspace,
                                    size_t workspace_bytes, void* stream) {
@@ -454,7 +495,8 @@ extern "C" int wv_fx_echo_backward(const float* x, const float* g, const void* r
         return fail(WV_EINVAL, "null pointer (x, g, rec, dx, workspace), rows outside [1, 65535], T < 1 or rows * T >= 2^32, n outside [2, T], rec not 8-byte or workspace not 4-byte aligned, or workspace too small");
     const size_t N = (size_t)rows * T;
     const int parts = wv::flat_grid(N, 1024, wv::ECHO_PARTS);
-    hipLaunchKernelGGL(wv::echo_dot_kernel, dim3(parts), dim3(256), 0, (hipStream_t)stream, x, g, (float*)workspace, N, T, n, volume);
+    hipLaunchKernelGGL(wv::echo_dot_kernel, dim3(parts), dim3(256), 0, (hipStream_t)stream, x, g, (const unsigned long long*)rec, (float*)workspace, N, T, n,
+                       volume);
     hipLaunchKernelGGL(wv::echo_backward_kernel, dim3(wv::flat_grid(N, 1024, 2048)), dim3(256), 0, (hipStream_t)stream, x, g, (const unsigned long long*)rec,
                        (const float*)workspace, parts, dx, N, T, n, volume);
     return launched();

@@ -303,7 +303,8 @@ def shush_forward(x: torch.Tensor, k: int, mask: Optional[torch.Tensor] = None):
 
 
 def echo_forward(x: torch.Tensor, n: int, volume: float):
-    """-> (y, record): the reference's echo with an impulse response of n taps; `record` (int64 [2], device) holds the two peaks."""
+    """-> (y, record): the reference's echo with an impulse response of n taps; `record` (int64 [2], device) holds the two peaks
+    (magnitude and earliest position; the backward reads the magnitudes)."""
     lib = _lib.load()
     xr = _rows(x)
     rec = torch.empty(2, dtype=torch.int64, device=xr.device)
@@ -314,7 +315,8 @@ def echo_forward(x: torch.Tensor, n: int, volume: float):
 
 
 def echo_backward(x: torch.Tensor, g: torch.Tensor, rec: torch.Tensor, n: int, volume: float) -> torch.Tensor:
-    """Gradient towards x of echo_forward(x, n, volume) given g towards its output, through the correlation and both maxima."""
+    """Gradient towards x of echo_forward(x, n, volume) given g towards its output, through the correlation and both maxima.  Tied
+    peaks (clipped audio) share a maximum's gradient evenly, as the reference's autograd of torch.max(torch.abs(.)) shares it."""
     lib = _lib.load()
     xr, gr = _rows(x), _rows(g)
     dx = torch.empty_like(xr)
@@ -355,7 +357,8 @@ def scatter_zero(y: torch.Tensor, idx: torch.Tensor, mask: Optional[torch.Tensor
 
 
 def stretch_linear(x: torch.Tensor, t_out: int) -> torch.Tensor:
-    """torch.nn.functional.interpolate(x, size=t_out, mode='linear', align_corners=False) along the last axis."""
+    """torch.nn.functional.interpolate(x, size=t_out, mode='linear', align_corners=False) along the last axis (the source coordinate
+    one fused multiply-add, as torch's CPU kernel forms it)."""
     xr = _rows(x)
     y = torch.empty(xr.shape[0], int(t_out), device=xr.device)
     _lib.check(_lib.load().wv_fx_stretch_linear(xr.data_ptr(), y.data_ptr(), xr.shape[0], xr.shape[1], int(t_out), _lib.stream()), "wv_fx_stretch_linear")
