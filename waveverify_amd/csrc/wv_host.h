@@ -1,4 +1,5 @@
-// Host-side policy shared by every file that exports part of include/waveverify_hip.h: how an entry point reports failure.
+// Host-side policy shared by every file that exports part of include/waveverify_hip.h: how an entry point reports failure, and how a
+// workspace is carved.
 // Host only: no kernel includes this for device code.
 #pragma once
 
@@ -18,6 +19,19 @@ int fail(int code, std::string msg);
 
 // workspace carve-outs: every sub-buffer starts on a 256-byte boundary
 inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// One description of a workspace for both of its readers: take(bytes) hands out the next sub-buffer and advances by al256(bytes).  Over
+// a null base it only counts (take returns null), and `used` is then the size the same sequence of takes needs.
+struct Carver {
+    char* base;
+    size_t used = 0;
+    explicit Carver(void* b) : base((char*)b) {}
+    float* take(size_t bytes) {
+        float* p = base ? (float*)(base + used) : nullptr;
+        used += al256(bytes);
+        return p;
+    }
+};
 
 }  // namespace wv
 

@@ -22,6 +22,11 @@
 // dw_param_grads_kernel).  A ResnetBlock keeps its two 1x1 outputs from the forward kernels' epilogues (K1 RES = 4 / 5, the latter also
 // emitting y = x + s v), so its backward has no GEMM to recompute; a standalone unit recomputes its 1x1 output.  Layers the LDS-DMA
 // core does not take (ragged / narrow) run the same steps as separate kernels (elu_bwd, axpy_res, scale_dot, add_inplace).
+// How the host half (below the C ABI banner) is put together: a handle's workspace is described once, by its layout function (unit_ws,
+// block_saved, block_ws, convpost_ws, head_ws, up_ws, film_ws: a wv::Carver over the caller's buffer, or over null to count), which
+// both the size query and the entry point read.  A weight-normed 1x1 with its packs is one WnLinear (unit, spec, conv_post, up): its
+// allocation, fold arguments, GEMM operands and dW path (launch_gemm_nt_sum, then wn_bwd_kernel).  The sequences the handles share
+// are one function each: plain_gemm (K1 with the identity stencil), row_sum, elu_bwd, launch_fold, convtr_frame_ratio.
 // Gradient parity against the reference's autograd: tests/test_gpu_train.py (units) and tests/test_gpu_trainer.py (whole nets).
 #include <hip/hip_runtime.h>
 
@@ -1134,43 +1139,19 @@ struct TrainHandle {
         return (d && hipMemcpy(d, taps.data(), taps.size() * 4, hipMemcpyHostToDevice) == hipSuccess) ? d : nullptr;
     }
 };
-}  // namespace wv
 
-struct wv_train_unit : wv::TrainHandle {
-    int K = 0, M = 0, ks = 5, stride = 1, pad = 4, Mp = 0, KpT = 0;
-    float *w_pw = nullptr, *inv_pw = nullptr, *wq = nullptr, *wqT = nullptr, *wt = nullptr, *wtT = nullptr;   // folded 1x1 weight + packs
-    float *w_dw = nullptr, *inv_dw = nullptr, *id_taps = nullptr;                 // folded taps [M][ks]; identity stencil rows
-    float *dW = nullptr, *dwdb = nullptr, *dw_taps = nullptr;                     // weight-gradient scratch
-    const float* folded[4] = {nullptr, nullptr, nullptr, nullptr};               // the (g_pw, v_pw, g_dw, v_dw) the folded copies were made from
-};
-
-extern "C" {
-
-int wv_train_unit_create(int K, int M, int ks, int stride, wv_train_unit** out) {
-    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096) return fail(WV_EINVAL, "bad channel count");
-    if (ks < 1 || ks > wv::TRAIN_MAX_KS || stride < 1 || ks - stride < 0) return fail(WV_EINVAL, "bad kernel size / stride");
-    auto* h = new wv_train_unit();
-    h->K = K; h->M = M; h->ks = ks; h->stride = stride; h->pad = ks - stride;
-    h->Mp = wv::round_up(M, wv::M_ALIGN); h->KpT = wv::round_up(K, wv::M_ALIGN);
-    const size_t nq = (size_t)wv::round_up(K, 32) * h->Mp, nqT = (size_t)wv::round_up(M, 32) * h->KpT;
-    const int R = std::max(K, M);
-    bool ok = (h->w_pw = h->alloc((size_t)M * K, false)) && (h->inv_pw = h->alloc(M, false)) && (h->wq = h->alloc(nq, true)) &&
-              (h->wqT = h->alloc(nqT, true)) && (h->wt = h->alloc((size_t)wv::round_up(K, wv::BK) * h->Mp, true)) &&
-              (h->wtT = h->alloc((size_t)wv::round_up(M, wv::BK) * h->KpT, true)) && (h->w_dw = h->alloc((size_t)M * ks, false)) && (h->inv_dw = h->alloc(M, false)) &&
-              (h->id_taps = h->identity_taps(R)) && (h->dW = h->alloc((size_t)M * K, false)) &&
-              (h->dwdb = h->alloc((size_t)M * (ks + 1), false)) && (h->dw_taps = h->alloc((size_t)M * ks, false));
+// how every create ends
+template <class H> static int created(H* h, bool ok, H** out) {
     if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
     *out = h;
     return WV_OK;
 }
 
-void wv_train_unit_destroy(wv_train_unit* h) { delete h; }
-
 // splits of the dW GEMM: enough workgroups to fill the chip even when the weight matrix is one 64 x 64 tile (C = 64 layers), within
 // a 128 MB scratch; a function of the shapes only, so the summation order -- and the result -- is reproducible
 struct NtPlan { int S, TC; };
 static NtPlan nt_plan(int B, int T, int M, int K) {
-    const int te = wv::nt_tile(M, K);
+    const int te = nt_tile(M, K);
     const long long tiles = (long long)((M + te - 1) / te) * ((K + te - 1) / te);
     const int TC = 512;
     const long long items = (long long)B * ((T + TC - 1) / TC);
@@ -1178,153 +1159,246 @@ static NtPlan nt_plan(int B, int T, int M, int K) {
     while (S > 1 && S * M * K > (32LL << 20)) S /= 2;          // <= 128 MB of partial sums (a 16 MB cap left one workgroup per CU: 1.07x the step)
     return NtPlan{(int)S, TC};
 }
+
+// The dW product of every handle below, out[M][K] = sum_{b,t} A[b][m][t] act(pre_scale X[b][k][t]): gemm_nt_kernel over nt_plan's splits
+// into `parts` (gemm_nt_sum_workspace_bytes of scratch), then their fixed-order sum.  wv_kernels.h declares the pair without the
+// activation operands for the STFT plan's basis gradient (wv_ops.hip), which so shares the kernel, the split plan and the finish.
+size_t gemm_nt_sum_workspace_bytes(int B, int T, int M, int K) {
+    if (B < 1 || T < 1 || M < 1 || K < 1) return 0;
+    return al256((size_t)nt_plan(B, T, M, K).S * M * K * 4);
+}
+static hipError_t launch_gemm_nt_sum(hipStream_t s, const float* A, const float* X, float* out, float* parts, float pre_scale, int pre_elu,
+                                     int B, int M, int K, int T) {
+    const NtPlan np_ = nt_plan(B, T, M, K);
+    const hipError_t e = launch_gemm_nt(s, A, X, parts, pre_scale, pre_elu, B, M, K, T, np_.S, np_.TC);
+    if (e != hipSuccess) return e;
+    launch_sum_parts(s, parts, out, np_.S, (size_t)M * K);
+    return hipGetLastError();
+}
+hipError_t launch_gemm_nt_sum(hipStream_t s, const float* A, const float* X, float* out, float* parts, int B, int M, int K, int T) {
+    if (!A || !X || !out || !parts || B < 1 || T < 1 || M < 1 || K < 1) return hipErrorInvalidValue;
+    return launch_gemm_nt_sum(s, A, X, out, parts, 1.f, 0, B, M, K, T);
+}
+
+// a weight without packs (stencil taps, a plain matrix): w = g v / ||v|| [M][K] and inv = 1 / ||v||
+static WnFoldArgs fold_plain(const float* g, const float* v, float* w, float* inv, int M, int K) {
+    return WnFoldArgs{g, v, w, inv, nullptr, nullptr, M, K, 0, 0, nullptr, 1.f, nullptr, nullptr};
+}
+static void launch_fold(hipStream_t s, const WnFoldArgs& a) {
+    hipLaunchKernelGGL(wn_fold_kernel, dim3((unsigned)a.M), dim3(256), 0, s, a.g, a.v, a.w, a.inv_norm, a.wq, a.wqT, a.M, a.K, a.Mp, a.KpT,
+                       a.pack_param, a.pack_scale, a.wt, a.wtT);
+}
+
+// A weight-normed 1x1 W(g, v) [M][K] as a handle keeps it: the folded weight, 1 / ||v||, the packs of W and of W^T for both cores
+// (wn_fold_row's layouts; their padding is zeroed here, once), and the scratch for dL/dW.
+struct WnLinear {
+    int M = 0, K = 0, Mp = 0, KpT = 0;
+    float *w = nullptr, *inv = nullptr, *wq = nullptr, *wqT = nullptr, *wt = nullptr, *wtT = nullptr, *dW = nullptr;
+    bool alloc(TrainHandle& o, int M_, int K_) {
+        M = M_; K = K_; Mp = round_up(M, M_ALIGN); KpT = round_up(K, M_ALIGN);
+        return (w = o.alloc((size_t)M * K, true)) && (inv = o.alloc(M, true)) && (wq = o.alloc((size_t)round_up(K, 32) * Mp, true)) &&
+               (wqT = o.alloc((size_t)round_up(M, 32) * KpT, true)) && (wt = o.alloc((size_t)round_up(K, BK) * Mp, true)) &&
+               (wtT = o.alloc((size_t)round_up(M, BK) * KpT, true)) && (dW = o.alloc((size_t)M * K, true));
+    }
+    // this step's fold into every pack; the scalar pack_scale * pack_param[0] rides in the packs only (the SpecBlock's s)
+    WnFoldArgs fold(const float* g, const float* v, const float* pack_param = nullptr, float pack_scale = 1.f) const {
+        return WnFoldArgs{g, v, w, inv, wq, wqT, M, K, Mp, KpT, pack_param, pack_scale, wt, wtT};
+    }
+    // the GEMM operand W [M][K], or W^T [K][M]
+    PwWeight pack(bool transposed) const {
+        PwWeight p;
+        if (!transposed) { p.M = M; p.K = K; p.Mp = Mp; p.Kp = round_up(K, BK); p.wq = wq; p.wt = wt; }
+        else { p.M = K; p.K = M; p.Mp = KpT; p.Kp = round_up(M, BK); p.wq = wqT; p.wt = wtT; }
+        return p;
+    }
+    // dW = sum_{b,t} dOut act(pre_scale x)^T, then the weight-norm backward into dg, dv
+    int grad(hipStream_t s, const float* dOut, const float* x, float* parts, float pre_scale, int pre_elu, int B, int T, const float* g,
+             const float* v, float* dg, float* dv) const {
+        WV_HIP_TRY(launch_gemm_nt_sum(s, dOut, x, dW, parts, pre_scale, pre_elu, B, M, K, T));
+        hipLaunchKernelGGL(wn_bwd_kernel, dim3(M), dim3(256), 0, s, g, v, inv, dW, dg, dv, K);
+        WV_HIP_TRY(hipGetLastError());
+        return WV_OK;
+    }
+};
+
+// A plain GEMM Y[B, pw.M, T] = pw @ act(pre_scale X[B, pw.K, T]) on the K1 kernel: id_taps (TrainHandle::identity_taps) is its stencil
+static PwDwArgs plain_gemm(const float* X, const PwWeight& pw, const float* id_taps, float* Y, int B, int T, float pre_scale = 1.f, int pre_elu = 0) {
+    PwDwArgs a{};
+    a.X = X; a.pw = pw; a.dw_w = id_taps; a.dw_b = nullptr; a.Y = Y;
+    a.B = B; a.Tin = T; a.Tout = T; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
+    a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
+    return a;
+}
+
+// out[rows] = the sum of g [B, rows, T] over clips and time: the bias slot of the stencil backward with one tap (partial: B * rows * 2
+// floats), the fixed-order sum over clips (scr: rows * 2) and the split (junk: rows, the unused tap column)
+static void row_sum(hipStream_t s, const float* g, float* out, float* partial, float* scr, float* junk, int rows, int B, int T) {
+    launch_dw_bwd(s, g, g, junk, (float*)nullptr, partial, rows, B, T, T, 1, 1, 0, 0);
+    launch_sum_parts(s, partial, scr, B, (size_t)rows * 2);
+    hipLaunchKernelGGL(split_dwdb_kernel, dim3((rows + 255) / 256), dim3(256), 0, s, scr, junk, out, rows, 1, 1.f);
+}
+
+// dx = da * d act(scale x) / dx over n elements: four per thread, and the ragged tail
+static void elu_bwd(hipStream_t s, const float* da, const float* x, float* dx, float scale, size_t n) {
+    const size_t n4 = n / 4;
+    if (n4) hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, da, x, dx, scale, n4);
+    if (n % 4) hipLaunchKernelGGL(elu_bwd_tail_kernel, dim3(1), dim3(256), 0, s, da, x, dx, scale, n4 * 4, n);
+}
+
+// The ConvTranspose frame kernels' R for a ratio and the upsampled buffer's address (R = 4, 8 store 16 bytes at a time); 0: the generic
+// kernel.  Forward and backward ask here, so they take the same route.
+static int convtr_frame_ratio(int ratio, const void* u) {
+    const bool al = (reinterpret_cast<uintptr_t>(u) & 15) == 0;
+    return (ratio == 2 || ratio == 5 || ((ratio == 4 || ratio == 8) && al)) ? ratio : 0;
+}
+}  // namespace wv
+
+struct wv_train_unit : wv::TrainHandle {
+    int ks = 5, stride = 1, pad = 4;
+    wv::WnLinear pw;                                                             // the 1x1 W(g_pw, v_pw) [M][K]
+    float *w_dw = nullptr, *inv_dw = nullptr, *id_taps = nullptr;                // folded taps [M][ks]; identity stencil rows
+    const float* folded[4] = {nullptr, nullptr, nullptr, nullptr};               // the (g_pw, v_pw, g_dw, v_dw) the folded copies were made from
+};
+
+extern "C" {
+
+// Workspace of the unit's backward, in carving order: H (the recomputed 1x1 output), DH, DA [B, K, Tin], the stencil backward's per-clip
+// partial sums, the dW GEMM's splits.
+struct UnitWs { float *H, *DH, *DA, *partial, *parts; size_t total; };
+static UnitWs unit_ws(const wv_train_unit* h, int B, int Tin, void* base) {
+    if (!h || B < 1 || Tin < 1) return {};
+    const int M = h->pw.M, K = h->pw.K;
+    const size_t am = (size_t)B * M * Tin * 4;
+    wv::Carver c(base);
+    return {c.take(am), c.take(am), c.take((size_t)B * K * Tin * 4), c.take((size_t)B * M * (h->ks + 1) * 4),
+            c.take(wv::gemm_nt_sum_workspace_bytes(B, Tin, M, K)), c.used};
+}
+
+// the unit's optional operands: the plain ABI calls pass them default-constructed, the ResnetBlock fills them by name
+struct UnitFwdOpt {
+    // with h_out: ysum = sum_x + sum_scale * sum_scale_ptr[0] * y from the same epilogue (the ResnetBlock's output); *summed reports
+    // whether the kernel took it (else the caller adds it)
+    const float* sum_x = nullptr; const float* sum_scale_ptr = nullptr; float sum_scale = 1.f; float* ysum = nullptr; bool* summed = nullptr;
+};
+struct UnitBwdOpt {
+    const float* h_saved = nullptr;                            // the forward's 1x1 output (unit_forward_impl's h_out), else it is recomputed
+    // with pre_elu: a tensor added to dx (the ResnetBlock's identity shortcut); *added reports whether the dx kernel's epilogue took it
+    const float* dx_add = nullptr; bool* added = nullptr;
+    // dy arrives unscaled (the stencil backward multiplies by dy_scale * dy_scale_ptr[0]) and leaves <dy, dot_v> per (clip, channel) row in
+    // dot_partial: launch_dw_bwd's fused form, the caller has checked dw_bwd_can_fuse_scale
+    const float* dy_scale_ptr = nullptr; float dy_scale = 1.f; const float* dot_v = nullptr; float* dot_partial = nullptr;
+};
+
 static int t_out(const wv_train_unit* h, int Tin) { return (Tin + h->stride - 1) / h->stride; }
 
-size_t wv_train_unit_workspace_bytes(const wv_train_unit* h, int B, int Tin) {
-    if (!h || B < 1 || Tin < 1) return 0;
-    const size_t am = al256((size_t)B * h->M * Tin * 4), ak = al256((size_t)B * h->K * Tin * 4);
-    return 2 * am + ak + al256((size_t)B * h->M * (h->ks + 1) * 4) + al256((size_t)nt_plan(B, Tin, h->M, h->K).S * h->M * h->K * 4);
-}
-
 // fold both weights of the unit for this step (live weight norm)
-static int fold_step(wv_train_unit* h, const float* g_pw, const float* v_pw, const float* g_dw, const float* v_dw, hipStream_t s) {
-    const wv::WnFoldArgs fa{g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->M, h->K, h->Mp, h->KpT, nullptr, 1.f, h->wt, h->wtT};
-    const wv::WnFoldArgs fb{g_dw, v_dw, h->w_dw, h->inv_dw, nullptr, nullptr, h->M, h->ks, 0, 0, nullptr, 1.f, nullptr, nullptr};
-    hipLaunchKernelGGL(wv::wn_fold_pair_kernel, dim3(2 * h->M), dim3(256), 0, s, fa, fb);
+static int fold_step(wv_train_unit* h, const wv_half_params& p, hipStream_t s) {
+    hipLaunchKernelGGL(wv::wn_fold_pair_kernel, dim3(2 * h->pw.M), dim3(256), 0, s, h->pw.fold(p.g_pw, p.v_pw),
+                       wv::fold_plain(p.g_dw, p.v_dw, h->w_dw, h->inv_dw, h->pw.M, h->ks));
     WV_HIP_TRY(hipGetLastError());
-    h->folded[0] = g_pw; h->folded[1] = v_pw; h->folded[2] = g_dw; h->folded[3] = v_dw;
+    h->folded[0] = p.g_pw; h->folded[1] = p.v_pw; h->folded[2] = p.g_dw; h->folded[3] = p.v_dw;
     return WV_OK;
-}
-
-static wv::PwWeight pack_of(const wv_train_unit* h, bool transposed) {
-    wv::PwWeight p;
-    if (!transposed) { p.M = h->M; p.K = h->K; p.Mp = h->Mp; p.Kp = wv::round_up(h->K, wv::BK); p.wq = h->wq; p.wt = h->wt; }
-    else { p.M = h->K; p.K = h->M; p.Mp = h->KpT; p.Kp = wv::round_up(h->M, wv::BK); p.wq = h->wqT; p.wt = h->wtT; }
-    return p;
 }
 
 // h_out (optional, stride-1 units): the 1x1 output H = W act(s x) [B, M, Tin], which the backward otherwise recomputes -- stored by the
 // forward kernel itself next to y where the LDS-DMA core runs the layer, else by one more pass with the identity stencil
-// sum_x / sum_scale_ptr / sum_scale / ysum (optional, with h_out): ysum = sum_x + sum_scale * sum_scale_ptr[0] * y from the same
-// epilogue (the ResnetBlock's output); *summed reports whether the kernel took it (else the caller adds it).
-static int unit_forward_impl(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw, const float* v_dw,
-                             const float* bias, float pre_scale, int pre_elu, float* y, float* h_out, int B, int Tin, void* stream,
-                             const float* sum_x = nullptr, const float* sum_scale_ptr = nullptr, float sum_scale = 1.f, float* ysum = nullptr,
-                             bool* summed = nullptr) {
-    if (summed) *summed = false;
-    if (!h || !x || !g_pw || !v_pw || !g_dw || !v_dw || !y || B < 1 || Tin < 1) return fail(WV_EINVAL, "null / bad argument");
+static int unit_forward_impl(wv_train_unit* h, const float* x, const wv_half_params& p, float pre_scale, int pre_elu, float* y, float* h_out,
+                             int B, int Tin, void* stream, const UnitFwdOpt& o) {
+    if (o.summed) *o.summed = false;
+    if (!h || !x || !p.g_pw || !p.v_pw || !p.g_dw || !p.v_dw || !y || B < 1 || Tin < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
-    int rc = fold_step(h, g_pw, v_pw, g_dw, v_dw, s);
+    int rc = fold_step(h, p, s);
     if (rc) return rc;
     wv::PwDwArgs a{};
-    a.X = x; a.pw = pack_of(h, false); a.dw_w = h->w_dw; a.dw_b = bias; a.Y = y;
+    a.X = x; a.pw = h->pw.pack(false); a.dw_w = h->w_dw; a.dw_b = p.bias; a.Y = y;
     a.B = B; a.Tin = Tin; a.Tout = t_out(h, Tin); a.ks = h->ks; a.stride = h->stride; a.dil = 1; a.pad = h->pad;
     a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
     if (h_out) {
         if (h->stride != 1) return fail(WV_EINVAL, "saved 1x1 output: stride-1 units only");
+        const bool sum = o.ysum && o.sum_x;
         wv::PwDwArgs f = a;
         f.Yraw = h_out;
-        if (ysum && sum_x) { f.resid = sum_x; f.Ysum = ysum; f.scale_ptr = sum_scale_ptr; f.out_scale = sum_scale; }
+        if (sum) { f.resid = o.sum_x; f.Ysum = o.ysum; f.scale_ptr = o.sum_scale_ptr; f.out_scale = o.sum_scale; }
         const hipError_t e = wv::launch_pw_dw(f, s);
-        if (e == hipSuccess) { if (summed && ysum && sum_x) *summed = true; return WV_OK; }
+        if (e == hipSuccess) { if (o.summed && sum) *o.summed = true; return WV_OK; }
         if (e != hipErrorNotSupported) WV_HIP_TRY(e);
-        wv::PwDwArgs r = a;                                   // ragged / narrow layers: H by the identity stencil, as the backward used to
-        r.dw_w = h->id_taps; r.dw_b = nullptr; r.Y = h_out; r.Tout = Tin; r.ks = 5; r.stride = 1; r.pad = 4;
-        WV_HIP_TRY(wv::launch_pw_dw(r, s));
+        // ragged / narrow layers: H by the identity stencil, as the backward used to
+        WV_HIP_TRY(wv::launch_pw_dw(wv::plain_gemm(x, a.pw, h->id_taps, h_out, B, Tin, pre_scale, pre_elu), s));
     }
     WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
 
-int wv_train_unit_forward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                          const float* v_dw, const float* bias, float pre_scale, int pre_elu, float* y, int B, int Tin, void* stream) {
-    return unit_forward_impl(h, x, g_pw, v_pw, g_dw, v_dw, bias, pre_scale, pre_elu, y, nullptr, B, Tin, stream);
-}
-
-// h_saved (optional): the forward's 1x1 output (unit_forward_impl), else it is recomputed here.  dx_add (optional, with pre_elu): a
-// tensor added to dx (the ResnetBlock's identity shortcut); *added reports whether the dx kernel's epilogue took it.
-static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                              const float* v_dw, float pre_scale, int pre_elu, const float* dy, float* dx, float* dg_pw, float* dv_pw,
-                              float* dg_dw, float* dv_dw, float* db, int B, int Tin, void* ws, size_t ws_bytes, void* stream,
-                              const float* h_saved, const float* dx_add, bool* added, const float* dy_scale_ptr = nullptr, float dy_scale = 1.f,
-                              const float* dot_v = nullptr, float* dot_partial = nullptr);
-
-int wv_train_unit_backward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                           const float* v_dw, float pre_scale, int pre_elu, const float* dy, float* dx, float* dg_pw, float* dv_pw,
-                           float* dg_dw, float* dv_dw, float* db, int B, int Tin, void* ws, size_t ws_bytes, void* stream) {
-    return unit_backward_impl(h, x, g_pw, v_pw, g_dw, v_dw, pre_scale, pre_elu, dy, dx, dg_pw, dv_pw, dg_dw, dv_dw, db, B, Tin, ws, ws_bytes, stream,
-                              nullptr, nullptr, nullptr);
-}
-
-static int unit_backward_impl(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
-                              const float* v_dw, float pre_scale, int pre_elu, const float* dy, float* dx, float* dg_pw, float* dv_pw,
-                              float* dg_dw, float* dv_dw, float* db, int B, int Tin, void* ws, size_t ws_bytes, void* stream,
-                              const float* h_saved, const float* dx_add, bool* added, const float* dy_scale_ptr, float dy_scale,
-                              const float* dot_v, float* dot_partial) {
-    if (added) *added = false;
-    if (!h || !x || !g_pw || !v_pw || !g_dw || !v_dw || !dy || !dg_pw || !dv_pw || !dg_dw || !dv_dw || !db)
+// p.bias is not read; dx may be null (no gradient towards the input wanted)
+static int unit_backward_impl(wv_train_unit* h, const float* x, const wv_half_params& p, float pre_scale, int pre_elu, const float* dy, float* dx,
+                              const wv_half_grads& g, int B, int Tin, void* ws, size_t ws_bytes, void* stream, const UnitBwdOpt& o) {
+    if (o.added) *o.added = false;
+    if (!h || !x || !p.g_pw || !p.v_pw || !p.g_dw || !p.v_dw || !dy || !g.dg_pw || !g.dv_pw || !g.dg_dw || !g.dv_dw || !g.db)
         return fail(WV_EINVAL, "null argument");
-    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_unit_workspace_bytes(h, B, Tin)) return fail(WV_ENOMEM, "workspace too small");
+    const UnitWs w = unit_ws(h, B, Tin, ws);
+    if (!w.total || !ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const int M = h->M, K = h->K, ks = h->ks, Tout = t_out(h, Tin);
-    const size_t am = al256((size_t)B * M * Tin * 4), ak = al256((size_t)B * K * Tin * 4);
-    char* w = (char*)ws;
-    float* Hws = (float*)w; float* DH = (float*)(w + am); float* DA = (float*)(w + 2 * am);
-    const float* H = h_saved ? h_saved : Hws;
-    float* partial = (float*)(w + 2 * am + ak);
-    float* parts = (float*)(w + 2 * am + ak + al256((size_t)B * M * (ks + 1) * 4));
+    const int M = h->pw.M, K = h->pw.K, ks = h->ks, Tout = t_out(h, Tin);
+    const float* H = o.h_saved ? o.h_saved : w.H;
     // the step's weights: folded here unless this call continues a forward that kept its 1x1 output (the block's forward folded the
     // same parameters into the same buffers moments ago)
     // A backward on saved activations reuses the folds (W, its packs, 1 / ||v||) its forward left in the handle: it must follow THAT forward,
     // with the same parameter tensors and no parameter update or other forward on this handle in between.  Other tensors are caught here.
-    if (h_saved && (h->folded[0] != g_pw || h->folded[1] != v_pw || h->folded[2] != g_dw || h->folded[3] != v_dw))
+    if (o.h_saved && (h->folded[0] != p.g_pw || h->folded[1] != p.v_pw || h->folded[2] != p.g_dw || h->folded[3] != p.v_dw))
         return fail(WV_ESTATE, "backward on saved activations: the parameters are not the ones this handle's last forward folded");
-    int rc = h_saved ? WV_OK : fold_step(h, g_pw, v_pw, g_dw, v_dw, s);
+    int rc = o.h_saved ? WV_OK : fold_step(h, p, s);
     if (rc) return rc;
-    if (!h_saved) {
-        // h = W @ act(s x), recomputed (this forward kept no activations): K1 with the identity stencil
-        wv::PwDwArgs a{};
-        a.X = x; a.pw = pack_of(h, false); a.dw_w = h->id_taps; a.dw_b = nullptr; a.Y = Hws;
-        a.B = B; a.Tin = Tin; a.Tout = Tin; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
-        a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
-        WV_HIP_TRY(wv::launch_pw_dw(a, s));
-    }
+    // h = W @ act(s x), recomputed where the forward kept no activations
+    if (!o.h_saved) WV_HIP_TRY(wv::launch_pw_dw(wv::plain_gemm(x, h->pw.pack(false), h->id_taps, w.H, B, Tin, pre_scale, pre_elu), s));
     // dh, and the per-clip partial sums of the tap / bias gradients
-    wv::launch_dw_bwd(s, dy, H, h->w_dw, DH, partial, M, B, Tin, Tout, ks, h->stride, h->pad, 0, dy_scale_ptr, dy_scale, dot_v, dot_partial);
-    hipLaunchKernelGGL(wv::dw_param_grads_kernel, dim3(M), dim3(256), 0, s, partial, g_dw, v_dw, h->inv_dw, dg_dw, dv_dw, db, B, M, ks);
+    wv::launch_dw_bwd(s, dy, H, h->w_dw, w.DH, w.partial, M, B, Tin, Tout, ks, h->stride, h->pad, 0, o.dy_scale_ptr, o.dy_scale, o.dot_v, o.dot_partial);
+    hipLaunchKernelGGL(wv::dw_param_grads_kernel, dim3(M), dim3(256), 0, s, w.partial, p.g_dw, p.v_dw, h->inv_dw, g.dg_dw, g.dv_dw, g.db, B, M, ks);
     WV_HIP_TRY(hipGetLastError());
     if (dx) {
-        // da = W^T @ dh on the forward's GEMM kernel, then through the activation
-        wv::PwDwArgs t{};
-        t.X = DH; t.pw = pack_of(h, true); t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = pre_elu ? DA : dx;
-        t.B = B; t.Tin = Tin; t.Tout = Tin; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
-        t.pre_scale = pre_elu ? 1.f : pre_scale; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;   // no ELU: dx = s W^T dh
+        // da = W^T @ dh on the forward's GEMM kernel, then through the activation (no ELU: dx = s W^T dh)
+        const wv::PwDwArgs t = wv::plain_gemm(w.DH, h->pw.pack(true), h->id_taps, pre_elu ? w.DA : dx, B, Tin, pre_elu ? 1.f : pre_scale, 0);
         bool fused = false;
         if (pre_elu) {
             // the activation's derivative in the GEMM's epilogue (x rides in as the residual operand): no da round trip through HBM
             wv::PwDwArgs f = t;
-            f.Y = dx; f.resid = x; f.res_mode = 2; f.out_scale = pre_scale; f.resid2 = dx_add;
+            f.Y = dx; f.resid = x; f.res_mode = 2; f.out_scale = pre_scale; f.resid2 = o.dx_add;
             const hipError_t e = wv::launch_pw_dw(f, s);
-            if (e == hipSuccess) { fused = true; if (added && dx_add) *added = true; }
+            if (e == hipSuccess) { fused = true; if (o.added && o.dx_add) *o.added = true; }
             else if (e != hipErrorNotSupported) WV_HIP_TRY(e);
         }
         if (!fused) {
             WV_HIP_TRY(wv::launch_pw_dw(t, s));
-            if (pre_elu) {
-                const size_t n = (size_t)B * K * Tin, n4 = n / 4;
-                if (n4) hipLaunchKernelGGL(wv::elu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, DA, x, dx, pre_scale, n4);
-                if (n % 4) hipLaunchKernelGGL(wv::elu_bwd_tail_kernel, dim3(1), dim3(256), 0, s, DA, x, dx, pre_scale, n4 * 4, n);
-            }
+            if (pre_elu) wv::elu_bwd(s, w.DA, x, dx, pre_scale, (size_t)B * K * Tin);
         }
     }
     // dW = sum dh a^T, then the weight-norm backward
-    const NtPlan np_ = nt_plan(B, Tin, M, K);
-    const int S = np_.S;
-    WV_HIP_TRY(wv::launch_gemm_nt(s, DH, x, parts, pre_scale, pre_elu, B, M, K, Tin, S, np_.TC));
-    wv::launch_sum_parts(s, parts, h->dW, S, (size_t)M * K);
-    hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(M), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, K);
-    WV_HIP_TRY(hipGetLastError());
-    return WV_OK;
+    return h->pw.grad(s, w.DH, x, w.parts, pre_scale, pre_elu, B, Tin, p.g_pw, p.v_pw, g.dg_pw, g.dv_pw);
+}
+
+int wv_train_unit_create(int K, int M, int ks, int stride, wv_train_unit** out) {
+    if (!out || K < 1 || K > 4096 || M < 1 || M > 4096) return fail(WV_EINVAL, "bad channel count");
+    if (ks < 1 || ks > wv::TRAIN_MAX_KS || stride < 1 || ks - stride < 0) return fail(WV_EINVAL, "bad kernel size / stride");
+    auto* h = new wv_train_unit();
+    h->ks = ks; h->stride = stride; h->pad = ks - stride;
+    const bool ok = h->pw.alloc(*h, M, K) && (h->w_dw = h->alloc((size_t)M * ks, false)) && (h->inv_dw = h->alloc(M, false)) &&
+                    (h->id_taps = h->identity_taps(std::max(K, M)));
+    return wv::created(h, ok, out);
+}
+
+void wv_train_unit_destroy(wv_train_unit* h) { delete h; }
+
+size_t wv_train_unit_workspace_bytes(const wv_train_unit* h, int B, int Tin) { return unit_ws(h, B, Tin, nullptr).total; }
+
+int wv_train_unit_forward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
+                          const float* v_dw, const float* bias, float pre_scale, int pre_elu, float* y, int B, int Tin, void* stream) {
+    return unit_forward_impl(h, x, wv_half_params{g_pw, v_pw, g_dw, v_dw, bias}, pre_scale, pre_elu, y, nullptr, B, Tin, stream, UnitFwdOpt{});
+}
+
+int wv_train_unit_backward(wv_train_unit* h, const float* x, const float* g_pw, const float* v_pw, const float* g_dw,
+                           const float* v_dw, float pre_scale, int pre_elu, const float* dy, float* dx, float* dg_pw, float* dv_pw,
+                           float* dg_dw, float* dv_dw, float* db, int B, int Tin, void* ws, size_t ws_bytes, void* stream) {
+    return unit_backward_impl(h, x, wv_half_params{g_pw, v_pw, g_dw, v_dw, nullptr}, pre_scale, pre_elu, dy, dx,
+                              wv_half_grads{dg_pw, dv_pw, dg_dw, dv_dw, db}, B, Tin, ws, ws_bytes, stream, UnitBwdOpt{});
 }
 
 // ---- whole SEANetResnetBlock: y = x + s * half2(half1(pre_scale * x)) (seanet.py:245-281) ------------------------------
@@ -1334,6 +1408,23 @@ struct wv_train_block {
     float* tab = nullptr;                                        // [2][C][8]: the one-launch forward kernel's stencil tables (rebuilt every step)
     ~wv_train_block() { delete h[0]; delete h[1]; if (partial) (void)hipFree(partial); if (tab) (void)hipFree(tab); }
 };
+
+// what the block keeps from forward to backward, each [B, C, T]: the halves' outputs u, v and their 1x1 outputs H0, H1
+struct BlockSaved { float *u, *v, *H0, *H1; size_t total; };
+static BlockSaved block_saved(const wv_train_block* b, int B, int T, void* base) {
+    if (!b || B < 1 || T < 1) return {};
+    const size_t act = (size_t)B * b->h[0]->pw.M * T * 4;
+    wv::Carver c(base);
+    return {c.take(act), c.take(act), c.take(act), c.take(act), c.used};
+}
+// the backward's workspace: dv and du [B, C, T], then the workspace each half's backward runs in
+struct BlockWs { float *DV, *DU; void* unit; size_t unit_bytes, total; };
+static BlockWs block_ws(const wv_train_block* b, int B, int T, void* base) {
+    if (!b || B < 1 || T < 1) return {};
+    const size_t act = (size_t)B * b->h[0]->pw.M * T * 4, ub = unit_ws(b->h[0], B, T, nullptr).total;
+    wv::Carver c(base);
+    return {c.take(act), c.take(act), c.take(ub), ub, c.used};
+}
 
 int wv_train_block_create(int C, wv_train_block** out) {
     if (!out) return fail(WV_EINVAL, "null argument");
@@ -1349,36 +1440,28 @@ int wv_train_block_create(int C, wv_train_block** out) {
 
 void wv_train_block_destroy(wv_train_block* b) { delete b; }
 
-size_t wv_train_block_saved_bytes(const wv_train_block* b, int B, int T) {
-    return (b && B > 0 && T > 0) ? 4 * al256((size_t)B * b->h[0]->M * T * 4) : 0;       // u, v and the two 1x1 outputs
-}
-
-size_t wv_train_block_workspace_bytes(const wv_train_block* b, int B, int T) {
-    if (!b || B < 1 || T < 1) return 0;
-    return wv_train_unit_workspace_bytes(b->h[0], B, T) + 2 * al256((size_t)B * b->h[0]->M * T * 4);
-}
+size_t wv_train_block_saved_bytes(const wv_train_block* b, int B, int T) { return block_saved(b, B, T, nullptr).total; }
+size_t wv_train_block_workspace_bytes(const wv_train_block* b, int B, int T) { return block_ws(b, B, T, nullptr).total; }
 
 int wv_train_block_forward(wv_train_block* b, const float* x, const wv_half_params* p, const float* res_scale_param,
                            float pre_scale, float res_scale, float* y, void* saved, size_t saved_bytes, int B, int T, void* stream) {
     if (!b || !x || !p || !y || !saved) return fail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || (T & 3) || saved_bytes < wv_train_block_saved_bytes(b, B, T)) return fail(WV_ENOMEM, "saved-activation buffer too small (or T % 4 != 0)");
+    const BlockSaved sv = block_saved(b, B, T, saved);
+    if (!sv.total || (T & 3) || saved_bytes < sv.total) return fail(WV_ENOMEM, "saved-activation buffer too small (or T % 4 != 0)");
     hipStream_t s = (hipStream_t)stream;
-    const size_t act = al256((size_t)B * b->h[0]->M * T * 4);
-    float* u = (float*)saved; float* v = (float*)((char*)saved + act);
-    float* H0 = (float*)((char*)saved + 2 * act); float* H1 = (float*)((char*)saved + 3 * act);
     // The narrow layers (C = 64, 96, 128, 192, k = 5): the whole block in ONE launch of the inference kernel (wv_rb.hip) in its training
     // form -- x read once, u kept in LDS for the second GEMM, and the four saved tensors written from the registers they are computed
     // in (6 HBM passes instead of the two launches' 8); same accumulation order, stencil and ELU as the two K1 launches below.
     if (b->h[0]->ks == 5 && b->h[1]->ks == 5) {
-        const int C = b->h[0]->M;
+        const int C = b->h[0]->pw.M;
         wv::RbArgs f{};
-        f.X = x; f.pre_scale = pre_scale; f.pw1 = pack_of(b->h[0], false); f.pw2 = pack_of(b->h[1], false);
+        f.X = x; f.pre_scale = pre_scale; f.pw1 = b->h[0]->pw.pack(false); f.pw2 = b->h[1]->pw.pack(false);
         f.tab1 = b->tab; f.tab2 = b->tab + (size_t)C * 8;
         f.Y = y; f.Yact = nullptr; f.out_scale = res_scale; f.out_scale_ptr = res_scale_param; f.act_scale = 0.f; f.B = B; f.C = C; f.T = T;
-        f.sv_h0 = H0; f.sv_u = u; f.sv_h1 = H1; f.sv_v = v;
+        f.sv_h0 = sv.H0; f.sv_u = sv.u; f.sv_h1 = sv.H1; f.sv_v = sv.v;
         if (wv::rb_supported(f)) {
-            int rc = fold_step(b->h[0], p[0].g_pw, p[0].v_pw, p[0].g_dw, p[0].v_dw, s);
-            if (!rc) rc = fold_step(b->h[1], p[1].g_pw, p[1].v_pw, p[1].g_dw, p[1].v_dw, s);
+            int rc = fold_step(b->h[0], p[0], s);
+            if (!rc) rc = fold_step(b->h[1], p[1], s);
             if (rc) return rc;
             hipLaunchKernelGGL(wv::rb_table_pair_kernel, dim3((2 * C * 8 + 255) / 256), dim3(256), 0, s, b->h[0]->w_dw, p[0].bias, b->tab,
                                b->h[1]->w_dw, p[1].bias, b->tab + (size_t)C * 8, C);
@@ -1387,14 +1470,15 @@ int wv_train_block_forward(wv_train_block* b, const float* x, const wv_half_para
             return WV_OK;
         }
     }
-    int rc = unit_forward_impl(b->h[0], x, p[0].g_pw, p[0].v_pw, p[0].g_dw, p[0].v_dw, p[0].bias, pre_scale, 1, u, H0, B, T, stream);
+    int rc = unit_forward_impl(b->h[0], x, p[0], pre_scale, 1, sv.u, sv.H0, B, T, stream, UnitFwdOpt{});
     bool summed = false;                                       // y = x + s v from the second half's own epilogue where the LDS-DMA core runs it
-    if (!rc) rc = unit_forward_impl(b->h[1], u, p[1].g_pw, p[1].v_pw, p[1].g_dw, p[1].v_dw, p[1].bias, 1.f, 1, v, H1, B, T, stream,
-                                    x, res_scale_param, res_scale, y, &summed);
+    UnitFwdOpt o;
+    o.sum_x = x; o.sum_scale_ptr = res_scale_param; o.sum_scale = res_scale; o.ysum = y; o.summed = &summed;
+    if (!rc) rc = unit_forward_impl(b->h[1], sv.u, p[1], 1.f, 1, sv.v, sv.H1, B, T, stream, o);
     if (rc) return rc;
-    const size_t n4 = (size_t)B * b->h[0]->M * T / 4;
+    const size_t n4 = (size_t)B * b->h[0]->pw.M * T / 4;
     if (!summed)
-        hipLaunchKernelGGL(wv::axpy_res_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float4*)x, (const float4*)v, (float4*)y,
+        hipLaunchKernelGGL(wv::axpy_res_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (const float4*)x, (const float4*)sv.v, (float4*)y,
                            res_scale_param, res_scale, n4);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
@@ -1404,39 +1488,35 @@ int wv_train_block_backward(wv_train_block* b, const float* x, const wv_half_par
                             float pre_scale, float res_scale, const float* dy, const void* saved, float* dx, const wv_half_grads* g,
                             float* d_res_scale_param, int B, int T, void* ws, size_t ws_bytes, void* stream) {
     if (!b || !x || !p || !dy || !saved || !dx || !g) return fail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || (T & 3) || !ws || ws_bytes < wv_train_block_workspace_bytes(b, B, T)) return fail(WV_ENOMEM, "workspace too small (or T % 4 != 0)");
+    const BlockWs w = block_ws(b, B, T, ws);
+    if (!w.total || (T & 3) || !ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small (or T % 4 != 0)");
     if (res_scale_param && !d_res_scale_param) return fail(WV_EINVAL, "res_scale_param without a gradient slot");
     hipStream_t s = (hipStream_t)stream;
-    const int C = b->h[0]->M;
-    const size_t act = al256((size_t)B * C * T * 4), n4 = (size_t)B * C * T / 4;
-    const float* u = (const float*)saved; const float* v = (const float*)((const char*)saved + act);
-    const float* H0 = (const float*)((const char*)saved + 2 * act); const float* H1 = (const float*)((const char*)saved + 3 * act);
-    float* DV = (float*)ws; float* DU = (float*)((char*)ws + act);
-    void* hws = (char*)ws + 2 * act;
-    const size_t hws_bytes = ws_bytes - 2 * act;
+    const int C = b->h[0]->pw.M;
+    const size_t n4 = (size_t)B * C * T / 4;
+    const BlockSaved sv = block_saved(b, B, T, const_cast<void*>(saved));        // read only here
     // dv = s * dy, d(res_scale_param) = res_scale * sum(dy * v): inside the second half's stencil backward when the operands are 16-byte
     // aligned (dy is scaled on the way in, the dot leaves one partial per (clip, channel) row in the otherwise unused DV region), else
     // by a pass of their own
-    const bool fuse = wv::dw_bwd_can_fuse_scale(dy, H1, (const float*)hws, v, T);
-    int rc;
-    if (fuse) {
-        rc = unit_backward_impl(b->h[1], u, p[1].g_pw, p[1].v_pw, p[1].g_dw, p[1].v_dw, 1.f, 1, dy, DU, g[1].dg_pw, g[1].dv_pw,
-                                g[1].dg_dw, g[1].dv_dw, g[1].db, B, T, hws, hws_bytes, stream, H1, nullptr, nullptr, res_scale_param, res_scale, v, DV);
-        if (!rc && d_res_scale_param) {
-            hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, DV, B * C, res_scale, d_res_scale_param);
-            WV_HIP_TRY(hipGetLastError());
-        }
-    } else {
-        hipLaunchKernelGGL(wv::scale_dot_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, (const float4*)dy, (const float4*)v, (float4*)DV,
+    const bool fuse = wv::dw_bwd_can_fuse_scale(dy, sv.H1, (const float*)w.unit, sv.v, T);
+    UnitBwdOpt o1;
+    o1.h_saved = sv.H1;
+    if (fuse) { o1.dy_scale_ptr = res_scale_param; o1.dy_scale = res_scale; o1.dot_v = sv.v; o1.dot_partial = w.DV; }
+    else {
+        hipLaunchKernelGGL(wv::scale_dot_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, (const float4*)dy, (const float4*)sv.v, (float4*)w.DV,
                            res_scale_param, res_scale, b->partial, n4);
         if (d_res_scale_param) hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, b->partial, wv::RED_BLOCKS, res_scale, d_res_scale_param);
         WV_HIP_TRY(hipGetLastError());
-        rc = unit_backward_impl(b->h[1], u, p[1].g_pw, p[1].v_pw, p[1].g_dw, p[1].v_dw, 1.f, 1, DV, DU, g[1].dg_pw, g[1].dv_pw,
-                                g[1].dg_dw, g[1].dv_dw, g[1].db, B, T, hws, hws_bytes, stream, H1, nullptr, nullptr);
+    }
+    int rc = unit_backward_impl(b->h[1], sv.u, p[1], 1.f, 1, fuse ? dy : w.DV, w.DU, g[1], B, T, w.unit, w.unit_bytes, stream, o1);
+    if (fuse && !rc && d_res_scale_param) {
+        hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, w.DV, B * C, res_scale, d_res_scale_param);
+        WV_HIP_TRY(hipGetLastError());
     }
     bool added = false;
-    if (!rc) rc = unit_backward_impl(b->h[0], x, p[0].g_pw, p[0].v_pw, p[0].g_dw, p[0].v_dw, pre_scale, 1, DU, dx, g[0].dg_pw, g[0].dv_pw,
-                                     g[0].dg_dw, g[0].dv_dw, g[0].db, B, T, hws, hws_bytes, stream, H0, dy, &added);      // + the identity shortcut
+    UnitBwdOpt o0;
+    o0.h_saved = sv.H0; o0.dx_add = dy; o0.added = &added;       // + the identity shortcut
+    if (!rc) rc = unit_backward_impl(b->h[0], x, p[0], pre_scale, 1, w.DU, dx, g[0], B, T, w.unit, w.unit_bytes, stream, o0);
     if (rc) return rc;
     if (!added) hipLaunchKernelGGL(wv::add_inplace_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, (float4*)dx, (const float4*)dy, n4);
     WV_HIP_TRY(hipGetLastError());
@@ -1469,14 +1549,12 @@ int wv_train_convpre_create(int C, int ks, wv_train_convpre** out) {
     if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size");
     auto* h = new wv_train_convpre();
     h->C = C; h->ks = ks;
-    if (!((h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(C, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) && (h->taps = h->alloc((size_t)C * ks, false)))) {
-        delete h;
-        return fail(WV_EHIP, "device allocation failed");
-    }
-    *out = h;
-    return WV_OK;
+    const bool ok = (h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(C, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) &&
+                    (h->taps = h->alloc((size_t)C * ks, false));
+    return wv::created(h, ok, out);
 }
 void wv_train_convpre_destroy(wv_train_convpre* h) { delete h; }
+// one buffer, so the size is the layout: per-clip partial sums of the tap and bias gradients
 size_t wv_train_convpre_workspace_bytes(const wv_train_convpre* h, int B, int T) {
     return (h && B > 0 && T > 0) ? al256((size_t)B * h->C * (h->ks + 1) * 4) : 0;
 }
@@ -1485,8 +1563,7 @@ int wv_train_convpre_forward(wv_train_convpre* h, const float* x, const float* g
                              float* y, int B, int T, void* stream) {
     if (!h || !x || !g || !v || !y || B < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, h->C, h->ks, 0, 0,
-                       (const float*)nullptr, 1.f);
+    wv::launch_fold(s, wv::fold_plain(g, v, h->w, h->inv, h->C, h->ks));
     WV_HIP_TRY(hipGetLastError());
     WV_HIP_TRY(wv::launch_conv_pre(x, h->w, bias, y, nullptr, 0.f, B, h->C, T, h->ks, in_scale, s));
     return WV_OK;
@@ -1498,8 +1575,7 @@ int wv_train_convpre_backward(wv_train_convpre* h, const float* x, const float* 
     if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpre_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, ks = h->ks;
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, C, ks, 0, 0,
-                       (const float*)nullptr, 1.f);
+    wv::launch_fold(s, wv::fold_plain(g, v, h->w, h->inv, C, ks));
     // per-clip partial sums of dW[c][i] = sum_t dy[c][t] x[t - (ks-1) + i] and of db, then the fixed-order sum over clips
     wv::launch_dw_bwd(s, dy, x, h->w, (float*)nullptr, (float*)ws, C, B, T, T, ks, 1, ks - 1, 1);
     wv::launch_sum_parts(s, (const float*)ws, h->dwdb, B, (size_t)C * (ks + 1));
@@ -1512,41 +1588,33 @@ int wv_train_convpre_backward(wv_train_convpre* h, const float* x, const float* 
 
 // ---- SpecBlock add: y = x + s * (W(g,v)[C,F] @ P[B,F,T]),  s = res_scale * scale_param[0] (seanet.py:463-511) ----------------
 struct wv_train_spec : wv::TrainHandle {
-    int C = 0, F = 0, Mp = 0;
-    float *w = nullptr, *inv = nullptr, *wq = nullptr, *wt = nullptr, *wqT = nullptr, *wtT = nullptr, *dW = nullptr, *id_taps = nullptr;
-    int KpT = 0;
+    wv::WnLinear lin;                                            // W [C][F]
+    float* id_taps = nullptr;
 };
 
 int wv_train_spec_create(int C, int F, wv_train_spec** out) {
     if (!out || C < 1 || C > 4096 || F < 1 || F > 4096) return fail(WV_EINVAL, "bad channel count");
     auto* h = new wv_train_spec();
-    h->C = C; h->F = F; h->Mp = wv::round_up(C, wv::M_ALIGN); h->KpT = wv::round_up(F, wv::M_ALIGN);
-    const int R = std::max(C, F);
-    bool ok = (h->wqT = h->alloc((size_t)wv::round_up(C, 32) * h->KpT, true)) && (h->wtT = h->alloc((size_t)wv::round_up(C, wv::BK) * h->KpT, true)) &&
-              (h->w = h->alloc((size_t)C * F, false)) && (h->inv = h->alloc(C, false)) && (h->wq = h->alloc((size_t)wv::round_up(F, 32) * h->Mp, true)) &&
-              (h->wt = h->alloc((size_t)wv::round_up(F, wv::BK) * h->Mp, true)) && (h->dW = h->alloc((size_t)C * F, false)) && (h->id_taps = h->identity_taps(R));
-    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
-    *out = h;
-    return WV_OK;
+    const bool ok = h->lin.alloc(*h, C, F) && (h->id_taps = h->identity_taps(std::max(C, F)));
+    return wv::created(h, ok, out);
 }
 void wv_train_spec_destroy(wv_train_spec* h) { delete h; }
+// one buffer: the dW GEMM's splits
 size_t wv_train_spec_workspace_bytes(const wv_train_spec* h, int B, int T) {
-    return (h && B > 0 && T > 0) ? al256((size_t)nt_plan(B, T, h->C, h->F).S * h->C * h->F * 4) : 0;
+    return h ? wv::gemm_nt_sum_workspace_bytes(B, T, h->lin.M, h->lin.K) : 0;
 }
 
 int wv_train_spec_forward(wv_train_spec* h, const float* x, const float* P, const float* g, const float* v, const float* scale_param,
                           float res_scale, float* y, int B, int T, void* stream) {
     if (!h || !x || !P || !g || !v || !y || B < 1 || T < 1) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
-    // the scalar s rides in the GEMM operand: wq = s * W
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->C), dim3(256), 0, s, g, v, h->w, h->inv, h->wq, (float*)nullptr, h->C, h->F, h->Mp, 0,
-                       scale_param, res_scale, h->wt, (float*)nullptr);
+    // the scalar s rides in the GEMM operand: wq = s * W (the packs of W only)
+    wv::WnFoldArgs fa = h->lin.fold(g, v, scale_param, res_scale);
+    fa.wqT = fa.wtT = nullptr; fa.KpT = 0;
+    wv::launch_fold(s, fa);
     WV_HIP_TRY(hipGetLastError());
-    wv::PwDwArgs a{};
-    a.X = P; a.pw.M = h->C; a.pw.K = h->F; a.pw.Mp = h->Mp; a.pw.Kp = wv::round_up(h->F, wv::BK); a.pw.wq = h->wq; a.pw.wt = h->wt;
-    a.dw_w = h->id_taps; a.dw_b = nullptr; a.resid = x; a.Y = y;
-    a.B = B; a.Tin = T; a.Tout = T; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
-    a.pre_scale = 1.f; a.pre_elu = 0; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
+    wv::PwDwArgs a = wv::plain_gemm(P, h->lin.pack(false), h->id_taps, y, B, T);
+    a.resid = x;
     WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
@@ -1557,79 +1625,69 @@ int wv_train_spec_backward(wv_train_spec* h, const float* P, const float* g, con
     if (scale_param && !d_scale_param) return fail(WV_EINVAL, "scale_param without a gradient slot");
     if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_spec_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const int C = h->C, F = h->F;
-    const NtPlan np_ = nt_plan(B, T, C, F);
-    const int S = np_.S;
+    const wv::WnLinear& L = h->lin;
+    const int C = L.M, F = L.K;
     const size_t n = (size_t)C * F;
     // plain W for the parameter gradients; (s W)^T packs when the gradient towards the features is wanted
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(C), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, dP ? h->wqT : (float*)nullptr, C, F, 0, h->KpT,
-                       scale_param, res_scale, (float*)nullptr, dP ? h->wtT : (float*)nullptr);
+    wv::WnFoldArgs fa = L.fold(g, v, scale_param, res_scale);
+    fa.wq = fa.wt = nullptr; fa.Mp = 0;
+    if (!dP) fa.wqT = fa.wtT = nullptr;
+    wv::launch_fold(s, fa);
     if (dP) {                                                   // dP = (s W)^T @ dy
         WV_HIP_TRY(hipGetLastError());
-        wv::PwDwArgs t{};
-        t.X = dy; t.pw.M = F; t.pw.K = C; t.pw.Mp = h->KpT; t.pw.Kp = wv::round_up(C, wv::BK); t.pw.wq = h->wqT; t.pw.wt = h->wtT;
-        t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = dP;
-        t.B = B; t.Tin = T; t.Tout = T; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
-        t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-        WV_HIP_TRY(wv::launch_pw_dw(t, s));
+        WV_HIP_TRY(wv::launch_pw_dw(wv::plain_gemm(dy, L.pack(true), h->id_taps, dP, B, T), s));
     }
-    // G = sum_{b,t} dy P^T;  d scale_param = res_scale * <W, G>  (= res_scale * sum dy . (W @ P));  dW = s * G
-    WV_HIP_TRY(wv::launch_gemm_nt(s, dy, P, (float*)ws, 1.f, 0, B, C, F, T, S, np_.TC));
-    wv::launch_sum_parts(s, (const float*)ws, h->dW, S, n);
+    // G = sum_{b,t} dy P^T;  d scale_param = res_scale * <W, G>  (= res_scale * sum dy . (W @ P));  dW = s * G, scaled between the sum and
+    // the weight-norm backward, so this is WnLinear::grad's GEMM-and-sum half with a finish of its own
+    WV_HIP_TRY(wv::launch_gemm_nt_sum(s, dy, P, L.dW, (float*)ws, 1.f, 0, B, C, F, T));
     if (d_scale_param) {
         if (ws_bytes >= wv::RED_BLOCKS * sizeof(float)) {        // the split partials have been summed: their buffer takes the dot's partials
-            hipLaunchKernelGGL(wv::dot_parts_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, h->w, h->dW, n, (float*)ws);
+            hipLaunchKernelGGL(wv::dot_parts_kernel, dim3(wv::RED_BLOCKS), dim3(256), 0, s, L.w, L.dW, n, (float*)ws);
             hipLaunchKernelGGL(wv::finish_sum_kernel, dim3(1), dim3(wv::FIN_T), 0, s, (const float*)ws, wv::RED_BLOCKS, res_scale, d_scale_param);
-        } else hipLaunchKernelGGL(wv::dot_small_kernel, dim3(1), dim3(256), 0, s, h->w, h->dW, n, res_scale, d_scale_param);
+        } else hipLaunchKernelGGL(wv::dot_small_kernel, dim3(1), dim3(256), 0, s, L.w, L.dW, n, res_scale, d_scale_param);
     }
-    hipLaunchKernelGGL(wv::scale_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->dW, n, scale_param, res_scale);
-    hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(C), dim3(256), 0, s, g, v, h->inv, h->dW, dg, dv, F);
+    hipLaunchKernelGGL(wv::scale_inplace_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, L.dW, n, scale_param, res_scale);
+    hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(C), dim3(256), 0, s, g, v, L.inv, L.dW, dg, dv, F);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
 
 // ---- conv_post: ELU -> causal depth-wise conv (ks, no bias) -> 1x1 (C -> D, bias) -> L2Norm * sqrt(D) (seanet.py:795-822) --------
 struct wv_train_convpost : wv::TrainHandle {
-    int C = 0, D = 0, ks = 0, Mp = 0, KpT = 0;
-    float *w_dw = nullptr, *inv_dw = nullptr, *w_pw = nullptr, *inv_pw = nullptr, *wt = nullptr, *wtT = nullptr, *wq = nullptr, *wqT = nullptr;
-    float *dW = nullptr, *dwdb = nullptr, *taps = nullptr, *dbsum = nullptr, *junk = nullptr, *id_taps = nullptr;
+    int C = 0, D = 0, ks = 0;
+    wv::WnLinear pw;                                             // the 1x1 [D][C]
+    float *w_dw = nullptr, *inv_dw = nullptr, *dwdb = nullptr, *taps = nullptr, *junk = nullptr, *id_taps = nullptr;
 };
+
+// Workspace of the backward, in carving order: a = ELU(x), h = DW(a) (later da), dh [B, C, T]; z [B, D, T]; the per-clip partial sums of
+// whichever row reduction runs; the dW GEMM's splits.
+struct ConvpostWs { float *A, *H, *DH, *Z, *partial, *parts; size_t total; };
+static ConvpostWs convpost_ws(const wv_train_convpost* h, int B, int T, void* base) {
+    if (!h || B < 1 || T < 1) return {};
+    const size_t ac = (size_t)B * h->C * T * 4;
+    wv::Carver c(base);
+    return {c.take(ac), c.take(ac), c.take(ac), c.take((size_t)B * h->D * T * 4), c.take((size_t)B * std::max(h->C * (h->ks + 1), h->D * 2) * 4),
+            c.take(wv::gemm_nt_sum_workspace_bytes(B, T, h->D, h->C)), c.used};
+}
 
 int wv_train_convpost_create(int C, int D, int ks, wv_train_convpost** out) {
     if (!out || C < 1 || C > 4096 || D < 1 || D > 128 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size (D <= 128)");
     auto* h = new wv_train_convpost();
-    h->C = C; h->D = D; h->ks = ks; h->Mp = wv::round_up(D, wv::M_ALIGN); h->KpT = wv::round_up(C, wv::M_ALIGN);
-    bool ok = (h->w_dw = h->alloc((size_t)C * ks, false)) && (h->inv_dw = h->alloc(C, false)) && (h->w_pw = h->alloc((size_t)D * C, false)) && (h->inv_pw = h->alloc(D, false)) &&
-              (h->wt = h->alloc((size_t)wv::round_up(C, wv::BK) * h->Mp, true)) && (h->wtT = h->alloc((size_t)wv::round_up(D, wv::BK) * h->KpT, true)) &&
-              (h->wq = h->alloc((size_t)wv::round_up(C, 32) * h->Mp, true)) && (h->wqT = h->alloc((size_t)wv::round_up(D, 32) * h->KpT, true)) &&
-              (h->dW = h->alloc((size_t)D * C, false)) && (h->dwdb = h->alloc((size_t)std::max(C * (ks + 1), D * 2), false)) && (h->taps = h->alloc((size_t)C * ks, false)) &&
-              (h->dbsum = h->alloc((size_t)D, false)) && (h->junk = h->alloc((size_t)std::max(C, D), false)) && (h->id_taps = h->identity_taps(C));
-    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
-    *out = h;
-    return WV_OK;
+    h->C = C; h->D = D; h->ks = ks;
+    const bool ok = h->pw.alloc(*h, D, C) && (h->w_dw = h->alloc((size_t)C * ks, false)) && (h->inv_dw = h->alloc(C, false)) &&
+                    (h->dwdb = h->alloc((size_t)std::max(C * (ks + 1), D * 2), false)) && (h->taps = h->alloc((size_t)C * ks, false)) &&
+                    (h->junk = h->alloc((size_t)std::max(C, D), false)) && (h->id_taps = h->identity_taps(C));
+    return wv::created(h, ok, out);
 }
 void wv_train_convpost_destroy(wv_train_convpost* h) { delete h; }
 
-size_t wv_train_convpost_workspace_bytes(const wv_train_convpost* h, int B, int T) {
-    if (!h || B < 1 || T < 1) return 0;
-    const size_t ac = al256((size_t)B * h->C * T * 4), ad = al256((size_t)B * h->D * T * 4);
-    return 3 * ac + ad + al256((size_t)B * std::max(h->C * (h->ks + 1), h->D * 2) * 4) + al256((size_t)nt_plan(B, T, h->D, h->C).S * h->D * h->C * 4);
-}
+size_t wv_train_convpost_workspace_bytes(const wv_train_convpost* h, int B, int T) { return convpost_ws(h, B, T, nullptr).total; }
 
 static int convpost_fold(wv_train_convpost* h, const float* g_dw, const float* v_dw, const float* g_pw, const float* v_pw, hipStream_t s) {
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->C), dim3(256), 0, s, g_dw, v_dw, h->w_dw, h->inv_dw, (float*)nullptr, (float*)nullptr, h->C, h->ks, 0, 0,
-                       (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->D), dim3(256), 0, s, g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->D, h->C, h->Mp, h->KpT,
-                       (const float*)nullptr, 1.f, h->wt, h->wtT);
+    wv::launch_fold(s, wv::fold_plain(g_dw, v_dw, h->w_dw, h->inv_dw, h->C, h->ks));
+    wv::launch_fold(s, h->pw.fold(g_pw, v_pw));
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
-}
-
-static wv::PwWeight convpost_pack(const wv_train_convpost* h, bool transposed) {
-    wv::PwWeight p;
-    if (!transposed) { p.M = h->D; p.K = h->C; p.Mp = h->Mp; p.Kp = wv::round_up(h->C, wv::BK); p.wq = h->wq; p.wt = h->wt; }
-    else { p.M = h->C; p.K = h->D; p.Mp = h->KpT; p.Kp = wv::round_up(h->D, wv::BK); p.wq = h->wqT; p.wt = h->wtT; }
-    return p;
 }
 
 int wv_train_convpost_forward(wv_train_convpost* h, const float* x, const float* g_dw, const float* v_dw, const float* g_pw, const float* v_pw,
@@ -1639,7 +1697,7 @@ int wv_train_convpost_forward(wv_train_convpost* h, const float* x, const float*
     int rc = convpost_fold(h, g_dw, v_dw, g_pw, v_pw, s);
     if (rc) return rc;
     wv::DwPwArgs a{};
-    a.X = x; a.dw_w = h->w_dw; a.pw = convpost_pack(h, false); a.bias = bias; a.Y = y;
+    a.X = x; a.dw_w = h->w_dw; a.pw = h->pw.pack(false); a.bias = bias; a.Y = y;
     a.B = B; a.Tin = T; a.Tout = T; a.mode = 1; a.ks = h->ks; a.pre_scale = 1.f; a.pre_elu = 1; a.l2norm = l2norm; a.out_scale = 1.f;
     WV_HIP_TRY(wv::launch_dw_pw(a, s));
     return WV_OK;
@@ -1649,52 +1707,36 @@ int wv_train_convpost_backward(wv_train_convpost* h, const float* x, const float
                                const float* bias, int l2norm, const float* dy, float* dx, float* dg_dw, float* dv_dw, float* dg_pw, float* dv_pw,
                                float* db, int B, int T, void* ws, size_t ws_bytes, void* stream) {
     if (!h || !x || !g_dw || !v_dw || !g_pw || !v_pw || !dy || !dx || !dg_dw || !dv_dw || !dg_pw || !dv_pw || !db) return fail(WV_EINVAL, "null argument");
-    if (B < 1 || T < 1 || !ws || ws_bytes < wv_train_convpost_workspace_bytes(h, B, T)) return fail(WV_ENOMEM, "workspace too small");
+    const ConvpostWs w = convpost_ws(h, B, T, ws);
+    if (!w.total || !ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, D = h->D, ks = h->ks;
-    const NtPlan np_ = nt_plan(B, T, D, C);
-    const int S = np_.S;
-    const size_t ac = al256((size_t)B * C * T * 4), ad = al256((size_t)B * D * T * 4);
-    char* w = (char*)ws;
-    float* A = (float*)w; float* H = (float*)(w + ac); float* DH = (float*)(w + 2 * ac); float* Z = (float*)(w + 3 * ac);
-    float* partial = (float*)(w + 3 * ac + ad);
-    float* parts = (float*)(w + 3 * ac + ad + al256((size_t)B * std::max(C * (ks + 1), D * 2) * 4));
     int rc = convpost_fold(h, g_dw, v_dw, g_pw, v_pw, s);
     if (rc) return rc;
     // recompute a = ELU(x), h = DW(a), z = W h + b
-    hipLaunchKernelGGL(wv::elu_dw_fwd_kernel, dim3(C, B), dim3(256), 0, s, x, h->w_dw, A, H, C, T, ks);
+    hipLaunchKernelGGL(wv::elu_dw_fwd_kernel, dim3(C, B), dim3(256), 0, s, x, h->w_dw, w.A, w.H, C, T, ks);
     WV_HIP_TRY(hipGetLastError());
     const float* dZ = dy;
     if (l2norm) {
         wv::DwPwArgs a{};
-        a.X = H; a.pw = convpost_pack(h, false); a.bias = bias; a.Y = Z;
+        a.X = w.H; a.pw = h->pw.pack(false); a.bias = bias; a.Y = w.Z;
         a.B = B; a.Tin = T; a.Tout = T; a.mode = 0; a.ks = 1; a.pre_scale = 1.f; a.pre_elu = 0; a.l2norm = 0; a.out_scale = 1.f;
         WV_HIP_TRY(wv::launch_dw_pw(a, s));
-        hipLaunchKernelGGL(wv::l2norm_bwd_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, Z, dy, D, T, 1e-12f);
-        dZ = Z;
+        hipLaunchKernelGGL(wv::l2norm_bwd_kernel, dim3((T + 255) / 256, B), dim3(256), 0, s, w.Z, dy, D, T, 1e-12f);
+        dZ = w.Z;
     }
-    // db = sum dz (the bias slot of the row-sum kernel with one tap), dW = sum dz h^T
-    wv::launch_dw_bwd(s, dZ, dZ, h->junk, (float*)nullptr, partial, D, B, T, T, 1, 1, 0, 0);
-    wv::launch_sum_parts(s, partial, h->dwdb, B, (size_t)D * 2);
-    hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((D + 255) / 256), dim3(256), 0, s, h->dwdb, h->junk, db, D, 1, 1.f);
-    WV_HIP_TRY(wv::launch_gemm_nt(s, dZ, H, parts, 1.f, 0, B, D, C, T, S, np_.TC));
-    wv::launch_sum_parts(s, parts, h->dW, S, (size_t)D * C);
-    hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(D), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, C);
-    WV_HIP_TRY(hipGetLastError());
+    // db = sum dz, dW = sum dz h^T
+    wv::row_sum(s, dZ, db, w.partial, h->dwdb, h->junk, D, B, T);
+    rc = h->pw.grad(s, dZ, w.H, w.parts, 1.f, 0, B, T, g_pw, v_pw, dg_pw, dv_pw);
+    if (rc) return rc;
     // dh = W^T dz
-    wv::PwDwArgs t{};
-    t.X = dZ; t.pw = convpost_pack(h, true); t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = DH;
-    t.B = B; t.Tin = T; t.Tout = T; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
-    t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-    WV_HIP_TRY(wv::launch_pw_dw(t, s));
+    WV_HIP_TRY(wv::launch_pw_dw(wv::plain_gemm(dZ, h->pw.pack(true), h->id_taps, w.DH, B, T), s));
     // through the depth-wise conv (da into the H buffer) and the ELU
-    wv::launch_dw_bwd(s, DH, A, h->w_dw, H, partial, C, B, T, T, ks, 1, ks - 1, 0);
-    wv::launch_sum_parts(s, partial, h->dwdb, B, (size_t)C * (ks + 1));
+    wv::launch_dw_bwd(s, w.DH, w.A, h->w_dw, w.H, w.partial, C, B, T, T, ks, 1, ks - 1, 0);
+    wv::launch_sum_parts(s, w.partial, h->dwdb, B, (size_t)C * (ks + 1));
     hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((C + 255) / 256), dim3(256), 0, s, h->dwdb, h->taps, h->junk, C, ks, 1.f);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(C), dim3(256), 0, s, g_dw, v_dw, h->inv_dw, h->taps, dg_dw, dv_dw, ks);
-    const size_t n = (size_t)B * C * T, n4 = n / 4;
-    if (n4) hipLaunchKernelGGL(wv::elu_bwd_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, H, x, dx, 1.f, n4);
-    if (n % 4) hipLaunchKernelGGL(wv::elu_bwd_tail_kernel, dim3(1), dim3(256), 0, s, H, x, dx, 1.f, n4 * 4, n);
+    wv::elu_bwd(s, w.H, x, dx, 1.f, (size_t)B * C * T);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -1705,31 +1747,35 @@ struct wv_train_head : wv::TrainHandle {
     float *wt_q = nullptr, *wt_dz = nullptr, *wt_l = nullptr, *wt_lT = nullptr, *bias_q = nullptr, *scr = nullptr, *junk = nullptr;
 };
 
+// One workspace for both directions, in carving order: the ConvTranspose frames q [B, O, hop*N]; dq (backward only); lq [B, nb, hop*N],
+// the last layer's frames in the forward and their gradient in the backward; the splits of the larger of the two dW GEMMs; the row
+// sums' per-clip partials.
+struct HeadWs { float *q, *dq, *lq, *parts, *partial; size_t total; };
+static HeadWs head_ws(const wv_train_head* h, int B, int N, void* base) {
+    if (!h || B < 1 || N < 1) return {};
+    const size_t hn = (size_t)h->hop * N, aq = (size_t)B * h->O * hn * 4;
+    wv::Carver c(base);
+    return {c.take(aq), c.take(aq), c.take((size_t)B * h->nb * hn * 4),
+            c.take(std::max(wv::gemm_nt_sum_workspace_bytes(B, N, h->D, h->O * h->hop), wv::gemm_nt_sum_workspace_bytes(B, (int)hn, h->nb, h->O))),
+            c.take((size_t)B * std::max(h->nb, h->O) * 2 * 4), c.used};
+}
+
 int wv_train_head_create(int D, int O, int nb, int hop, wv_train_head** out) {
     if (!out || D < 1 || D > 4096 || O < 1 || O > 4096 || nb < 1 || nb > 4096 || hop < 1 || (long long)O * hop > (1 << 20)) return fail(WV_EINVAL, "bad head shape");
     auto* h = new wv_train_head();
     h->D = D; h->O = O; h->nb = nb; h->hop = hop;
     const int OH = O * hop;
     const size_t big = std::max<size_t>((size_t)std::max(nb, O) * 2, 64);
-    bool ok = (h->wt_q = h->alloc((size_t)wv::round_up(D, wv::BK) * wv::round_up(OH, wv::M_ALIGN), true)) &&
-              (h->wt_dz = h->alloc((size_t)wv::round_up(OH, wv::BK) * wv::round_up(D, wv::M_ALIGN), true)) &&
-              (h->wt_l = h->alloc((size_t)wv::round_up(O, wv::BK) * wv::round_up(nb, wv::M_ALIGN), true)) &&
-              (h->wt_lT = h->alloc((size_t)wv::round_up(nb, wv::BK) * wv::round_up(O, wv::M_ALIGN), true)) && (h->bias_q = h->alloc((size_t)OH, true)) &&
-              (h->scr = h->alloc(big, true)) && (h->junk = h->alloc(big, true));
-    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
-    *out = h;
-    return WV_OK;
+    const bool ok = (h->wt_q = h->alloc((size_t)wv::round_up(D, wv::BK) * wv::round_up(OH, wv::M_ALIGN), true)) &&
+                    (h->wt_dz = h->alloc((size_t)wv::round_up(OH, wv::BK) * wv::round_up(D, wv::M_ALIGN), true)) &&
+                    (h->wt_l = h->alloc((size_t)wv::round_up(O, wv::BK) * wv::round_up(nb, wv::M_ALIGN), true)) &&
+                    (h->wt_lT = h->alloc((size_t)wv::round_up(nb, wv::BK) * wv::round_up(O, wv::M_ALIGN), true)) && (h->bias_q = h->alloc((size_t)OH, true)) &&
+                    (h->scr = h->alloc(big, true)) && (h->junk = h->alloc(big, true));
+    return wv::created(h, ok, out);
 }
 void wv_train_head_destroy(wv_train_head* h) { delete h; }
 
-
-size_t wv_train_head_workspace_bytes(const wv_train_head* h, int B, int N) {
-    if (!h || B < 1 || N < 1) return 0;
-    const size_t hn = (size_t)h->hop * N;
-    const size_t aq = al256((size_t)B * h->O * hn * 4), al = al256((size_t)B * h->nb * hn * 4);
-    const size_t p1 = (size_t)nt_plan(B, N, h->D, h->O * h->hop).S * h->D * h->O * h->hop, p2 = (size_t)nt_plan(B, (int)hn, h->nb, h->O).S * h->nb * h->O;
-    return 2 * aq + al + al256(std::max(p1, p2) * 4) + al256((size_t)B * std::max(h->nb, h->O) * 2 * 4);
-}
+size_t wv_train_head_workspace_bytes(const wv_train_head* h, int B, int N) { return head_ws(h, B, N, nullptr).total; }
 
 static wv::PwWeight head_pw(int M, int K, const float* wt) {
     wv::PwWeight p; p.M = M; p.K = K; p.Mp = wv::round_up(M, wv::M_ALIGN); p.Kp = wv::round_up(K, wv::BK); p.wt = wt; p.wq = nullptr;
@@ -1754,16 +1800,16 @@ static int head_q(wv_train_head* h, const float* z, const float* w_rev, const fl
 int wv_train_head_forward(wv_train_head* h, const float* z, const float* w_rev, const float* b_rev, const float* w_last, const float* b_last,
                           float* logits, int B, int N, int T, void* ws, size_t ws_bytes, void* stream) {
     if (!h || !z || !w_rev || !w_last || !logits || B < 1 || N < 1 || T < 1 || T > N * h->hop) return fail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return fail(WV_ENOMEM, "workspace too small");
+    const HeadWs w = head_ws(h, B, N, ws);
+    if (!ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const size_t hn = (size_t)h->hop * N, aq = al256((size_t)B * h->O * hn * 4);
-    float* q = (float*)ws; float* lq = (float*)((char*)ws + 2 * aq);
-    int rc = head_q(h, z, w_rev, b_rev, q, B, N, s);
+    const int hn = h->hop * N;
+    int rc = head_q(h, z, w_rev, b_rev, w.q, B, N, s);
     if (rc) return rc;
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)h->nb * h->O + 255) / 256)), dim3(256), 0, s, w_last, h->wt_l, h->nb, h->O, wv::round_up(h->nb, wv::M_ALIGN), 0);
     WV_HIP_TRY(hipGetLastError());
-    WV_HIP_TRY(head_gemm(q, head_pw(h->nb, h->O, h->wt_l), b_last, lq, B, (int)hn, s));
-    hipLaunchKernelGGL(wv::frames_to_time_kernel, dim3((T + 255) / 256, B * h->nb), dim3(256), 0, s, lq, logits, T, h->hop, N);
+    WV_HIP_TRY(head_gemm(w.q, head_pw(h->nb, h->O, h->wt_l), b_last, w.lq, B, hn, s));
+    hipLaunchKernelGGL(wv::frames_to_time_kernel, dim3((T + 255) / 256, B * h->nb), dim3(256), 0, s, w.lq, logits, T, h->hop, N);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -1773,79 +1819,67 @@ int wv_train_head_backward(wv_train_head* h, const float* z, const float* w_rev,
                            void* ws, size_t ws_bytes, void* stream) {
     if (!h || !z || !w_rev || !w_last || !dlogits || !dz || !dw_rev || !db_rev || !dw_last || !db_last || B < 1 || N < 1 || T < 1 || T > N * h->hop)
         return fail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_head_workspace_bytes(h, B, N)) return fail(WV_ENOMEM, "workspace too small");
+    const HeadWs w = head_ws(h, B, N, ws);
+    if (!ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const int D = h->D, O = h->O, nb = h->nb, hop = h->hop, OH = O * hop;
-    const size_t hn = (size_t)hop * N, aq = al256((size_t)B * O * hn * 4), al = al256((size_t)B * nb * hn * 4);
-    const NtPlan np1 = nt_plan(B, N, D, OH), np2 = nt_plan(B, (int)hn, nb, O);
-    const size_t p1 = (size_t)np1.S * D * OH, p2 = (size_t)np2.S * nb * O;
-    char* w = (char*)ws;
-    float* q = (float*)w; float* dq = (float*)(w + aq); float* dlq = (float*)(w + 2 * aq);
-    float* parts = (float*)(w + 2 * aq + al);
-    float* partial = (float*)(w + 2 * aq + al + al256(std::max(p1, p2) * 4));
-    int rc = head_q(h, z, w_rev, b_rev, q, B, N, s);                               // recomputed (forward keeps nothing)
+    const int D = h->D, O = h->O, nb = h->nb, hop = h->hop, OH = O * hop, hn = hop * N;
+    int rc = head_q(h, z, w_rev, b_rev, w.q, B, N, s);                             // recomputed (forward keeps nothing)
     if (rc) return rc;
-    hipLaunchKernelGGL(wv::time_to_frames_kernel, dim3((unsigned)((hn + 255) / 256), B * nb), dim3(256), 0, s, dlogits, dlq, T, hop, N);
+    hipLaunchKernelGGL(wv::time_to_frames_kernel, dim3((unsigned)((hn + 255) / 256), B * nb), dim3(256), 0, s, dlogits, w.lq, T, hop, N);
     // last layer: dw_last[k][o] = sum dlq[k] . q[o] over (b, j, n);  db_last[k] = sum dlogits
-    const int S2 = np2.S;
-    WV_HIP_TRY(wv::launch_gemm_nt(s, dlq, q, parts, 1.f, 0, B, nb, O, (int)hn, S2, np2.TC));
-    wv::launch_sum_parts(s, parts, dw_last, S2, (size_t)nb * O);
-    wv::launch_dw_bwd(s, dlq, dlq, h->junk, (float*)nullptr, partial, nb, B, (int)hn, (int)hn, 1, 1, 0, 0);
-    wv::launch_sum_parts(s, partial, h->scr, B, (size_t)nb * 2);
-    hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((nb + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db_last, nb, 1, 1.f);
+    WV_HIP_TRY(wv::launch_gemm_nt_sum(s, w.lq, w.q, dw_last, w.parts, 1.f, 0, B, nb, O, hn));
+    wv::row_sum(s, w.lq, db_last, w.partial, h->scr, h->junk, nb, B, hn);
     // dq = w_last^T @ dlq
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)O * nb + 255) / 256)), dim3(256), 0, s, w_last, h->wt_lT, O, nb, wv::round_up(O, wv::M_ALIGN), 1);
     WV_HIP_TRY(hipGetLastError());
-    WV_HIP_TRY(head_gemm(dlq, head_pw(O, nb, h->wt_lT), nullptr, dq, B, (int)hn, s));
+    WV_HIP_TRY(head_gemm(w.lq, head_pw(O, nb, h->wt_lT), nullptr, w.dq, B, hn, s));
     // db_rev[o] = sum dq[o];  dw_rev[d][(o,j)] = sum_{b,n} z[d][n] dq[(o,j)][n];  dz = w_rev @ dq
-    wv::launch_dw_bwd(s, dq, dq, h->junk, (float*)nullptr, partial, O, B, (int)hn, (int)hn, 1, 1, 0, 0);
-    wv::launch_sum_parts(s, partial, h->scr, B, (size_t)O * 2);
-    hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((O + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db_rev, O, 1, 1.f);
-    const int S1 = np1.S;
-    WV_HIP_TRY(wv::launch_gemm_nt(s, z, dq, parts, 1.f, 0, B, D, OH, N, S1, np1.TC));
-    wv::launch_sum_parts(s, parts, dw_rev, S1, (size_t)D * OH);
+    wv::row_sum(s, w.dq, db_rev, w.partial, h->scr, h->junk, O, B, hn);
+    WV_HIP_TRY(wv::launch_gemm_nt_sum(s, z, w.dq, dw_rev, w.parts, 1.f, 0, B, D, OH, N));
     hipLaunchKernelGGL(wv::pack_wt_kernel, dim3((unsigned)(((size_t)D * OH + 255) / 256)), dim3(256), 0, s, w_rev, h->wt_dz, D, OH, wv::round_up(D, wv::M_ALIGN), 0);
     WV_HIP_TRY(hipGetLastError());
-    WV_HIP_TRY(head_gemm(dq, head_pw(D, OH, h->wt_dz), nullptr, dz, B, N, s));
+    WV_HIP_TRY(head_gemm(w.dq, head_pw(D, OH, h->wt_dz), nullptr, dz, B, N, s));
     return WV_OK;
 }
 
 // ---- upsample unit: y[B,M,r*Tin] = W(g,v)[M,K] @ ConvT_dw(act(s x[B,K,Tin]); taps(g,v)[K,2r]) + bias (seanet.py:1110-1135) -------
 struct wv_train_up : wv::TrainHandle {
-    int K = 0, M = 0, r = 0, Mp = 0, KpT = 0, Kp = 0;
-    float *w_ct = nullptr, *inv_ct = nullptr, *ct_wt = nullptr, *w_pw = nullptr, *inv_pw = nullptr, *wq = nullptr, *wqT = nullptr, *wt = nullptr, *wtT = nullptr;
-    float *id_taps = nullptr, *dW = nullptr, *taps = nullptr, *scr = nullptr, *junk = nullptr;
+    int r = 0;
+    wv::WnLinear pw;                                             // the 1x1 [M][K]
+    float *w_ct = nullptr, *inv_ct = nullptr, *ct_wt = nullptr;  // folded ConvTranspose taps [K][2r] and their [2r][Kp] pack
+    float *id_taps = nullptr, *taps = nullptr, *scr = nullptr, *junk = nullptr;
 };
+
+// Workspace of the backward, in carving order: the upsampled activations u and du [B, K, r*Tin]; the per-clip partial sums of
+// whichever row reduction runs; the dW GEMM's splits.
+struct UpWs { float *U, *DU, *partial, *parts; size_t total; };
+static UpWs up_ws(const wv_train_up* h, int B, int Tin, void* base) {
+    if (!h || B < 1 || Tin < 1) return {};
+    const int M = h->pw.M, K = h->pw.K, Tout = Tin * h->r;
+    const size_t au = (size_t)B * K * Tout * 4;
+    wv::Carver c(base);
+    return {c.take(au), c.take(au), c.take((size_t)B * std::max(K * 2 * h->r, M * 2) * 4), c.take(wv::gemm_nt_sum_workspace_bytes(B, Tout, M, K)), c.used};
+}
 
 int wv_train_up_create(int K, int M, int ratio, wv_train_up** out) {
     if (!out || K < 1 || K > 4096 || M < 1 || M > 4096 || ratio < 1 || 2 * ratio > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad upsample shape (ratio <= 8)");
     auto* h = new wv_train_up();
-    h->K = K; h->M = M; h->r = ratio; h->Mp = wv::round_up(M, wv::M_ALIGN); h->KpT = wv::round_up(K, wv::M_ALIGN); h->Kp = wv::round_up(K, wv::BK);
+    h->r = ratio;
     const int R = std::max(K, M), ks = 2 * ratio;
-    bool ok = (h->w_ct = h->alloc((size_t)K * ks, true)) && (h->inv_ct = h->alloc(K, true)) && (h->ct_wt = h->alloc((size_t)ks * h->Kp, true)) && (h->w_pw = h->alloc((size_t)M * K, true)) &&
-              (h->inv_pw = h->alloc(M, true)) && (h->wq = h->alloc((size_t)wv::round_up(K, 32) * h->Mp, true)) && (h->wqT = h->alloc((size_t)wv::round_up(M, 32) * h->KpT, true)) &&
-              (h->wt = h->alloc((size_t)h->Kp * h->Mp, true)) && (h->wtT = h->alloc((size_t)wv::round_up(M, wv::BK) * h->KpT, true)) && (h->id_taps = h->identity_taps(R)) &&
-              (h->dW = h->alloc((size_t)M * K, true)) && (h->taps = h->alloc((size_t)K * ks, true)) && (h->scr = h->alloc((size_t)R * 2, true)) && (h->junk = h->alloc((size_t)R, true));
-    if (!ok) { delete h; return fail(WV_EHIP, "device allocation failed"); }
-    *out = h;
-    return WV_OK;
+    const bool ok = h->pw.alloc(*h, M, K) && (h->w_ct = h->alloc((size_t)K * ks, true)) && (h->inv_ct = h->alloc(K, true)) &&
+                    (h->ct_wt = h->alloc((size_t)ks * wv::round_up(K, wv::BK), true)) && (h->id_taps = h->identity_taps(R)) &&
+                    (h->taps = h->alloc((size_t)K * ks, true)) && (h->scr = h->alloc((size_t)R * 2, true)) && (h->junk = h->alloc((size_t)R, true));
+    return wv::created(h, ok, out);
 }
 void wv_train_up_destroy(wv_train_up* h) { delete h; }
 
-size_t wv_train_up_workspace_bytes(const wv_train_up* h, int B, int Tin) {
-    if (!h || B < 1 || Tin < 1) return 0;
-    const int Tout = Tin * h->r;
-    const size_t au = al256((size_t)B * h->K * Tout * 4);
-    return 2 * au + al256((size_t)B * std::max(h->K * 2 * h->r, h->M * 2) * 4) + al256((size_t)nt_plan(B, Tout, h->M, h->K).S * h->M * h->K * 4);
-}
+size_t wv_train_up_workspace_bytes(const wv_train_up* h, int B, int Tin) { return up_ws(h, B, Tin, nullptr).total; }
 
 static int up_fold(wv_train_up* h, const float* g_ct, const float* v_ct, const float* g_pw, const float* v_pw, hipStream_t s) {
-    const int ks = 2 * h->r;
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->K), dim3(256), 0, s, g_ct, v_ct, h->w_ct, h->inv_ct, (float*)nullptr, (float*)nullptr, h->K, ks, 0, 0,
-                       (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
-    hipLaunchKernelGGL(wv::pack_ct_wt_kernel, dim3((h->K * ks + 255) / 256), dim3(256), 0, s, h->w_ct, h->ct_wt, h->K, h->Kp, ks);
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(h->M), dim3(256), 0, s, g_pw, v_pw, h->w_pw, h->inv_pw, h->wq, h->wqT, h->M, h->K, h->Mp, h->KpT,
-                       (const float*)nullptr, 1.f, h->wt, h->wtT);
+    const int K = h->pw.K, ks = 2 * h->r;
+    wv::launch_fold(s, wv::fold_plain(g_ct, v_ct, h->w_ct, h->inv_ct, K, ks));
+    hipLaunchKernelGGL(wv::pack_ct_wt_kernel, dim3((K * ks + 255) / 256), dim3(256), 0, s, h->w_ct, h->ct_wt, K, wv::round_up(K, wv::BK), ks);
+    wv::launch_fold(s, h->pw.fold(g_pw, v_pw));
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -1856,11 +1890,9 @@ int wv_train_up_forward(wv_train_up* h, const float* x, const float* g_ct, const
     hipStream_t s = (hipStream_t)stream;
     int rc = up_fold(h, g_ct, v_ct, g_pw, v_pw, s);
     if (rc) return rc;
-    wv::PwDwArgs a{};
-    a.X = x; a.pw.M = h->M; a.pw.K = h->K; a.pw.Mp = h->Mp; a.pw.Kp = h->Kp; a.pw.wq = h->wq; a.pw.wt = h->wt;
-    a.ct_w = h->w_ct; a.ct_wt = h->ct_wt; a.ratio = h->r; a.dw_w = h->id_taps; a.dw_b = bias; a.Y = y;
-    a.B = B; a.Tin = Tin; a.Tout = Tin * h->r; a.ks = 5; a.stride = 1; a.dil = 1; a.pad = 4;
-    a.pre_scale = pre_scale; a.pre_elu = pre_elu; a.out_scale = 1.f; a.bands = 1; a.film_stride = 2;
+    // the plain GEMM with the ConvTranspose in its loader and the bias in its stencil epilogue
+    wv::PwDwArgs a = wv::plain_gemm(x, h->pw.pack(false), h->id_taps, y, B, Tin, pre_scale, pre_elu);
+    a.ct_w = h->w_ct; a.ct_wt = h->ct_wt; a.ratio = h->r; a.dw_b = bias; a.Tout = Tin * h->r;
     WV_HIP_TRY(wv::launch_pw_dw(a, s));
     return WV_OK;
 }
@@ -1869,48 +1901,27 @@ int wv_train_up_backward(wv_train_up* h, const float* x, const float* g_ct, cons
                          int pre_elu, const float* dy, float* dx, float* dg_ct, float* dv_ct, float* dg_pw, float* dv_pw, float* db, int B, int Tin,
                          void* ws, size_t ws_bytes, void* stream) {
     if (!h || !x || !g_ct || !v_ct || !g_pw || !v_pw || !dy || !dx || !dg_ct || !dv_ct || !dg_pw || !dv_pw || !db) return fail(WV_EINVAL, "null argument");
-    if (B < 1 || Tin < 1 || !ws || ws_bytes < wv_train_up_workspace_bytes(h, B, Tin)) return fail(WV_ENOMEM, "workspace too small");
+    const UpWs w = up_ws(h, B, Tin, ws);
+    if (!w.total || !ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
-    const int K = h->K, M = h->M, r = h->r, ks = 2 * r, Tout = Tin * r;
-    const size_t au = al256((size_t)B * K * Tout * 4);
-    char* w = (char*)ws;
-    float* U = (float*)w; float* DU = (float*)(w + au);
-    float* partial = (float*)(w + 2 * au);
-    float* parts = (float*)(w + 2 * au + al256((size_t)B * std::max(K * ks, M * 2) * 4));
+    const int K = h->pw.K, M = h->pw.M, r = h->r, ks = 2 * r, Tout = Tin * r;
     int rc = up_fold(h, g_ct, v_ct, g_pw, v_pw, s);
     if (rc) return rc;
-    {
-        const bool al = (reinterpret_cast<uintptr_t>(U) & 15) == 0;
-#define WV_CTF(R) hipLaunchKernelGGL((wv::convtr_fwd_frame_kernel<R>), dim3(K, B), dim3(256), 0, s, x, h->w_ct, U, K, Tin, pre_scale, pre_elu)
-        if (r == 2) WV_CTF(2); else if (r == 4 && al) WV_CTF(4); else if (r == 5) WV_CTF(5); else if (r == 8 && al) WV_CTF(8);
-        else hipLaunchKernelGGL(wv::convtr_fwd_kernel, dim3(K, B), dim3(256), 0, s, x, h->w_ct, U, K, Tin, r, pre_scale, pre_elu);
-#undef WV_CTF
-    }
+    const int R = wv::convtr_frame_ratio(r, w.U);              // du sits a multiple of 256 bytes behind u: one answer for both directions
+    auto* fwd = R == 2 ? wv::convtr_fwd_frame_kernel<2> : R == 4 ? wv::convtr_fwd_frame_kernel<4> : R == 5 ? wv::convtr_fwd_frame_kernel<5> : wv::convtr_fwd_frame_kernel<8>;
+    if (R) hipLaunchKernelGGL(fwd, dim3(K, B), dim3(256), 0, s, x, h->w_ct, w.U, K, Tin, pre_scale, pre_elu);
+    else hipLaunchKernelGGL(wv::convtr_fwd_kernel, dim3(K, B), dim3(256), 0, s, x, h->w_ct, w.U, K, Tin, r, pre_scale, pre_elu);
     // db = sum dy;  dW = sum dy u^T
-    wv::launch_dw_bwd(s, dy, dy, h->junk, (float*)nullptr, partial, M, B, Tout, Tout, 1, 1, 0, 0);
-    wv::launch_sum_parts(s, partial, h->scr, B, (size_t)M * 2);
-    hipLaunchKernelGGL(wv::split_dwdb_kernel, dim3((M + 255) / 256), dim3(256), 0, s, h->scr, h->junk, db, M, 1, 1.f);
-    const NtPlan np_ = nt_plan(B, Tout, M, K);
-    WV_HIP_TRY(wv::launch_gemm_nt(s, dy, U, parts, 1.f, 0, B, M, K, Tout, np_.S, np_.TC));
-    wv::launch_sum_parts(s, parts, h->dW, np_.S, (size_t)M * K);
-    hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(M), dim3(256), 0, s, g_pw, v_pw, h->inv_pw, h->dW, dg_pw, dv_pw, K);
-    WV_HIP_TRY(hipGetLastError());
+    wv::row_sum(s, dy, db, w.partial, h->scr, h->junk, M, B, Tout);
+    rc = h->pw.grad(s, dy, w.U, w.parts, 1.f, 0, B, Tout, g_pw, v_pw, dg_pw, dv_pw);
+    if (rc) return rc;
     // du = W^T dy
-    wv::PwDwArgs t{};
-    t.X = dy; t.pw.M = K; t.pw.K = M; t.pw.Mp = h->KpT; t.pw.Kp = wv::round_up(M, wv::BK); t.pw.wq = h->wqT; t.pw.wt = h->wtT;
-    t.dw_w = h->id_taps; t.dw_b = nullptr; t.Y = DU;
-    t.B = B; t.Tin = Tout; t.Tout = Tout; t.ks = 5; t.stride = 1; t.dil = 1; t.pad = 4;
-    t.pre_scale = 1.f; t.pre_elu = 0; t.out_scale = 1.f; t.bands = 1; t.film_stride = 2;
-    WV_HIP_TRY(wv::launch_pw_dw(t, s));
+    WV_HIP_TRY(wv::launch_pw_dw(wv::plain_gemm(dy, h->pw.pack(true), h->id_taps, w.DU, B, Tout), s));
     // through the transposed conv and the activation
-    {
-        const bool al = (reinterpret_cast<uintptr_t>(DU) & 15) == 0;
-#define WV_CTB(R) hipLaunchKernelGGL((wv::convtr_bwd_frame_kernel<R>), dim3(K, B), dim3(256), 0, s, DU, x, h->w_ct, dx, partial, K, Tin, pre_scale, pre_elu)
-        if (r == 2) WV_CTB(2); else if (r == 4 && al) WV_CTB(4); else if (r == 5) WV_CTB(5); else if (r == 8 && al) WV_CTB(8);
-        else hipLaunchKernelGGL(wv::convtr_bwd_kernel, dim3(K, B), dim3(256), 0, s, DU, x, h->w_ct, dx, partial, K, Tin, r, pre_scale, pre_elu);
-#undef WV_CTB
-    }
-    wv::launch_sum_parts(s, partial, h->taps, B, (size_t)K * ks);
+    auto* bwd = R == 2 ? wv::convtr_bwd_frame_kernel<2> : R == 4 ? wv::convtr_bwd_frame_kernel<4> : R == 5 ? wv::convtr_bwd_frame_kernel<5> : wv::convtr_bwd_frame_kernel<8>;
+    if (R) hipLaunchKernelGGL(bwd, dim3(K, B), dim3(256), 0, s, w.DU, x, h->w_ct, dx, w.partial, K, Tin, pre_scale, pre_elu);
+    else hipLaunchKernelGGL(wv::convtr_bwd_kernel, dim3(K, B), dim3(256), 0, s, w.DU, x, h->w_ct, dx, w.partial, K, Tin, r, pre_scale, pre_elu);
+    wv::launch_sum_parts(s, w.partial, h->taps, B, (size_t)K * ks);
     hipLaunchKernelGGL(wv::wn_bwd_kernel, dim3(K), dim3(256), 0, s, g_ct, v_ct, h->inv_ct, h->taps, dg_ct, dv_ct, ks);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
@@ -1926,22 +1937,19 @@ int wv_train_tail_create(int C, int ks, wv_train_tail** out) {
     if (!out || C < 1 || C > 4096 || ks < 1 || ks > wv::TRAIN_MAX_KS) return fail(WV_EINVAL, "bad channel count / kernel size");
     auto* h = new wv_train_tail();
     h->C = C; h->ks = ks;
-    if (!((h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(1, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) && (h->taps = h->alloc((size_t)C * ks, false)) && (h->dbv = h->alloc(C, false)))) {
-        delete h;
-        return fail(WV_EHIP, "device allocation failed");
-    }
-    *out = h;
-    return WV_OK;
+    const bool ok = (h->w = h->alloc((size_t)C * ks, false)) && (h->inv = h->alloc(1, false)) && (h->dwdb = h->alloc((size_t)C * (ks + 1), false)) &&
+                    (h->taps = h->alloc((size_t)C * ks, false)) && (h->dbv = h->alloc(C, false));
+    return wv::created(h, ok, out);
 }
 void wv_train_tail_destroy(wv_train_tail* h) { delete h; }
+// one buffer, so the size is the layout: per-clip partial sums of the tap and bias gradients
 size_t wv_train_tail_workspace_bytes(const wv_train_tail* h, int B) { return (h && B > 0) ? al256((size_t)B * h->C * (h->ks + 1) * 4) : 0; }
 
 int wv_train_tail_forward(wv_train_tail* h, const float* x, const float* g, const float* v, const float* bias, float post, float wav_std,
                           float* delta, int B, int Tin, int T, void* stream) {
     if (!h || !x || !g || !v || !delta || B < 1 || T < 1 || T > Tin) return fail(WV_EINVAL, "null / bad argument");
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(1), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, 1, h->C * h->ks, 0, 0,
-                       (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
+    wv::launch_fold(s, wv::fold_plain(g, v, h->w, h->inv, 1, h->C * h->ks));      // one norm over the whole [C][ks] weight
     WV_HIP_TRY(hipGetLastError());
     WV_HIP_TRY(wv::launch_tail(x, h->w, bias, nullptr, delta, B, h->C, Tin, T, h->ks, post, wav_std, s));
     return WV_OK;
@@ -1953,8 +1961,7 @@ int wv_train_tail_backward(wv_train_tail* h, const float* x, const float* g, con
     if (B < 1 || T < 1 || T > Tin || !ws || ws_bytes < wv_train_tail_workspace_bytes(h, B)) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const int C = h->C, ks = h->ks;
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3(1), dim3(256), 0, s, g, v, h->w, h->inv, (float*)nullptr, (float*)nullptr, 1, C * ks, 0, 0,
-                       (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
+    wv::launch_fold(s, wv::fold_plain(g, v, h->w, h->inv, 1, C * ks));
     if (ks == 5 && (T & 3) == 0 && (Tin & 3) == 0 &&
         ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(delta) | reinterpret_cast<uintptr_t>(d_delta) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0)
         hipLaunchKernelGGL(wv::tail_bwd5_vec_kernel, dim3(C, B), dim3(256), 0, s, x, h->w, delta, d_delta, dx, (float*)ws, C, Tin, T, post, wav_std);
@@ -1973,8 +1980,14 @@ size_t wv_train_film_param_count(int msg_dim, int E, int layers, int n_scales, i
     if (msg_dim < 1 || E < 1 || layers < 0 || n_scales < 1 || bands < 1) return 0;
     return (size_t)E * msg_dim + E + (size_t)layers * ((size_t)E * E + E) + (size_t)n_scales * bands * 2 * (E + 1);
 }
+// the MLP's activations [B][layers + 1][E], which the forward leaves for the backward, and the backward's per-clip parameter gradients
+struct FilmWs { float *acts, *gpart; size_t total; };
+static FilmWs film_ws(int B, int msg_dim, int E, int layers, int n_scales, int bands, void* base) {
+    wv::Carver c(base);
+    return {c.take((size_t)B * (layers + 1) * E * 4), c.take((size_t)B * wv_train_film_param_count(msg_dim, E, layers, n_scales, bands) * 4), c.used};
+}
 size_t wv_train_film_workspace_bytes(int B, int msg_dim, int E, int layers, int n_scales, int bands) {
-    return al256((size_t)B * (layers + 1) * E * 4) + al256((size_t)B * wv_train_film_param_count(msg_dim, E, layers, n_scales, bands) * 4);
+    return film_ws(B, msg_dim, E, layers, n_scales, bands, nullptr).total;
 }
 
 static bool film_shape_ok(int B, int Dm, int E, int L, int S, int bands) {
@@ -1984,8 +1997,9 @@ static bool film_shape_ok(int B, int Dm, int E, int L, int S, int bands) {
 int wv_train_film_forward(const float* msg, const float* params, float* film, int B, int msg_dim, int E, int layers, int n_scales, int bands,
                           void* ws, size_t ws_bytes, void* stream) {
     if (!msg || !params || !film || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_EINVAL, "null / bad argument (E <= 256, layers <= 4)");
-    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_ENOMEM, "workspace too small");
-    hipLaunchKernelGGL(wv::msg_film_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, msg, params, film, (float*)ws, msg_dim, E, layers, n_scales * bands * 2);
+    const FilmWs w = film_ws(B, msg_dim, E, layers, n_scales, bands, ws);
+    if (!ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
+    hipLaunchKernelGGL(wv::msg_film_fwd_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, msg, params, film, w.acts, msg_dim, E, layers, n_scales * bands * 2);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -1994,13 +2008,12 @@ int wv_train_film_forward(const float* msg, const float* params, float* film, in
 int wv_train_film_backward(const float* msg, const float* params, const float* dfilm, float* dparams, int B, int msg_dim, int E, int layers,
                            int n_scales, int bands, void* ws, size_t ws_bytes, void* stream) {
     if (!msg || !params || !dfilm || !dparams || !film_shape_ok(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_EINVAL, "null / bad argument");
-    if (!ws || ws_bytes < wv_train_film_workspace_bytes(B, msg_dim, E, layers, n_scales, bands)) return fail(WV_ENOMEM, "workspace too small");
+    const FilmWs w = film_ws(B, msg_dim, E, layers, n_scales, bands, ws);
+    if (!ws || ws_bytes < w.total) return fail(WV_ENOMEM, "workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t np = wv_train_film_param_count(msg_dim, E, layers, n_scales, bands);
-    float* acts = (float*)ws;
-    float* gpart = (float*)((char*)ws + al256((size_t)B * (layers + 1) * E * 4));
-    hipLaunchKernelGGL(wv::msg_film_bwd_kernel, dim3(B), dim3(256), 0, s, msg, params, acts, dfilm, gpart, msg_dim, E, layers, n_scales * bands * 2, np);
-    wv::launch_sum_parts(s, gpart, dparams, B, np);
+    hipLaunchKernelGGL(wv::msg_film_bwd_kernel, dim3(B), dim3(256), 0, s, msg, params, w.acts, dfilm, w.gpart, msg_dim, E, layers, n_scales * bands * 2, np);
+    wv::launch_sum_parts(s, w.gpart, dparams, B, np);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -2039,8 +2052,7 @@ int wv_train_l1(const float* a, const float* b, float* loss, float* da, float gr
 // ---- gradient norm + AdamW over flat arenas ---------------------------------------------------------------------------------
 int wv_train_fold_weight(const float* g, const float* v, float* w, float* inv_norm, int M, int K, void* stream) {
     if (!g || !v || !w || !inv_norm || M < 1 || K < 1) return fail(WV_EINVAL, "null / bad argument");
-    hipLaunchKernelGGL(wv::wn_fold_kernel, dim3((unsigned)M), dim3(256), 0, (hipStream_t)stream, g, v, w, inv_norm, (float*)nullptr,
-                       (float*)nullptr, M, K, 0, 0, (const float*)nullptr, 1.f, (float*)nullptr, (float*)nullptr);
+    wv::launch_fold((hipStream_t)stream, wv::fold_plain(g, v, w, inv_norm, M, K));
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }
@@ -2068,20 +2080,3 @@ int wv_train_adamw(float* p, const float* g, float* m, float* v, size_t n, float
 }
 
 }  // extern "C"
-
-// The dW product for callers outside this file (the STFT plan's basis gradient, wv_ops.hip): the same kernel, split plan and
-// fixed-order finish as every dW above.
-namespace wv {
-size_t gemm_nt_sum_workspace_bytes(int B, int T, int M, int K) {
-    if (B < 1 || T < 1 || M < 1 || K < 1) return 0;
-    return al256((size_t)nt_plan(B, T, M, K).S * M * K * 4);
-}
-hipError_t launch_gemm_nt_sum(hipStream_t s, const float* A, const float* X, float* out, float* parts, int B, int M, int K, int T) {
-    if (!A || !X || !out || !parts || B < 1 || T < 1 || M < 1 || K < 1) return hipErrorInvalidValue;
-    const NtPlan np_ = nt_plan(B, T, M, K);
-    const hipError_t e = launch_gemm_nt(s, A, X, parts, 1.f, 0, B, M, K, T, np_.S, np_.TC);
-    if (e != hipSuccess) return e;
-    launch_sum_parts(s, parts, out, np_.S, (size_t)M * K);
-    return hipGetLastError();
-}
-}  // namespace wv
