@@ -12,7 +12,7 @@
  *                         (+ sigmoid/mean-over-time of waveverify/core.py:577-580 when
  *                          mean_prob != NULL, so the [B,nbits,T] logits need not be stored)
  *   wv_locator_forward    Locator.forward              model/locator.py:268-299
- *   wv_window_* / wv_session_advance / wv_detector_forward_windowed
+ *   wv_window_* / wv_session_advance / wv_segment_track / wv_detector_forward_windowed
  *                         not in the reference: windowed long-form and live-session execution
  *   wv_loudness / wv_pool_sample
  *                         the data path of scripts/train.py:440-475 (audiotools' AudioDataset: a random excerpt,
@@ -193,7 +193,31 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          to report.  A segment reaching outside the tensor counts as empty.  Segments may overlap.
  *   wv_session_advance     one tick of S lockstep sessions: stream s's samples are cat(hist[s][0 .. hv), x[s][0 .. n)) with
  *                          hist [S,hcap], x [S,n]; win [S,1,wlen] = their first wlen samples (wlen may be 0), hist_out [S,hcap] =
- *                          their samples [drop, drop + hv2); drop + hv2 == hv + n, hist_out != hist. */
+ *                          their samples [drop, drop + hv2); drop + hv2 == hv + n, hist_out != hist.
+ *   wv_segment_track       the streaming form of localize.segments_from_counts + wv_frames_reduce: one tick of S lockstep segment trackers.
+ *                          fsum [S, nb + 1, Fr_stride] as above; this tick's frames are its columns [f_lo, f_hi) (f_hi == f_lo: none), column f_lo
+ *                          being the stream's frame number frame0 (the caller counts frames; ticks must follow one another without a gap).
+ *                          A frame is ON when valid > 0 and (double)count >= min_on * valid, valid = hop, or last_valid for the last frame of a
+ *                          `final` tick.  An on frame opens a run, or extends the open run [lo, hi): the off frames since hi are added first,
+ *                          one by one in ascending order, then the frame itself, each as one f64 add per row, which is the order
+ *                          wv_frames_reduce takes over [lo, hi).  A run CLOSES once min_gap_frames off frames have followed it, or on `final`;
+ *                          a run shorter than min_len_frames is dropped, any other becomes the stream's next event {lo, hi, count = N,
+ *                          prob = S / (float(N) + eps), 0 where N == 0} exactly as wv_frames_reduce computes it.  After a final tick the
+ *                          stream's state is closed; zero both buffers to start over.  One workgroup per stream, one thread per row; no
+ *                          atomics.  Nothing outside state and events is written, and fsum is only read.
+ *                          A state that cannot follow from zeros and gapless ticks (lo, hi or the counter out of range for this frame0) is
+ *                          taken as closed with no events, so that garbage in the buffers never becomes an address outside them.
+ *                          Both buffers are the caller's, 8-byte aligned, all zeros before the first tick, sized by wv_segment_track_bytes:
+ *                            state,  per stream (stride 32 + 8 (nb + 1) + roundup8(4 (min_gap_frames - 1)(nb + 1)) bytes):
+ *                                    int64 {open 0/1, lo, hi, frames seen}; f64 sum[nb + 1] of the open run's rows over [lo, hi) (row nb = N);
+ *                                    f32 ring[min_gap_frames - 1][nb + 1], the raw off frames after hi, frame j in slot j % (min_gap_frames - 1)
+ *                            events, per stream (stride 8 + capacity * rec bytes, rec = 24 + roundup8(4 nb)):
+ *                                    int64 n = events so far (monotonic); record c: int64 lo, int64 hi, f64 count, f32 prob[nb]; event number e
+ *                                    (from 0) is record e % capacity, so a reader that polls before `capacity` events pile up loses none.
+ *                          Refused with WV_EINVAL: S outside [1, 65535], nb outside [1, WV_SEGMENT_MAX_BITS], min_gap_frames outside
+ *                          [1, WV_SEGMENT_MAX_GAP], capacity < 1, null or short buffers, frames outside the tensor. */
+#define WV_SEGMENT_MAX_GAP 64
+#define WV_SEGMENT_MAX_BITS 255
 int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream);
 int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream);
 int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
@@ -206,6 +230,10 @@ int wv_frames_reduce(const float* fsum, int B, int nb, int Fr_stride, const int*
                      void* stream);
 int wv_session_advance(const float* hist, int hcap, int hv, const float* x, int n, float* win, int wlen,
                        float* hist_out, int drop, int hv2, int S, void* stream);
+int wv_segment_track_bytes(int S, int nb, int min_gap_frames, int capacity, size_t* state_bytes, size_t* event_bytes);
+int wv_segment_track(const float* fsum, int S, int nb, int Fr_stride, int f_lo, int f_hi, int64_t frame0, int hop, int last_valid,
+                     int final, double min_on, int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes,
+                     void* events, size_t event_bytes, int capacity, void* stream);
 
 /* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------

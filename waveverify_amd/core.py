@@ -285,6 +285,19 @@ class WaveVerify:
             return session.LocateSession(self._need("locator"), n, self.locator_precision)
         return native_session.NativeLocateSession(self._need("locator"), n, sample_rate, channels, self.locator_precision)
 
+    def open_segment_session(self, n: int = 1, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5,
+                             sample_rate: int = 16000, channels: int = 1, capacity: int = 64):
+        """Live localized detection of n streams in lockstep, the live twin of detect_segments_batch: session.SegmentSession, push(x [n, k],
+        gate=None) returns nothing, poll() -> per stream the Segments that have ended since the last poll, open_segments() the runs still
+        open, flush() the rest.  Any other sample_rate or channels: native_session.NativeSegmentSession, push(x [n, C, k]) (no gate there);
+        segment times stay seconds on the stream's own clock.  capacity: closed segments the device holds per stream between reads."""
+        det, loc = self._need("detector"), self._need("locator")
+        kw = dict(threshold=threshold, min_on=min_on, min_gap_frames=min_gap_frames, min_len_frames=min_len_frames,
+                  precision=self.detector_precision, locator_precision=self.locator_precision, capacity=capacity)
+        if (int(sample_rate), int(channels)) == (self.sample_rate, 1):
+            return session.SegmentSession(det, loc, n, sample_rate=self.sample_rate, **kw)
+        return native_session.NativeSegmentSession(det, loc, n, sample_rate, channels, **kw)
+
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],
               output_path: Optional[Union[str, Path]] = None, *, native: bool = False, strength: float = 1.0,

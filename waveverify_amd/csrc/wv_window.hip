@@ -8,6 +8,7 @@
 //   frames_reduce_kernel   the localized heads' per-frame sums fsum[B, nb + 1, Fr] -> per SEGMENT {clip, f_lo, f_hi} the masked mean probability
 //                          of every bit and the gated sample count, frames added in order in f64
 //   session_advance_kernel a live session's tick: [S, H] history + [S, n] new samples -> the tick's window and the next history
+//   segment_track_kernel   a live segment session's tick: the new frames' sums -> the per-stream open run, gap ring and ring of closed segments
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
 #include <hip/hip_runtime.h>
 
@@ -110,6 +111,121 @@ __global__ __launch_bounds__(WIN_NT) void session_advance_kernel(const float* __
     }
 }
 
+// ---- the streaming form of segments_from_counts + frames_reduce_kernel ----------------------------------------
+// Byte layout of the two caller-owned buffers (the header states it for callers): per stream `state` holds int64 {open, lo, hi, frames seen},
+// f64 sums [nb + 1] of the open run and the gap ring [G - 1][nb + 1] f32; `events` holds an int64 event counter and `capacity` records
+// {int64 lo, int64 hi, f64 count, f32 prob[nb]}.  Every section starts on an 8-byte boundary.
+struct SegLayout {
+    size_t state_stride, event_stride, rec;
+};
+
+static inline size_t up8(size_t x) { return (x + 7) & ~(size_t)7; }
+
+static inline SegLayout seg_layout(int nb, int G, int capacity) {
+    SegLayout l;
+    l.state_stride = 32 + 8 * (size_t)(nb + 1) + up8(4 * (size_t)(G - 1) * (nb + 1));
+    l.rec = 24 + up8(4 * (size_t)nb);
+    l.event_stride = 8 + (size_t)capacity * l.rec;
+    return l;
+}
+
+// grid (S), block = nb + 1 rounded up to a wave.  Thread k <= nb owns row k of the sums (row nb is the count row); EVERY thread reads the count
+// row of every frame and keeps the run's count sum itself, so all threads of a stream take the same decisions without exchanging anything.
+// Frames of this tick are read from fsum wherever they are needed; the ring only carries the off frames after `hi` over to the next tick
+// (frame j in slot j % (G - 1); at most G - 1 consecutive frames are ever held, so slots never collide).  A run is closed as soon as G off
+// frames have passed, hence an on frame that meets an open run always has a gap < G and merges.  Reads of the state come before the barrier,
+// writes after it; event records are write-only.
+__global__ __launch_bounds__(256) void segment_track_kernel(const float* __restrict__ fsum, int nb, int Fr, int f_lo, int n, long long frame0, int hop,
+                                                            int last_valid, int final_, double min_on, int G, int min_len, float eps, char* state,
+                                                            size_t state_stride, char* events, size_t event_stride, size_t rec, int capacity) {
+    const int s = blockIdx.x, k = threadIdx.x;
+    const bool owns = k <= nb;
+    const int r = owns ? k : nb;
+    const float* fs = fsum + (size_t)s * (nb + 1) * Fr + f_lo;
+    const float* crow = fs + (size_t)nb * Fr;
+    const float* krow = fs + (size_t)r * Fr;
+    long long* hdr = reinterpret_cast<long long*>(state + (size_t)s * state_stride);
+    double* accp = reinterpret_cast<double*>(hdr + 4);
+    float* ring = reinterpret_cast<float*>(accp + nb + 1);
+    long long* nevp = reinterpret_cast<long long*>(events + (size_t)s * event_stride);
+    char* recs = reinterpret_cast<char*>(nevp + 1);
+    const int R = G - 1;
+
+    bool open = hdr[0] != 0;
+    long long lo = hdr[1], hi = hdr[2], nev = *nevp;
+    double acc = accp[r], cnt = accp[nb];
+    // a state that cannot follow from zeros and gapless ticks (another frame0, a buffer never cleared) is taken as closed, so that no ring
+    // slot or event record is ever addressed outside its buffer
+    if (open && !(lo >= 0 && lo < hi && hi <= frame0 && frame0 - hi < G)) open = false;
+    if (nev < 0 || nev > (1LL << 62)) nev = 0;
+
+    auto close = [&]() {
+        if (hi - lo >= min_len) {
+            char* e = recs + (size_t)(nev % capacity) * rec;
+            if (k == 0) {
+                reinterpret_cast<long long*>(e)[0] = lo;
+                reinterpret_cast<long long*>(e)[1] = hi;
+                reinterpret_cast<double*>(e)[2] = cnt;
+            }
+            if (k < nb) {
+                const float d = (float)cnt + eps;
+                reinterpret_cast<float*>(e + 24)[k] = cnt > 0.0 ? (float)(acc / (double)d) : 0.f;
+            }
+            ++nev;
+        }
+        open = false;
+    };
+
+    for (int i = 0; i < n; ++i) {
+        const long long g = frame0 + i;
+        const float c = crow[i];
+        const int valid = (final_ && i == n - 1) ? last_valid : hop;
+        const bool on = valid > 0 && (double)c >= min_on * (double)valid;
+        if (on) {
+            if (open) {
+                for (long long j = hi; j < g; ++j) {                 // the gap's off frames first, one by one, then the frame itself
+                    float v, vc;
+                    if (j >= frame0) {
+                        v = krow[j - frame0];
+                        vc = crow[j - frame0];
+                    } else {
+                        const float* slot = ring + (size_t)(j % R) * (nb + 1);
+                        v = slot[r];
+                        vc = slot[nb];
+                    }
+                    acc += (double)v;
+                    cnt += (double)vc;
+                }
+            } else {
+                open = true;
+                lo = g;
+                acc = cnt = 0.0;
+            }
+            acc += (double)krow[i];
+            cnt += (double)c;
+            hi = g + 1;
+        } else if (open && g + 1 - hi >= G) {
+            close();
+        }
+    }
+    if (final_ && open) close();
+    __syncthreads();
+
+    const long long fend = frame0 + n;
+    if (owns) {
+        if (open)
+            for (long long j = hi > frame0 ? hi : frame0; j < fend; ++j) ring[(size_t)(j % R) * (nb + 1) + k] = krow[j - frame0];
+        accp[k] = acc;
+    }
+    if (k == 0) {
+        hdr[0] = open ? 1 : 0;
+        hdr[1] = lo;
+        hdr[2] = hi;
+        hdr[3] = fend;
+        *nevp = nev;
+    }
+}
+
 }  // namespace wv
 
 using wv::fail;
@@ -157,5 +273,38 @@ extern "C" int wv_session_advance(const float* hist, int hcap, int hv, const flo
     if (m == 0) return WV_OK;
     hipLaunchKernelGGL(wv::session_advance_kernel, dim3((m + wv::WIN_NT - 1) / wv::WIN_NT, S), dim3(wv::WIN_NT), 0, (hipStream_t)stream, hist, hcap, hv,
                        x, n, win, wlen, hist_out, drop, hv2);
+    return launched();
+}
+
+extern "C" int wv_segment_track_bytes(int S, int nb, int min_gap_frames, int capacity, size_t* state_bytes, size_t* event_bytes) {
+    if (!state_bytes || !event_bytes || S < 1 || S > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS || min_gap_frames < 1 ||
+        min_gap_frames > WV_SEGMENT_MAX_GAP || capacity < 1)
+        return fail(WV_EINVAL, "wv_segment_track_bytes: null output, S outside [1, 65535], nb outside [1, " WV_STR(WV_SEGMENT_MAX_BITS)
+                               "], min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP) "] or capacity < 1");
+    const wv::SegLayout l = wv::seg_layout(nb, min_gap_frames, capacity);
+    *state_bytes = (size_t)S * l.state_stride;
+    *event_bytes = (size_t)S * l.event_stride;
+    return WV_OK;
+}
+
+extern "C" int wv_segment_track(const float* fsum, int S, int nb, int Fr_stride, int f_lo, int f_hi, int64_t frame0, int hop, int last_valid,
+                                int final, double min_on, int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes,
+                                void* events, size_t event_bytes, int capacity, void* stream) {
+    if (!state || !events || S < 1 || S > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS)
+        return fail(WV_EINVAL, "wv_segment_track: null state / events, S outside [1, 65535] or nb outside [1, " WV_STR(WV_SEGMENT_MAX_BITS) "]");
+    if (min_gap_frames < 1 || min_gap_frames > WV_SEGMENT_MAX_GAP || min_len_frames < 0 || capacity < 1 || !(min_on == min_on))
+        return fail(WV_EINVAL, "wv_segment_track: min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP) "], min_len_frames < 0, capacity < 1 or "
+                               "min_on not a number");
+    if (f_lo < 0 || f_hi < f_lo || f_hi > Fr_stride || (f_hi > f_lo && !fsum) || frame0 < 0 || hop < 1 || last_valid < 0 || last_valid > hop)
+        return fail(WV_EINVAL, "wv_segment_track: frames [f_lo, f_hi) outside [0, Fr_stride] (or frames without fsum), frame0 < 0, hop < 1 or "
+                               "last_valid outside [0, hop]");
+    const wv::SegLayout l = wv::seg_layout(nb, min_gap_frames, capacity);
+    if (state_bytes < (size_t)S * l.state_stride || event_bytes < (size_t)S * l.event_stride || ((uintptr_t)state & 7) || ((uintptr_t)events & 7))
+        return fail(WV_EINVAL, "wv_segment_track: state or events shorter than wv_segment_track_bytes gives, or not 8-byte aligned");
+    if (f_hi == f_lo && !final) return WV_OK;
+    const int nt = (nb + 1 + 63) / 64 * 64;
+    hipLaunchKernelGGL(wv::segment_track_kernel, dim3(S), dim3(nt), 0, (hipStream_t)stream, fsum, nb, Fr_stride, f_lo, f_hi - f_lo, (long long)frame0,
+                       hop, last_valid, final, min_on, min_gap_frames, min_len_frames, eps, (char*)state, l.state_stride, (char*)events,
+                       l.event_stride, l.rec, capacity);
     return launched();
 }

@@ -65,3 +65,92 @@ def segments_from_counts(count: Sequence[float], valid: Sequence[float], min_on:
             runs.append([f, g])
         f = g
     return [(lo, hi) for lo, hi in runs if hi - lo >= min_len_frames]
+
+
+class SegmentTracker:
+    """segments_from_counts + the f64 reduction of wv_frames_reduce as a STREAMING state machine over S lockstep streams: the host twin of
+    wv_segment_track (csrc/wv_window.hip), the same decisions and the same order of additions, on numpy arrays.
+
+    advance(fsum [S, nb + 1, Fr], f_lo, f_hi, last_valid, final) takes the next frames of every stream.  Per stream it holds the open run
+    {lo, hi, f64 sums of every row over [lo, hi)} and the raw off frames after hi (fewer than min_gap_frames of them).  An on frame
+    (valid > 0 and float64(count) >= min_on * valid) extends the open run: the held off frames are added first, one by one, then the frame,
+    so the sums are those of one ascending pass over [lo, hi).  A run closes once min_gap_frames off frames have followed it, or on `final`;
+    it is dropped if shorter than min_len_frames, else it becomes an event (lo, hi, count, prob [nb] float32) with
+    prob = S / (float32(count) + float32(eps)) rounded once, 0 where count == 0.  poll() hands out the events closed since the last poll."""
+
+    def __init__(self, S: int, nb: int, hop: int, min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5, eps: float = 1e-8,
+                 dtype=np.float32):
+        if S < 1 or nb < 1 or hop < 1 or min_gap_frames < 1 or min_len_frames < 0:
+            raise ValueError("need S, nb, hop, min_gap_frames >= 1 and min_len_frames >= 0")
+        self.S, self.nb, self.hop, self.min_on = int(S), int(nb), int(hop), float(min_on)
+        self.G, self.min_len, self.eps, self.dtype = int(min_gap_frames), int(min_len_frames), np.float32(eps), dtype
+        self.reset()
+
+    def reset(self) -> None:
+        self.frames_seen = 0
+        self.closed = False
+        self._open = [False] * self.S
+        self._lo, self._hi = [0] * self.S, [0] * self.S
+        self._acc = np.zeros((self.S, self.nb + 1), np.float64)
+        self._gap: List[List[np.ndarray]] = [[] for _ in range(self.S)]         # the off frames after hi, oldest first
+        self._events: List[list] = [[] for _ in range(self.S)]
+        self.events_total = [0] * self.S
+
+    def _prob(self, acc: np.ndarray) -> np.ndarray:
+        cnt = acc[self.nb]
+        if not cnt > 0.0:
+            return np.zeros(self.nb, np.float32)
+        return (acc[:self.nb] / np.float64(np.float32(cnt) + self.eps)).astype(np.float32)
+
+    def _close(self, s: int) -> None:
+        if self._hi[s] - self._lo[s] >= self.min_len:
+            self._events[s].append((self._lo[s], self._hi[s], float(self._acc[s, self.nb]), self._prob(self._acc[s])))
+            self.events_total[s] += 1
+        self._open[s] = False
+        self._gap[s] = []
+
+    def advance(self, fsum, f_lo: int = 0, f_hi: Optional[int] = None, last_valid: Optional[int] = None, final: bool = False) -> None:
+        if self.closed:
+            raise RuntimeError("tracker saw its final frame; call reset() to start over")
+        fsum = np.asarray(fsum, self.dtype)
+        if fsum.ndim != 3 or fsum.shape[0] != self.S or fsum.shape[1] != self.nb + 1:
+            raise ValueError(f"expected frame sums [{self.S}, {self.nb + 1}, Fr], got {fsum.shape}")
+        f_hi = fsum.shape[2] if f_hi is None else int(f_hi)
+        n = f_hi - int(f_lo)
+        if n < 0 or f_lo < 0 or f_hi > fsum.shape[2]:
+            raise ValueError("frames [f_lo, f_hi) lie outside fsum")
+        last_valid = self.hop if last_valid is None else int(last_valid)
+        cols = fsum[:, :, f_lo:f_hi].astype(np.float64)                          # exact: every value widens
+        for s in range(self.S):
+            for i in range(n):
+                g = self.frames_seen + i
+                col = cols[s, :, i]
+                valid = last_valid if final and i == n - 1 else self.hop
+                if valid > 0 and col[self.nb] >= self.min_on * valid:
+                    if self._open[s]:
+                        for off in self._gap[s]:
+                            self._acc[s] += off
+                    else:
+                        self._open[s], self._lo[s] = True, g
+                        self._acc[s] = 0.0
+                    self._gap[s] = []
+                    self._acc[s] += col
+                    self._hi[s] = g + 1
+                elif self._open[s]:
+                    if g + 1 - self._hi[s] >= self.G:
+                        self._close(s)
+                    else:
+                        self._gap[s].append(col)
+            if final and self._open[s]:
+                self._close(s)
+        self.frames_seen += n
+        self.closed = bool(final)
+
+    def poll(self) -> List[list]:
+        out, self._events = self._events, [[] for _ in range(self.S)]
+        return out
+
+    def open_runs(self) -> List[Optional[tuple]]:
+        """Per stream the provisional open run (lo, hi, count, prob) over [lo, hi) as it stands (held off frames not included), or None."""
+        return [(self._lo[s], self._hi[s], float(self._acc[s, self.nb]), self._prob(self._acc[s])) if self._open[s] else None
+                for s in range(self.S)]

@@ -408,3 +408,27 @@ class NativeLocateSession(_HipStages, HostFrontSession):
 
     def _join(self, a, b):
         return self._cat([a, b])
+
+
+class NativeSegmentSession(_HipStages, HostFrontSession):
+    """Watermarked segments of S live streams of C channels at `sample_rate`: push(x [S, C, n]) returns nothing; poll(), open_segments() and
+    flush() are session.SegmentSession's on the 16 kHz samples the front stage has made final, so a Segment's frames count 16 kHz detector
+    frames and its start_s / end_s are seconds on the stream's own clock.  After flush() the segments are those of a 16 kHz SegmentSession
+    given to_model_rate of the recording in the same pieces.  A caller's gate has no native-rate form and is refused."""
+
+    def __init__(self, detector, locator, S: int, sample_rate: int = MODEL_RATE, channels: int = 1, **kw):
+        from .session import SegmentSession
+        native.check_rate(sample_rate)                                  # refused before anything is built on the device
+        self.device = detector.device
+        HostFrontSession.__init__(self, SegmentSession(detector, locator, S, sample_rate=MODEL_RATE, **kw), sample_rate, channels)
+
+    def push(self, x, gate=None) -> None:
+        if gate is not None:
+            raise ValueError("a gate is given per 16 kHz sample; a session at another rate or channel count takes none")
+        HostFrontSession.push(self, x)
+
+    def poll(self):
+        return self.inner.poll()
+
+    def open_segments(self):
+        return self.inner.open_segments()

@@ -213,6 +213,54 @@ def frames_reduce(fsum, segments, eps: float = 1e-8):
     return prob, count
 
 
+def segment_track_bytes(S: int, nb: int, min_gap_frames: int, capacity: int):
+    """wv_segment_track_bytes -> (state bytes, event bytes) of S trackers."""
+    import ctypes as C
+    sb, eb = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.load().wv_segment_track_bytes(int(S), int(nb), int(min_gap_frames), int(capacity), C.byref(sb), C.byref(eb)),
+               "wv_segment_track_bytes")
+    return sb.value, eb.value
+
+
+def segment_track(fsum, f_lo: int, f_hi: int, frame0: int, hop: int, last_valid: int, final: bool, min_on: float, min_gap_frames: int,
+                  min_len_frames: int, state, events, capacity: int, eps: float = 1e-8) -> None:
+    """wv_segment_track: one tick of S streaming segment trackers on fsum [S, nb + 1, Fr] (Fr may be 0 for a final tick without frames);
+    state / events are uint8 device tensors of segment_track_bytes, all zeros before the first tick, updated in place."""
+    lib = _lib.load()
+    fsum = _lib.dev(fsum, _ON_GPU)
+    S, nb1, Fr = fsum.shape
+    if not (state.is_cuda and events.is_cuda and state.dtype == torch.uint8 and events.dtype == torch.uint8 and state.is_contiguous()
+            and events.is_contiguous()):
+        raise ValueError("state and events must be contiguous uint8 tensors on the GPU")
+    _lib.check(lib.wv_segment_track(fsum.data_ptr() if Fr else None, S, nb1 - 1, max(Fr, 1), int(f_lo), int(f_hi), int(frame0), int(hop),
+                                    int(last_valid), int(bool(final)), float(min_on), int(min_gap_frames), int(min_len_frames), float(eps),
+                                    state.data_ptr(), state.numel(), events.data_ptr(), events.numel(), int(capacity), _lib.stream()),
+               "wv_segment_track")
+
+
+def segment_event_dtype(nb: int) -> np.dtype:
+    """One event record of wv_segment_track's `events` buffer as a numpy structured dtype."""
+    return np.dtype({"names": ["lo", "hi", "count", "prob"], "formats": ["<i8", "<i8", "<f8", ("<f4", (int(nb),))], "offsets": [0, 8, 16, 24],
+                     "itemsize": 24 + (4 * int(nb) + 7) // 8 * 8})
+
+
+def segment_events(events, S: int, nb: int, capacity: int):
+    """The `events` buffer read back (one device-to-host copy) -> (n [S] int64 events so far, records [S, capacity] of segment_event_dtype)."""
+    raw = events.cpu().numpy().reshape(S, -1)
+    rec = segment_event_dtype(nb)
+    n = raw[:, :8].copy().view("<i8").reshape(S)
+    recs = raw[:, 8:8 + capacity * rec.itemsize].copy().view(rec).reshape(S, capacity)
+    return n, recs
+
+
+def segment_state(state, S: int, nb: int):
+    """The `state` buffer read back -> (header [S, 4] int64 {open, lo, hi, frames seen}, sums [S, nb + 1] float64 of the open runs)."""
+    raw = state.cpu().numpy().reshape(S, -1)
+    hdr = raw[:, :32].copy().view("<i8").reshape(S, 4)
+    acc = raw[:, 32:32 + 8 * (nb + 1)].copy().view("<f8").reshape(S, nb + 1)
+    return hdr, acc
+
+
 # ---- the f16 mode's units (csrc/wv_h16.hip).  A "c8" tensor is torch.float16 [B, roundup(C,16)/8, T, 8] --------------------------
 def _c8(t: torch.Tensor) -> torch.Tensor:
     if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 4 and t.shape[-1] == 8 and t.is_contiguous()):
