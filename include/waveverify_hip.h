@@ -215,9 +215,34 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                                    int64 n = events so far (monotonic); record c: int64 lo, int64 hi, f64 count, f32 prob[nb]; event number e
  *                                    (from 0) is record e % capacity, so a reader that polls before `capacity` events pile up loses none.
  *                          Refused with WV_EINVAL: S outside [1, 65535], nb outside [1, WV_SEGMENT_MAX_BITS], min_gap_frames outside
- *                          [1, WV_SEGMENT_MAX_GAP], capacity < 1, null or short buffers, frames outside the tensor. */
+ *                          [1, WV_SEGMENT_MAX_GAP], capacity < 1, null or short buffers, frames outside the tensor.
+ *   wv_bank_advance        one tick of a session BANK (session.py): `capacity` independent streams, of which the P
+ *                          named by desc pushed samples this tick.  hist [capacity, hcap] is updated IN PLACE; x (n_x floats) holds the new
+ *                          samples of all pushed slots, packed; desc [P][8] int64 device = {slot, hv, x_off, n, row, wlen, drop, hv2}.  The
+ *                          stream's samples are cat(hist[slot][0 .. hv), x[x_off .. x_off + n)).  Where wlen > 0, win[row][0 .. wlen) = their
+ *                          first wlen samples and win[row][wlen .. Lmax) = 0, win being [A, 1, Lmax]; hist[slot][0 .. hv2) becomes their samples
+ *                          [drop, drop + hv2).  hist[slot][hv2 .. hcap) keeps whatever it held and is never read back (the next tick's hv is
+ *                          this tick's hv2).  History rows and window rows that desc does not name are not touched, and the launch grows
+ *                          with P and Lmax, not with capacity.
+ *                          THE CALLER'S DUTY: the slots of one call are distinct, and so are the rows of its windowed descriptors; two rows
+ *                          naming one slot would shift one history twice, in no defined order.
+ *                          A descriptor row is SKIPPED whole (no window columns, no history change) unless 0 <= slot < capacity,
+ *                          0 <= hv <= hcap, 0 <= hv2 <= hcap, n >= 0, drop >= 0, drop + hv2 == hv + n, 0 <= wlen <= min(hv + n, Lmax),
+ *                          0 <= x_off and x_off + n <= n_x, and, where wlen > 0, 0 <= row < A; the other rows of the call are served.
+ *                          Refused with WV_EINVAL and nothing written: null hist or desc, n_x > 0 without x, A > 0 without win;
+ *                          capacity outside [1, WV_BANK_MAX_SLOTS], hcap < 1, n_x < 0, P or A outside [0, 65535], Lmax < 0 (or < 1 with
+ *                          A > 0); hist, x and win ranges that overlap.  P == 0 is success without a launch.
+ *                          The descriptor carries nothing of a net: a second per-slot history (a segment bank's gate) goes through the
+ *                          same call with the same rows.
+ *   wv_bank_detect_update  one tick of a detect bank: psum [A, nb] (wv_detector_forward_windowed on the tick's windows), desc [A][2] int64
+ *                          device = {slot, samples}.  Per row r and bit k: acc[slot][k] += (double)psum[r][k]; seen[slot] += samples;
+ *                          mean_prob[r][k] = (float)(acc[slot][k] / max(seen[slot], 1)); bits[r][k] = mean_prob[r][k] >= 0.5f.  acc
+ *                          [capacity, nb] f64 and seen [capacity] int64 are the bank's state, zero for a fresh slot; slots not named are
+ *                          untouched; a row whose slot is outside [0, capacity) or whose samples < 0 is skipped.  The slots of one call
+ *                          are distinct (the caller's duty).  One thread per (row, bit), no atomics.  A == 0 is success without a launch. */
 #define WV_SEGMENT_MAX_GAP 64
 #define WV_SEGMENT_MAX_BITS 255
+#define WV_BANK_MAX_SLOTS 1048576
 int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream);
 int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream);
 int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
@@ -234,6 +259,10 @@ int wv_segment_track_bytes(int S, int nb, int min_gap_frames, int capacity, size
 int wv_segment_track(const float* fsum, int S, int nb, int Fr_stride, int f_lo, int f_hi, int64_t frame0, int hop, int last_valid,
                      int final, double min_on, int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes,
                      void* events, size_t event_bytes, int capacity, void* stream);
+int wv_bank_advance(float* hist, int capacity, int hcap, const float* x, int64_t n_x, const int64_t* desc, int P, float* win, int A,
+                    int Lmax, void* stream);
+int wv_bank_detect_update(double* acc, int64_t* seen, int capacity, int nb, const float* psum, const int64_t* desc, int A,
+                          float* mean_prob, int* bits, void* stream);
 
 /* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------

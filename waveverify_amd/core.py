@@ -285,6 +285,21 @@ class WaveVerify:
             return session.LocateSession(self._need("locator"), n, self.locator_precision)
         return native_session.NativeLocateSession(self._need("locator"), n, sample_rate, channels, self.locator_precision)
 
+    def open_embed_bank(self, capacity: int = 64, pad_limit: float = 1.5):
+        """session.EmbedBank: up to `capacity` live 16 kHz mono streams that open, push and close on their own.
+        bank.open(watermark_id) -> slot; bank.push({slot: x [n], ...}) -> {slot: the watermarked samples of the frames that push completed};
+        bank.close(slot) -> the rest.  The streams that complete frames on a tick share one generator launch per pad_limit group."""
+        return session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit,
+                                 messages=lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0])
+
+    def open_detect_bank(self, capacity: int = 64, pad_limit: float = 1.5):
+        """session.DetectBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: DetectState over that stream's completed frames}."""
+        return session.DetectBank(self._need("detector"), capacity, self.detector_precision, pad_limit)
+
+    def open_locate_bank(self, capacity: int = 64, pad_limit: float = 1.5):
+        """session.LocateBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: locator logits of the frames that push completed}."""
+        return session.LocateBank(self._need("locator"), capacity, self.locator_precision, pad_limit)
+
     def open_segment_session(self, n: int = 1, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5,
                              sample_rate: int = 16000, channels: int = 1, capacity: int = 64):
         """Live localized detection of n streams in lockstep, the live twin of detect_segments_batch: session.SegmentSession, push(x [n, k],

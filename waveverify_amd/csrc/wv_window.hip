@@ -8,6 +8,8 @@
 //   frames_reduce_kernel   the localized heads' per-frame sums fsum[B, nb + 1, Fr] -> per SEGMENT {clip, f_lo, f_hi} the masked mean probability
 //                          of every bit and the gated sample count, frames added in order in f64
 //   session_advance_kernel a live session's tick: [S, H] history + [S, n] new samples -> the tick's window and the next history
+//   bank_advance_kernel    a session bank's tick: a descriptor per stream that pushed, its history shifted in place, its window row filled
+//   bank_detect_update_kernel  a detect bank's tick: the windows' sigmoid sums into the per-slot f64 accumulators, mean probabilities and bits out
 //   segment_track_kernel   a live segment session's tick: the new frames' sums -> the per-stream open run, gap ring and ring of closed segments
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
 #include <hip/hip_runtime.h>
@@ -108,6 +110,120 @@ __global__ __launch_bounds__(WIN_NT) void session_advance_kernel(const float* __
     if (j < hv2) {
         const int q = drop + j;
         hist_out[(size_t)s * hcap + j] = q < hv ? h[q] : xs[q - hv];
+    }
+}
+
+// ---- session banks: every stream its own tick --------------------------------------------------------------------
+// One descriptor row of wv_bank_advance, checked the same way by every workgroup that serves it: a row that breaks the contract is skipped whole.
+struct BankRow {
+    int64_t slot, hv, x_off, n, row, wlen, drop, hv2;
+    bool ok;
+};
+
+__device__ __forceinline__ BankRow bank_row(const int64_t* __restrict__ desc, int p, int capacity, int hcap, int64_t n_x, int A, int Lmax) {
+    const int64_t* d = desc + 8 * (size_t)p;
+    BankRow r = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], false};
+    if (r.slot < 0 || r.slot >= capacity || r.hv < 0 || r.hv > hcap || r.hv2 < 0 || r.hv2 > hcap || r.n < 0 || r.n > n_x || r.x_off < 0 ||
+        r.x_off > n_x - r.n)
+        return r;
+    const int64_t len = r.hv + r.n;                             // both within their ranges: no overflow
+    r.ok = r.drop >= 0 && r.drop <= len && r.drop + r.hv2 == len && r.wlen >= 0 && r.wlen <= len && r.wlen <= Lmax &&
+           (r.wlen == 0 || (r.row >= 0 && r.row < A));
+    return r;
+}
+
+// four samples q .. q + 3 (the first `count` of them) of cat(h[0 .. hv), xs[0 .. n)): one 16-byte load where all four lie in one source and
+// that address is aligned
+__device__ __forceinline__ float4 bank_load4(const float* h, int hv, const float* xs, int q, int count) {
+    if (count == 4 && q + 4 <= hv && aligned16(h + q)) return *reinterpret_cast<const float4*>(h + q);
+    if (count == 4 && q >= hv && aligned16(xs + (q - hv))) return *reinterpret_cast<const float4*>(xs + (q - hv));
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (count > 0) v.x = q < hv ? h[q] : xs[q - hv];
+    if (count > 1) v.y = q + 1 < hv ? h[q + 1] : xs[q + 1 - hv];
+    if (count > 2) v.z = q + 2 < hv ? h[q + 2] : xs[q + 2 - hv];
+    if (count > 3) v.w = q + 3 < hv ? h[q + 3] : xs[q + 3 - hv];
+    return v;
+}
+
+__device__ __forceinline__ void bank_store4(float* d, int count, float4 v) {
+    if (count == 4 && aligned16(d)) {
+        *reinterpret_cast<float4*>(d) = v;
+        return;
+    }
+    if (count > 0) d[0] = v.x;
+    if (count > 1) d[1] = v.y;
+    if (count > 2) d[2] = v.z;
+    if (count > 3) d[3] = v.w;
+}
+
+// grid (1 + ceil(Lmax / WIN_TILE), P).  Row p's stream is cat(hist[slot][0 .. hv), x[x_off .. x_off + n)).
+//   blockIdx.x == 0  owns the slot's history, the only memory of this launch that is read and written: it first copies the window's
+//                    history-sourced columns [0, min(hv, wlen)), then shifts the history IN PLACE to the stream's samples [drop, drop + hv2) in
+//                    ascending chunks of WIN_TILE.  A chunk at offset c reads hist[c + drop ..) (or x) and writes hist[c .. c + WIN_TILE): every
+//                    load of a chunk comes before the barrier, every store after it, so a store never meets a load of its own chunk, and the
+//                    loads of the next chunk start at or beyond where this one's stores end.  No other workgroup touches this history row.
+//   blockIdx.x >= 1  tile blockIdx.x - 1 of the window row: the x-sourced columns [hv, wlen) and the zeros [wlen, Lmax).  x and win alias
+//                    nothing, so these tiles need no order among themselves or with the owner, whose columns they leave out.
+__global__ __launch_bounds__(WIN_NT) void bank_advance_kernel(float* hist, int capacity, int hcap, const float* __restrict__ x, int64_t n_x,
+                                                              const int64_t* __restrict__ desc, float* __restrict__ win, int A, int Lmax) {
+    const BankRow r = bank_row(desc, blockIdx.y, capacity, hcap, n_x, A, Lmax);
+    if (!r.ok) return;
+    const int hv = (int)r.hv, wlen = (int)r.wlen, drop = (int)r.drop, hv2 = (int)r.hv2;
+    const int hw = hv < wlen ? hv : wlen;                       // window columns that come from the history
+    const float* xs = x + r.x_off;                              // never dereferenced where n == 0
+    float* w = wlen ? win + (size_t)r.row * Lmax : win;         // never dereferenced where wlen == 0 (then hw == 0 and no tile has work)
+    if (blockIdx.x > 0) {
+        if (wlen == 0) return;
+        const int j = (blockIdx.x - 1) * WIN_TILE + threadIdx.x * WIN_PER_THREAD;
+        if (j >= Lmax) return;
+        const int count = Lmax - j < 4 ? Lmax - j : 4;
+        if (j >= wlen) {
+            bank_store4(w + j, count, make_float4(0.f, 0.f, 0.f, 0.f));
+        } else if (j >= hw && j + count <= wlen) {              // j >= hw and j < wlen: hw == hv, so every sample is x's
+            bank_store4(w + j, count, bank_load4(xs, 0, xs, j - hv, count));
+        } else {
+            for (int i = 0; i < count; ++i)                     // a group that straddles hw or wlen
+                if (j + i >= hw) w[j + i] = j + i < wlen ? xs[j + i - hv] : 0.f;
+        }
+        return;
+    }
+    float* h = hist + (size_t)r.slot * hcap;
+    for (int c = 0; c < hw; c += WIN_TILE) {
+        const int j = c + threadIdx.x * WIN_PER_THREAD;
+        if (j < hw) {
+            const int count = hw - j < 4 ? hw - j : 4;
+            bank_store4(w + j, count, bank_load4(h, hv, xs, j, count));
+        }
+    }
+    if (drop == 0 && r.n == 0) return;                          // nothing moves
+    // with drop == 0 the first hv samples stay where they are: the copy starts at the chunk that holds hv
+    for (int c = drop == 0 ? hv / WIN_TILE * WIN_TILE : 0; c < hv2; c += WIN_TILE) {
+        const int j = c + threadIdx.x * WIN_PER_THREAD;
+        const int count = j >= hv2 ? 0 : (hv2 - j < 4 ? hv2 - j : 4);
+        const float4 v = bank_load4(h, hv, xs, j + drop, count);
+        __syncthreads();
+        bank_store4(h + j, count, v);
+    }
+}
+
+// grid (A), one thread per (row, bit), bits beyond the block in a stride loop.  desc[r] = {slot, samples}.  Every thread reads the slot's
+// counter before the barrier, thread 0 writes it after.
+__global__ __launch_bounds__(WIN_NT) void bank_detect_update_kernel(double* acc, int64_t* seen, int capacity, int nb, const float* __restrict__ psum,
+                                                                    const int64_t* __restrict__ desc, float* __restrict__ mean_prob,
+                                                                    int* __restrict__ bits) {
+    const int r = blockIdx.x;
+    const int64_t slot = desc[2 * r], samples = desc[2 * r + 1];
+    if (slot < 0 || slot >= capacity || samples < 0) return;
+    const int64_t total = seen[slot] + samples;
+    __syncthreads();
+    if (threadIdx.x == 0) seen[slot] = total;
+    const double den = (double)(total > 1 ? total : 1);
+    for (int k = threadIdx.x; k < nb; k += blockDim.x) {
+        const double a = acc[(size_t)slot * nb + k] + (double)psum[(size_t)r * nb + k];
+        acc[(size_t)slot * nb + k] = a;
+        const float mp = (float)(a / den);
+        mean_prob[(size_t)r * nb + k] = mp;
+        bits[(size_t)r * nb + k] = mp >= 0.5f ? 1 : 0;
     }
 }
 
@@ -273,6 +389,40 @@ extern "C" int wv_session_advance(const float* hist, int hcap, int hv, const flo
     if (m == 0) return WV_OK;
     hipLaunchKernelGGL(wv::session_advance_kernel, dim3((m + wv::WIN_NT - 1) / wv::WIN_NT, S), dim3(wv::WIN_NT), 0, (hipStream_t)stream, hist, hcap, hv,
                        x, n, win, wlen, hist_out, drop, hv2);
+    return launched();
+}
+
+static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return a && b && a_bytes && b_bytes && p < q + b_bytes && q < p + a_bytes;
+}
+
+extern "C" int wv_bank_advance(float* hist, int capacity, int hcap, const float* x, int64_t n_x, const int64_t* desc, int P, float* win, int A,
+                               int Lmax, void* stream) {
+    if (!hist || !desc || (n_x > 0 && !x) || (A > 0 && !win))
+        return fail(WV_EINVAL, "wv_bank_advance: null hist or desc, samples without x, or window rows without win");
+    if (capacity < 1 || capacity > WV_BANK_MAX_SLOTS || hcap < 1 || n_x < 0 || P < 0 || P > 65535 || A < 0 || A > 65535 || Lmax < 0 || (A > 0 && Lmax < 1))
+        return fail(WV_EINVAL, "wv_bank_advance: capacity outside [1, " WV_STR(WV_BANK_MAX_SLOTS) "], hcap < 1, n_x < 0, P or A outside [0, 65535], "
+                               "Lmax < 0, or window rows of no length");
+    const size_t hb = (size_t)capacity * hcap * 4, xb = (size_t)n_x * 4, wb = (size_t)A * Lmax * 4;
+    if (overlap(hist, hb, x, xb) || overlap(hist, hb, win, wb) || overlap(x, xb, win, wb))
+        return fail(WV_EINVAL, "wv_bank_advance: hist, x and win must not overlap");
+    if (P == 0) return WV_OK;
+    const int tiles = A > 0 ? (Lmax + wv::WIN_TILE - 1) / wv::WIN_TILE : 0;
+    hipLaunchKernelGGL(wv::bank_advance_kernel, dim3(1 + tiles, P), dim3(wv::WIN_NT), 0, (hipStream_t)stream, hist, capacity, hcap, x, n_x, desc, win,
+                       A, Lmax);
+    return launched();
+}
+
+extern "C" int wv_bank_detect_update(double* acc, int64_t* seen, int capacity, int nb, const float* psum, const int64_t* desc, int A,
+                                     float* mean_prob, int* bits, void* stream) {
+    if (!acc || !seen || !psum || !desc || !mean_prob || !bits)
+        return fail(WV_EINVAL, "wv_bank_detect_update: null pointer (acc, seen, psum, desc, mean_prob, bits)");
+    if (capacity < 1 || capacity > WV_BANK_MAX_SLOTS || nb < 1 || A < 0 || A > 65535)
+        return fail(WV_EINVAL, "wv_bank_detect_update: capacity outside [1, " WV_STR(WV_BANK_MAX_SLOTS) "], nb < 1 or A outside [0, 65535]");
+    if (A == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::bank_detect_update_kernel, dim3(A), dim3(nb <= 64 ? 64 : wv::WIN_NT), 0, (hipStream_t)stream, acc, seen, capacity, nb, psum,
+                       desc, mean_prob, bits);
     return launched();
 }
 

@@ -9,6 +9,11 @@ the whole-clip forward on the concatenated input.  ("Session", not "stream", to 
 Segment sessions (SegmentSession, section 7d-5) run the locator and the detector's gated per-frame sums on one shared window per tick and
 turn the frame sums into closed localize.Segments on the device (wv_segment_track); their push returns nothing, poll() reads.
 
+Session banks (StreamBank, section 7d-6) drop the lockstep: `capacity` slots, each an independent stream with its own _Ticker that is opened,
+pushed to (any number of samples, or not at all on a tick) and closed on its own.  The slots that complete frames on a tick become the rows of
+one left-aligned, right-zero-padded window batch per pad_limit group (wv_bank_advance, the histories updated in place); per stream the
+concatenated outputs are still the whole-clip forward on what it pushed.
+
 The bookkeeping is independent of the backend: a session takes the net forward as a callable, and the history update as
 another, so the same state machine runs on the numpy oracle on a CPU.
 """
@@ -446,3 +451,343 @@ class SegmentSession(SegmentStreamSession, _HipSession):
 
     def _confidence(self, prob: np.ndarray) -> float:
         return float(self._torch.from_numpy(np.ascontiguousarray(prob, np.float32)).mean())      # as WaveVerify._segments takes it
+
+
+# ---------------------------------------------------------------------------------------------------------------- session banks
+@dataclass
+class BankLaunch:
+    """One wv_bank_advance call and, where A > 0, one net forward on its [A, 1, Lmax] window batch: rows [p_lo, p_hi) of the tick's descriptor
+    table, the first A of them the windows (row r of the batch is descriptor p_lo + r and window a_lo + r of the tick)."""
+    p_lo: int
+    p_hi: int
+    a_lo: int
+    A: int
+    Lmax: int
+
+
+@dataclass
+class BankPlan:
+    """One tick of a bank, integers only.  desc [P, 8] int64 = {slot, hv, x_off, n, row, wlen, drop, hv2} as wv_bank_advance reads it; slots: the
+    pushed slots in the order their samples are packed; windows: [(slot, Tick)] launch by launch, row by row; out: slot -> (offset, count) of
+    its new columns in the tick's packed output of n_out samples; padded: samples the launches run only as right padding."""
+    desc: np.ndarray
+    launches: list
+    slots: list
+    n_x: int
+    windows: list
+    out: dict
+    n_out: int
+    padded: int
+
+
+def plan_tick(ticks: dict, sizes: dict, pad_limit: float = 1.5) -> BankPlan:
+    """ticks {slot: Tick}, sizes {slot: samples pushed} -> the tick's launches.  The windows are sorted by (wlen, slot) and cut greedily
+    wherever the next would be longer than pad_limit times the shortest of the launch, so a launch pads no row by more than that factor.
+    Slots that complete no frame ride in the first launch (a launch of their own without windows if there is none); a slot with nothing to
+    do at all has no descriptor."""
+    slots = sorted(ticks)
+    x_off, n_x = {}, 0
+    for s in slots:
+        x_off[s] = n_x
+        n_x += sizes[s]
+    groups: list = []
+    for s in sorted((s for s in slots if ticks[s].wlen > 0), key=lambda s: (ticks[s].wlen, s)):
+        if groups and ticks[s].wlen <= pad_limit * ticks[groups[-1][0]].wlen:
+            groups[-1].append(s)
+        else:
+            groups.append([s])
+    idle = [s for s in slots if ticks[s].wlen == 0 and sizes[s] > 0]
+    if idle and not groups:
+        groups.append([])
+    rows, launches, windows, out, n_out, padded = [], [], [], {}, 0, 0
+    for g, members in enumerate(groups):
+        p_lo, a_lo = len(rows), len(windows)
+        Lmax = ticks[members[-1]].wlen if members else 0
+        for r, s in enumerate(members):
+            t = ticks[s]
+            rows.append([s, t.hv, x_off[s], sizes[s], r, t.wlen, t.drop, t.hv2])
+            windows.append((s, t))
+            out[s] = (n_out, t.wlen - t.keep)
+            n_out += t.wlen - t.keep
+            padded += Lmax - t.wlen
+        for s in (idle if g == 0 else ()):
+            t = ticks[s]
+            rows.append([s, t.hv, x_off[s], sizes[s], 0, 0, t.drop, t.hv2])
+        launches.append(BankLaunch(p_lo, len(rows), a_lo, len(members), Lmax))
+    for s in slots:
+        out.setdefault(s, (n_out, 0))
+    return BankPlan(np.array(rows, np.int64).reshape(-1, 8), launches, slots, n_x, windows, out, n_out, padded)
+
+
+def bank_row_ok(row, capacity: int, hcap: int, n_x: int, A: int, Lmax: int) -> bool:
+    """Whether wv_bank_advance serves a descriptor row (it skips any other whole)."""
+    slot, hv, x_off, n, r, wlen, drop, hv2 = (int(v) for v in row)
+    return (0 <= slot < capacity and 0 <= hv <= hcap and 0 <= hv2 <= hcap and n >= 0 and drop >= 0 and drop + hv2 == hv + n
+            and 0 <= wlen <= min(hv + n, Lmax) and 0 <= x_off and x_off + n <= n_x and (wlen == 0 or 0 <= r < A))
+
+
+def numpy_bank_advance(hist: np.ndarray, x: np.ndarray, desc: np.ndarray, A: int, Lmax: int) -> np.ndarray:
+    """Reference of wv_bank_advance on host arrays: hist [capacity, hcap] is updated IN PLACE (only the named slots, only [0, hv2)), x the
+    packed new samples -> win [A, 1, Lmax], zeros beyond each row's wlen (and in rows no descriptor names, which the kernel leaves alone)."""
+    capacity, hcap = hist.shape
+    win = np.zeros((A, 1, Lmax), hist.dtype)
+    for row in desc:
+        if not bank_row_ok(row, capacity, hcap, int(x.shape[0]), A, Lmax):
+            continue
+        slot, hv, x_off, n, r, wlen, drop, hv2 = (int(v) for v in row)
+        seq = np.concatenate([hist[slot, :hv], x[x_off:x_off + n]])
+        if wlen:
+            win[r, 0, :wlen] = seq[:wlen]
+        hist[slot, :hv2] = seq[drop:drop + hv2]
+    return win
+
+
+class StreamBank:
+    """`capacity` independent live streams: each slot has its own _Ticker, is opened, pushed to and closed on its own,
+    and the slots that complete frames on a tick share one launch per net (per pad_limit group).  forward(window batch [A, 1, Lmax], slots)
+    -> [A, C, Lmax]; advance(history, packed x, desc, A, Lmax) -> window batch, the history updated in place (numpy_bank_advance's contract).
+    A window batch is left-aligned: column 0 of row r is that stream's own h0, rows are zero beyond their wlen; the nets are causal and
+    push-time wlen are hop multiples, so the padding changes no kept column.  close() runs its ragged window alone, at its true length.
+    This base class runs on host arrays; push / close return per slot the kept columns [C, k], or None where nothing completed."""
+
+    def __init__(self, capacity: int, hop: int, H: int, forward: Optional[Callable], advance: Optional[Callable] = numpy_bank_advance,
+                 new_history: Optional[Callable] = None, pad_limit: float = 1.5):
+        if capacity < 1:
+            raise ValueError("a bank needs at least one slot")
+        if not pad_limit >= 1.0:
+            raise ValueError("pad_limit must be at least 1 (float('inf'): one launch per tick)")
+        self.capacity, self.pad_limit = int(capacity), float(pad_limit)
+        self.hop, self.H, self.hcap = hop, H, H + hop
+        self._tickers = [_Ticker(hop, H) for _ in range(self.capacity)]
+        self._is_open = [False] * self.capacity
+        self._forward, self._advance = forward, advance
+        self._hist = (new_history or (lambda c, cap: np.zeros((c, cap), np.float32)))(self.capacity, self.hcap)
+        self.stats = {"ticks": 0, "launches": 0, "window_samples": 0, "padded_samples": 0}
+
+    # ---- slots
+    def open(self, *args) -> int:
+        """-> the lowest free slot, starting from nothing: its ticker is reset, so the history the slot's last stream left is never read."""
+        for slot, taken in enumerate(self._is_open):
+            if not taken:
+                self._on_open(slot, *args)
+                self._tickers[slot].reset()
+                self._is_open[slot] = True
+                return slot
+        raise RuntimeError(f"all {self.capacity} slots of the bank are open")
+
+    def _on_open(self, slot: int) -> None:
+        pass
+
+    def open_slots(self) -> list:
+        return [s for s, taken in enumerate(self._is_open) if taken]
+
+    def samples_seen(self, slot: int) -> int:
+        """Samples of the slot's stream whose outputs have been produced."""
+        self._check_slot(slot)
+        return self._tickers[slot].t_out
+
+    def _check_slot(self, slot) -> None:
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.capacity or not self._is_open[slot]:
+            raise ValueError(f"slot {slot!r} is not open")
+
+    # ---- ticks
+    def push(self, items: dict) -> dict:
+        """{slot: 1-D samples, any length} -> {slot: this push's result}.  Everything is checked before any stream's state changes."""
+        for slot, x in items.items():
+            self._check_slot(slot)
+            if len(x.shape) != 1:
+                raise ValueError(f"slot {slot}: expected 1-D samples, got shape {tuple(x.shape)}")
+        return self._tick(items, {slot: self._tickers[slot].push(int(x.shape[0])) for slot, x in items.items()})
+
+    def close(self, slot: int):
+        """The stream's partial last frame at its true length (what flush() is to a lockstep session) -> its last result; frees the slot."""
+        self._check_slot(slot)
+        out = self._tick({slot: self._empty()}, {slot: self._tickers[slot].flush()})[slot]
+        self._is_open[slot] = False
+        return out
+
+    def _empty(self):
+        return np.zeros(0, np.float32)
+
+    def _count(self, plan: BankPlan) -> None:
+        self.stats["ticks"] += 1
+        self.stats["launches"] += sum(1 for ln in plan.launches if ln.A)
+        self.stats["window_samples"] += sum(ln.A * ln.Lmax for ln in plan.launches)
+        self.stats["padded_samples"] += plan.padded
+
+    def _tick(self, xs: dict, ticks: dict) -> dict:
+        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
+        self._count(plan)
+        x = np.concatenate([np.asarray(xs[s]) for s in plan.slots]) if plan.slots else self._empty()
+        res = {s: None for s in xs}
+        for ln in plan.launches:
+            win = self._advance(self._hist, x, plan.desc[ln.p_lo:ln.p_hi], ln.A, ln.Lmax)
+            if ln.A:
+                rows = plan.windows[ln.a_lo:ln.a_lo + ln.A]
+                y = self._forward(win, [s for s, _ in rows])
+                for r, (s, t) in enumerate(rows):
+                    res[s] = y[r][..., t.keep:t.wlen]
+        return res
+
+
+class _HipBank(StreamBank):
+    """StreamBank on a HipNet: histories, windows and outputs stay on the device.  A tick uploads ONE table (the wv_bank_advance descriptors and
+    whatever else its launches read), then runs per launch wv_bank_advance and the net on the window batch."""
+
+    def __init__(self, net, capacity: int, precision: str, pad_limit: float):
+        import torch
+        if precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16'")
+        self.net, self.precision, self._torch = net, precision, torch
+        super().__init__(capacity, net.cfg.hop_length, _halo(net.cfg), None, None,
+                         lambda c, cap: torch.zeros((c, cap), dtype=torch.float32, device=net.device), pad_limit)
+
+    def _empty(self):
+        return self._torch.zeros(0, dtype=self._torch.float32, device=self.net.device)
+
+    def _upload(self, sections: list) -> dict:
+        """[(name, host array)] -> {name: device tensor}: one buffer, every section on an 8-byte boundary, one copy."""
+        torch = self._torch
+        offs, total = [], 0
+        for _, a in sections:
+            offs.append(total)
+            total += -(-a.nbytes // 8) * 8
+        buf = np.zeros(total, np.uint8)
+        for o, (_, a) in zip(offs, sections):
+            buf[o:o + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        dev = torch.from_numpy(buf).to(self.net.device)
+        return {name: dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).view(a.shape)
+                for o, (name, a) in zip(offs, sections)}
+
+    def _sections(self, plan: BankPlan) -> list:
+        return []
+
+    def _begin(self, plan: BankPlan, tabs: dict) -> None:
+        pass
+
+    def _tick(self, xs: dict, ticks: dict) -> dict:
+        torch, dev = self._torch, self.net.device
+        from . import _lib
+        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
+        self._count(plan)
+        if plan.launches:
+            with torch.cuda.device(dev):
+                parts = [xs[s].to(dev, torch.float32) for s in plan.slots if xs[s].shape[0]]
+                x = torch.cat(parts) if parts else None
+                tabs = self._upload([("desc", plan.desc)] + self._sections(plan))
+                self._begin(plan, tabs)
+                for ln in plan.launches:
+                    win = torch.empty((ln.A, 1, ln.Lmax), dtype=torch.float32, device=dev) if ln.A else None
+                    _lib.check(self.net._lib.wv_bank_advance(
+                        self._hist.data_ptr(), self.capacity, self.hcap, _lib.ptr(x), plan.n_x, tabs["desc"][ln.p_lo:].data_ptr(),
+                        ln.p_hi - ln.p_lo, _lib.ptr(win), ln.A, ln.Lmax, _lib.stream()), "wv_bank_advance")
+                    if ln.A:
+                        self._launch(win, tabs, plan, ln)
+                return self._finish(plan, tabs)
+        return self._finish(plan, None)
+
+
+class EmbedBank(_HipBank):
+    """Watermark up to `capacity` live 16 kHz mono streams, each on its own clock: open(message) -> slot, push({slot: x [n]}) -> {slot: the
+    watermarked samples of the frames that push completed [k]}, close(slot) -> the rest.  The values of a tick are views of one tensor.
+    messages: what turns open()'s argument into a [msg_dimension] bit tensor (WaveVerify passes its watermark-id table); without it open()
+    takes the bits themselves.  The messages live on the host and travel in the tick's table, so open() touches no device memory."""
+
+    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5, messages: Optional[Callable] = None):
+        super().__init__(net, capacity, precision, pad_limit)
+        self._messages = messages
+        self._msg = np.zeros((self.capacity, net.cfg.msg_dimension), np.float32)
+
+    def _on_open(self, slot: int, message) -> None:
+        m = self._messages(message) if self._messages is not None else message
+        m = np.asarray(m.detach().cpu() if hasattr(m, "detach") else m, np.float32).reshape(-1)
+        if m.shape[0] != self._msg.shape[1]:
+            raise ValueError(f"a message has {self._msg.shape[1]} bits, got {m.shape[0]}")
+        self._msg[slot] = m
+
+    def _scatter_section(self, plan: BankPlan):
+        # wv_window_scatter's descriptor per window: {offset in `out` of the window's column 0, row stride (one row: unused), keep lo, keep hi}
+        return "scatter", np.array([[plan.out[s][0] - t.keep, plan.n_out, t.keep, t.wlen] for s, t in plan.windows], np.int64).reshape(-1, 4)
+
+    def _sections(self, plan: BankPlan) -> list:
+        return [self._scatter_section(plan), ("msg", self._msg[[s for s, _ in plan.windows]])]
+
+    def _begin(self, plan: BankPlan, tabs: dict) -> None:
+        self._out = self._torch.empty(plan.n_out, dtype=self._torch.float32, device=self.net.device)
+
+    def _net_forward(self, win, tabs: dict, ln: BankLaunch):
+        return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=True, precision=self.precision)
+
+    def _launch(self, win, tabs: dict, plan: BankPlan, ln: BankLaunch) -> None:
+        from . import _lib
+        y = self._net_forward(win, tabs, ln)
+        _lib.check(self.net._lib.wv_window_scatter(y.data_ptr(), tabs["scatter"][ln.a_lo:].data_ptr(), self._out.data_ptr(), plan.n_out, ln.A, 1,
+                                                   ln.Lmax, _lib.stream()), "wv_window_scatter")
+
+    def _finish(self, plan: BankPlan, tabs) -> dict:
+        out = self._out if tabs is not None else self._empty()
+        self._out = None
+        return {s: out[o:o + k] for s, (o, k) in plan.out.items()}
+
+
+class LocateBank(EmbedBank):
+    """Locate the watermark in up to `capacity` live streams: open() -> slot, push({slot: x [n]}) -> {slot: locator logits of the newly completed
+    frames [k]}."""
+
+    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5):
+        _HipBank.__init__(self, net, capacity, precision, pad_limit)
+
+    def _on_open(self, slot: int) -> None:
+        pass
+
+    def _sections(self, plan: BankPlan) -> list:
+        return [self._scatter_section(plan)]
+
+    def _net_forward(self, win, tabs: dict, ln: BankLaunch):
+        return self.net.locator(win, precision=self.precision)
+
+
+class DetectBank(_HipBank):
+    """Detect the watermark in up to `capacity` live streams: push({slot: x [n]}) -> {slot: DetectState(mean_prob [nb], bits [nb], samples_seen)}
+    over that stream's completed frames.  Each window's sigmoid sum over its own new columns [keep, wlen) goes into the slot's f64 accumulator
+    (wv_bank_detect_update), in the order and the arithmetic of DetectSession."""
+
+    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5):
+        super().__init__(net, capacity, precision, pad_limit)
+        torch, nb = self._torch, net.cfg.head_bits
+        self._acc = torch.zeros((self.capacity, nb), dtype=torch.float64, device=net.device)
+        self._seen = torch.zeros(self.capacity, dtype=torch.int64, device=net.device)
+        self._zero = (torch.zeros(nb, dtype=torch.float32, device=net.device), torch.zeros(nb, dtype=torch.int32, device=net.device))
+        self._last = [self._zero] * self.capacity
+
+    def _on_open(self, slot: int) -> None:
+        self._acc[slot].zero_()                                            # two fills on the stream; nothing waits for them
+        self._seen[slot].zero_()
+        self._last[slot] = self._zero
+
+    def _sections(self, plan: BankPlan) -> list:
+        w = plan.windows
+        return [("det", np.array([[s, t.wlen - t.keep] for s, t in w], np.int64).reshape(-1, 2)),
+                ("lo", np.array([t.keep for _, t in w], np.int32)), ("hi", np.array([t.wlen for _, t in w], np.int32))]
+
+    def _begin(self, plan: BankPlan, tabs: dict) -> None:
+        self._psum = self._torch.empty((len(plan.windows), self.net.cfg.head_bits), dtype=self._torch.float32, device=self.net.device)
+
+    def _launch(self, win, tabs: dict, plan: BankPlan, ln: BankLaunch) -> None:
+        a, b = ln.a_lo, ln.a_lo + ln.A
+        self.net.detector_window_psum(win, tabs["lo"][a:b], tabs["hi"][a:b], psum=self._psum[a:b], precision=self.precision)
+
+    def _finish(self, plan: BankPlan, tabs) -> dict:
+        torch, A, nb = self._torch, len(plan.windows), self.net.cfg.head_bits
+        if A:
+            from . import _lib
+            mp = torch.empty((A, nb), dtype=torch.float32, device=self.net.device)
+            bits = torch.empty((A, nb), dtype=torch.int32, device=self.net.device)
+            with torch.cuda.device(self.net.device):
+                _lib.check(self.net._lib.wv_bank_detect_update(self._acc.data_ptr(), self._seen.data_ptr(), self.capacity, nb, self._psum.data_ptr(),
+                                                               tabs["det"].data_ptr(), A, mp.data_ptr(), bits.data_ptr(), _lib.stream()),
+                           "wv_bank_detect_update")
+            for r, (s, _) in enumerate(plan.windows):
+                self._last[s] = (mp[r], bits[r])
+            self._psum = None
+        return {s: DetectState(*self._last[s], self._tickers[s].t_out) for s in plan.slots}
