@@ -246,13 +246,18 @@ def rb_geometry(C):
     return dict(WD=WD, TTO=WD - 8, per_cu=max(1, min(160 * 1024 // smem, 4 * WPS // nwaves)), name=f"resblock<{C},{WD}>")
 
 
+def rh16_width(C):
+    """rh16_width (wv_kernels.h): the widths rh_kernel is built for, one RH<> row each in launch_resblock16's switch."""
+    return C in RH_CFG
+
+
 def rh_geometry(C):
-    """-> dict(WD, TTO, per_cu, name) of the f16 rh_kernel at C channels."""
+    """-> dict(WD, TTO, SMEM, waves, per_cu, name) of the f16 rh_kernel at C channels: the RH<...> row and rh_launch's workgroups per CU."""
     NG, NT, WPS, SPW = RH_CFG[C]
     WD = NG * (32 * NT - 4) + 4
     smem = C // 8 * WD * 16 + 2 * (C // 2 * 12) * 4
     nwaves = C // (32 * SPW) * NG
-    return dict(WD=WD, TTO=WD - 8, per_cu=max(1, min(160 * 1024 // smem, 4 * WPS // nwaves)), name=f"resblock16<{C},{WD}>")
+    return dict(WD=WD, TTO=WD - 8, SMEM=smem, waves=nwaves, per_cu=max(1, min(160 * 1024 // smem, 4 * WPS // nwaves)), name=f"resblock16<{C},{WD}>")
 
 
 def persistent_grid(geo, B, T, cus):

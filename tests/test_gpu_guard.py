@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 import torch
 
+import h16_fuzz_cases as H16
 from guard import GuardError, Guards, PoisonedWorkspace
 from oracle import wv_oracle as O
 from test_gpu_ops import close, rnd
@@ -936,6 +937,72 @@ def test_h16_upsample_guarded(ops, K, M, Tin, r, offset):
     fx = ops.h16_from_f32(torch.from_numpy(X).cuda())
     _f16_case(ops, f"h16_upsample K={K} r={r} Tin={Tin}", lambda: ops.h16_upsample(fx, w_ct, w_pw, b, r, act_scale=0.9),
               lambda: ops.h16_upsample(x.t, w_ct, w_pw, b, r, act_scale=0.9, out=y.t, out_act=ya.t), [y, ya], g)
+
+
+# The written-out cases of the f16 fuzz (tests/h16_fuzz_cases.py: every launch_conv16 route at its smallest shape, the Tout / Tin edges, odd
+# batches whose last two-clip tile holds one clip, ragged row blocks): a stray read or write there lands in padding, which no numeric
+# comparison sees.  tests/test_gpu_h16_fuzz.py holds the same cases to the mode's oracle and to the restated route.
+def _ids(cases):
+    return ["-".join(str(v) for v in c) for c in cases]
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("case", H16.DENSE_EXPLICIT, ids=_ids(H16.DENSE_EXPLICIT))
+def test_h16_conv_placed_cases_guarded(ops, case, offset):
+    B, K, M, Tin, ks, stride, pad, epi, outs = case
+    a = H16.dense_args(case)
+    rng = np.random.default_rng(B + K + M + Tin + ks)
+    X = rnd(rng, B, K, Tin)
+    w_pw, w_dw = rnd(rng, M, K, 1, scale=K ** -0.5), (rnd(rng, M, 1, ks, scale=ks ** -0.5) if ks > 1 else None)
+    bias = rnd(rng, M, scale=0.1)
+    Gm = (M + 15) // 16 * 2
+    g = Guards(offset=offset)
+    x = _c8_input(ops, g, X, "X16")
+    fx = ops.h16_from_f32(torch.from_numpy(X).cuda())
+    y = g.output((B, Gm, a.Tout, 8), torch.float16, name="raw") if a.Y else None
+    ya = g.output((B, Gm, a.Tout, 8), torch.float16, name="act") if a.Yact else None
+    yf = g.output((B, M, a.Tout), name="f32") if a.Yf32 else None
+    arenas = [o for o in (y, ya, yf) if o is not None]
+    t = lambda o: None if o is None else o.t
+    act = 0.9 if a.Yact else None
+    if a.film:
+        film = rnd(rng, B, a.bands, 2)
+        f = g.input(film, "film")
+        as_list = lambda r: list(r) if isinstance(r, (tuple, list)) else [r]
+        fresh = lambda: as_list(ops.h16_conv_film(fx, w_pw, w_dw, bias, torch.from_numpy(film).cuda(), ks, stride, pad, act_scale=act, want_raw=a.Y))
+        guarded = lambda: ops.h16_conv_film(x.t, w_pw, w_dw, bias, f.t, ks, stride, pad, act_scale=act, want_raw=a.Y, out=t(y), out_act=t(ya))
+    else:
+        kw = dict(ks=ks, stride=stride, pad=pad, out_scale=0.7, act_scale=act, want_raw=a.Y, want_f32=a.Yf32)
+        r = fr = None
+        if a.resid:
+            R = rnd(rng, B, M, a.Tout)
+            r, fr = _c8_input(ops, g, R, "resid16"), ops.h16_from_f32(torch.from_numpy(R).cuda())
+
+        def fresh():
+            o = ops.h16_conv(fx, w_pw, w_dw, bias, resid16=fr, **kw)
+            return [o[k] for k in ("raw", "act", "f32") if k in o]
+        guarded = lambda: ops.h16_conv(x.t, w_pw, w_dw, bias, resid16=t(r), out=t(y), out_act=t(ya), out_f32=t(yf), **kw)
+    _f16_case(ops, f"h16_conv placed {case}", fresh, guarded, arenas, g)
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("case", H16.UP_EXPLICIT, ids=_ids(H16.UP_EXPLICIT))
+def test_h16_upsample_placed_cases_guarded(ops, case, offset):
+    B, K, Mo, Tin, r, outs = case
+    a = H16.up_args(case)
+    rng = np.random.default_rng(B + K + Mo + Tin + r)
+    X = rnd(rng, B, K, Tin)
+    w_ct, w_pw, b = rnd(rng, K, 1, 2 * r, scale=0.5), rnd(rng, Mo, K, 1, scale=K ** -0.5), rnd(rng, Mo, scale=0.1)
+    g = Guards(offset=offset)
+    x = _c8_input(ops, g, X, "X16")
+    shp = (B, Mo // 8, Tin * r, 8)
+    y = g.output(shp, torch.float16, name="Y16") if a.Y else None
+    ya = g.output(shp, torch.float16, name="Yact16") if a.Yact else None
+    fx = ops.h16_from_f32(torch.from_numpy(X).cuda())
+    act = 0.9 if a.Yact else None
+    _f16_case(ops, f"h16_upsample placed {case}", lambda: ops.h16_upsample(fx, w_ct, w_pw, b, r, act_scale=act, want_raw=a.Y),
+              lambda: ops.h16_upsample(x.t, w_ct, w_pw, b, r, act_scale=act, want_raw=a.Y, out=None if y is None else y.t,
+                                       out_act=None if ya is None else ya.t), [o for o in (y, ya) if o is not None], g)
 
 
 @pytest.mark.parametrize("offset", [0, 1])

@@ -10,9 +10,11 @@ import torch
 
 from oracle import wv_oracle as O
 
-pytestmark = pytest.mark.gpu
+from h16_refs import (BLOCK_BOUND, COMPOSED_BOUND, L2E, TOL, close, cu, h, resblock16_ref, resblock_plain, rnd,  # noqa: F401  (other test files import these from here)
+                      upsample16_ref, upsample_plain)
+from h16_refs import dense_conv_ref as _dense_conv_ref
 
-TOL = 3 * 2.0 ** -11
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -22,45 +24,8 @@ def ops():
     return _ops
 
 
-def rnd(rng, *shape, scale=1.0):
-    return (scale * rng.standard_normal(shape)).astype(np.float32)
-
-
-def h(a):
-    """round to f16 and back (what the kernels store)"""
-    return np.asarray(a, np.float32).astype(np.float16).astype(np.float32)
-
-
-def cu(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def close(got, ref, what="", tol=TOL):
-    got = got.detach().float().cpu().numpy() if isinstance(got, torch.Tensor) else np.asarray(got)
-    assert got.shape == ref.shape, (what, got.shape, ref.shape)
-    assert np.isfinite(got).all(), what
-    err = float(np.abs(got - ref).max()) if ref.size else 0.0
-    lim = tol * max(1.0, float(np.abs(ref).max()) if ref.size else 1.0)
-    assert err <= lim, f"{what}: max|d|={err:.3e} > {lim:.3e}"
-
-
 def c8_to_np(ops, t, C):
     return ops.h16_to_f32(t, C).cpu().numpy()
-
-
-L2E = 1.4426950408889634
-
-
-def resblock16_ref(X, w1, d1, b1, w2, d2, b2, pre, s_out):
-    """The block with the kernel's roundings restated (csrc/wv_h16.hip rh_kernel): both activations are kept TIMES log2(e) and rounded
-    to f16 there, the 1x1 weights are packed DIVIDED by log2(e) and rounded to f16 (pack_rh_pw), sums in float64."""
-    C = X.shape[1]
-    w1s, w2s = h(w1.astype(np.float64) / L2E), h(w2.astype(np.float64) / L2E)
-    xa = h(L2E * O.elu((X * np.float32(pre)).astype(np.float64)))
-    y1 = O.sconv1d(O.sconv1d(xa.astype(np.float64), w1s.astype(np.float64), None), d1.astype(np.float64), b1.astype(np.float64), groups=C)
-    u = h(L2E * O.elu(y1))
-    y = X + np.float64(s_out) * O.sconv1d(O.sconv1d(u.astype(np.float64), w2s.astype(np.float64), None), d2.astype(np.float64), b2.astype(np.float64), groups=C)
-    return y.astype(np.float32)
 
 
 @pytest.mark.parametrize("B,C,T", [(2, 64, 1000), (3, 33, 17), (1, 8, 1), (2, 129, 300)])
@@ -106,10 +71,8 @@ def test_resblock(ops, C, T):
     pre, s_out, s_act = np.float32(0.8660254), np.float32(0.41), np.float32(0.7071)
     y = resblock16_ref(X, w1, d1, b1, w2, d2, b2, pre, s_out)
     # ... and the restated roundings are the block itself: against the plain composition in float64 (f16 rounding of operands only)
-    plain = X + s_out * O.sconv1d(O.sconv1d(O.elu(O.sconv1d(O.sconv1d(O.elu((X * pre).astype(np.float64)), w1.astype(np.float64), None), d1.astype(np.float64),
-                                                                       b1.astype(np.float64), groups=C)), w2.astype(np.float64), None),
-                                  d2.astype(np.float64), b2.astype(np.float64), groups=C)
-    assert np.abs(plain - y).max() <= 6 * 2.0 ** -11 * max(1.0, np.abs(plain).max())
+    plain = resblock_plain(X, w1, d1, b1, w2, d2, b2, pre, s_out)
+    assert np.abs(plain - y).max() <= BLOCK_BOUND * max(1.0, np.abs(plain).max())
     X16 = ops.h16_from_f32(cu(X))
     got, gact = ops.h16_resblock(X16, w1, d1, b1, w2, d2, b2, pre_scale=float(pre), out_scale=float(s_out), act_scale=float(s_act))
     close(ops.h16_to_f32(got, C), h(y), "resblock16")
@@ -359,20 +322,8 @@ def test_waveverify_api_opt_in():
 
 # ---- seeded sweep of geometries the detector does not use: the generic conv (any taps / stride / pad, ragged channel counts on the f32
 # output, residual + both c8 outputs), the ResnetBlock at random lengths and batch sizes
-def _dense_conv_ref(xa, wc, bias, stride, pad, Tout):
-    """y[b][m][to] = bias[m] + sum_i sum_k wc[m][i][k] * xa[b][k][to * stride + i - pad], x = 0 outside (float64)."""
-    B, K, Tin = xa.shape
-    M, ks, _ = wc.shape
-    xp = np.zeros((B, K, pad + Tout * stride + ks + stride), np.float64)
-    xp[:, :, pad:pad + Tin] = xa
-    ref = np.zeros((B, M, Tout), np.float64)
-    for i in range(ks):
-        ref += np.einsum("mk,bkt->bmt", wc[:, i, :].astype(np.float64), xp[:, :, i:i + Tout * stride:stride][:, :, :Tout])
-    return ref + (0.0 if bias is None else bias[None, :, None])
-
-
-@pytest.mark.parametrize("seed", range(24))
-def test_conv16_generic_geometries(ops, seed):
+def _generic_geometry(seed):
+    """The shape draw of test_conv16_generic_geometries -> (rng, B, K, ks, stride, pad, Tin, c8_out, M); the test goes on drawing its data from rng."""
     rng = np.random.default_rng(1000 + seed)
     B = int(rng.integers(1, 6))
     K = int(rng.choice([8, 16, 24, 40, 64, 100, 144, 272]))
@@ -382,6 +333,12 @@ def test_conv16_generic_geometries(ops, seed):
     Tin = int(rng.choice([1, 2, 17, 50, 63, 64, 65, 200, 513, 1000]))
     c8_out = bool(rng.integers(0, 2))
     M = int(rng.choice([16, 32, 64, 96, 128, 320])) if c8_out else int(rng.choice([1, 7, 16, 33, 64, 130, 256]))
+    return rng, B, K, ks, stride, pad, Tin, c8_out, M
+
+
+@pytest.mark.parametrize("seed", range(24))
+def test_conv16_generic_geometries(ops, seed):
+    rng, B, K, ks, stride, pad, Tin, c8_out, M = _generic_geometry(seed)
     X = rnd(rng, B, K, Tin)
     w_pw, w_dw = rnd(rng, M, K, 1, scale=K ** -0.5), (rnd(rng, M, 1, ks, scale=ks ** -0.5) if ks > 1 else None)
     bias = rnd(rng, M, scale=0.1) if rng.integers(0, 2) else None
@@ -404,12 +361,18 @@ def test_conv16_generic_geometries(ops, seed):
         close(out["f32"], ref.astype(np.float32), f"conv16 f32 (K={K} M={M} ks={ks} s={stride} pad={pad} Tin={Tin})", tol=2e-4)
 
 
-@pytest.mark.parametrize("seed", range(18))
-def test_resblock16_random_lengths(ops, seed):
+def _random_block_shape(seed):
+    """The shape draw of test_resblock16_random_lengths -> (rng, C, T, B)."""
     rng = np.random.default_rng(2000 + seed)
     C = int(rng.choice([32, 64, 96, 128, 192, 256, 384, 512, 768]))
     T = int(rng.integers(1, 700))
     B = int(rng.integers(1, 5))
+    return rng, C, T, B
+
+
+@pytest.mark.parametrize("seed", range(18))
+def test_resblock16_random_lengths(ops, seed):
+    rng, C, T, B = _random_block_shape(seed)
     X = h(rnd(rng, B, C, T))
     w1, w2 = rnd(rng, C, C, 1, scale=C ** -0.5), rnd(rng, C, C, 1, scale=C ** -0.5)
     d1, d2 = rnd(rng, C, 1, 5, scale=0.45), rnd(rng, C, 1, 5, scale=0.45)
@@ -447,16 +410,10 @@ def test_upsample_as_one_conv(ops, K, M, Tin, r):
     w_ct, w_pw, b = rnd(rng, K, 1, 2 * r, scale=0.5), rnd(rng, M, K, 1, scale=K ** -0.5), rnd(rng, M, scale=0.1)
     pre = np.float32(0.7071)
     xa = h(O.elu(X * pre))
-    two = O.sconv1d(O.sconvtr1d_depthwise(xa.astype(np.float64), w_ct.astype(np.float64), r).astype(np.float64), w_pw.astype(np.float64), b.astype(np.float64))
+    two = upsample_plain(xa, w_ct, w_pw, b, r)
     # the composed weight as the packer rounds it: rows (p, m), tap 0 = frame l - 1 (ct[k][p + r]), tap 1 = frame l (ct[k][p])
-    ref = np.zeros((B, M, Tin * r), np.float64)
-    xprev = np.concatenate([np.zeros((B, K, 1)), xa[:, :, :-1]], axis=2).astype(np.float64)
-    for p in range(r):
-        w0 = h(w_pw[:, :, 0] * w_ct[None, :, 0, p + r]).astype(np.float64)
-        w1 = h(w_pw[:, :, 0] * w_ct[None, :, 0, p]).astype(np.float64)
-        ref[:, :, p::r] = np.einsum("mk,bkt->bmt", w0, xprev) + np.einsum("mk,bkt->bmt", w1, xa.astype(np.float64))
-    ref = (ref + b[None, :, None]).astype(np.float32)
-    assert two.shape == ref.shape and np.abs(two - ref).max() <= 4 * 2.0 ** -11 * max(1.0, np.abs(two).max())
+    ref = upsample16_ref(xa, w_ct, w_pw, b, r)
+    assert two.shape == ref.shape and np.abs(two - ref).max() <= COMPOSED_BOUND * max(1.0, np.abs(two).max())
     X16 = ops.h16_from_f32(cu(X), scale=float(pre), elu=True)
     got, gact = ops.h16_upsample(X16, w_ct, w_pw, b, r, act_scale=0.5)
     close(ops.h16_to_f32(got, M), h(ref), "upsample16")
