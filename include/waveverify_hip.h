@@ -239,7 +239,35 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          mean_prob[r][k] = (float)(acc[slot][k] / max(seen[slot], 1)); bits[r][k] = mean_prob[r][k] >= 0.5f.  acc
  *                          [capacity, nb] f64 and seen [capacity] int64 are the bank's state, zero for a fresh slot; slots not named are
  *                          untouched; a row whose slot is outside [0, capacity) or whose samples < 0 is skipped.  The slots of one call
- *                          are distinct (the caller's duty).  One thread per (row, bit), no atomics.  A == 0 is success without a launch. */
+ *                          are distinct (the caller's duty).  One thread per (row, bit), no atomics.  A == 0 is success without a launch.
+ *   wv_bank_segment_track  one tick of a segment BANK (session.py SegmentBank): `capacity` independent segment trackers,
+ *                          of which the P named by desc take frames this tick, each its own range.  state and events hold `capacity` streams
+ *                          in exactly wv_segment_track's per-stream layouts (above), sized by wv_segment_track_bytes(capacity, nb,
+ *                          min_gap_frames, ring, ...), `ring` being the event records per slot; slot s is stream s of them, so a slot's bytes
+ *                          after the same ticks are those wv_segment_track leaves, and the same host readers serve both.  A fresh slot is all
+ *                          zeros in both buffers (the caller clears a slot it hands to a new stream).
+ *                          fsum is ONE arena of n_fsum floats that holds the frame sums of every launch of the tick, each launch with its
+ *                          own row length; desc [P][8] int64 device = {slot, fsum_off, Fr_stride, f_lo, f_hi, frame0, last_valid, final}.
+ *                          Row k (k <= nb, row nb the count row) of that stream's sums starts at fsum + fsum_off + k * Fr_stride; this tick's
+ *                          frames are its columns [f_lo, f_hi), column f_lo being the stream's frame number frame0 (the caller counts a slot's
+ *                          frames; its ticks follow one another without a gap).  final != 0 ends the stream: last_valid counts as the valid
+ *                          samples of the last frame of such a row only (any other frame has hop), the open run closes, and f_hi == f_lo
+ *                          with final closes it without adding a frame.  A row with f_hi == f_lo that is not final changes nothing.
+ *                          Per stream the tick is wv_segment_track's, the same device function: the ON rule, the f64 adds in ascending frame
+ *                          order with the gap's off frames first, the gap ring (frame j in slot j % (min_gap_frames - 1)), the close after
+ *                          min_gap_frames off frames, the min_len_frames drop, prob = S / (float(N) + eps), and a state that cannot follow
+ *                          from zeros and gapless ticks taken as closed with no events.  One workgroup per descriptor, thread k <= nb owns
+ *                          row k; no atomics; state is read before one barrier and written after it.  Nothing outside the named slots'
+ *                          state and event sections is written, and fsum and desc are only read.
+ *                          THE CALLER'S DUTY: the slots of one call are distinct; two rows naming one slot would run one tracker twice at
+ *                          once.  The frames of one slot may be split over several calls on the same fsum with sub-ranges of [f_lo, f_hi).
+ *                          A descriptor row is SKIPPED whole (its slot untouched) unless 0 <= slot < capacity, 0 <= f_lo <= f_hi <= Fr_stride
+ *                          <= 2^31 - 1, 0 <= fsum_off and fsum_off + (nb + 1) * Fr_stride <= n_fsum, frame0 >= 0 and 0 <= last_valid <= hop;
+ *                          the other rows of the call are served.
+ *                          Refused with WV_EINVAL and nothing written: null desc, state or events, n_fsum < 0 or n_fsum > 0 without fsum;
+ *                          capacity outside [1, WV_BANK_MAX_SLOTS], P outside [0, 65535], nb outside [1, WV_SEGMENT_MAX_BITS], hop < 1,
+ *                          min_gap_frames outside [1, WV_SEGMENT_MAX_GAP], min_len_frames < 0, ring < 1, min_on not a number; state or
+ *                          events shorter than `capacity` streams need, or not 8-byte aligned.  P == 0 is success without a launch. */
 #define WV_SEGMENT_MAX_GAP 64
 #define WV_SEGMENT_MAX_BITS 255
 #define WV_BANK_MAX_SLOTS 1048576
@@ -263,6 +291,9 @@ int wv_bank_advance(float* hist, int capacity, int hcap, const float* x, int64_t
                     int Lmax, void* stream);
 int wv_bank_detect_update(double* acc, int64_t* seen, int capacity, int nb, const float* psum, const int64_t* desc, int A,
                           float* mean_prob, int* bits, void* stream);
+int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
+                          int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes, void* events, size_t event_bytes,
+                          int ring, void* stream);
 
 /* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------

@@ -313,6 +313,15 @@ class WaveVerify:
             return session.SegmentSession(det, loc, n, sample_rate=self.sample_rate, **kw)
         return native_session.NativeSegmentSession(det, loc, n, sample_rate, channels, **kw)
 
+    def open_segment_bank(self, capacity: int = 64, pad_limit: float = 1.5, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2,
+                          min_len_frames: int = 5, ring: int = 64, gated: bool = False):
+        """session.SegmentBank: live localized detection of up to `capacity` 16 kHz mono streams that open, push and close on their own
+        (DESIGN.md section 7d-7).  bank.open() -> slot; bank.push({slot: x [n]}) returns nothing; bank.poll() -> {slot: the Segments that have
+        ended since the last poll}; bank.open_segments() -> {slot: the run still open, or None}; bank.close(slot) -> the rest.  gated=True:
+        push({slot: (x [n], gate [n])}), the 0 / 1 gate replacing the locator.  ring: closed segments the device holds per slot between reads."""
+        return session.SegmentBank(self._need("detector"), self._need("locator"), capacity, pad_limit, threshold, min_on, min_gap_frames,
+                                   min_len_frames, ring, gated, self.detector_precision, self.locator_precision, self.sample_rate)
+
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],
               output_path: Optional[Union[str, Path]] = None, *, native: bool = False, strength: float = 1.0,

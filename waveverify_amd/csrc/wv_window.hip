@@ -11,6 +11,7 @@
 //   bank_advance_kernel    a session bank's tick: a descriptor per stream that pushed, its history shifted in place, its window row filled
 //   bank_detect_update_kernel  a detect bank's tick: the windows' sigmoid sums into the per-slot f64 accumulators, mean probabilities and bits out
 //   segment_track_kernel   a live segment session's tick: the new frames' sums -> the per-stream open run, gap ring and ring of closed segments
+//   bank_segment_track_kernel  a segment bank's tick: the same per-stream body, a descriptor per slot with its own frame range and row block
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
 #include <hip/hip_runtime.h>
 
@@ -245,25 +246,26 @@ static inline SegLayout seg_layout(int nb, int G, int capacity) {
     return l;
 }
 
-// grid (S), block = nb + 1 rounded up to a wave.  Thread k <= nb owns row k of the sums (row nb is the count row); EVERY thread reads the count
-// row of every frame and keeps the run's count sum itself, so all threads of a stream take the same decisions without exchanging anything.
-// Frames of this tick are read from fsum wherever they are needed; the ring only carries the off frames after `hi` over to the next tick
-// (frame j in slot j % (G - 1); at most G - 1 consecutive frames are ever held, so slots never collide).  A run is closed as soon as G off
-// frames have passed, hence an on frame that meets an open run always has a gap < G and merges.  Reads of the state come before the barrier,
-// writes after it; event records are write-only.
-__global__ __launch_bounds__(256) void segment_track_kernel(const float* __restrict__ fsum, int nb, int Fr, int f_lo, int n, long long frame0, int hop,
-                                                            int last_valid, int final_, double min_on, int G, int min_len, float eps, char* state,
-                                                            size_t state_stride, char* events, size_t event_stride, size_t rec, int capacity) {
-    const int s = blockIdx.x, k = threadIdx.x;
+// One stream's tick, run by one workgroup of nb + 1 threads rounded up to a wave (segment_track_kernel and bank_segment_track_kernel both call
+// it, every thread of the workgroup together).  fs: the stream's rows at this tick's first column, row k at fs + k * Fr; n frames, the first
+// being the stream's frame frame0; st / ev: the stream's own state and event sections.  Thread k <= nb owns row k of the sums (row nb is the
+// count row); EVERY thread reads the count row of every frame and keeps the run's count sum itself, so all threads of a stream take the same
+// decisions without exchanging anything.  Frames of this tick are read from fsum wherever they are needed; the ring only carries the off
+// frames after `hi` over to the next tick (frame j in slot j % (G - 1); at most G - 1 consecutive frames are ever held, so slots never
+// collide).  A run is closed as soon as G off frames have passed, hence an on frame that meets an open run always has a gap < G and merges.
+// Reads of the state come before the barrier, writes after it; event records are write-only.
+__device__ __forceinline__ void segment_track_stream(const float* __restrict__ fs, size_t Fr, int nb, int n, long long frame0, int hop, int last_valid,
+                                                     int final_, double min_on, int G, int min_len, float eps, char* st, char* ev, size_t rec,
+                                                     int capacity) {
+    const int k = threadIdx.x;
     const bool owns = k <= nb;
     const int r = owns ? k : nb;
-    const float* fs = fsum + (size_t)s * (nb + 1) * Fr + f_lo;
     const float* crow = fs + (size_t)nb * Fr;
     const float* krow = fs + (size_t)r * Fr;
-    long long* hdr = reinterpret_cast<long long*>(state + (size_t)s * state_stride);
+    long long* hdr = reinterpret_cast<long long*>(st);
     double* accp = reinterpret_cast<double*>(hdr + 4);
     float* ring = reinterpret_cast<float*>(accp + nb + 1);
-    long long* nevp = reinterpret_cast<long long*>(events + (size_t)s * event_stride);
+    long long* nevp = reinterpret_cast<long long*>(ev);
     char* recs = reinterpret_cast<char*>(nevp + 1);
     const int R = G - 1;
 
@@ -340,6 +342,45 @@ __global__ __launch_bounds__(256) void segment_track_kernel(const float* __restr
         hdr[3] = fend;
         *nevp = nev;
     }
+}
+
+// grid (S), block = nb + 1 rounded up to a wave: stream s = blockIdx.x of S lockstep streams, all on the same frame range.
+__global__ __launch_bounds__(256) void segment_track_kernel(const float* __restrict__ fsum, int nb, int Fr, int f_lo, int n, long long frame0, int hop,
+                                                            int last_valid, int final_, double min_on, int G, int min_len, float eps, char* state,
+                                                            size_t state_stride, char* events, size_t event_stride, size_t rec, int capacity) {
+    const int s = blockIdx.x;
+    segment_track_stream(fsum + (size_t)s * (nb + 1) * Fr + f_lo, (size_t)Fr, nb, n, frame0, hop, last_valid, final_, min_on, G, min_len, eps,
+                         state + (size_t)s * state_stride, events + (size_t)s * event_stride, rec, capacity);
+}
+
+// ---- segment banks: every slot its own frame range ------------------------------------------------------------
+// One descriptor row of wv_bank_segment_track = {slot, fsum_off, Fr_stride, f_lo, f_hi, frame0, last_valid, final}; a row that breaks the
+// contract is skipped whole (session.bank_track_row_ok restates the predicate).  The divisions keep every product inside int64.
+struct TrackRow {
+    int64_t slot, off, Fr, f_lo, f_hi, frame0, last_valid, final_;
+    bool ok;
+};
+
+__device__ __forceinline__ TrackRow track_row(const int64_t* __restrict__ desc, int p, int capacity, int nb, int hop, int64_t n_fsum) {
+    const int64_t* d = desc + 8 * (size_t)p;
+    TrackRow r = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], false};
+    r.ok = r.slot >= 0 && r.slot < capacity && r.Fr >= 0 && r.Fr <= 0x7fffffffLL && r.f_lo >= 0 && r.f_lo <= r.f_hi && r.f_hi <= r.Fr && r.off >= 0 &&
+           r.off <= n_fsum && r.Fr <= (n_fsum - r.off) / (nb + 1) && r.frame0 >= 0 && r.last_valid >= 0 && r.last_valid <= hop;
+    return r;
+}
+
+// grid (P), block = nb + 1 rounded up to a wave.  Workgroup p serves descriptor p: the body is segment_track_stream on the slot's own state and
+// event sections, its rows at fsum + fsum_off.  A row without frames that is not final changes nothing and returns at once, as wv_segment_track
+// launches nothing for such a tick.  The row is read alike by every thread, so a workgroup leaves whole or runs whole.
+__global__ __launch_bounds__(256) void bank_segment_track_kernel(const float* __restrict__ fsum, int64_t n_fsum, const int64_t* __restrict__ desc,
+                                                                 int capacity, int nb, int hop, double min_on, int G, int min_len, float eps,
+                                                                 char* state, size_t state_stride, char* events, size_t event_stride, size_t rec,
+                                                                 int ring) {
+    const TrackRow r = track_row(desc, blockIdx.x, capacity, nb, hop, n_fsum);
+    if (!r.ok || (r.f_hi == r.f_lo && !r.final_)) return;
+    segment_track_stream(fsum + r.off + r.f_lo, (size_t)r.Fr, nb, (int)(r.f_hi - r.f_lo), (long long)r.frame0, hop, (int)r.last_valid,
+                         r.final_ != 0, min_on, G, min_len, eps, state + (size_t)r.slot * state_stride, events + (size_t)r.slot * event_stride,
+                         rec, ring);
 }
 
 }  // namespace wv
@@ -456,5 +497,28 @@ extern "C" int wv_segment_track(const float* fsum, int S, int nb, int Fr_stride,
     hipLaunchKernelGGL(wv::segment_track_kernel, dim3(S), dim3(nt), 0, (hipStream_t)stream, fsum, nb, Fr_stride, f_lo, f_hi - f_lo, (long long)frame0,
                        hop, last_valid, final, min_on, min_gap_frames, min_len_frames, eps, (char*)state, l.state_stride, (char*)events,
                        l.event_stride, l.rec, capacity);
+    return launched();
+}
+
+extern "C" int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
+                                     int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes, void* events,
+                                     size_t event_bytes, int ring, void* stream) {
+    if (!desc || !state || !events || n_fsum < 0 || (n_fsum > 0 && !fsum))
+        return fail(WV_EINVAL, "wv_bank_segment_track: null desc, state or events, n_fsum < 0, or frame sums without fsum");
+    if (capacity < 1 || capacity > WV_BANK_MAX_SLOTS || P < 0 || P > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS || hop < 1)
+        return fail(WV_EINVAL, "wv_bank_segment_track: capacity outside [1, " WV_STR(WV_BANK_MAX_SLOTS) "], P outside [0, 65535], nb outside [1, "
+                               WV_STR(WV_SEGMENT_MAX_BITS) "] or hop < 1");
+    if (min_gap_frames < 1 || min_gap_frames > WV_SEGMENT_MAX_GAP || min_len_frames < 0 || ring < 1 || !(min_on == min_on))
+        return fail(WV_EINVAL, "wv_bank_segment_track: min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP) "], min_len_frames < 0, ring < 1 or "
+                               "min_on not a number");
+    const wv::SegLayout l = wv::seg_layout(nb, min_gap_frames, ring);
+    if (state_bytes / l.state_stride < (size_t)capacity || event_bytes / l.event_stride < (size_t)capacity || ((uintptr_t)state & 7) ||
+        ((uintptr_t)events & 7))
+        return fail(WV_EINVAL, "wv_bank_segment_track: state or events shorter than wv_segment_track_bytes gives for `capacity` streams, or not "
+                               "8-byte aligned");
+    if (P == 0) return WV_OK;
+    const int nt = (nb + 1 + 63) / 64 * 64;
+    hipLaunchKernelGGL(wv::bank_segment_track_kernel, dim3(P), dim3(nt), 0, (hipStream_t)stream, fsum, n_fsum, desc, capacity, nb, hop, min_on,
+                       min_gap_frames, min_len_frames, eps, (char*)state, l.state_stride, (char*)events, l.event_stride, l.rec, ring);
     return launched();
 }

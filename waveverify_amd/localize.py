@@ -154,3 +154,64 @@ class SegmentTracker:
         """Per stream the provisional open run (lo, hi, count, prob) over [lo, hi) as it stands (held off frames not included), or None."""
         return [(self._lo[s], self._hi[s], float(self._acc[s, self.nb]), self._prob(self._acc[s])) if self._open[s] else None
                 for s in range(self.S)]
+
+
+def bank_track_row_ok(row, capacity: int, nb: int, hop: int, n_fsum: int) -> bool:
+    """Whether wv_bank_segment_track serves a descriptor row {slot, fsum_off, Fr_stride, f_lo, f_hi, frame0, last_valid, final} (it skips any
+    other whole)."""
+    slot, off, Fr, f_lo, f_hi, frame0, last_valid, _ = (int(v) for v in row)
+    return (0 <= slot < capacity and 0 <= f_lo <= f_hi <= Fr <= 2 ** 31 - 1 and 0 <= off and off + (nb + 1) * Fr <= n_fsum
+            and frame0 >= 0 and 0 <= last_valid <= hop)
+
+
+class BankSegmentTracker:
+    """`capacity` independent SegmentTracker states behind wv_bank_segment_track's descriptor interface: the host twin
+    of that kernel, on numpy arrays.  advance(fsum, desc) takes fsum as ONE flat arena of frame sums and desc rows {slot, fsum_off, Fr_stride,
+    f_lo, f_hi, frame0, last_valid, final}; row k of a stream's sums starts at fsum_off + k * Fr_stride, its frames this tick are columns
+    [f_lo, f_hi), column f_lo being the slot's frame frame0.  A row that breaks the contract (bank_track_row_ok) is skipped whole, and so is a row
+    without frames that is not final.  A slot whose state cannot follow from frame0 (an open run that does not end within min_gap_frames
+    frames before it) is taken as closed, as the kernel takes it.  reset(slot) is what zeroing the slot's state and event sections is on the
+    device.  `ring` is the event ring: poll() refuses, as session.HipSegmentTracker does, a slot on which more events closed since its last
+    read than the ring holds."""
+
+    def __init__(self, capacity: int, nb: int, hop: int, min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5, ring: int = 64,
+                 eps: float = 1e-8, dtype=np.float32):
+        if capacity < 1 or ring < 1:
+            raise ValueError("need capacity, ring >= 1")
+        self.capacity, self.nb, self.hop, self.ring, self.dtype = int(capacity), int(nb), int(hop), int(ring), dtype
+        self.G = int(min_gap_frames)
+        self._t = [SegmentTracker(1, nb, hop, min_on, min_gap_frames, min_len_frames, eps, dtype) for _ in range(self.capacity)]
+
+    def reset(self, slot: int) -> None:
+        self._t[slot].reset()
+
+    def advance(self, fsum, desc) -> None:
+        fsum = np.asarray(fsum, self.dtype).reshape(-1)
+        for row in np.asarray(desc, np.int64).reshape(-1, 8):
+            if not bank_track_row_ok(row, self.capacity, self.nb, self.hop, fsum.shape[0]):
+                continue
+            slot, off, Fr, f_lo, f_hi, frame0, last_valid, final = (int(v) for v in row)
+            if f_hi == f_lo and not final:
+                continue
+            t = self._t[slot]
+            if t._open[0] and not (0 <= t._lo[0] < t._hi[0] <= frame0 and frame0 - t._hi[0] < self.G):
+                t._open[0], t._gap[0] = False, []
+            t.frames_seen, t.closed = frame0, False
+            t.advance(fsum[off: off + (self.nb + 1) * Fr].reshape(1, self.nb + 1, Fr), f_lo, f_hi, last_valid, bool(final))
+            t.closed = False
+
+    def frames_seen(self, slot: int) -> int:
+        return self._t[slot].frames_seen
+
+    def poll(self, slots) -> dict:
+        """-> {slot: the events closed since the slot's last poll}."""
+        out = {}
+        for s in slots:
+            evs = self._t[s].poll()[0]
+            if len(evs) > self.ring:
+                raise RuntimeError(f"slot {s}: {len(evs)} segments closed since the last read of a ring of {self.ring}: events were lost")
+            out[s] = evs
+        return out
+
+    def open_runs(self, slots) -> dict:
+        return {s: self._t[s].open_runs()[0] for s in slots}

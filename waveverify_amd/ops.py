@@ -238,6 +238,25 @@ def segment_track(fsum, f_lo: int, f_hi: int, frame0: int, hop: int, last_valid:
                "wv_segment_track")
 
 
+def bank_segment_track(fsum, desc, P: int, capacity: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int,
+                       state, events, ring: int, eps: float = 1e-8) -> None:
+    """wv_bank_segment_track: one tick of a segment bank.  fsum: the tick's arena of frame sums (a float32 device tensor, or None where no row
+    has frames); desc: int64 device tensor, its first P rows of 8 are served; state / events: uint8 device tensors of
+    segment_track_bytes(capacity, nb, min_gap_frames, ring), a fresh slot all zeros, updated in place."""
+    lib = _lib.load()
+    if fsum is not None and not (fsum.is_cuda and fsum.dtype == torch.float32 and fsum.is_contiguous()):
+        raise ValueError("fsum must be a contiguous float32 tensor on the GPU")
+    if not (desc.is_cuda and desc.dtype == torch.int64 and desc.is_contiguous() and desc.numel() >= 8 * int(P)):
+        raise ValueError("desc must be a contiguous int64 tensor on the GPU with 8 values per row")
+    if not (state.is_cuda and events.is_cuda and state.dtype == torch.uint8 and events.dtype == torch.uint8 and state.is_contiguous()
+            and events.is_contiguous()):
+        raise ValueError("state and events must be contiguous uint8 tensors on the GPU")
+    n_fsum = 0 if fsum is None else fsum.numel()
+    _lib.check(lib.wv_bank_segment_track(fsum.data_ptr() if n_fsum else None, n_fsum, desc.data_ptr(), int(P), int(capacity), int(nb), int(hop),
+                                         float(min_on), int(min_gap_frames), int(min_len_frames), float(eps), state.data_ptr(), state.numel(),
+                                         events.data_ptr(), events.numel(), int(ring), _lib.stream()), "wv_bank_segment_track")
+
+
 def segment_event_dtype(nb: int) -> np.dtype:
     """One event record of wv_segment_track's `events` buffer as a numpy structured dtype."""
     return np.dtype({"names": ["lo", "hi", "count", "prob"], "formats": ["<i8", "<i8", "<f8", ("<f4", (int(nb),))], "offsets": [0, 8, 16, 24],

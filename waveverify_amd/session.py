@@ -14,6 +14,10 @@ pushed to (any number of samples, or not at all on a tick) and closed on its own
 one left-aligned, right-zero-padded window batch per pad_limit group (wv_bank_advance, the histories updated in place); per stream the
 concatenated outputs are still the whole-clip forward on what it pushed.
 
+Segment banks (SegmentBank, section 7d-7) are the two together: per slot the segment session's tracker, fed by the bank's launches.  The frame
+sums of a tick's launches lie in one arena, and one wv_bank_segment_track call takes a descriptor per slot with that slot's own frame range,
+so the frames a short row computes on the batch's zero padding are never tracked.
+
 The bookkeeping is independent of the backend: a session takes the net forward as a callable, and the history update as
 another, so the same state machine runs on the numpy oracle on a CPU.
 """
@@ -24,6 +28,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from .localize import bank_track_row_ok  # noqa: F401  (wv_bank_segment_track's row predicate, restated beside bank_row_ok)
 from .window import halo as _halo
 
 
@@ -240,6 +245,29 @@ def segment_halo(detector_cfg, locator_cfg) -> int:
     return max(_halo(detector_cfg), -(-_halo(locator_cfg) // hop) * hop)
 
 
+def _segment_of(ev, hop: int, t_in: int, sample_rate: int, confidence: Callable):
+    """A tracker event (lo, hi, count, prob) of a stream that has pushed t_in samples -> localize.Segment.  t_in is the true length once the
+    stream has ended and never short of a closed run before, so `end` is clipped only on the partial last frame."""
+    from .localize import Segment
+    from .watermark_id import WatermarkID
+    lo, hi, count, prob = ev
+    end = min(int(hi) * hop, t_in)
+    prob = np.asarray(prob, np.float32)
+    bits = "".join("1" if p >= np.float32(0.5) else "0" for p in prob)
+    wid = WatermarkID.custom(bits) if len(bits) == 16 else None           # an id has 16 bits; a net of another width leaves prob to read
+    return Segment(int(lo) * hop / sample_rate, end / sample_rate, wid, confidence(prob), float(count) / (end - int(lo) * hop), prob,
+                   (int(lo), int(hi)))
+
+
+def _open_run_of(hdr, acc, nb: int, eps: float):
+    """One stream's header and sums as ops.segment_state reads them -> its provisional open run (lo, hi, count, prob), or None."""
+    if not hdr[0]:
+        return None
+    cnt = acc[nb]
+    prob = (acc[:nb] / np.float64(np.float32(cnt) + np.float32(eps))).astype(np.float32) if cnt > 0.0 else np.zeros(nb, np.float32)
+    return int(hdr[1]), int(hdr[2]), float(cnt), prob
+
+
 class SegmentStreamSession(StreamSession):
     """Localized detection of S live streams: push(x [S, n], gate=None) returns nothing; the watermarked stretches
     come out of poll() as localize.Segments once they have ended.  Backend independent: frame_sums(window [S,1,L], gate window [S,L] or
@@ -277,15 +305,7 @@ class SegmentStreamSession(StreamSession):
         return float(np.asarray(prob, np.float32).mean())
 
     def _segment(self, ev):
-        from .localize import Segment
-        from .watermark_id import WatermarkID
-        lo, hi, count, prob = ev
-        hop, end = self._t.hop, min(int(hi) * self._t.hop, self._t.t_in)   # t_in: the true length once flushed, never short before
-        prob = np.asarray(prob, np.float32)
-        bits = "".join("1" if p >= np.float32(0.5) else "0" for p in prob)
-        wid = WatermarkID.custom(bits) if len(bits) == 16 else None       # an id has 16 bits; a net of another width leaves prob to read
-        return Segment(int(lo) * hop / self.sample_rate, end / self.sample_rate, wid, self._confidence(prob),
-                       float(count) / (end - int(lo) * hop), prob, (int(lo), int(hi)))
+        return _segment_of(ev, self._t.hop, self._t.t_in, self.sample_rate, self._confidence)
 
     def _drain(self) -> None:
         for s, evs in enumerate(self._tracker.poll()):
@@ -405,16 +425,7 @@ class HipSegmentTracker:
 
     def open_runs(self):
         hdr, acc = self._ops.segment_state(self.state, self.S, self.nb)
-        out = []
-        for s in range(self.S):
-            if not hdr[s, 0]:
-                out.append(None)
-                continue
-            cnt = acc[s, self.nb]
-            prob = (acc[s, :self.nb] / np.float64(np.float32(cnt) + np.float32(self.eps))).astype(np.float32) if cnt > 0.0 \
-                else np.zeros(self.nb, np.float32)
-            out.append((int(hdr[s, 1]), int(hdr[s, 2]), float(cnt), prob))
-        return out
+        return [_open_run_of(hdr[s], acc[s], self.nb, self.eps) for s in range(self.S)]
 
 
 class SegmentSession(SegmentStreamSession, _HipSession):
@@ -791,3 +802,281 @@ class DetectBank(_HipBank):
                 self._last[s] = (mp[r], bits[r])
             self._psum = None
         return {s: DetectState(*self._last[s], self._tickers[s].t_out) for s in plan.slots}
+
+
+# ---------------------------------------------------------------------------------------------------------------- segment banks
+class SegmentStreamBank(StreamBank):
+    """Localized detection of up to `capacity` live streams, each on its own clock: open() -> slot, push({slot: x [n]})
+    returns nothing (a gated bank takes {slot: (x [n], gate [n])}, the 0 / 1 gate replacing the locator), poll() -> {slot: the Segments that
+    closed since the last poll}, open_segments() -> {slot: the run still open, or None}, close(slot) -> the slot's Segments not yet polled.
+    Backend independent: frame_sums(window batch [A, 1, Lmax], gate windows [A, Lmax] or None) -> the batch's per-frame gated sums
+    [A, nb + 1, ceil(Lmax / hop)]; `tracker` has the interface of localize.BankSegmentTracker; `advance` is numpy_bank_advance's contract and
+    serves the gate's histories with the same descriptor rows.
+
+    The launches of a tick are plan_tick's.  Their frame sums lie one after another in ONE arena, and a descriptor per window tells the tracker
+    where that stream's rows are and which of their frames are its own: [keep / hop, ceil(wlen / hop)).  The frames of a row beyond its wlen
+    are computed on the batch's zero padding and belong to nobody; no descriptor reaches them.
+
+    ring is the tracker's event ring per slot.  The frames tracked since a slot was last read bound its waiting events by
+    frames // max(1, min_len_frames + min_gap_frames) + 1; before a tick would let any slot's bound reach `ring` the bank reads the rings
+    itself (the one host synchronisation a push can make), and a long push is tracked in pieces that stay within the bound, so nothing is lost."""
+
+    def __init__(self, capacity: int, hop: int, H: int, frame_sums: Callable, tracker, advance: Optional[Callable] = numpy_bank_advance,
+                 new_history: Optional[Callable] = None, pad_limit: float = 1.5, gated: bool = False, sample_rate: int = 16000, ring: int = 64,
+                 min_gap_frames: int = 2, min_len_frames: int = 5):
+        if ring < 1:
+            raise ValueError("ring must be at least 1")
+        new_history = new_history or (lambda c, cap: np.zeros((c, cap), np.float32))
+        StreamBank.__init__(self, capacity, hop, H, None, advance, new_history, pad_limit)
+        self._frame_sums, self._tracker, self.gated = frame_sums, tracker, bool(gated)
+        self.sample_rate, self.ring = int(sample_rate), int(ring)
+        self._period = max(1, int(min_len_frames) + int(min_gap_frames))
+        self._ghist = new_history(self.capacity, self.hcap) if self.gated else None
+        self._frames = [0] * self.capacity                                 # frames tracked so far: the next tick's frame0
+        self._unread = [0] * self.capacity                                 # frames tracked since the slot's ring was last read
+        self._pending = [[] for _ in range(self.capacity)]
+
+    # ---- slots
+    def _on_open(self, slot: int) -> None:
+        self._tracker.reset(slot)                                          # whatever the slot's last stream left is never seen
+        self._frames[slot] = self._unread[slot] = 0
+        self._pending[slot] = []
+
+    # ---- events -> Segments
+    def _confidence(self, prob: np.ndarray) -> float:
+        return float(np.asarray(prob, np.float32).mean())
+
+    def _segment(self, slot: int, ev):
+        return _segment_of(ev, self.hop, self._tickers[slot].t_in, self.sample_rate, self._confidence)
+
+    def _drain(self) -> None:
+        slots = self.open_slots()
+        for s, evs in self._tracker.poll(slots).items():
+            self._pending[s] += [self._segment(s, ev) for ev in evs]
+        for s in slots:
+            self._unread[s] = 0
+
+    def poll(self) -> dict:
+        """-> {slot: the Segments closed since the last poll, in stream order} for every open slot."""
+        self._drain()
+        out = {s: self._pending[s] for s in self.open_slots()}
+        for s in out:
+            self._pending[s] = []
+        return out
+
+    def open_segments(self) -> dict:
+        """-> {slot: the run that is open now as a provisional Segment (its frames so far), or None} for every open slot."""
+        return {s: None if ev is None else self._segment(s, ev) for s, ev in self._tracker.open_runs(self.open_slots()).items()}
+
+    # ---- ticks
+    def push(self, items: dict) -> None:
+        """{slot: samples [n]} ({slot: (samples [n], gate [n])} on a gated bank), any length per slot.  Everything is checked before any stream's
+        state changes."""
+        xs, gs = {}, {}
+        for slot, item in items.items():
+            self._check_slot(slot)
+            pair = isinstance(item, (tuple, list))
+            if self.gated and not (pair and len(item) == 2):
+                raise ValueError(f"slot {slot}: a gated bank takes (samples, gate) on every push")
+            if pair and not self.gated:
+                raise ValueError(f"slot {slot}: this bank is not gated; it takes the samples alone")
+            x, g = item if pair else (item, None)
+            if len(x.shape) != 1:
+                raise ValueError(f"slot {slot}: expected 1-D samples, got shape {tuple(x.shape)}")
+            if g is not None and tuple(g.shape) != tuple(x.shape):
+                raise ValueError(f"slot {slot}: gate must have the samples' shape {tuple(x.shape)}, got {tuple(g.shape)}")
+            xs[slot], gs[slot] = x, g
+        self._tick(xs, gs, {slot: self._tickers[slot].push(int(x.shape[0])) for slot, x in xs.items()}, False)
+
+    def close(self, slot: int) -> list:
+        """The stream's partial last frame alone at its true length, its open run closed -> the slot's Segments not yet polled; frees the slot."""
+        self._check_slot(slot)
+        if self._unread[slot]:
+            self._drain()                                                  # a close at `final` may follow the last one closely
+        e = self._empty()
+        self._tick({slot: e}, {slot: e if self.gated else None}, {slot: self._tickers[slot].flush()}, True)
+        self._drain()
+        out, self._pending[slot] = self._pending[slot], []
+        self._is_open[slot] = False
+        return out
+
+    def _track_rows(self, plan: BankPlan, ticks: dict, final: bool):
+        """-> (offset of every launch's frame sums in the tick's arena, the arena's length, the tracker's descriptor rows)."""
+        hop, nb1 = self.hop, self._tracker.nb + 1
+        offs, rows, n_fsum = [], [], 0
+        for ln in plan.launches:
+            Fr = -(-ln.Lmax // hop)
+            offs.append(n_fsum)
+            for r, (s, t) in enumerate(plan.windows[ln.a_lo:ln.a_lo + ln.A]):
+                f_hi = -(-t.wlen // hop)                                   # the frames from f_hi on are the batch's padding
+                rows.append([s, n_fsum + r * nb1 * Fr, Fr, t.keep // hop, f_hi, self._frames[s], t.wlen - (f_hi - 1) * hop, int(final)])
+            n_fsum += -(-ln.A * nb1 * Fr // 4) * 4                         # every launch's block starts on a 16-byte boundary
+        if final:
+            named = {r[0] for r in rows}
+            rows += [[s, 0, 0, 0, 0, self._frames[s], hop, 1] for s in ticks if s not in named]     # no frame left: the open run still closes
+        return offs, n_fsum, rows
+
+    def _pieces(self, rows: list):
+        """The tick's descriptor rows cut so that no slot's bound reaches `ring` between two reads -> ([(read the rings first, rows [P, 8])],
+        the slots' unread frames after them); the slots' frame counters move on to the tick's end.  A tick of ordinary pushes is one piece."""
+        step = max(1, self.ring * self._period - 1)                        # frames // period + 1 <= ring
+        unread, hop = list(self._unread), self.hop
+        out, left = [], [list(r) for r in rows]
+        while left:
+            m = [min(step, r[4] - r[3]) for r in left]
+            drain = any(unread[r[0]] and (unread[r[0]] + k) // self._period + 1 >= self.ring for r, k in zip(left, m))
+            if drain:
+                unread = [0] * self.capacity
+            piece, nxt = [], []
+            for (s, off, Fr, lo, hi, f0, lv, fin), k in zip(left, m):
+                last = lo + k == hi
+                piece.append([s, off, Fr, lo, lo + k, f0, lv if last else hop, fin if last else 0])
+                unread[s] += k
+                self._frames[s] = f0 + k
+                if not last:
+                    nxt.append([s, off, Fr, lo + k, hi, f0 + k, lv, fin])
+            out.append((drain, np.array(piece, np.int64).reshape(-1, 8)))
+            left = nxt
+        return out, unread
+
+    def _tick(self, xs: dict, gs: dict, ticks: dict, final: bool) -> None:
+        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
+        self._count(plan)
+        offs, n_fsum, rows = self._track_rows(plan, ticks, final)
+        pieces, unread = self._pieces(rows)
+        self._run(plan, xs, gs, offs, n_fsum, pieces)
+        self._unread = unread
+
+    def _run(self, plan: BankPlan, xs: dict, gs: dict, offs: list, n_fsum: int, pieces: list) -> None:
+        x = np.concatenate([np.asarray(xs[s]) for s in plan.slots]) if plan.slots else self._empty()
+        g = np.concatenate([np.asarray(gs[s]) for s in plan.slots]) if plan.slots and self.gated else None
+        arena = np.zeros(n_fsum, self._tracker.dtype)
+        for ln, off in zip(plan.launches, offs):
+            desc = plan.desc[ln.p_lo:ln.p_hi]
+            win = self._advance(self._hist, x, desc, ln.A, ln.Lmax)
+            gwin = self._advance(self._ghist, g, desc, ln.A, ln.Lmax).reshape(ln.A, ln.Lmax) if self.gated else None
+            if ln.A:
+                fs = np.asarray(self._frame_sums(win, gwin))
+                arena[off:off + fs.size] = fs.reshape(-1)
+        for drain, rows in pieces:
+            if drain:
+                self._drain()
+            self._tracker.advance(arena, rows)
+
+
+class HipBankSegmentTracker:
+    """localize.BankSegmentTracker's interface on wv_bank_segment_track: the slots' state and event rings stay on the device in
+    wv_segment_track's per-stream layouts; advance() is one launch and no synchronisation, reset() two fills on the stream, poll() and
+    open_runs() one device-to-host copy each."""
+
+    def __init__(self, capacity: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int, ring: int, device,
+                 eps: float = 1e-8):
+        import torch
+        from . import ops
+        self.capacity, self.nb, self.hop, self.min_on = int(capacity), int(nb), int(hop), float(min_on)
+        self.G, self.min_len, self.ring, self.eps, self.device = int(min_gap_frames), int(min_len_frames), int(ring), float(eps), device
+        self._torch, self._ops = torch, ops
+        with torch.cuda.device(device):
+            sb, eb = ops.segment_track_bytes(self.capacity, self.nb, self.G, self.ring)          # refuses what the kernel would
+        self._strides = (sb // self.capacity, eb // self.capacity)
+        self.state = torch.zeros(sb, dtype=torch.uint8, device=device)
+        self.events = torch.zeros(eb, dtype=torch.uint8, device=device)
+        self._read = [0] * self.capacity
+
+    def reset(self, slot: int) -> None:
+        ss, es = self._strides
+        self.state[slot * ss:(slot + 1) * ss].zero_()                       # two fills on the stream; nothing waits for them
+        self.events[slot * es:(slot + 1) * es].zero_()
+        self._read[slot] = 0
+
+    def advance(self, fsum, desc, P: Optional[int] = None) -> None:
+        """fsum: the tick's arena (device float32, or None / empty); desc: int64 device tensor of rows [P, 8] (a host array is uploaded)."""
+        torch = self._torch
+        if not hasattr(desc, "data_ptr"):
+            desc = torch.from_numpy(np.ascontiguousarray(desc, np.int64)).to(self.device)
+        P = int(desc.numel() // 8) if P is None else int(P)
+        with torch.cuda.device(self.device):
+            self._ops.bank_segment_track(fsum if fsum is not None and fsum.numel() else None, desc, P, self.capacity, self.nb, self.hop,
+                                         self.min_on, self.G, self.min_len, self.state, self.events, self.ring, self.eps)
+
+    def poll(self, slots) -> dict:
+        n, recs = self._ops.segment_events(self.events, self.capacity, self.nb, self.ring)
+        out = {}
+        for s in slots:
+            new = int(n[s]) - self._read[s]
+            if new > self.ring:
+                raise RuntimeError(f"slot {s}: {new} segments closed since the last read of a ring of {self.ring}: events were lost")
+            out[s] = [(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy())
+                      for r in (recs[s, e % self.ring] for e in range(self._read[s], int(n[s])))]
+            self._read[s] = int(n[s])
+        return out
+
+    def open_runs(self, slots) -> dict:
+        hdr, acc = self._ops.segment_state(self.state, self.capacity, self.nb)
+        return {s: _open_run_of(hdr[s], acc[s], self.nb, self.eps) for s in slots}
+
+
+class SegmentBank(SegmentStreamBank, _HipBank):
+    """SegmentStreamBank on a detector and a locator HipNet: one history per slot for both nets (a gated bank has a second one for the gate,
+    advanced by a second wv_bank_advance with the same rows), per launch the locator's logits (or the gate windows) gating the detector's
+    frames kernel into that launch's block of the tick's arena, then ONE wv_bank_segment_track.  A tick uploads one table: the
+    wv_bank_advance descriptors and the tracker's.  Nothing comes back to the host in push() but the ring read described above."""
+
+    def __init__(self, detector, locator, capacity: int = 64, pad_limit: float = 1.5, threshold: float = 0.5, min_on: float = 0.5,
+                 min_gap_frames: int = 2, min_len_frames: int = 5, ring: int = 64, gated: bool = False, precision: str = "f32",
+                 locator_precision: Optional[str] = None, sample_rate: int = 16000):
+        import torch
+        from .localize import gate_threshold
+        locator_precision = precision if locator_precision is None else locator_precision
+        if precision not in ("f32", "f16") or locator_precision not in ("f32", "f16"):
+            raise ValueError("precision must be 'f32' or 'f16'")
+        if detector.cfg.kind != "detector" or locator.cfg.kind != "locator":
+            raise ValueError("need a detector and a locator")
+        if ring < 1:
+            raise ValueError("ring must be at least 1")
+        self.net, self.locator, self.precision, self.locator_precision, self._torch = detector, locator, precision, locator_precision, torch
+        self._logit_thr = gate_threshold(threshold)
+        hop, H = detector.cfg.hop_length, segment_halo(detector.cfg, locator.cfg)
+        tracker = HipBankSegmentTracker(capacity, detector.cfg.head_bits, hop, min_on, min_gap_frames, min_len_frames, ring, detector.device)
+        SegmentStreamBank.__init__(self, capacity, hop, H, None, tracker, None,
+                                   lambda c, cap: torch.zeros((c, cap), dtype=torch.float32, device=detector.device), pad_limit, gated,
+                                   sample_rate, ring, min_gap_frames, min_len_frames)
+
+    def _confidence(self, prob: np.ndarray) -> float:
+        return float(self._torch.from_numpy(np.ascontiguousarray(prob, np.float32)).mean())      # as WaveVerify._segments takes it
+
+    def _bank_advance(self, hist, x, desc, ln: BankLaunch, n_x: int):
+        from . import _lib
+        win = self._torch.empty((ln.A, 1, ln.Lmax), dtype=self._torch.float32, device=self.net.device) if ln.A else None
+        _lib.check(self.net._lib.wv_bank_advance(hist.data_ptr(), self.capacity, self.hcap, _lib.ptr(x), n_x, desc[ln.p_lo:].data_ptr(),
+                                                 ln.p_hi - ln.p_lo, _lib.ptr(win), ln.A, ln.Lmax, _lib.stream()), "wv_bank_advance")
+        return win
+
+    def _run(self, plan: BankPlan, xs: dict, gs: dict, offs: list, n_fsum: int, pieces: list) -> None:
+        torch, dev, nb1 = self._torch, self.net.device, self._tracker.nb + 1
+        if not plan.launches and not pieces:
+            return
+        with torch.cuda.device(dev):
+            pushed = [s for s in plan.slots if xs[s].shape[0]]
+            x = torch.cat([xs[s].to(dev, torch.float32) for s in pushed]) if pushed else None
+            g = torch.cat([gs[s].to(dev, torch.float32) for s in pushed]) if pushed and self.gated else None
+            track = np.concatenate([rows for _, rows in pieces]) if pieces else np.zeros((0, 8), np.int64)
+            tabs = self._upload([(name, a) for name, a in (("desc", plan.desc), ("track", track)) if a.size])
+            arena = torch.empty(n_fsum, dtype=torch.float32, device=dev) if n_fsum else None
+            for ln, off in zip(plan.launches, offs):
+                win = self._bank_advance(self._hist, x, tabs["desc"], ln, plan.n_x)
+                gwin = self._bank_advance(self._ghist, g, tabs["desc"], ln, plan.n_x) if self.gated else None
+                if ln.A:
+                    Fr = -(-ln.Lmax // self.hop)
+                    out = arena[off:off + ln.A * nb1 * Fr].view(ln.A, nb1, Fr)
+                    if self.gated:
+                        self.net.detector_frame_sums(win, gwin, 0.5, self.precision, out=out)
+                    else:
+                        self.net.detector_frame_sums(win, self.locator.locator(win, precision=self.locator_precision), self._logit_thr,
+                                                     self.precision, out=out)
+            p = 0
+            for drain, rows in pieces:
+                if drain:
+                    self._drain()
+                self._tracker.advance(arena, tabs["track"][p:], len(rows))
+                p += len(rows)
