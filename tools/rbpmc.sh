@@ -17,7 +17,7 @@ acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"]
-        if "rb_kernel" not in k and "k1_kernel" not in k: continue
+        if "rb_kernel" not in k and "rb_halo_kernel" not in k and "k1_kernel" not in k: continue
         acc[k[:90]][r["Counter_Name"]].append(float(r["Counter_Value"]))
 for k, cs in acc.items():
     print(k)

@@ -71,7 +71,8 @@ struct RbArgs {
     float* Yact;          // [B, C, T] ELU(act_scale * y), or null
     float out_scale, act_scale;
     int B, C, T;
-    int num_t, ntiles;    // filled by the launcher: tiles per clip, tiles in all
+    int num_t, ntiles;    // filled by the launcher, halo scheme (C = 64, 128): tiles per clip, tiles in all
+    int run_w, runs_per_clip, nruns;   // ... carried scheme (C = 96, 192): windows per run, runs per clip, runs in all (wv_rb.hip, "Runs")
     // training forward (wv_train_block_forward): out_scale is multiplied by out_scale_ptr[0] (a device scalar: res_scale_param) when
     // given; sv_* (all four or none, with Y): the tensors the block's backward wants, [B, C, T] each -- h0 = W1 @ ELU(c x), u = DW5(h0) + b1
     // (BEFORE the second half's ELU), h1 = W2 @ ELU(u), v = DW5(h1) + b2 (y = x + s v) -- written from the same registers the kernel computes them in
