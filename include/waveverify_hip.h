@@ -828,6 +828,48 @@ int wv_native_session_up_add(const float* rhist, int rcap, int rv, const float* 
                              const float* x, int n, float* out, int k, int pad, float gain, float* pend_out, float* rhist_out, int rdrop, int rv2,
                              int S, int C, int orig, int nw, int L, int width, void* stream);
 
+/* ---- and for session BANKS (waveverify_amd/native_bank.py): up to `capacity` slots, each a stream with its OWN rate, channel
+ * count, packet length and resampler state; the P slots a tick names are served by one launch per stage, whatever the mix of rates.
+ * A RATE TABLE is a host array of at most WV_NATIVE_BANK_MAX_RATES entries, one resampler each (kernels_t a DEVICE pointer to the transposed table
+ * [L][nw] described above).  The entry point copies the table into the kernel's arguments by value; a descriptor names a rate by its index.  The
+ * launch's LDS is the largest 256-output window of the table, and an entry whose window passes 64 KB is refused as above.
+ * STATE is ping-pong per slot, so that no launch reads and writes the same bytes:  hist [capacity][2][hcap] (channel means),
+ * rhist [capacity][2][rcap], pend [capacity][2][Cmax][pcap].  A descriptor's `half` names the half that holds the slot's current state; the launch
+ * reads it and writes the next state into the other half, and the caller flips its bit for every slot a call named.  Slots that no descriptor names
+ * are not touched, and the work grows with the rows and samples pushed, not with capacity.  The slots of one call must be distinct (the caller's
+ * duty, as for wv_bank_advance: two rows of one slot would race on its next state).
+ * Descriptors are int64 rows on the device; offsets count floats in the call's arenas, which hold planar [C][count] blocks:
+ *   wv_native_bank_down    desc [P][12] = {slot, rate, C, hv, x_off, n, y_off, n_out, pad, drop, hv2, half}: the row's new samples are C planar
+ *                          channels of n floats at x + x_off, its n_out outputs go to y + y_off, the other half's [0, hv2) becomes sequence
+ *                          samples [drop, drop + hv2); the arithmetic is wv_native_session_down's for that stream.
+ *   wv_native_bank_up_add  desc [P][15] = {slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half}, gain [P] f32 on the device
+ *                          (row p's strength): the row's nr residual samples lie at r + r_off, its new originals (C x n) at x + x_off, and its output,
+ *                          C planar channels of k floats, goes to out + out_off, formed as wv_native_session_up_add forms it; the next residual
+ *                          history [0, rv2) and the next delay line [c][0, pv2), pv2 = pv + n - k, go to the other half.
+ * `blocks` is the launch's x-extent, which the entry point cannot read from device descriptors: at least the largest per-row need, which is
+ * ceil(n_out / 256) + ceil(hv2 / 256) for the front stage and ceil(k / 256) + ceil(rv2 / 256) + ceil(pv2 / 256) for the back stage.  Blocks past
+ * a row's own need exit; a row that needs more than `blocks` is served only in part.
+ * ROW RULE (native_bank.native_bank_down_row_ok / native_bank_up_row_ok state it in Python): a row is served only if
+ *   0 <= slot < capacity, 0 <= rate < n_rates, 1 <= C <= 64 (and C <= Cmax for the back stage), half in {0, 1};
+ *   each rolled state is a fitting suffix: 0 <= valid <= cap, 0 <= next <= cap, fresh >= 0, drop >= 0, drop + next == valid + fresh, for
+ *   (hcap, hv, n, drop, hv2) and (rcap, rv, nr, rdrop, rv2);  0 <= pv <= pcap, n >= 0, k >= 0, 0 <= pv + n - k <= pcap;
+ *   0 <= pad <= the rate's width;  0 <= outputs <= (ceil((pad + valid + fresh) / orig) + 1) * nw;  every sample count <= 2^31 - 257;
+ *   every range inside its arena: x_off >= 0 and x_off + C * n <= n_x, and likewise y_off + n_out <= n_y, r_off + nr <= n_r, out_off + C * k <= n_out.
+ * Any other row is skipped WHOLE: none of its outputs is written and both halves of its slot stay untouched; the other rows of the call are served.
+ * Refused with WV_EINVAL, nothing launched or written: a null pointer where a count is positive (hist, rhist, pend and rates always; desc and gain
+ * with P > 0), capacity outside [1, WV_BANK_MAX_SLOTS], P outside [0, 65535], blocks outside [0, WV_NATIVE_BANK_MAX_BLOCKS], n_rates outside
+ * [1, WV_NATIVE_BANK_MAX_RATES], a rate entry with orig, nw or L < 1, width < 0 or a null table, hcap, rcap or pcap < 1, Cmax outside [1, 64], a
+ * negative arena length, or arenas that overlap each other or the state buffers (r and x, both only read, may).  P == 0 or blocks == 0 is success
+ * without a launch. */
+#define WV_NATIVE_BANK_MAX_RATES 8
+#define WV_NATIVE_BANK_MAX_BLOCKS 16777216
+typedef struct { const float* kernels_t; int orig, nw, L, width; } wv_native_rate;
+int wv_native_bank_down(float* hist, int capacity, int hcap, const float* x, int64_t n_x, const wv_native_rate* rates, int n_rates, const int64_t* desc,
+                        int P, int blocks, float* y, int64_t n_y, void* stream);
+int wv_native_bank_up_add(float* rhist, int rcap, float* pend, int pcap, int Cmax, int capacity, const float* r, int64_t n_r, const float* x, int64_t n_x,
+                          const wv_native_rate* rates, int n_rates, const int64_t* desc, const float* gain, int P, int blocks, float* out, int64_t n_out,
+                          void* stream);
+
 /* ==== csrc/wv_fx_time.hip: plain-arithmetic time-domain effects ----------------------------------------------------------------
  * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
  * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding

@@ -30,6 +30,11 @@ class WvConfig(C.Structure):
     ]
 
 
+class WvNativeRate(C.Structure):
+    """wv_native_rate: one resampler of a native-rate bank's rate table (kernels_t a device address)."""
+    _fields_ = [("kernels_t", C.c_void_p), ("orig", C.c_int), ("nw", C.c_int), ("L", C.c_int), ("width", C.c_int)]
+
+
 _FP = C.POINTER(C.c_float)
 _VP = C.c_void_p
 
@@ -205,6 +210,9 @@ SIGNATURES = {
     "wv_native_session_down": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP] + [C.c_int] * 8 + [_VP]),
     "wv_native_session_up_add": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int,
                                            C.c_float, _VP, _VP] + [C.c_int] * 8 + [_VP]),
+    "wv_native_bank_down": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int64, C.POINTER(WvNativeRate), C.c_int, _VP, C.c_int, C.c_int, _VP, C.c_int64, _VP]),
+    "wv_native_bank_up_add": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(WvNativeRate), C.c_int, _VP,
+                                        _VP, C.c_int, C.c_int, _VP, C.c_int64, _VP]),
     "wv_fx_pointwise": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
     "wv_fx_median": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_shush": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),

@@ -17,7 +17,7 @@ from typing import Dict, List, Mapping, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import localize, native, native_session, ops, session, window
+from . import localize, native, native_bank, native_session, ops, session, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
@@ -285,20 +285,35 @@ class WaveVerify:
             return session.LocateSession(self._need("locator"), n, self.locator_precision)
         return native_session.NativeLocateSession(self._need("locator"), n, sample_rate, channels, self.locator_precision)
 
-    def open_embed_bank(self, capacity: int = 64, pad_limit: float = 1.5):
+    def open_embed_bank(self, capacity: int = 64, pad_limit: float = 1.5, rates=None, max_channels: int = 2):
         """session.EmbedBank: up to `capacity` live 16 kHz mono streams that open, push and close on their own.
         bank.open(watermark_id) -> slot; bank.push({slot: x [n], ...}) -> {slot: the watermarked samples of the frames that push completed};
-        bank.close(slot) -> the rest.  The streams that complete frames on a tick share one generator launch per pad_limit group."""
-        return session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit,
-                                 messages=lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0])
+        bank.close(slot) -> the rest.  The streams that complete frames on a tick share one generator launch per pad_limit group.
+        rates=(48000, 8000, ...): native_bank.NativeEmbedBank, every slot at its own rate and channel count:
+        bank.open(watermark_id, sample_rate, channels, strength) with sample_rate one of up to 8 `rates` and channels <= max_channels,
+        bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it."""
+        messages = lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0]        # noqa: E731
+        if rates is None:
+            return session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit, messages=messages)
+        rates = native_bank.check_rates(rates)                             # before anything is built on the device
+        return native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
 
-    def open_detect_bank(self, capacity: int = 64, pad_limit: float = 1.5):
-        """session.DetectBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: DetectState over that stream's completed frames}."""
-        return session.DetectBank(self._need("detector"), capacity, self.detector_precision, pad_limit)
+    def open_detect_bank(self, capacity: int = 64, pad_limit: float = 1.5, rates=None, max_channels: int = 2):
+        """session.DetectBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: DetectState over that stream's completed frames}.
+        rates=(...): native_bank.NativeDetectBank, bank.open(sample_rate=, channels=), push({slot: x [C, n]})."""
+        if rates is None:
+            return session.DetectBank(self._need("detector"), capacity, self.detector_precision, pad_limit)
+        rates = native_bank.check_rates(rates)
+        return native_bank.NativeDetectBank(self._need("detector"), rates, capacity, max_channels, self.detector_precision, pad_limit)
 
-    def open_locate_bank(self, capacity: int = 64, pad_limit: float = 1.5):
-        """session.LocateBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: locator logits of the frames that push completed}."""
-        return session.LocateBank(self._need("locator"), capacity, self.locator_precision, pad_limit)
+    def open_locate_bank(self, capacity: int = 64, pad_limit: float = 1.5, rates=None, max_channels: int = 2):
+        """session.LocateBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: locator logits of the frames that push completed}.
+        rates=(...): native_bank.NativeLocateBank, bank.open(sample_rate=, channels=), push({slot: x [C, n]}); the logits stay on the 16 kHz
+        time line."""
+        if rates is None:
+            return session.LocateBank(self._need("locator"), capacity, self.locator_precision, pad_limit)
+        rates = native_bank.check_rates(rates)
+        return native_bank.NativeLocateBank(self._need("locator"), rates, capacity, max_channels, self.locator_precision, pad_limit)
 
     def open_segment_session(self, n: int = 1, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5,
                              sample_rate: int = 16000, channels: int = 1, capacity: int = 64):
@@ -321,6 +336,18 @@ class WaveVerify:
         push({slot: (x [n], gate [n])}), the 0 / 1 gate replacing the locator.  ring: closed segments the device holds per slot between reads."""
         return session.SegmentBank(self._need("detector"), self._need("locator"), capacity, pad_limit, threshold, min_on, min_gap_frames,
                                    min_len_frames, ring, gated, self.detector_precision, self.locator_precision, self.sample_rate)
+
+    def open_native_segment_bank(self, rates, max_channels: int = 2, capacity: int = 64, pad_limit: float = 1.5, threshold: float = 0.5,
+                                 min_on: float = 0.5, min_gap_frames: int = 2, min_len_frames: int = 5, ring: int = 64, gated: bool = False):
+        """native_bank.NativeSegmentBank: open_segment_bank for streams at their own rates (up to 8 `rates`) and channel counts (DESIGN.md section
+        7d-8): bank.open(sample_rate=, channels=) -> slot; bank.push({slot: x [C, n]}); poll(), open_segments() and close() as there, segment times
+        in seconds on the stream's own clock.  A gate has no native-rate form: gated=True is refused."""
+        if gated:
+            raise ValueError("a gate is given per 16 kHz sample; a bank at the streams' own rates takes none")
+        rates = native_bank.check_rates(rates)
+        return native_bank.NativeSegmentBank(self._need("detector"), self._need("locator"), rates, capacity, max_channels, pad_limit=pad_limit,
+                                             threshold=threshold, min_on=min_on, min_gap_frames=min_gap_frames, min_len_frames=min_len_frames,
+                                             ring=ring, precision=self.detector_precision, locator_precision=self.locator_precision)
 
     # ------------------------------------------------------------------ reference file API
     def embed(self, audio_path: Union[str, Path], watermark_id: Union[WatermarkID, str, int],

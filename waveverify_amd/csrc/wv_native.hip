@@ -143,25 +143,75 @@ struct SessionMono {
     }
 };
 
-__global__ __launch_bounds__(256) void native_session_down_kernel(const float* __restrict__ hist, int hcap, int hv, const float* __restrict__ x, int n,
-                                                                   const float* __restrict__ Kt, float* __restrict__ y, int n_out, int pad,
-                                                                   float* __restrict__ hist_out, int drop, int hv2, int tiles, int C, int orig, int nw,
-                                                                   int L) {
-    extern __shared__ float win[];
-    const int s = blockIdx.y, tid = threadIdx.x;
-    const SessionMono seq{hist + (size_t)s * hcap, x + (size_t)s * C * (size_t)n, hv, C, (long long)n};
-    if ((int)blockIdx.x >= tiles) {                                    // the next history: sequence samples [drop, drop + hv2)
-        const int j = ((int)blockIdx.x - tiles) * NATIVE_TILE + tid;
-        if (j < hv2) hist_out[(size_t)s * hcap + j] = seq((long long)drop + j);
+// One workgroup of the front stage for ONE stream, shared by the lockstep kernel and the bank kernel (which differ only in where a stream's
+// operands lie): block bx < tiles is the 256-output tile bx, the blocks from `tiles` on write the next history, sequence samples
+// [drop, drop + hv2).  y and hist_out are the stream's own rows.  Every thread of the workgroup must call it (it holds a barrier).
+__device__ __forceinline__ void native_down_stream(float* win, int bx, int tid, const SessionMono& seq, const float* __restrict__ Kt, float* __restrict__ y,
+                                                   int n_out, int pad, float* __restrict__ hist_out, int drop, int hv2, int tiles, int orig, int nw, int L) {
+    if (bx >= tiles) {                                                 // the next history: sequence samples [drop, drop + hv2)
+        const int j = (bx - tiles) * NATIVE_TILE + tid;
+        if (j < hv2) hist_out[j] = seq((long long)drop + j);
         return;
     }
-    const int m0 = blockIdx.x * NATIVE_TILE;
+    const int m0 = bx * NATIVE_TILE;
     const int n_lo = m0 / nw, cnt = min(NATIVE_TILE, n_out - m0), n_hi = (m0 + cnt - 1) / nw;
     const long long p_base = (long long)n_lo * orig - pad;
     const int wlen = (n_hi - n_lo) * orig + L;
     for (int i = tid; i < wlen; i += 256) win[i] = seq(p_base + i);
     __syncthreads();
-    if (tid < cnt) y[(size_t)s * n_out + m0 + tid] = native_chain(Kt, win, m0 + tid, n_lo, orig, nw, L);
+    if (tid < cnt) y[m0 + tid] = native_chain(Kt, win, m0 + tid, n_lo, orig, nw, L);
+}
+
+__global__ __launch_bounds__(256) void native_session_down_kernel(const float* __restrict__ hist, int hcap, int hv, const float* __restrict__ x, int n,
+                                                                   const float* __restrict__ Kt, float* __restrict__ y, int n_out, int pad,
+                                                                   float* __restrict__ hist_out, int drop, int hv2, int tiles, int C, int orig, int nw,
+                                                                   int L) {
+    extern __shared__ float win[];
+    const int s = blockIdx.y;
+    const SessionMono seq{hist + (size_t)s * hcap, x + (size_t)s * C * (size_t)n, hv, C, (long long)n};
+    native_down_stream(win, blockIdx.x, threadIdx.x, seq, Kt, y + (size_t)s * n_out, n_out, pad, hist_out + (size_t)s * hcap, drop, hv2, tiles, orig, nw, L);
+}
+
+// The back stage's operands for ONE stream: the residual sequence cat(rh[0 .. rv), rs[0 .. nr)) and the originals cat(pend[c][0 .. pv), x[c][0 .. n)),
+// channel c of the delay line pcap floats after channel c - 1, channel c of the new samples n floats after it.
+struct SessionBack {
+    const float* rh;
+    const float* rs;
+    const float* pend;
+    const float* x;
+    int rv, nr, pcap, pv, n;
+    __device__ float resid(long long p) const { return (p < 0 || p >= (long long)rv + nr) ? 0.f : p < rv ? rh[(size_t)p] : rs[(size_t)(p - rv)]; }
+    __device__ float orig_ch(int c, long long i) const {
+        return i < pv ? pend[(size_t)c * pcap + (size_t)i] : x[(size_t)c * (size_t)n + (size_t)(i - pv)];
+    }
+};
+
+// One workgroup of the back stage for ONE stream, shared like native_down_stream: blocks [0, tiles) are output tiles (out: the stream's C rows of
+// k floats), [tiles, tiles + rblocks) write the next residual history, the rest the next delay line (pend_out: the stream's C rows of pcap floats).
+__device__ __forceinline__ void native_up_add_stream(float* win, int bx, int tid, const SessionBack& b, const float* __restrict__ Kt, float* __restrict__ out,
+                                                     int k, int pad, float gain, float* __restrict__ pend_out, int pv2, float* __restrict__ rhist_out, int rdrop,
+                                                     int rv2, int tiles, int rblocks, int C, int orig, int nw, int L) {
+    if (bx >= tiles + rblocks) {                                       // the next delay line: the originals not yet emitted, [k, k + pv2)
+        const int j = (bx - tiles - rblocks) * NATIVE_TILE + tid;
+        if (j < pv2)
+            for (int c = 0; c < C; ++c) pend_out[(size_t)c * b.pcap + j] = b.orig_ch(c, (long long)k + j);
+        return;
+    }
+    if (bx >= tiles) {                                                 // the next residual history
+        const int j = (bx - tiles) * NATIVE_TILE + tid;
+        if (j < rv2) rhist_out[j] = b.resid((long long)rdrop + j);
+        return;
+    }
+    const int m0 = bx * NATIVE_TILE;
+    const int n_lo = m0 / nw, cnt = min(NATIVE_TILE, k - m0), n_hi = (m0 + cnt - 1) / nw;
+    const long long p_base = (long long)n_lo * orig - pad;
+    const int wlen = (n_hi - n_lo) * orig + L;
+    for (int i = tid; i < wlen; i += 256) win[i] = b.resid(p_base + i);
+    __syncthreads();
+    if (tid >= cnt) return;
+    const int m = m0 + tid;
+    const float gu = gain * native_chain(Kt, win, m, n_lo, orig, nw, L);
+    for (int c = 0; c < C; ++c) out[(size_t)c * (size_t)k + m] = b.orig_ch(c, m) + gu;
 }
 
 __global__ __launch_bounds__(256) void native_session_up_add_kernel(const float* __restrict__ rhist, int rcap, int rv, const float* __restrict__ r, int nr,
@@ -170,37 +220,10 @@ __global__ __launch_bounds__(256) void native_session_up_add_kernel(const float*
                                                                      float* __restrict__ pend_out, int pv2, float* __restrict__ rhist_out, int rdrop, int rv2,
                                                                      int tiles, int rblocks, int C, int orig, int nw, int L) {
     extern __shared__ float win[];
-    const int s = blockIdx.y, tid = threadIdx.x, bx = blockIdx.x;
-    const float* rh = rhist + (size_t)s * rcap;
-    const float* rs = r + (size_t)s * (size_t)nr;
-    const long long r_end = (long long)rv + nr;
-    auto resid = [&](long long p) -> float { return (p < 0 || p >= r_end) ? 0.f : p < rv ? rh[(size_t)p] : rs[(size_t)(p - rv)]; };
-    // sample i of channel c of cat(pending[0 .. pv), x[0 .. n))
-    auto orig_ch = [&](int c, long long i) -> float {
-        const size_t row = (size_t)s * C + c;
-        return i < pv ? pend[row * pcap + (size_t)i] : x[row * (size_t)n + (size_t)(i - pv)];
-    };
-    if (bx >= tiles + rblocks) {                                       // the next delay line: the originals not yet emitted, [k, k + pv2)
-        const int j = (bx - tiles - rblocks) * NATIVE_TILE + tid;
-        if (j < pv2)
-            for (int c = 0; c < C; ++c) pend_out[((size_t)s * C + c) * pcap + j] = orig_ch(c, (long long)k + j);
-        return;
-    }
-    if (bx >= tiles) {                                                 // the next residual history
-        const int j = (bx - tiles) * NATIVE_TILE + tid;
-        if (j < rv2) rhist_out[(size_t)s * rcap + j] = resid((long long)rdrop + j);
-        return;
-    }
-    const int m0 = bx * NATIVE_TILE;
-    const int n_lo = m0 / nw, cnt = min(NATIVE_TILE, k - m0), n_hi = (m0 + cnt - 1) / nw;
-    const long long p_base = (long long)n_lo * orig - pad;
-    const int wlen = (n_hi - n_lo) * orig + L;
-    for (int i = tid; i < wlen; i += 256) win[i] = resid(p_base + i);
-    __syncthreads();
-    if (tid >= cnt) return;
-    const int m = m0 + tid;
-    const float gu = gain * native_chain(Kt, win, m, n_lo, orig, nw, L);
-    for (int c = 0; c < C; ++c) out[((size_t)s * C + c) * (size_t)k + m] = orig_ch(c, m) + gu;
+    const size_t s = blockIdx.y;
+    const SessionBack b{rhist + s * rcap, r + s * (size_t)nr, pend + s * C * pcap, x + s * C * (size_t)n, rv, nr, pcap, pv, n};
+    native_up_add_stream(win, blockIdx.x, threadIdx.x, b, Kt, out + s * C * (size_t)k, k, pad, gain, pend_out + s * C * pcap, pv2, rhist_out + s * rcap, rdrop,
+                         rv2, tiles, rblocks, C, orig, nw, L);
 }
 
 }  // namespace wv
@@ -258,6 +281,175 @@ extern "C" int wv_native_session_up_add(const float* rhist, int rcap, int rv, co
     if (blocks == 0) return WV_OK;
     hipLaunchKernelGGL(wv::native_session_up_add_kernel, dim3(blocks, S), dim3(256), smem, (hipStream_t)stream, rhist, rcap, rv, r, nr, kernels_t, pend, pcap,
                        pv, x, n, out, k, pad, gain, pend_out, (int)pv2, rhist_out, rdrop, rv2, tiles, rblocks, C, orig, nw, L);
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
+
+// ---- native-rate session banks ---------------------------------------------------------------------------------------
+// The same two stages for the slots of a bank, each slot with its own rate, channel count, packet length and resampler state: one workgroup row
+// (blockIdx.y) per descriptor, the per-stream bodies above.  A slot's state is ping-pong: the descriptor's `half` names the half a launch reads,
+// the launch writes the other, so no byte is read and written by one launch and the blocks of a row need no order among themselves.  The rate
+// table travels in the kernel's arguments; a descriptor names a rate by index.
+namespace wv {
+
+struct NativeRates {
+    wv_native_rate r[WV_NATIVE_BANK_MAX_RATES];
+};
+
+constexpr int64_t NATIVE_BANK_MAX_COUNT = 2147483647 - NATIVE_TILE;    // per-row sample counts stay ints, tile arithmetic included
+
+__device__ __forceinline__ int native_tiles(int v) { return v / NATIVE_TILE + (v % NATIVE_TILE != 0); }
+
+// 0 <= valid <= cap, and the next state a suffix of the sequence that fits: session_roll_ok on a descriptor's 64-bit fields.
+__device__ __forceinline__ bool native_roll_ok(int64_t cap, int64_t valid, int64_t fresh, int64_t drop, int64_t next) {
+    return valid >= 0 && valid <= cap && fresh >= 0 && fresh <= NATIVE_BANK_MAX_COUNT && drop >= 0 && next >= 0 && next <= cap && drop <= valid + fresh &&
+           drop + next == valid + fresh;
+}
+
+// off >= 0 and off + rows * len <= total, with rows <= 64 and len <= NATIVE_BANK_MAX_COUNT (no overflow)
+__device__ __forceinline__ bool native_range_ok(int64_t off, int64_t rows, int64_t len, int64_t total) {
+    return off >= 0 && off <= total && rows * len <= total - off;
+}
+
+// native_session_check's output count bound: no more than (ceil((pad + sequence) / orig) + 1) * nw
+__device__ __forceinline__ bool native_count_ok(int64_t cnt, int64_t seq, int64_t pad, int orig, int nw) {
+    return cnt >= 0 && cnt <= NATIVE_BANK_MAX_COUNT && cnt <= ((seq + pad + orig - 1) / orig + 1) * (int64_t)nw;
+}
+
+// One descriptor row of wv_native_bank_down, checked the same way by every workgroup that serves it: a row that breaks the contract is skipped
+// whole (native_bank.native_bank_down_row_ok states the same rule).
+struct NativeDownRow {
+    int64_t slot, rate, C, hv, x_off, n, y_off, n_out, pad, drop, hv2, half;
+    bool ok;
+};
+
+__device__ __forceinline__ NativeDownRow native_bank_down_row(const int64_t* __restrict__ desc, int p, const NativeRates& rates, int n_rates, int capacity,
+                                                              int hcap, int64_t n_x, int64_t n_y) {
+    const int64_t* d = desc + 12 * (size_t)p;
+    NativeDownRow r = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], false};
+    if (r.slot < 0 || r.slot >= capacity || r.rate < 0 || r.rate >= n_rates || r.C < 1 || r.C > 64 || (r.half != 0 && r.half != 1)) return r;
+    if (!native_roll_ok(hcap, r.hv, r.n, r.drop, r.hv2)) return r;
+    const wv_native_rate& t = rates.r[r.rate];
+    r.ok = r.pad >= 0 && r.pad <= t.width && native_count_ok(r.n_out, r.hv + r.n, r.pad, t.orig, t.nw) && native_range_ok(r.x_off, r.C, r.n, n_x) &&
+           native_range_ok(r.y_off, 1, r.n_out, n_y);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void native_bank_down_kernel(float* hist, int capacity, int hcap, const float* __restrict__ x, int64_t n_x, NativeRates rates,
+                                                                int n_rates, const int64_t* __restrict__ desc, float* __restrict__ y, int64_t n_y) {
+    extern __shared__ float win[];
+    const NativeDownRow r = native_bank_down_row(desc, blockIdx.y, rates, n_rates, capacity, hcap, n_x, n_y);
+    if (!r.ok) return;
+    const int n_out = (int)r.n_out, hv2 = (int)r.hv2, tiles = native_tiles(n_out);
+    if ((int64_t)blockIdx.x >= (int64_t)tiles + native_tiles(hv2)) return;        // the grid is as wide as the tick's longest row
+    const wv_native_rate& t = rates.r[r.rate];
+    float* h = hist + (size_t)r.slot * 2 * hcap;
+    const SessionMono seq{h + (size_t)r.half * hcap, x + r.x_off, (int)r.hv, (int)r.C, r.n};
+    native_down_stream(win, blockIdx.x, threadIdx.x, seq, t.kernels_t, y + r.y_off, n_out, (int)r.pad, h + (size_t)(1 - r.half) * hcap, (int)r.drop, hv2,
+                       tiles, t.orig, t.nw, t.L);
+}
+
+// One descriptor row of wv_native_bank_up_add (native_bank.native_bank_up_row_ok states the same rule).
+struct NativeUpRow {
+    int64_t slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half, pv2;
+    bool ok;
+};
+
+__device__ __forceinline__ NativeUpRow native_bank_up_row(const int64_t* __restrict__ desc, int p, const NativeRates& rates, int n_rates, int capacity, int rcap,
+                                                          int pcap, int Cmax, int64_t n_r, int64_t n_x, int64_t n_out) {
+    const int64_t* d = desc + 15 * (size_t)p;
+    NativeUpRow r = {d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], d[8], d[9], d[10], d[11], d[12], d[13], d[14], 0, false};
+    if (r.slot < 0 || r.slot >= capacity || r.rate < 0 || r.rate >= n_rates || r.C < 1 || r.C > 64 || r.C > Cmax || (r.half != 0 && r.half != 1)) return r;
+    if (!native_roll_ok(rcap, r.rv, r.nr, r.rdrop, r.rv2)) return r;
+    if (r.pv < 0 || r.pv > pcap || r.n < 0 || r.n > NATIVE_BANK_MAX_COUNT || r.k < 0 || r.k > r.pv + r.n) return r;
+    r.pv2 = r.pv + r.n - r.k;
+    const wv_native_rate& t = rates.r[r.rate];
+    r.ok = r.pv2 <= pcap && r.pad >= 0 && r.pad <= t.width && native_count_ok(r.k, r.rv + r.nr, r.pad, t.orig, t.nw) &&
+           native_range_ok(r.r_off, 1, r.nr, n_r) && native_range_ok(r.x_off, r.C, r.n, n_x) && native_range_ok(r.out_off, r.C, r.k, n_out);
+    return r;
+}
+
+__global__ __launch_bounds__(256) void native_bank_up_add_kernel(float* rhist, int rcap, float* pend, int pcap, int Cmax, int capacity,
+                                                                  const float* __restrict__ res, int64_t n_r, const float* __restrict__ x, int64_t n_x,
+                                                                  NativeRates rates, int n_rates, const int64_t* __restrict__ desc,
+                                                                  const float* __restrict__ gain, float* __restrict__ out, int64_t n_out) {
+    extern __shared__ float win[];
+    const NativeUpRow r = native_bank_up_row(desc, blockIdx.y, rates, n_rates, capacity, rcap, pcap, Cmax, n_r, n_x, n_out);
+    if (!r.ok) return;
+    const int k = (int)r.k, rv2 = (int)r.rv2, pv2 = (int)r.pv2, tiles = native_tiles(k), rblocks = native_tiles(rv2);
+    if ((int64_t)blockIdx.x >= (int64_t)tiles + rblocks + native_tiles(pv2)) return;
+    const wv_native_rate& t = rates.r[r.rate];
+    float* rh = rhist + (size_t)r.slot * 2 * rcap;
+    float* pd = pend + (size_t)r.slot * 2 * Cmax * pcap;
+    const size_t cur = (size_t)r.half, nxt = (size_t)(1 - r.half);
+    const SessionBack b{rh + cur * rcap, res + r.r_off, pd + cur * Cmax * pcap, x + r.x_off, (int)r.rv, (int)r.nr, pcap, (int)r.pv, (int)r.n};
+    native_up_add_stream(win, blockIdx.x, threadIdx.x, b, t.kernels_t, out + r.out_off, k, (int)r.pad, gain[blockIdx.y], pd + nxt * Cmax * pcap, pv2,
+                         rh + nxt * rcap, (int)r.rdrop, rv2, tiles, rblocks, (int)r.C, t.orig, t.nw, t.L);
+}
+
+}  // namespace wv
+
+static bool native_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+    const uintptr_t p = (uintptr_t)a, q = (uintptr_t)b;
+    return a && b && a_bytes && b_bytes && p < q + b_bytes && q < p + a_bytes;
+}
+
+// The refusals both bank calls share: the counts, and the rate table, which is copied into `out`.  -> WV_OK, or the code already reported.
+static int native_bank_check(const char* who, int capacity, int P, int blocks, const wv_native_rate* rates, int n_rates, wv::NativeRates* out, size_t* smem) {
+    const std::string w(who);
+    if (capacity < 1 || capacity > WV_BANK_MAX_SLOTS) return fail(WV_EINVAL, w + ": capacity outside [1, " WV_STR(WV_BANK_MAX_SLOTS) "]");
+    if (P < 0 || P > 65535) return fail(WV_EINVAL, w + ": P outside [0, 65535]");
+    if (blocks < 0 || blocks > WV_NATIVE_BANK_MAX_BLOCKS) return fail(WV_EINVAL, w + ": blocks outside [0, " WV_STR(WV_NATIVE_BANK_MAX_BLOCKS) "]");
+    if (!rates || n_rates < 1 || n_rates > WV_NATIVE_BANK_MAX_RATES) return fail(WV_EINVAL, w + ": null rates, or n_rates outside [1, " WV_STR(WV_NATIVE_BANK_MAX_RATES) "]");
+    long long bytes = 0;
+    *out = wv::NativeRates{};
+    for (int i = 0; i < n_rates; ++i) {
+        const wv_native_rate& t = rates[i];
+        if (!t.kernels_t || t.orig < 1 || t.nw < 1 || t.L < 1 || t.width < 0) return fail(WV_EINVAL, w + ": rate " + std::to_string(i) + ": null table, orig, nw or L < 1, or width < 0");
+        const long long b = wv::native_window(t.orig, t.nw, t.L) * (long long)sizeof(float);
+        if (b > (long long)wv::NATIVE_LDS_BYTES) return fail(WV_EINVAL, w + ": rate " + std::to_string(i) + ": the input window of a 256-output tile (" + std::to_string(b) + " bytes) exceeds 64 KB of LDS");
+        bytes = b > bytes ? b : bytes;
+        out->r[i] = t;
+    }
+    *smem = (size_t)bytes;
+    return WV_OK;
+}
+
+extern "C" int wv_native_bank_down(float* hist, int capacity, int hcap, const float* x, int64_t n_x, const wv_native_rate* rates, int n_rates,
+                                   const int64_t* desc, int P, int blocks, float* y, int64_t n_y, void* stream) {
+    const char* who = "wv_native_bank_down";
+    wv::NativeRates tab;
+    size_t smem = 0;
+    if (int rc = native_bank_check(who, capacity, P, blocks, rates, n_rates, &tab, &smem)) return rc;
+    if (hcap < 1 || n_x < 0 || n_y < 0) return fail(WV_EINVAL, std::string(who) + ": hcap < 1, n_x < 0 or n_y < 0");
+    if (!hist || (P > 0 && !desc) || (n_x > 0 && !x) || (n_y > 0 && !y)) return fail(WV_EINVAL, std::string(who) + ": null hist, descriptors without desc, samples without x, or outputs without y");
+    const size_t hb = (size_t)capacity * 2 * hcap * 4, xb = (size_t)n_x * 4, yb = (size_t)n_y * 4;
+    if (native_overlap(hist, hb, x, xb) || native_overlap(hist, hb, y, yb) || native_overlap(x, xb, y, yb)) return fail(WV_EINVAL, std::string(who) + ": hist, x and y must not overlap");
+    if (P == 0 || blocks == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::native_bank_down_kernel, dim3(blocks, P), dim3(256), smem, (hipStream_t)stream, hist, capacity, hcap, x, n_x, tab, n_rates, desc, y,
+                       n_y);
+    WV_HIP_TRY(hipGetLastError());
+    return WV_OK;
+}
+
+extern "C" int wv_native_bank_up_add(float* rhist, int rcap, float* pend, int pcap, int Cmax, int capacity, const float* r, int64_t n_r, const float* x,
+                                     int64_t n_x, const wv_native_rate* rates, int n_rates, const int64_t* desc, const float* gain, int P, int blocks,
+                                     float* out, int64_t n_out, void* stream) {
+    const char* who = "wv_native_bank_up_add";
+    wv::NativeRates tab;
+    size_t smem = 0;
+    if (int rc = native_bank_check(who, capacity, P, blocks, rates, n_rates, &tab, &smem)) return rc;
+    if (rcap < 1 || pcap < 1 || Cmax < 1 || Cmax > 64 || n_r < 0 || n_x < 0 || n_out < 0) return fail(WV_EINVAL, std::string(who) + ": rcap or pcap < 1, Cmax outside [1, 64], or n_r, n_x or n_out < 0");
+    if (!rhist || !pend || (P > 0 && (!desc || !gain)) || (n_r > 0 && !r) || (n_x > 0 && !x) || (n_out > 0 && !out))
+        return fail(WV_EINVAL, std::string(who) + ": null rhist or pend, descriptors without desc or gain, or a positive count without its arena (r, x, out)");
+    const size_t hb = (size_t)capacity * 2 * rcap * 4, pb = (size_t)capacity * 2 * Cmax * pcap * 4, rb = (size_t)n_r * 4, xb = (size_t)n_x * 4, ob = (size_t)n_out * 4;
+    if (native_overlap(rhist, hb, pend, pb) || native_overlap(rhist, hb, r, rb) || native_overlap(rhist, hb, x, xb) || native_overlap(rhist, hb, out, ob) ||
+        native_overlap(pend, pb, r, rb) || native_overlap(pend, pb, x, xb) || native_overlap(pend, pb, out, ob) || native_overlap(r, rb, out, ob) ||
+        native_overlap(x, xb, out, ob))
+        return fail(WV_EINVAL, std::string(who) + ": rhist, pend, r, x and out must not overlap (r and x are only read and may)");
+    if (P == 0 || blocks == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::native_bank_up_add_kernel, dim3(blocks, P), dim3(256), smem, (hipStream_t)stream, rhist, rcap, pend, pcap, Cmax, capacity, r, n_r, x,
+                       n_x, tab, n_rates, desc, gain, out, n_out);
     WV_HIP_TRY(hipGetLastError());
     return WV_OK;
 }

@@ -1,0 +1,509 @@
+"""Session banks at the streams' own sample rates and channel counts.
+
+`session.py`'s banks let 16 kHz mono streams open, push and close on their own; `native_session.py` lets streams in lockstep keep their rate and
+channels.  Here every slot of a bank has its OWN rate (one of the bank's `rates`), channel count, packet length and resampler state:
+
+    front stage   every pushed slot's new samples -> f32 channel mean -> 16 kHz, ONE launch per tick (wv_native_bank_down)
+    inner bank    the 16 kHz bank of session.py (the generator returning its residual alone)
+    back stage    every slot's residual -> its own rate, strength times it added to its delayed originals, ONE launch (wv_native_bank_up_add)
+
+whatever the mix of rates on the tick.  The integer plans are native_session's StagePlan / EmbedPlan, one per slot; a tick turns them into
+descriptor rows.  The stages' state is ping-pong per slot: a row's `half` names the half holding the slot's state, the launch writes the next
+state into the other, and the bank flips the bit of every slot the tick named.  The Host* classes run the state machine on numpy arrays (any
+float dtype) through numpy_bank_down / numpy_bank_up_add, which restate the kernels row rule included; the Native* classes bind it to the HIP
+entry points and the HipNet banks, where there is no CPU fallback."""
+from __future__ import annotations
+
+import numpy as np
+
+from . import native
+from .native import MODEL_RATE
+from .native_session import EmbedPlan, EmbedTick, StagePlan, StageTick, numpy_down, numpy_up_add
+from .session import plan_tick
+
+MAX_RATES = 8                                        # WV_NATIVE_BANK_MAX_RATES
+MAX_COUNT = 2 ** 31 - 257                            # the largest sample count of a descriptor row
+TILE = 256
+
+
+def _tiles(v: int) -> int:
+    return -(-int(v) // TILE)
+
+
+def check_rates(rates) -> tuple:
+    """-> the bank's rates as a tuple of distinct ints; ValueError for none, more than 8, a repeat or a rate native.check_rate refuses."""
+    rates = tuple(int(r) for r in rates)
+    if not 1 <= len(rates) <= MAX_RATES:
+        raise ValueError(f"a native-rate bank serves 1 to {MAX_RATES} distinct sample rates, got {len(rates)}")
+    if len(set(rates)) != len(rates):
+        raise ValueError(f"the rates of a bank must be distinct, got {rates}")
+    for r in rates:
+        native.check_rate(r)
+    return rates
+
+
+# ---------------------------------------------------------------------------------------------------------------- the row rule
+def _roll_ok(cap: int, valid: int, fresh: int, drop: int, nxt: int) -> bool:
+    return 0 <= valid <= cap and 0 <= fresh <= MAX_COUNT and drop >= 0 and 0 <= nxt <= cap and drop + nxt == valid + fresh
+
+
+def _count_ok(cnt: int, seq: int, pad: int, orig: int, nw: int) -> bool:
+    return 0 <= cnt <= MAX_COUNT and cnt <= (-(-(seq + pad) // orig) + 1) * nw
+
+
+def _range_ok(off: int, rows: int, length: int, total: int) -> bool:
+    return 0 <= off and off + rows * length <= total
+
+
+def native_bank_down_row_ok(row, capacity: int, hcap: int, n_x: int, n_y: int, rates) -> bool:
+    """Whether wv_native_bank_down serves a descriptor row (it skips any other whole).  rates: [(orig, nw, L, width)] of the call's table."""
+    slot, rate, C, hv, x_off, n, y_off, n_out, pad, drop, hv2, half = (int(v) for v in row)
+    if not (0 <= slot < capacity and 0 <= rate < len(rates) and 1 <= C <= 64 and half in (0, 1)):
+        return False
+    orig, nw, _, width = rates[rate]
+    return (_roll_ok(hcap, hv, n, drop, hv2) and 0 <= pad <= width and _count_ok(n_out, hv + n, pad, orig, nw) and _range_ok(x_off, C, n, n_x)
+            and _range_ok(y_off, 1, n_out, n_y))
+
+
+def native_bank_up_row_ok(row, capacity: int, rcap: int, pcap: int, Cmax: int, n_r: int, n_x: int, n_out: int, rates) -> bool:
+    """Whether wv_native_bank_up_add serves a descriptor row (it skips any other whole)."""
+    slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half = (int(v) for v in row)
+    if not (0 <= slot < capacity and 0 <= rate < len(rates) and 1 <= C <= min(64, Cmax) and half in (0, 1)):
+        return False
+    orig, nw, _, width = rates[rate]
+    return (_roll_ok(rcap, rv, nr, rdrop, rv2) and 0 <= pv <= pcap and 0 <= n <= MAX_COUNT and k >= 0 and 0 <= pv + n - k <= pcap
+            and 0 <= pad <= width and _count_ok(k, rv + nr, pad, orig, nw) and _range_ok(r_off, 1, nr, n_r) and _range_ok(x_off, C, n, n_x)
+            and _range_ok(out_off, C, k, n_out))
+
+
+def down_row(slot: int, rate: int, C: int, t: StageTick, x_off: int, y_off: int, half: int) -> list:
+    return [slot, rate, C, t.hv, x_off, t.n, y_off, t.n_out, t.pad, t.drop, t.hv2, half]
+
+
+def up_row(slot: int, rate: int, C: int, t: EmbedTick, r_off: int, x_off: int, n: int, out_off: int, half: int) -> list:
+    b = t.back
+    return [slot, rate, C, b.hv, r_off, b.n, x_off, n, out_off, b.n_out, b.pad, b.drop, b.hv2, t.pv, half]
+
+
+def down_blocks(desc) -> int:
+    """The x-extent wv_native_bank_down needs for these rows: the largest tile-plus-history-block count."""
+    return max((_tiles(r[7]) + _tiles(r[10]) for r in np.asarray(desc).reshape(-1, 12)), default=0)
+
+
+def up_blocks(desc) -> int:
+    return max((_tiles(r[9]) + _tiles(r[12]) + _tiles(r[13] + r[7] - r[9]) for r in np.asarray(desc).reshape(-1, 15)), default=0)
+
+
+def _geometry(tables) -> list:
+    return [tuple(int(v) for v in t[1:]) for t in tables]
+
+
+# ---------------------------------------------------------------------------------------------------------------- the stages on host arrays
+def numpy_bank_down(hist: np.ndarray, x: np.ndarray, desc: np.ndarray, tables, n_y: int) -> np.ndarray:
+    """Reference of wv_native_bank_down: hist [capacity, 2, hcap] (the half a row does not name is written, only [0, hv2)), x the packed new
+    samples, tables [native.transposed_table(...)] -> y [n_y] (zeros where no served row writes; the kernel leaves those alone)."""
+    capacity, _, hcap = hist.shape
+    y = np.zeros(n_y, hist.dtype)
+    geo = _geometry(tables)
+    for row in np.asarray(desc).reshape(-1, 12):
+        if not native_bank_down_row_ok(row, capacity, hcap, int(x.shape[0]), n_y, geo):
+            continue
+        slot, rate, C, hv, x_off, n, y_off, n_out, pad, drop, hv2, half = (int(v) for v in row)
+        xs = np.asarray(x[x_off:x_off + C * n], hist.dtype).reshape(1, C, n)
+        out, nxt = numpy_down(hist[slot, half][None], xs, StageTick(hv, n, pad, n_out, drop, hv2), tables[rate])
+        y[y_off:y_off + n_out] = out[0]
+        hist[slot, 1 - half, :hv2] = nxt[0, :hv2]
+    return y
+
+
+def numpy_bank_up_add(rhist: np.ndarray, pend: np.ndarray, r: np.ndarray, x: np.ndarray, desc: np.ndarray, gain: np.ndarray, tables,
+                      n_out: int) -> np.ndarray:
+    """Reference of wv_native_bank_up_add: rhist [capacity, 2, rcap], pend [capacity, 2, Cmax, pcap], r and x the packed residuals and new
+    originals, gain [P] -> out [n_out]."""
+    capacity, _, rcap = rhist.shape
+    Cmax, pcap = pend.shape[2:]
+    out = np.zeros(n_out, pend.dtype)
+    geo = _geometry(tables)
+    for p, row in enumerate(np.asarray(desc).reshape(-1, 15)):
+        if not native_bank_up_row_ok(row, capacity, rcap, pcap, Cmax, int(r.shape[0]), int(x.shape[0]), n_out, geo):
+            continue
+        slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half = (int(v) for v in row)
+        pv2 = pv + n - k
+        t = EmbedTick(None, (), nr, StageTick(rv, nr, pad, k, rdrop, rv2), pv, pv2)
+        xs = np.asarray(x[x_off:x_off + C * n], pend.dtype).reshape(1, C, n)
+        o, pnxt, rnxt = numpy_up_add(rhist[slot, half][None], np.asarray(r[r_off:r_off + nr])[None], pend[slot, half, :C][None], xs, t, tables[rate],
+                                     gain[p])
+        out[out_off:out_off + C * k] = o.reshape(-1)
+        pend[slot, 1 - half, :C, :pv2] = pnxt[0, :, :pv2]
+        rhist[slot, 1 - half, :rv2] = rnxt[0, :rv2]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- the banks
+class _BankStages:
+    """The two stages and their state on numpy arrays of `dtype`; _HipBankStages states the same on the device."""
+    dtype = np.float32
+
+    def _tables(self):
+        return ([native.transposed_table(r, MODEL_RATE) for r in self.rates], [native.transposed_table(MODEL_RATE, r) for r in self.rates])
+
+    def _zeros(self, *shape):
+        return np.zeros(shape, self.dtype)
+
+    def _flat(self, x):
+        return np.asarray(x, self.dtype).reshape(-1)
+
+    def _cat(self, parts):
+        return np.concatenate(parts) if parts else self._zeros(0)
+
+    def _upload(self, sections: list) -> dict:
+        return dict(sections)
+
+    def _down(self, x, tabs: dict, n_y: int, blocks: int):
+        return numpy_bank_down(self._hist, x, tabs["front"], self._ftabs, n_y)
+
+    def _up_add(self, r, x, tabs: dict, n_out: int, blocks: int):
+        return numpy_bank_up_add(self._rhist, self._pend, r, x, tabs["back"], tabs["gain"], self._btabs, n_out)
+
+
+class _HipBankStages(_BankStages):
+    """The stages as one launch each on the inner bank's device; the rate tables are native.tables' cached device tensors."""
+
+    def _tables(self):
+        from . import _lib
+        pairs = [native.tables(r, self.device) for r in self.rates]
+        front, back = [p[0] for p in pairs], [p[1] for p in pairs]
+        self._frates = (_lib.WvNativeRate * len(front))(*[_lib.WvNativeRate(t[0].data_ptr(), *t[1:]) for t in front])
+        self._brates = (_lib.WvNativeRate * len(back))(*[_lib.WvNativeRate(t[0].data_ptr(), *t[1:]) for t in back])
+        return front, back
+
+    def _zeros(self, *shape):
+        import torch
+        return torch.zeros(shape, dtype=torch.float32, device=self.device)
+
+    def _flat(self, x):
+        import torch
+        return x.to(self.device, torch.float32).reshape(-1)
+
+    def _cat(self, parts):
+        import torch
+        return torch.cat(parts) if parts else self._zeros(0)
+
+    def _upload(self, sections: list) -> dict:
+        return self.inner._upload(sections)
+
+    def _down(self, x, tabs: dict, n_y: int, blocks: int):
+        import torch
+        from . import _lib
+        y = torch.empty(n_y, dtype=torch.float32, device=self.device)
+        desc = tabs["front"]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().wv_native_bank_down(
+                self._hist.data_ptr(), self.capacity, self._hist.shape[2], x.data_ptr() if x.numel() else None, x.numel(), self._frates,
+                len(self.rates), desc.data_ptr(), desc.shape[0], blocks, y.data_ptr() if n_y else None, n_y, _lib.stream()), "wv_native_bank_down")
+        return y
+
+    def _up_add(self, r, x, tabs: dict, n_out: int, blocks: int):
+        import torch
+        from . import _lib
+        out = torch.empty(n_out, dtype=torch.float32, device=self.device)
+        desc = tabs["back"]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().wv_native_bank_up_add(
+                self._rhist.data_ptr(), self._rhist.shape[2], self._pend.data_ptr(), self._pend.shape[3], self._pend.shape[2], self.capacity,
+                r.data_ptr() if r.numel() else None, r.numel(), x.data_ptr() if x.numel() else None, x.numel(), self._brates, len(self.rates),
+                desc.data_ptr(), tabs["gain"].data_ptr(), desc.shape[0], blocks, out.data_ptr() if n_out else None, n_out, _lib.stream()),
+                "wv_native_bank_up_add")
+        return out
+
+
+class HostFrontBank(_BankStages):
+    """The front stage in front of a 16 kHz bank `inner` (session.StreamBank or a subclass): open(*inner's arguments, sample_rate, channels) ->
+    slot; push({slot: x [C, n]}) at each slot's own rate -> inner.push of the 16 kHz samples that became final, per slot (a slot whose stage
+    emitted nothing still pushes an empty array, so the result has every pushed slot); close(slot) -> the rest, then inner.close.  Whatever the
+    inner bank returns stays on the 16 kHz time line."""
+
+    def __init__(self, inner, rates, max_channels: int = 2, dtype=None):
+        self.rates = check_rates(rates)
+        if not 1 <= int(max_channels) <= 64:
+            raise ValueError(f"max_channels must be within [1, 64], got {max_channels}")
+        self.inner, self.capacity, self.max_channels = inner, inner.capacity, int(max_channels)
+        if dtype is not None:
+            self.dtype = dtype
+        self._ftabs, self._btabs = self._tables()
+        self._is_open = [False] * self.capacity
+        self._plans = [None] * self.capacity
+        self._rate = [0] * self.capacity
+        self._chan = [1] * self.capacity
+        self._half = [0] * self.capacity
+        self.stats = {"ticks": 0, "uploads": 0, "front_launches": 0, "back_launches": 0}
+        self._new_state()
+
+    # ---- state: allocated once, sized by the largest table of the bank's rates
+    def _new_state(self) -> None:
+        self._hist = self._zeros(self.capacity, 2, max(t[3] for t in self._ftabs))
+
+    def _new_plan(self, sample_rate: int):
+        return StagePlan(*native.table_geometry(sample_rate, MODEL_RATE))
+
+    # ---- slots
+    def open(self, *args, sample_rate: int = MODEL_RATE, channels: int = 1) -> int:
+        """open(*the inner bank's arguments, sample_rate=, channels=) -> the lowest free slot, a stream of `channels` channels at `sample_rate`
+        (one of the bank's rates) starting from nothing: its plan is new, so whatever state the slot's last stream left in either half is never
+        read.  Refusals come before any state changes."""
+        if int(sample_rate) not in self.rates:
+            raise ValueError(f"sample rate {sample_rate} Hz is not one of this bank's rates {self.rates}")
+        if not 1 <= int(channels) <= self.max_channels:
+            raise ValueError(f"channels must be within [1, {self.max_channels}], got {channels}")
+        plan = self._new_plan(int(sample_rate))
+        slot = self.inner.open(*args)                                      # RuntimeError when every slot is open
+        assert slot == self._is_open.index(False), (slot, self._is_open)   # the two lowest-free-slot rules coincide
+        self._is_open[slot], self._plans[slot] = True, plan
+        self._rate[slot], self._chan[slot] = self.rates.index(int(sample_rate)), int(channels)
+        return slot
+
+    def open_slots(self) -> list:
+        return [s for s, taken in enumerate(self._is_open) if taken]
+
+    def _check_slot(self, slot) -> None:
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.capacity or not self._is_open[slot]:
+            raise ValueError(f"slot {slot!r} is not open")
+
+    def sample_rate(self, slot: int) -> int:
+        self._check_slot(slot)
+        return self.rates[self._rate[slot]]
+
+    def channels(self, slot: int) -> int:
+        self._check_slot(slot)
+        return self._chan[slot]
+
+    def samples_in(self, slot: int) -> int:
+        """Samples the slot's stream has pushed, at its own rate."""
+        self._check_slot(slot)
+        return self._plans[slot].t_in
+
+    # ---- ticks
+    def _checked(self, items: dict) -> dict:
+        for slot, x in items.items():
+            self._check_slot(slot)
+            if len(x.shape) != 2 or x.shape[0] != self._chan[slot]:
+                raise ValueError(f"slot {slot}: expected new samples of shape [{self._chan[slot]}, n], got {tuple(x.shape)}")
+        return {s: items[s] for s in sorted(items)}
+
+    def _packed(self, ticks: dict, count) -> tuple:
+        """-> ({slot: offset}, total) of the tick's slots packed one after another, count(slot, tick) floats each."""
+        off, total = {}, 0
+        for s, t in ticks.items():
+            off[s] = total
+            total += count(s, t)
+        return off, total
+
+    def _front_tick(self, xs: dict, ticks: dict, extra=()):
+        """One upload and one front launch for the tick's slots (ticks {slot: StageTick}) -> (the packed x, {slot: its 16 kHz samples, a view
+        of the tick's y arena}, the uploaded tables).  extra: further sections of the same upload (the back stage's)."""
+        self.stats["ticks"] += 1
+        x_off, _ = self._packed(ticks, lambda s, t: self._chan[s] * t.n)
+        y_off, n_y = self._packed(ticks, lambda s, t: t.n_out)
+        front = np.array([down_row(s, self._rate[s], self._chan[s], t, x_off[s], y_off[s], self._half[s]) for s, t in ticks.items()],
+                         np.int64).reshape(-1, 12)
+        x = self._cat([self._flat(xs[s]) for s in ticks if ticks[s].n])
+        tabs = self._upload([("front", front)] + list(extra))
+        self.stats["uploads"] += 1
+        y = self._down(x, tabs, n_y, down_blocks(front))
+        self.stats["front_launches"] += 1
+        for s in ticks:
+            self._half[s] ^= 1
+        return x, {s: y[y_off[s]:y_off[s] + t.n_out] for s, t in ticks.items()}, tabs
+
+    def _join(self, a, b):
+        return b
+
+    def push(self, items: dict):
+        """{slot: x [C, n]}, any n per slot -> the inner bank's result per slot.  Everything is checked before any stream's state changes."""
+        xs = self._checked(items)
+        if not xs:
+            return self.inner.push({})
+        ticks = {s: self._plans[s].push(int(x.shape[1])) for s, x in xs.items()}
+        return self.inner.push(self._front_tick(xs, ticks)[1])
+
+    def close(self, slot: int):
+        """The stream's last 16 kHz samples (zeros past its end, as the file kernels take them), then the inner bank's close; frees the slot."""
+        self._check_slot(slot)
+        ys = self._front_tick({slot: self._zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()})[1]
+        first = self.inner.push(ys)
+        first = None if first is None else first[slot]
+        out = self._join(first, self.inner.close(slot))
+        self._is_open[slot] = False
+        return out
+
+
+class HostEmbedBank(HostFrontBank):
+    """Watermark up to `capacity` live streams, each at its own rate and channel count: open(message, sample_rate, channels, strength) -> slot;
+    push({slot: x [C, n]}) -> {slot: [C, k]}, the watermarked samples that no later input can change, each x + strength * (the generator's
+    residual brought to the slot's rate) on every channel; close(slot) -> the rest, after which as many samples have come out as went in and their
+    concatenation is that of a NativeEmbedSession given the same pushes.  `inner` returns the RESIDUAL of its new frames per slot."""
+
+    def _new_plan(self, sample_rate: int):
+        return EmbedPlan(sample_rate, self.inner.hop, self.inner.H)
+
+    def _new_state(self) -> None:
+        super()._new_state()
+        self._rhist = self._zeros(self.capacity, 2, max(t[3] for t in self._btabs))
+        self._pend = self._zeros(self.capacity, 2, self.max_channels, max(EmbedPlan(r, self.inner.hop, self.inner.H).pcap for r in self.rates))
+        self._strength = [1.0] * self.capacity
+
+    def open(self, message, sample_rate: int = MODEL_RATE, channels: int = 1, strength: float = 1.0) -> int:
+        strength = float(strength)
+        slot = super().open(message, sample_rate=sample_rate, channels=channels)
+        self._strength[slot] = strength
+        return slot
+
+    def latency_samples(self, slot: int) -> int:
+        """The slot's output lags its input by fewer than this many samples at its own rate."""
+        self._check_slot(slot)
+        return self._plans[slot].latency_samples
+
+    def samples_out(self, slot: int) -> int:
+        self._check_slot(slot)
+        return self._plans[slot].t_out
+
+    def _residual_offsets(self, ticks: dict) -> dict:
+        """Where the inner bank will put each slot's residual in its packed output of this tick: session.plan_tick on the inner ticks."""
+        plan = plan_tick({s: t.inner[0] for s, t in ticks.items()}, {s: t.front.n_out for s, t in ticks.items()}, self.inner.pad_limit)
+        return {s: plan.out[s][0] for s in ticks}
+
+    def _embed_tick(self, xs: dict, ticks: dict, final: bool) -> dict:
+        r_off = {s: 0 for s in ticks} if final else self._residual_offsets(ticks)
+        x_off, _ = self._packed(ticks, lambda s, t: self._chan[s] * t.front.n)
+        out_off, n_out = self._packed(ticks, lambda s, t: self._chan[s] * t.back.n_out)
+        back = [up_row(s, self._rate[s], self._chan[s], t, r_off[s], x_off[s], t.front.n, out_off[s], self._half[s]) for s, t in ticks.items()]
+        x, ys, tabs = self._front_tick(xs, {s: t.front for s, t in ticks.items()},
+                                       [("back", np.array(back, np.int64).reshape(-1, 15)),
+                                        ("gain", np.array([self._strength[s] for s in ticks], self.dtype))])
+        r = self._residuals(ys, ticks, r_off, final)
+        out = self._up_add(r, x, tabs, n_out, up_blocks(back))
+        self.stats["back_launches"] += 1
+        return {s: out[out_off[s]:out_off[s] + self._chan[s] * t.back.n_out].reshape(self._chan[s], t.back.n_out) for s, t in ticks.items()}
+
+    def _one(self, v):
+        return self._zeros(0) if v is None else v.reshape(-1)
+
+    def _residuals(self, ys: dict, ticks: dict, r_off: dict, final: bool):
+        """The inner bank's residuals of the tick as ONE packed array whose offsets are r_off."""
+        if final:
+            (s, t), = ticks.items()
+            r = self._cat([self._one(self.inner.push(ys)[s]), self._one(self.inner.close(s))])
+            assert r.shape[0] == t.n_res, (r.shape, t.n_res)
+            return r
+        res = self.inner.push(ys)
+        total = max((r_off[s] + t.n_res for s, t in ticks.items()), default=0)
+        return self._pack(res, ticks, r_off, total)
+
+    def _pack(self, res: dict, ticks: dict, r_off: dict, total: int):
+        r = self._zeros(total)
+        for s, t in ticks.items():
+            v = self._one(res[s])
+            assert v.shape[0] == t.n_res, (s, v.shape, t.n_res)
+            r[r_off[s]:r_off[s] + t.n_res] = v
+        return r
+
+    def push(self, items: dict) -> dict:
+        xs = self._checked(items)
+        if not xs:
+            return {}
+        return self._embed_tick(xs, {s: self._plans[s].push(int(x.shape[1])) for s, x in xs.items()}, False)
+
+    def close(self, slot: int):
+        self._check_slot(slot)
+        out = self._embed_tick({slot: self._zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()}, True)[slot]
+        self._is_open[slot] = False
+        return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- on the device
+def _residual_embed_bank(net, capacity, precision, pad_limit, messages):
+    from .session import EmbedBank
+
+    class ResidualEmbedBank(EmbedBank):
+        """EmbedBank whose generator returns its residual alone: what the back stage brings to each slot's own rate."""
+
+        def _net_forward(self, win, tabs, ln):
+            return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=False, precision=self.precision)
+
+    return ResidualEmbedBank(net, capacity, precision, pad_limit, messages)
+
+
+class NativeEmbedBank(_HipBankStages, HostEmbedBank):
+    """HostEmbedBank on a HipNet generator: open(message or watermark id, sample_rate, channels, strength); everything stays on the device.  A tick
+    uploads ONE table for the native stages (front descriptors, back descriptors, gains) and makes one front and one back launch, whatever the
+    mix of rates; the values of a push are views of one tensor."""
+
+    def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5,
+                 messages=None):
+        rates = check_rates(rates)                                         # refused before anything is built on the device
+        self.device = net.device
+        HostEmbedBank.__init__(self, _residual_embed_bank(net, capacity, precision, pad_limit, messages), rates, max_channels)
+
+    def _residuals(self, ys: dict, ticks: dict, r_off: dict, final: bool):
+        if final:
+            return HostEmbedBank._residuals(self, ys, ticks, r_off, final)
+        res = self.inner.push(ys)
+        live = [(s, res[s]) for s, t in ticks.items() if t.n_res]
+        if not live:
+            return self._zeros(0)
+        # the inner bank's views of its own packed output: that tensor is the r arena, the views' offsets the rows' r_off
+        base = live[0][1].untyped_storage().data_ptr()
+        for s, v in live:
+            assert v.untyped_storage().data_ptr() == base and v.storage_offset() == r_off[s] and v.shape[0] == ticks[s].n_res, s
+        return live[0][1].as_strided((max(r_off[s] + ticks[s].n_res for s, _ in live),), (1,), 0)
+
+
+class NativeDetectBank(_HipBankStages, HostFrontBank):
+    """Detect the watermark in up to `capacity` live streams at their own rates: push({slot: x [C, n]}) -> {slot: session.DetectState over the
+    16 kHz frames that stream has completed} (samples_seen counts 16 kHz samples)."""
+
+    def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5):
+        from .session import DetectBank
+        rates = check_rates(rates)
+        self.device = net.device
+        HostFrontBank.__init__(self, DetectBank(net, capacity, precision, pad_limit), rates, max_channels)
+
+
+class NativeLocateBank(_HipBankStages, HostFrontBank):
+    """Locate the watermark in up to `capacity` live streams at their own rates: push({slot: x [C, n]}) -> {slot: locator logits of the 16 kHz
+    frames that push completed [k]}; the logits stay on the 16 kHz time line."""
+
+    def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5):
+        from .session import LocateBank
+        rates = check_rates(rates)
+        self.device = net.device
+        HostFrontBank.__init__(self, LocateBank(net, capacity, precision, pad_limit), rates, max_channels)
+
+    def _join(self, a, b):
+        return self._cat([a, b])
+
+
+class NativeSegmentBank(_HipBankStages, HostFrontBank):
+    """Watermarked segments of up to `capacity` live streams at their own rates: push({slot: x [C, n]}) returns nothing; poll(), open_segments()
+    and close() are session.SegmentBank's on the 16 kHz samples the front stage has made final, so a Segment's frames count 16 kHz detector
+    frames and its start_s / end_s are seconds on the stream's own clock.  A caller's gate has no native-rate form and is refused."""
+
+    def __init__(self, detector, locator, rates, capacity: int = 64, max_channels: int = 2, gated: bool = False, **kw):
+        from .session import SegmentBank
+        if gated:
+            raise ValueError("a gate is given per 16 kHz sample; a bank at the streams' own rates takes none")
+        rates = check_rates(rates)
+        self.device = detector.device
+        HostFrontBank.__init__(self, SegmentBank(detector, locator, capacity, gated=False, sample_rate=MODEL_RATE, **kw), rates, max_channels)
+
+    def push(self, items: dict) -> None:
+        for slot, item in items.items():
+            if isinstance(item, (tuple, list)):
+                raise ValueError(f"slot {slot}: a gate is given per 16 kHz sample; a bank at the streams' own rates takes none")
+        HostFrontBank.push(self, items)
+
+    def poll(self) -> dict:
+        return self.inner.poll()
+
+    def open_segments(self) -> dict:
+        return self.inner.open_segments()
