@@ -387,7 +387,7 @@ def play_16k(ref, steps, xs, who, open_args, join):
 @pytest.mark.parametrize("precision", ["f32", "f16"])
 @pytest.mark.parametrize("kind", ["embed", "detect", "locate", "segment"])
 def test_mixed_rates_are_the_16k_bank_behind_the_front_stage_bit_for_bit(kind, precision):
-    from waveverify_amd.session import DetectBank, LocateBank, SegmentBank
+    from waveverify_amd.session import DetectBank, EmbedBank, LocateBank, SegmentBank
     gen, det, loc = nets(precision)
     net = {"embed": gen, "detect": det, "locate": loc, "segment": det}[kind]
     from waveverify_amd.window import halo
@@ -405,7 +405,7 @@ def test_mixed_rates_are_the_16k_bank_behind_the_front_stage_bit_for_bit(kind, p
                 return super().open(message(gen, name), strength=gains[name], **kw)
         bank = Bank(gen, NBC.RATES, cap, Cm, precision)
         out, slot = NBC.run(bank, steps, xs, who, open_args=lambda n: (n,))
-        ref = play_16k(NB._residual_embed_bank(gen, cap, precision, 1.5, None), steps, xs, who, lambda n: (message(gen, n),), cat)
+        ref = play_16k(EmbedBank(gen, cap, precision, 1.5, None, add_input=False), steps, xs, who, lambda n: (message(gen, n),), cat)
         # slots are reused (G takes B's, Z takes C's): walk the recorded residuals per slot in stream order
         taken = {s: list(v) for s, v in bank.residuals.items()}
         for n in out:

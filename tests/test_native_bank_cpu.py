@@ -12,7 +12,7 @@ import native_bank_cases as NBC
 from waveverify_amd import _lib, native
 from waveverify_amd import native_bank as NB
 from waveverify_amd import native_session as NS
-from waveverify_amd.session import StreamBank, StreamSession
+from waveverify_amd.session import NumpyArrays, StreamBank, StreamSession
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("wv_native_bank_down", "wv_native_bank_up_add")
@@ -31,11 +31,11 @@ class ToyBank(StreamBank):
 
 
 def inner_bank(capacity: int, forward):
-    return ToyBank(capacity, HOP, HALO, lambda win, slots: forward(win), new_history=lambda c, cap: np.zeros((c, cap), np.float64))
+    return ToyBank(capacity, HOP, HALO, lambda win, slots: forward(win), arrays=NumpyArrays(np.float64))
 
 
 def inner_session(forward):
-    return StreamSession(1, HOP, HALO, lambda win, keep: forward(win[:, :, keep:]), new_history=lambda S_, cap: np.zeros((S_, cap), np.float64))
+    return StreamSession(1, HOP, HALO, lambda win, keep: forward(win[:, :, keep:]), arrays=NumpyArrays(np.float64))
 
 
 def embed_bank(capacity: int = 6):
@@ -164,7 +164,7 @@ def test_open_refusals_change_no_state():
     bank = embed_bank(2)
 
     def state():
-        return (list(bank._is_open), list(bank.inner._is_open), [id(p) for p in bank._plans], list(bank._half), list(bank._rate), list(bank._chan),
+        return (list(bank.inner._is_open), [id(p) for p in bank._plans], list(bank._half), list(bank._rate), list(bank._chan),
                 list(bank._strength), bank._hist.copy(), dict(bank.stats))
 
     def same(a, b):

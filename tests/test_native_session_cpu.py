@@ -12,7 +12,7 @@ import pytest
 import native_cases as NC
 from waveverify_amd import _lib, native
 from waveverify_amd import native_session as NS
-from waveverify_amd.session import StreamSession
+from waveverify_amd.session import NumpyArrays, StreamSession
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXPORTS = ("wv_native_session_down", "wv_native_session_up_add")
@@ -55,7 +55,7 @@ def whole_embed(x: np.ndarray, sr: int) -> np.ndarray:
 
 
 def inner_session(S: int, forward):
-    return StreamSession(S, HOP, HALO, forward, new_history=lambda S_, cap: np.zeros((S_, cap), np.float64))
+    return StreamSession(S, HOP, HALO, forward, arrays=NumpyArrays(np.float64))
 
 
 def schedules(sr: int):

@@ -18,7 +18,7 @@ import segment_session_cases as SC
 from bank_cases import CAPACITY, PAD_LIMITS, mixed_schedule, stream_lengths
 from localized_cases import frame_sums_ref
 from waveverify_amd.localize import BankSegmentTracker, Segment, SegmentTracker, gate_threshold
-from waveverify_amd.session import SegmentStreamBank, bank_track_row_ok, numpy_bank_advance, segment_halo
+from waveverify_amd.session import NumpyArrays, SegmentStreamBank, bank_track_row_ok, numpy_bank_advance, segment_halo
 
 W = SB.W
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -146,7 +146,7 @@ def test_bank_state_machine_on_the_oracle(det_id, loc_id, gated):
     worst, stats = 0.0, {}
     for pad in PAD_LIMITS:
         bank = SegmentStreamBank(CAPACITY, hop, H, frame_sums, BankSegmentTracker(CAPACITY, nb, hop, min_on, G, ml, ring=2, dtype=np.float64),
-                                 numpy_bank_advance, lambda c, cap: np.zeros((c, cap), np.float64), pad, gated, 16000, 2, G, ml)
+                                 numpy_bank_advance, NumpyArrays(np.float64), pad, gated, 16000, 2, G, ml)
         got, _ = SB.play(bank, steps, xs, gates, poll_every=3)
         assert bank.open_slots() == []
         for n, x in xs.items():

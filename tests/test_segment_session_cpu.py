@@ -13,8 +13,8 @@ import pytest
 import segment_session_cases as SC
 import window_cases as W
 from localized_cases import SEGMENT_CASES, frame_sums_ref
-from waveverify_amd.localize import Segment, SegmentTracker, gate_threshold
-from waveverify_amd.session import SegmentStreamSession, numpy_advance, segment_halo
+from waveverify_amd.localize import BankSegmentTracker, Segment, SegmentTracker, gate_threshold
+from waveverify_amd.session import SegmentStreamBank, SegmentStreamSession, cut_rows, numpy_advance, segment_halo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -247,6 +247,79 @@ def test_session_automatic_poll_loses_nothing_at_capacity_one():
             segs = sess.flush()[0]
             assert [s.frames for s in segs] == [(2 * i, 2 * i + 1) for i in range(13)], (cap, sizes[:3])
             assert all(s.coverage == 1.0 and s.prob[0] == np.float32(0.75) for s in segs)
+
+
+def test_a_ring_of_one_with_period_one_terminates_and_equals_the_bank():
+    """capacity = 1 with min_gap_frames + min_len_frames = 1: ring * period - 1 = 0 frames, the step a lockstep session once cut its ticks by
+    without the bank's floor of one frame, so its loop never advanced.  The tracker here refuses a second advance in a row that brings no
+    frame and is not final, so the old behaviour fails instead of hanging.  The session's segments are those of a bank of one slot."""
+    hop, nb = 4, 2
+
+    class Progress(SegmentTracker):
+        idle = 0
+
+        def advance(self, fsum, f_lo=0, f_hi=None, last_valid=None, final=False):
+            n = (fsum.shape[2] if f_hi is None else f_hi) - f_lo
+            self.idle = self.idle + 1 if n == 0 and not final else 0
+            assert self.idle < 2, "two advances in a row without a frame: the cut makes no progress"
+            super().advance(fsum, f_lo, f_hi, last_valid, final)
+
+    def fs(win, gwin):                                                       # the "locator" is the sign of x
+        on = np.pad(win[:, 0] > 0, ((0, 0), (0, -win.shape[-1] % hop))).reshape(win.shape[0], -1, hop).sum(-1)
+        return np.stack([on * 0.75, on * 0.25, on], axis=1).astype(np.float32)
+
+    for frames, want in (([1, 1, 0], [(0, 2)]), ([1, 1, 1], [(0, 3)]), ([1, 0, 1], [(0, 1), (2, 3)])):
+        x = np.repeat(np.asarray(frames, np.float32), hop)
+        sess = SegmentStreamSession(1, hop, 2 * hop, fs, Progress(1, nb, hop, 0.5, 1, 0), capacity=1, min_gap_frames=1, min_len_frames=0)
+        assert sess.push(x[None]) is None
+        got = sess.flush()[0]
+        bank = SegmentStreamBank(1, hop, 2 * hop, fs, BankSegmentTracker(1, nb, hop, 0.5, 1, 0, ring=1), ring=1, min_gap_frames=1, min_len_frames=0)
+        slot = bank.open()
+        bank.push({slot: x})
+        ref = bank.close(slot)
+        assert [g.frames for g in got] == [r.frames for r in ref] == want, (frames, got, ref)
+        for g, r in zip(got, ref):
+            assert (g.start_s, g.end_s, g.coverage, g.confidence) == (r.start_s, r.end_s, r.coverage, r.confidence) and g.prob.tobytes() == r.prob.tobytes()
+            assert g.coverage == 1.0 and g.prob.tolist() == [0.75, 0.25]
+
+
+def _lockstep_cut_before(capacity, period, hop, unread, f_lo, f_hi, last_valid, final):
+    """The lockstep session's own loop as it stood before cut_rows, the tracker's advance and the ring's read replaced by a log."""
+    log = []
+    step = capacity * period - 1                                             # frames // period + 1 <= capacity
+    while True:
+        m = min(step, f_hi - f_lo)
+        last = f_lo + m == f_hi
+        drained = False
+        if unread and (unread + m) // period + 1 >= capacity:
+            drained, unread = True, 0
+        log.append((drained, f_lo, f_lo + m, last_valid if last else hop, final and last))
+        unread += m
+        f_lo += m
+        if last:
+            return log, unread
+
+
+def test_the_shared_cut_rule_is_the_lockstep_rule_wherever_that_one_terminates():
+    hop, f_lo, n, multi, drains = 4, 3, 0, 0, 0
+    for ring in (1, 2, 3, 64):
+        for period in (1, 2, 7):
+            step = ring * period - 1
+            if step < 1:
+                continue                                                     # the old loop does not end there (the test above)
+            for unread in sorted({0, 1, ring * period - 2} - {-1}):
+                for frames in sorted({0, 1, step - 1, step, step + 1, 3 * step + 2}):
+                    for last_valid, final in ((hop, False), (hop - 1, True)):
+                        want, left = _lockstep_cut_before(ring, period, hop, unread, f_lo, f_lo + frames, last_valid, final)
+                        pieces, after = cut_rows([[0, 5, 9, f_lo, f_lo + frames, 11, last_valid, int(final)]], [unread], ring, period, hop)
+                        got = [(drain, lo, hi, lv, bool(fin)) for drain, ((_, _, _, lo, hi, _, lv, fin),) in pieces]
+                        assert got == want and after == [left], (ring, period, unread, frames, final, got, want)
+                        at = 11
+                        for _, ((s, off, Fr, lo, hi, f0, _, _),) in pieces:   # what names the stream's rows goes through; frame0 moves on
+                            assert (s, off, Fr, f0) == (0, 5, 9, at)
+                            at += hi - lo
+                        n, multi, drains = n + 1, multi + (len(got) > 1), drains + sum(g[0] for g in got)
+    assert n > 300 and multi > 50 and drains > 100, (n, multi, drains)
 
 
 # ---- 3. the margin of the GPU tests' locator-driven recording ----------------------------------------------------------------------------

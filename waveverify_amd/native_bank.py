@@ -11,15 +11,16 @@ whatever the mix of rates on the tick.  The integer plans are native_session's S
 descriptor rows.  The stages' state is ping-pong per slot: a row's `half` names the half holding the slot's state, the launch writes the next
 state into the other, and the bank flips the bit of every slot the tick named.  The Host* classes run the state machine on numpy arrays (any
 float dtype) through numpy_bank_down / numpy_bank_up_add, which restate the kernels row rule included; the Native* classes bind it to the HIP
-entry points and the HipNet banks, where there is no CPU fallback."""
+entry points and the HipNet banks, where there is no CPU fallback.  A bank's arrays come from its inner bank's backend (session.NumpyArrays /
+TorchArrays), and its slot table is the inner bank's."""
 from __future__ import annotations
 
 import numpy as np
 
-from . import native
+from . import _lib, native
 from .native import MODEL_RATE
 from .native_session import EmbedPlan, EmbedTick, StagePlan, StageTick, numpy_down, numpy_up_add
-from .session import plan_tick
+from .session import DetectBank, EmbedBank, LocateBank, NumpyArrays, SegmentBank, plan_tick
 
 MAX_RATES = 8                                        # WV_NATIVE_BANK_MAX_RATES
 MAX_COUNT = 2 ** 31 - 257                            # the largest sample count of a descriptor row
@@ -141,20 +142,10 @@ def numpy_bank_up_add(rhist: np.ndarray, pend: np.ndarray, r: np.ndarray, x: np.
 
 # ---------------------------------------------------------------------------------------------------------------- the banks
 class _BankStages:
-    """The two stages and their state on numpy arrays of `dtype`; _HipBankStages states the same on the device."""
-    dtype = np.float32
+    """The two stages and their state on host arrays of the backend's dtype; _HipBankStages states the same on the device."""
 
     def _tables(self):
         return ([native.transposed_table(r, MODEL_RATE) for r in self.rates], [native.transposed_table(MODEL_RATE, r) for r in self.rates])
-
-    def _zeros(self, *shape):
-        return np.zeros(shape, self.dtype)
-
-    def _flat(self, x):
-        return np.asarray(x, self.dtype).reshape(-1)
-
-    def _cat(self, parts):
-        return np.concatenate(parts) if parts else self._zeros(0)
 
     def _upload(self, sections: list) -> dict:
         return dict(sections)
@@ -170,45 +161,30 @@ class _HipBankStages(_BankStages):
     """The stages as one launch each on the inner bank's device; the rate tables are native.tables' cached device tensors."""
 
     def _tables(self):
-        from . import _lib
-        pairs = [native.tables(r, self.device) for r in self.rates]
+        pairs = [native.tables(r, self._arr.device) for r in self.rates]
         front, back = [p[0] for p in pairs], [p[1] for p in pairs]
         self._frates = (_lib.WvNativeRate * len(front))(*[_lib.WvNativeRate(t[0].data_ptr(), *t[1:]) for t in front])
         self._brates = (_lib.WvNativeRate * len(back))(*[_lib.WvNativeRate(t[0].data_ptr(), *t[1:]) for t in back])
         return front, back
 
-    def _zeros(self, *shape):
-        import torch
-        return torch.zeros(shape, dtype=torch.float32, device=self.device)
-
-    def _flat(self, x):
-        import torch
-        return x.to(self.device, torch.float32).reshape(-1)
-
-    def _cat(self, parts):
-        import torch
-        return torch.cat(parts) if parts else self._zeros(0)
-
     def _upload(self, sections: list) -> dict:
         return self.inner._upload(sections)
 
     def _down(self, x, tabs: dict, n_y: int, blocks: int):
-        import torch
-        from . import _lib
-        y = torch.empty(n_y, dtype=torch.float32, device=self.device)
+        torch, dev = self._arr.torch, self._arr.device
+        y = torch.empty(n_y, dtype=torch.float32, device=dev)
         desc = tabs["front"]
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(dev):
             _lib.check(_lib.load().wv_native_bank_down(
                 self._hist.data_ptr(), self.capacity, self._hist.shape[2], x.data_ptr() if x.numel() else None, x.numel(), self._frates,
                 len(self.rates), desc.data_ptr(), desc.shape[0], blocks, y.data_ptr() if n_y else None, n_y, _lib.stream()), "wv_native_bank_down")
         return y
 
     def _up_add(self, r, x, tabs: dict, n_out: int, blocks: int):
-        import torch
-        from . import _lib
-        out = torch.empty(n_out, dtype=torch.float32, device=self.device)
+        torch, dev = self._arr.torch, self._arr.device
+        out = torch.empty(n_out, dtype=torch.float32, device=dev)
         desc = tabs["back"]
-        with torch.cuda.device(self.device):
+        with torch.cuda.device(dev):
             _lib.check(_lib.load().wv_native_bank_up_add(
                 self._rhist.data_ptr(), self._rhist.shape[2], self._pend.data_ptr(), self._pend.shape[3], self._pend.shape[2], self.capacity,
                 r.data_ptr() if r.numel() else None, r.numel(), x.data_ptr() if x.numel() else None, x.numel(), self._brates, len(self.rates),
@@ -221,17 +197,17 @@ class HostFrontBank(_BankStages):
     """The front stage in front of a 16 kHz bank `inner` (session.StreamBank or a subclass): open(*inner's arguments, sample_rate, channels) ->
     slot; push({slot: x [C, n]}) at each slot's own rate -> inner.push of the 16 kHz samples that became final, per slot (a slot whose stage
     emitted nothing still pushes an empty array, so the result has every pushed slot); close(slot) -> the rest, then inner.close.  Whatever the
-    inner bank returns stays on the 16 kHz time line."""
+    inner bank returns stays on the 16 kHz time line.  The slot table is the inner bank's: open_slots() and the open-slot check are its own.
+    The stages' arrays live on the inner bank's backend; dtype: numpy arrays of that dtype instead."""
 
     def __init__(self, inner, rates, max_channels: int = 2, dtype=None):
         self.rates = check_rates(rates)
         if not 1 <= int(max_channels) <= 64:
             raise ValueError(f"max_channels must be within [1, 64], got {max_channels}")
         self.inner, self.capacity, self.max_channels = inner, inner.capacity, int(max_channels)
-        if dtype is not None:
-            self.dtype = dtype
+        self.open_slots, self._check_slot = inner.open_slots, inner._check_slot         # the inner bank's own: no mirror, no second call per slot
+        self._arr = inner._arr if dtype is None else NumpyArrays(dtype)
         self._ftabs, self._btabs = self._tables()
-        self._is_open = [False] * self.capacity
         self._plans = [None] * self.capacity
         self._rate = [0] * self.capacity
         self._chan = [1] * self.capacity
@@ -241,33 +217,24 @@ class HostFrontBank(_BankStages):
 
     # ---- state: allocated once, sized by the largest table of the bank's rates
     def _new_state(self) -> None:
-        self._hist = self._zeros(self.capacity, 2, max(t[3] for t in self._ftabs))
+        self._hist = self._arr.zeros(self.capacity, 2, max(t[3] for t in self._ftabs))
 
     def _new_plan(self, sample_rate: int):
         return StagePlan(*native.table_geometry(sample_rate, MODEL_RATE))
 
     # ---- slots
     def open(self, *args, sample_rate: int = MODEL_RATE, channels: int = 1) -> int:
-        """open(*the inner bank's arguments, sample_rate=, channels=) -> the lowest free slot, a stream of `channels` channels at `sample_rate`
-        (one of the bank's rates) starting from nothing: its plan is new, so whatever state the slot's last stream left in either half is never
-        read.  Refusals come before any state changes."""
+        """open(*the inner bank's arguments, sample_rate=, channels=) -> the inner bank's lowest free slot, a stream of `channels` channels at
+        `sample_rate` (one of the bank's rates) starting from nothing: its plan is new, so whatever state the slot's last stream left in either
+        half is never read.  Refusals, the inner bank's among them, come before any state changes."""
         if int(sample_rate) not in self.rates:
             raise ValueError(f"sample rate {sample_rate} Hz is not one of this bank's rates {self.rates}")
         if not 1 <= int(channels) <= self.max_channels:
             raise ValueError(f"channels must be within [1, {self.max_channels}], got {channels}")
         plan = self._new_plan(int(sample_rate))
         slot = self.inner.open(*args)                                      # RuntimeError when every slot is open
-        assert slot == self._is_open.index(False), (slot, self._is_open)   # the two lowest-free-slot rules coincide
-        self._is_open[slot], self._plans[slot] = True, plan
-        self._rate[slot], self._chan[slot] = self.rates.index(int(sample_rate)), int(channels)
+        self._plans[slot], self._rate[slot], self._chan[slot] = plan, self.rates.index(int(sample_rate)), int(channels)
         return slot
-
-    def open_slots(self) -> list:
-        return [s for s, taken in enumerate(self._is_open) if taken]
-
-    def _check_slot(self, slot) -> None:
-        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.capacity or not self._is_open[slot]:
-            raise ValueError(f"slot {slot!r} is not open")
 
     def sample_rate(self, slot: int) -> int:
         self._check_slot(slot)
@@ -306,7 +273,7 @@ class HostFrontBank(_BankStages):
         y_off, n_y = self._packed(ticks, lambda s, t: t.n_out)
         front = np.array([down_row(s, self._rate[s], self._chan[s], t, x_off[s], y_off[s], self._half[s]) for s, t in ticks.items()],
                          np.int64).reshape(-1, 12)
-        x = self._cat([self._flat(xs[s]) for s in ticks if ticks[s].n])
+        x = self._arr.cat([self._arr.take(xs[s]).reshape(-1) for s in ticks if ticks[s].n])
         tabs = self._upload([("front", front)] + list(extra))
         self.stats["uploads"] += 1
         y = self._down(x, tabs, n_y, down_blocks(front))
@@ -329,12 +296,9 @@ class HostFrontBank(_BankStages):
     def close(self, slot: int):
         """The stream's last 16 kHz samples (zeros past its end, as the file kernels take them), then the inner bank's close; frees the slot."""
         self._check_slot(slot)
-        ys = self._front_tick({slot: self._zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()})[1]
+        ys = self._front_tick({slot: self._arr.zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()})[1]
         first = self.inner.push(ys)
-        first = None if first is None else first[slot]
-        out = self._join(first, self.inner.close(slot))
-        self._is_open[slot] = False
-        return out
+        return self._join(None if first is None else first[slot], self.inner.close(slot))
 
 
 class HostEmbedBank(HostFrontBank):
@@ -348,8 +312,9 @@ class HostEmbedBank(HostFrontBank):
 
     def _new_state(self) -> None:
         super()._new_state()
-        self._rhist = self._zeros(self.capacity, 2, max(t[3] for t in self._btabs))
-        self._pend = self._zeros(self.capacity, 2, self.max_channels, max(EmbedPlan(r, self.inner.hop, self.inner.H).pcap for r in self.rates))
+        zeros = self._arr.zeros
+        self._rhist = zeros(self.capacity, 2, max(t[3] for t in self._btabs))
+        self._pend = zeros(self.capacity, 2, self.max_channels, max(EmbedPlan(r, self.inner.hop, self.inner.H).pcap for r in self.rates))
         self._strength = [1.0] * self.capacity
 
     def open(self, message, sample_rate: int = MODEL_RATE, channels: int = 1, strength: float = 1.0) -> int:
@@ -379,32 +344,25 @@ class HostEmbedBank(HostFrontBank):
         back = [up_row(s, self._rate[s], self._chan[s], t, r_off[s], x_off[s], t.front.n, out_off[s], self._half[s]) for s, t in ticks.items()]
         x, ys, tabs = self._front_tick(xs, {s: t.front for s, t in ticks.items()},
                                        [("back", np.array(back, np.int64).reshape(-1, 15)),
-                                        ("gain", np.array([self._strength[s] for s in ticks], self.dtype))])
+                                        ("gain", np.array([self._strength[s] for s in ticks], self._arr.dtype))])
         r = self._residuals(ys, ticks, r_off, final)
         out = self._up_add(r, x, tabs, n_out, up_blocks(back))
         self.stats["back_launches"] += 1
         return {s: out[out_off[s]:out_off[s] + self._chan[s] * t.back.n_out].reshape(self._chan[s], t.back.n_out) for s, t in ticks.items()}
 
-    def _one(self, v):
-        return self._zeros(0) if v is None else v.reshape(-1)
-
     def _residuals(self, ys: dict, ticks: dict, r_off: dict, final: bool):
         """The inner bank's residuals of the tick as ONE packed array whose offsets are r_off."""
         if final:
             (s, t), = ticks.items()
-            r = self._cat([self._one(self.inner.push(ys)[s]), self._one(self.inner.close(s))])
+            r = self._arr.cat([v.reshape(-1) for v in (self.inner.push(ys)[s], self.inner.close(s)) if v is not None])
             assert r.shape[0] == t.n_res, (r.shape, t.n_res)
             return r
         res = self.inner.push(ys)
-        total = max((r_off[s] + t.n_res for s, t in ticks.items()), default=0)
-        return self._pack(res, ticks, r_off, total)
-
-    def _pack(self, res: dict, ticks: dict, r_off: dict, total: int):
-        r = self._zeros(total)
+        r = self._arr.zeros(max((r_off[s] + t.n_res for s, t in ticks.items()), default=0))
         for s, t in ticks.items():
-            v = self._one(res[s])
-            assert v.shape[0] == t.n_res, (s, v.shape, t.n_res)
-            r[r_off[s]:r_off[s] + t.n_res] = v
+            assert (0 if res[s] is None else res[s].shape[-1]) == t.n_res, (s, t.n_res)
+            if t.n_res:
+                r[r_off[s]:r_off[s] + t.n_res] = res[s].reshape(-1)
         return r
 
     def push(self, items: dict) -> dict:
@@ -415,24 +373,10 @@ class HostEmbedBank(HostFrontBank):
 
     def close(self, slot: int):
         self._check_slot(slot)
-        out = self._embed_tick({slot: self._zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()}, True)[slot]
-        self._is_open[slot] = False
-        return out
+        return self._embed_tick({slot: self._arr.zeros(self._chan[slot], 0)}, {slot: self._plans[slot].flush()}, True)[slot]
 
 
 # ---------------------------------------------------------------------------------------------------------------- on the device
-def _residual_embed_bank(net, capacity, precision, pad_limit, messages):
-    from .session import EmbedBank
-
-    class ResidualEmbedBank(EmbedBank):
-        """EmbedBank whose generator returns its residual alone: what the back stage brings to each slot's own rate."""
-
-        def _net_forward(self, win, tabs, ln):
-            return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=False, precision=self.precision)
-
-    return ResidualEmbedBank(net, capacity, precision, pad_limit, messages)
-
-
 class NativeEmbedBank(_HipBankStages, HostEmbedBank):
     """HostEmbedBank on a HipNet generator: open(message or watermark id, sample_rate, channels, strength); everything stays on the device.  A tick
     uploads ONE table for the native stages (front descriptors, back descriptors, gains) and makes one front and one back launch, whatever the
@@ -441,8 +385,7 @@ class NativeEmbedBank(_HipBankStages, HostEmbedBank):
     def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5,
                  messages=None):
         rates = check_rates(rates)                                         # refused before anything is built on the device
-        self.device = net.device
-        HostEmbedBank.__init__(self, _residual_embed_bank(net, capacity, precision, pad_limit, messages), rates, max_channels)
+        HostEmbedBank.__init__(self, EmbedBank(net, capacity, precision, pad_limit, messages, add_input=False), rates, max_channels)
 
     def _residuals(self, ys: dict, ticks: dict, r_off: dict, final: bool):
         if final:
@@ -450,7 +393,7 @@ class NativeEmbedBank(_HipBankStages, HostEmbedBank):
         res = self.inner.push(ys)
         live = [(s, res[s]) for s, t in ticks.items() if t.n_res]
         if not live:
-            return self._zeros(0)
+            return self._arr.zeros(0)
         # the inner bank's views of its own packed output: that tensor is the r arena, the views' offsets the rows' r_off
         base = live[0][1].untyped_storage().data_ptr()
         for s, v in live:
@@ -463,9 +406,7 @@ class NativeDetectBank(_HipBankStages, HostFrontBank):
     16 kHz frames that stream has completed} (samples_seen counts 16 kHz samples)."""
 
     def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5):
-        from .session import DetectBank
         rates = check_rates(rates)
-        self.device = net.device
         HostFrontBank.__init__(self, DetectBank(net, capacity, precision, pad_limit), rates, max_channels)
 
 
@@ -474,13 +415,11 @@ class NativeLocateBank(_HipBankStages, HostFrontBank):
     frames that push completed [k]}; the logits stay on the 16 kHz time line."""
 
     def __init__(self, net, rates, capacity: int = 64, max_channels: int = 2, precision: str = "f32", pad_limit: float = 1.5):
-        from .session import LocateBank
         rates = check_rates(rates)
-        self.device = net.device
         HostFrontBank.__init__(self, LocateBank(net, capacity, precision, pad_limit), rates, max_channels)
 
     def _join(self, a, b):
-        return self._cat([a, b])
+        return self._arr.cat([a, b])
 
 
 class NativeSegmentBank(_HipBankStages, HostFrontBank):
@@ -489,11 +428,9 @@ class NativeSegmentBank(_HipBankStages, HostFrontBank):
     frames and its start_s / end_s are seconds on the stream's own clock.  A caller's gate has no native-rate form and is refused."""
 
     def __init__(self, detector, locator, rates, capacity: int = 64, max_channels: int = 2, gated: bool = False, **kw):
-        from .session import SegmentBank
         if gated:
             raise ValueError("a gate is given per 16 kHz sample; a bank at the streams' own rates takes none")
         rates = check_rates(rates)
-        self.device = detector.device
         HostFrontBank.__init__(self, SegmentBank(detector, locator, capacity, gated=False, sample_rate=MODEL_RATE, **kw), rates, max_channels)
 
     def push(self, items: dict) -> None:

@@ -15,8 +15,8 @@ file kernels.  Each output is the file kernels' fmaf chain over the same values,
 
 The bookkeeping (StagePlan, EmbedPlan) is plain integer arithmetic: stream positions are Python ints and may pass 2^31; what a kernel is handed is
 relative to the history's first sample and to the first phase group not yet emitted.  The sessions take the two stages as methods, stated here on
-numpy arrays (any float dtype) so that the state machine runs on a CPU; the Native*Session classes bind them to the HIP entry points and the HipNet sessions, where there
-is no CPU fallback."""
+numpy arrays (any float dtype) so that the state machine runs on a CPU, and their arrays from the inner session's backend (session.NumpyArrays
+/ TorchArrays); the Native*Session classes bind the stages to the HIP entry points and the HipNet sessions, where there is no CPU fallback."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -24,11 +24,9 @@ from typing import Optional
 
 import numpy as np
 
-from . import native
+from . import _lib, native
 from .native import MODEL_RATE
-from .session import Tick, _Ticker
-
-_CLOSED = "session was flushed; call reset() to start over"
+from .session import _CLOSED, DetectSession, EmbedSession, LocateSession, NumpyArrays, SegmentSession, Tick, _Ticker
 
 
 # ---------------------------------------------------------------------------------------------------------------- the plan: integers only
@@ -193,20 +191,13 @@ def numpy_up_add(rhist: np.ndarray, r: np.ndarray, pend: np.ndarray, x: np.ndarr
 
 # ---------------------------------------------------------------------------------------------------------------- the sessions
 class _Stages:
-    """The two stages and their state on numpy arrays of `dtype`; _HipStages states the same on the device."""
-    dtype = np.float32
+    """The two stages and their state on host arrays of the backend's dtype; _HipStages states the same on the device."""
 
     def _table(self, of: int, nf: int):
         return native.transposed_table(of, nf)
 
-    def _zeros(self, *shape):
-        return np.zeros(shape, self.dtype)
-
-    def _cat(self, parts):
-        return np.concatenate(parts, axis=-1)
-
-    def _take(self, x):
-        return np.asarray(x, self.dtype)
+    def _state(self, *shape):
+        return self._arr.zeros(*shape)
 
     def _down(self, x, t: StageTick):
         y, self._hist = numpy_down(self._hist, x, t, self._ftab)
@@ -218,74 +209,57 @@ class _Stages:
 
 
 class _HipStages(_Stages):
-    """The stages as one launch each; every state buffer has a second buffer that the launch writes and the next push reads."""
+    """The stages as one launch each.  Every state buffer is a pair (current, next), the halves of one allocation: a launch reads the first,
+    writes the next state into the second, and the pair swaps."""
 
     def _table(self, of: int, nf: int):
-        front, back = native.tables(self.sample_rate, self.device)
+        front, back = native.tables(self.sample_rate, self._arr.device)
         return front if nf == MODEL_RATE else back
 
-    def _zeros(self, *shape):
-        import torch
-        return torch.zeros(shape, dtype=torch.float32, device=self.device)
-
-    def _cat(self, parts):
-        import torch
-        return torch.cat(parts, dim=-1)
-
-    def _take(self, x):
-        import torch
-        return x.to(self.device, torch.float32).contiguous()
-
-    def _second(self, name: str, like):
-        import torch
-        spare = self.__dict__.get(name)
-        return spare if spare is not None and spare.shape == like.shape else torch.empty_like(like)
+    def _state(self, *shape):
+        return tuple(self._arr.zeros(2, *shape))
 
     def _down(self, x, t: StageTick):
-        import torch
-        from . import _lib
+        torch, dev = self._arr.torch, self._arr.device
         kt, orig, nw, L, width = self._ftab
-        y = torch.empty((self.S, t.n_out), dtype=torch.float32, device=self.device)
-        nxt = self._second("_hist_spare", self._hist)
-        with torch.cuda.device(self.device):
+        hist, nxt = self._hist
+        y = torch.empty((self.S, t.n_out), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
             _lib.check(_lib.load().wv_native_session_down(
-                self._hist.data_ptr(), self._hist.shape[1], t.hv, x.data_ptr() if t.n else None, t.n, kt.data_ptr(),
+                hist.data_ptr(), hist.shape[1], t.hv, x.data_ptr() if t.n else None, t.n, kt.data_ptr(),
                 y.data_ptr() if t.n_out else None, t.n_out, t.pad, nxt.data_ptr(), t.drop, t.hv2, self.S, self.channels, orig, nw, L, width,
                 _lib.stream()), "wv_native_session_down")
-        self._hist, self._hist_spare = nxt, self._hist
+        self._hist = (nxt, hist)
         return y
 
     def _up_add(self, r, x, t: EmbedTick):
-        import torch
-        from . import _lib
+        torch, dev = self._arr.torch, self._arr.device
         kt, orig, nw, L, width = self._btab
         b = t.back
         r = r.contiguous()
-        out = torch.empty((self.S, self.channels, b.n_out), dtype=torch.float32, device=self.device)
-        pnxt, rnxt = self._second("_pend_spare", self._pend), self._second("_rhist_spare", self._rhist)
-        with torch.cuda.device(self.device):
+        (rhist, rnxt), (pend, pnxt) = self._rhist, self._pend
+        out = torch.empty((self.S, self.channels, b.n_out), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
             _lib.check(_lib.load().wv_native_session_up_add(
-                self._rhist.data_ptr(), self._rhist.shape[1], b.hv, r.data_ptr() if b.n else None, b.n, kt.data_ptr(),
-                self._pend.data_ptr(), self._pend.shape[2], t.pv, x.data_ptr() if x.shape[2] else None, x.shape[2],
+                rhist.data_ptr(), rhist.shape[1], b.hv, r.data_ptr() if b.n else None, b.n, kt.data_ptr(),
+                pend.data_ptr(), pend.shape[2], t.pv, x.data_ptr() if x.shape[2] else None, x.shape[2],
                 out.data_ptr() if b.n_out else None, b.n_out, b.pad, float(self.strength), pnxt.data_ptr(), rnxt.data_ptr(), b.drop, b.hv2,
                 self.S, self.channels, orig, nw, L, width, _lib.stream()), "wv_native_session_up_add")
-        self._pend, self._pend_spare = pnxt, self._pend
-        self._rhist, self._rhist_spare = rnxt, self._rhist
+        self._rhist, self._pend = (rnxt, rhist), (pnxt, pend)
         return out
 
 
 class HostFrontSession(_Stages):
     """The front stage in front of a 16 kHz session `inner` (session.StreamSession or a subclass): push(x [S, C, n]) at `sample_rate` ->
     inner.push of the 16 kHz samples that became final; flush() -> the rest, then inner.flush().  Whatever the inner session returns stays on
-    the 16 kHz time line."""
+    the 16 kHz time line.  The stage's arrays live on the inner session's backend; dtype: numpy arrays of that dtype instead."""
 
     def __init__(self, inner, sample_rate: int = MODEL_RATE, channels: int = 1, dtype=None):
         native.check_rate(sample_rate)
         if not 1 <= int(channels) <= 64:
             raise ValueError(f"channels must be within [1, 64], got {channels}")
         self.inner, self.S, self.sample_rate, self.channels = inner, inner.S, int(sample_rate), int(channels)
-        if dtype is not None:
-            self.dtype = dtype
+        self._arr = inner._arr if dtype is None else NumpyArrays(dtype)
         self._ftab, self._btab = self._table(self.sample_rate, MODEL_RATE), self._table(MODEL_RATE, self.sample_rate)
         self._plan = self._new_plan()
         self._new_state()
@@ -294,7 +268,7 @@ class HostFrontSession(_Stages):
         return StagePlan(*native.table_geometry(self.sample_rate, MODEL_RATE))
 
     def _new_state(self) -> None:
-        self._hist = self._zeros(self.S, self._ftab[3])
+        self._hist = self._state(self.S, self._ftab[3])
 
     @property
     def samples_in(self) -> int:
@@ -309,7 +283,7 @@ class HostFrontSession(_Stages):
     def _checked(self, x):
         if len(x.shape) != 3 or x.shape[0] != self.S or x.shape[1] != self.channels:
             raise ValueError(f"expected new samples of shape [{self.S}, {self.channels}, n], got {tuple(x.shape)}")
-        return self._take(x)
+        return self._arr.take(x)
 
     def _join(self, a, b):
         return b
@@ -319,7 +293,7 @@ class HostFrontSession(_Stages):
         return self.inner.push(self._down(x, self._plan.push(int(x.shape[2]))))
 
     def flush(self):
-        y = self._down(self._zeros(self.S, self.channels, 0), self._plan.flush())
+        y = self._down(self._arr.zeros(self.S, self.channels, 0), self._plan.flush())
         first = self.inner.push(y)
         return self._join(first, self.inner.flush())
 
@@ -339,8 +313,8 @@ class HostEmbedSession(HostFrontSession):
 
     def _new_state(self) -> None:
         super()._new_state()
-        self._rhist = self._zeros(self.S, self._btab[3])
-        self._pend = self._zeros(self.S, self.channels, self._plan.pcap)
+        self._rhist = self._state(self.S, self._btab[3])
+        self._pend = self._state(self.S, self.channels, self._plan.pcap)
 
     @property
     def latency_samples(self) -> int:
@@ -357,8 +331,7 @@ class HostEmbedSession(HostFrontSession):
             parts.append(self.inner.push(y))
         if t.final:
             parts.append(self.inner.flush())
-        parts = [p.reshape(self.S, -1) for p in parts if p is not None]
-        r = self._cat(parts) if parts else self._zeros(self.S, 0)
+        r = self._arr.cat([p.reshape(self.S, -1) for p in parts if p is not None], self.S)
         assert r.shape[-1] == t.n_res, (r.shape, t.n_res)
         return r
 
@@ -371,16 +344,14 @@ class HostEmbedSession(HostFrontSession):
         return self._run(x, self._plan.push(int(x.shape[2])))
 
     def flush(self):
-        return self._run(self._zeros(self.S, self.channels, 0), self._plan.flush())
+        return self._run(self._arr.zeros(self.S, self.channels, 0), self._plan.flush())
 
 
 class NativeEmbedSession(_HipStages, HostEmbedSession):
     """HostEmbedSession on a HipNet generator: msg [S, 16] (or [16]) the streams' messages; everything stays on the device."""
 
     def __init__(self, net, msg, sample_rate: int = MODEL_RATE, channels: int = 1, strength: float = 1.0, precision: str = "f32"):
-        from .session import EmbedSession
         native.check_rate(sample_rate)                                  # refused before anything is built on the device
-        self.device = net.device
         HostEmbedSession.__init__(self, EmbedSession(net, msg, precision, add_input=False), sample_rate, channels, strength)
 
 
@@ -390,9 +361,7 @@ class NativeDetectSession(_HipStages, HostFrontSession):
     to_model_rate of the recording in the same pieces."""
 
     def __init__(self, net, S: int, sample_rate: int = MODEL_RATE, channels: int = 1, precision: str = "f32"):
-        from .session import DetectSession
         native.check_rate(sample_rate)                                  # refused before anything is built on the device
-        self.device = net.device
         HostFrontSession.__init__(self, DetectSession(net, S, precision), sample_rate, channels)
 
 
@@ -401,13 +370,11 @@ class NativeLocateSession(_HipStages, HostFrontSession):
     The logits stay on the 16 kHz time line: logit i of the concatenation belongs to the native samples around i * sample_rate / 16000."""
 
     def __init__(self, net, S: int, sample_rate: int = MODEL_RATE, channels: int = 1, precision: str = "f32"):
-        from .session import LocateSession
         native.check_rate(sample_rate)                                  # refused before anything is built on the device
-        self.device = net.device
         HostFrontSession.__init__(self, LocateSession(net, S, precision), sample_rate, channels)
 
     def _join(self, a, b):
-        return self._cat([a, b])
+        return self._arr.cat([a, b])
 
 
 class NativeSegmentSession(_HipStages, HostFrontSession):
@@ -417,9 +384,7 @@ class NativeSegmentSession(_HipStages, HostFrontSession):
     given to_model_rate of the recording in the same pieces.  A caller's gate has no native-rate form and is refused."""
 
     def __init__(self, detector, locator, S: int, sample_rate: int = MODEL_RATE, channels: int = 1, **kw):
-        from .session import SegmentSession
         native.check_rate(sample_rate)                                  # refused before anything is built on the device
-        self.device = detector.device
         HostFrontSession.__init__(self, SegmentSession(detector, locator, S, sample_rate=MODEL_RATE, **kw), sample_rate, channels)
 
     def push(self, x, gate=None) -> None:

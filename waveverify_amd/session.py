@@ -18,8 +18,10 @@ Segment banks (SegmentBank, section 7d-7) are the two together: per slot the seg
 sums of a tick's launches lie in one arena, and one wv_bank_segment_track call takes a descriptor per slot with that slot's own frame range,
 so the frames a short row computes on the batch's zero padding are never tracked.
 
-The bookkeeping is independent of the backend: a session takes the net forward as a callable, and the history update as
-another, so the same state machine runs on the numpy oracle on a CPU.
+The bookkeeping is independent of the backend: a session takes the net forward as a callable, the history update as another and its arrays
+from NumpyArrays or TorchArrays, so the same state machine runs on the numpy oracle on a CPU.  What the lockstep and the bank classes share is
+written once: _SegmentReader (tracker events -> Segments, and cut_rows, the rule that reads an event ring before it can overflow),
+_HipTrackerState (the device trackers' buffers and read-backs) and _SegmentNets (the detector and the locator bound for frame sums).
 """
 from __future__ import annotations
 
@@ -28,8 +30,49 @@ from typing import Callable, Optional
 
 import numpy as np
 
+from . import _lib
 from .localize import bank_track_row_ok  # noqa: F401  (wv_bank_segment_track's row predicate, restated beside bank_row_ok)
 from .window import halo as _halo
+
+_CLOSED = "session was flushed; call reset() to start over"
+_PRECISIONS = ("f32", "f16")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the array backends
+class NumpyArrays:
+    """The arrays of a session or bank on the host, in one float dtype (the float64 oracle runs pass theirs)."""
+
+    def __init__(self, dtype=np.float32):
+        self.dtype = dtype
+
+    def zeros(self, *shape, dtype: Optional[str] = None):
+        return np.zeros(shape, dtype or self.dtype)
+
+    def cat(self, parts: list, *lead):
+        """Along the last axis; no parts: an empty array [*lead, 0]."""
+        return np.concatenate(parts, axis=-1) if parts else self.zeros(*lead, 0)
+
+    def take(self, x):
+        """x on this backend as a contiguous float array."""
+        return np.ascontiguousarray(x, self.dtype)
+
+
+class TorchArrays:
+    """The same on a torch device in float32; torch is imported when the first of these is built.  dtype: what goes into a tick's table for it."""
+    dtype = np.float32
+
+    def __init__(self, device):
+        import torch
+        self.torch, self.device = torch, device
+
+    def zeros(self, *shape, dtype: Optional[str] = None):
+        return self.torch.zeros(shape, dtype=getattr(self.torch, dtype or "float32"), device=self.device)
+
+    def cat(self, parts: list, *lead):
+        return self.torch.cat(parts, dim=-1) if parts else self.zeros(*lead, 0)
+
+    def take(self, x):
+        return x.to(self.device, self.torch.float32).contiguous()
 
 
 @dataclass
@@ -58,7 +101,7 @@ class _Ticker:
 
     def push(self, n: int) -> Tick:
         if self.closed:
-            raise RuntimeError("session was flushed; call reset() to start over")
+            raise RuntimeError(_CLOSED)
         hv = self.t_in - self.h0
         t_in = self.t_in + n
         t_new = t_in // self.hop * self.hop
@@ -74,7 +117,7 @@ class _Ticker:
 
     def flush(self) -> Tick:
         if self.closed:
-            raise RuntimeError("session was flushed; call reset() to start over")
+            raise RuntimeError(_CLOSED)
         hv = self.t_in - self.h0
         wlen = hv if self.t_in > self.t_out else 0
         tick = Tick(hv, wlen, self.t_out - self.h0, hv, 0)
@@ -93,17 +136,17 @@ def numpy_advance(hist: np.ndarray, x: np.ndarray, t: Tick):
 
 class StreamSession:
     """Lockstep state machine over S streams.  forward(window [S,1,L], keep) -> that window's result for its columns
-    [keep, L); advance(history, x, Tick) -> (window, next history).  Subclasses bind both to a HipNet."""
+    [keep, L); advance(history, x, Tick) -> (window, next history); arrays: the backend of the history (NumpyArrays() if None).
+    Subclasses bind all three to a HipNet."""
 
-    def __init__(self, S: int, hop: int, H: int, forward: Callable, advance: Callable = numpy_advance,
-                 new_history: Optional[Callable] = None):
+    def __init__(self, S: int, hop: int, H: int, forward: Callable, advance: Callable = numpy_advance, arrays=None):
         if S < 1:
             raise ValueError("need at least one session")
         self.S = S
         self._t = _Ticker(hop, H)
         self._forward, self._advance = forward, advance
-        self._new_history = new_history or (lambda S_, cap: np.zeros((S_, cap), np.float32))
-        self._hist = self._new_history(S, self._t.cap)
+        self._arr = arrays or NumpyArrays()
+        self.reset()
 
     @property
     def samples_seen(self) -> int:
@@ -112,7 +155,7 @@ class StreamSession:
 
     def reset(self) -> None:
         self._t.reset()
-        self._hist = self._new_history(self.S, self._t.cap)
+        self._hist = self._arr.zeros(self.S, self._t.cap)
         self._on_reset()
 
     def _on_reset(self) -> None:
@@ -128,30 +171,22 @@ class StreamSession:
         return self._step(x, self._t.push(int(x.shape[1])))
 
     def flush(self):
-        return self._step(x=self._empty(), t=self._t.flush())
-
-    def _empty(self):
-        return np.zeros((self.S, 0), np.float32)
+        return self._step(self._arr.zeros(self.S, 0), self._t.flush())
 
 
 class _HipSession(StreamSession):
     """StreamSession on a HipNet: history, window and outputs stay on the device."""
 
-    def __init__(self, net, S: int, precision: str):
-        import torch
-        if precision not in ("f32", "f16"):
+    def __init__(self, net, S: int, precision: str = "f32"):
+        if precision not in _PRECISIONS:
             raise ValueError("precision must be 'f32' or 'f16'")
-        self.net, self.precision, self._torch = net, precision, torch
-        super().__init__(S, net.cfg.hop_length, _halo(net.cfg), self._net_forward, self._hip_advance,
-                         lambda S_, cap: torch.zeros((S_, cap), dtype=torch.float32, device=net.device))
-
-    def _empty(self):
-        return self._torch.zeros((self.S, 0), dtype=self._torch.float32, device=self.net.device)
+        arrays = TorchArrays(net.device)
+        self.net, self.precision, self._torch = net, precision, arrays.torch
+        super().__init__(S, net.cfg.hop_length, _halo(net.cfg), self._net_forward, self._hip_advance, arrays)
 
     def _hip_advance(self, hist, x, t: Tick):
         torch = self._torch
-        from . import _lib
-        x = x.to(self.net.device, torch.float32).contiguous()
+        x = self._arr.take(x)
         nxt = torch.empty_like(hist)
         win = torch.empty((self.S, 1, t.wlen), dtype=torch.float32, device=self.net.device)
         with torch.cuda.device(self.net.device):
@@ -163,7 +198,18 @@ class _HipSession(StreamSession):
         return win, nxt
 
 
-class EmbedSession(_HipSession):
+class _ColumnsSession(_HipSession):
+    """A _HipSession that returns the kept columns of _net(window [S, 1, L]) -> [S, 1, L]: [S, 1, k], k = 0 where no frame completed."""
+
+    def _net_forward(self, win, keep):
+        return self._net(win)[:, :, keep:].contiguous()
+
+    def _step(self, x, t: Tick):
+        y = super()._step(x, t)
+        return self._arr.zeros(self.S, 1, 0) if y is None else y
+
+
+class EmbedSession(_ColumnsSession):
     """Watermark S live streams: push(x [S, n]) -> watermarked samples of the frames completed by this push [S, 1, k].
     add_input=False: the generator's residual alone (what native_session.py brings back to a stream's own rate)."""
 
@@ -175,29 +221,15 @@ class EmbedSession(_HipSession):
         self.msg, self.add_input = msg.contiguous(), bool(add_input)
         super().__init__(net, msg.shape[0], precision)
 
-    def _net_forward(self, win, keep):
-        return self.net.generator(win, self.msg, add_input=self.add_input, precision=self.precision)[:, :, keep:].contiguous()
-
-    def _no_output(self):
-        return self._torch.zeros((self.S, 1, 0), dtype=self._torch.float32, device=self.net.device)
-
-    def push(self, x):
-        y = super().push(x)
-        return self._no_output() if y is None else y
-
-    def flush(self):
-        y = super().flush()
-        return self._no_output() if y is None else y
+    def _net(self, win):
+        return self.net.generator(win, self.msg, add_input=self.add_input, precision=self.precision)
 
 
-class LocateSession(EmbedSession):
+class LocateSession(_ColumnsSession):
     """Locate the watermark in S live streams: push(x [S, n]) -> locator logits of the newly completed frames [S, 1, k]."""
 
-    def __init__(self, net, S: int, precision: str = "f32"):
-        _HipSession.__init__(self, net, S, precision)
-
-    def _net_forward(self, win, keep):
-        return self.net.locator(win, precision=self.precision)[:, :, keep:].contiguous()
+    def _net(self, win):
+        return self.net.locator(win, precision=self.precision)
 
 
 @dataclass
@@ -211,28 +243,19 @@ class DetectSession(_HipSession):
     """Detect the watermark in S live streams: push(x [S, n]) -> the running DetectState over every completed frame so far.
     Each window's sigmoid sum over its new columns (the head's windowed mode) is added to an f64 accumulator."""
 
-    def __init__(self, net, S: int, precision: str = "f32"):
-        super().__init__(net, S, precision)
-        self._on_reset()
-
     def _on_reset(self):
-        self._acc = self._torch.zeros((self.S, self.net.cfg.head_bits), dtype=self._torch.float64, device=self.net.device)
+        self._acc = self._arr.zeros(self.S, self.net.cfg.head_bits, dtype="float64")
 
     def _net_forward(self, win, keep):
         L = win.shape[-1]
         return self.net.detector_window_psum(win, [keep] * self.S, [L] * self.S, precision=self.precision)
 
-    def _state(self, psum):
+    def _step(self, x, t: Tick):
+        psum = super()._step(x, t)
         if psum is not None:
             self._acc += psum.double()
         mp = (self._acc / max(self.samples_seen, 1)).float()
         return DetectState(mp, (mp >= 0.5).to(self._torch.int32), self.samples_seen)
-
-    def push(self, x):
-        return self._state(super().push(x))
-
-    def flush(self):
-        return self._state(super().flush())
 
 
 # ---------------------------------------------------------------------------------------------------------------- live segment sessions
@@ -245,18 +268,29 @@ def segment_halo(detector_cfg, locator_cfg) -> int:
     return max(_halo(detector_cfg), -(-_halo(locator_cfg) // hop) * hop)
 
 
-def _segment_of(ev, hop: int, t_in: int, sample_rate: int, confidence: Callable):
-    """A tracker event (lo, hi, count, prob) of a stream that has pushed t_in samples -> localize.Segment.  t_in is the true length once the
-    stream has ended and never short of a closed run before, so `end` is clipped only on the partial last frame."""
-    from .localize import Segment
-    from .watermark_id import WatermarkID
-    lo, hi, count, prob = ev
-    end = min(int(hi) * hop, t_in)
-    prob = np.asarray(prob, np.float32)
-    bits = "".join("1" if p >= np.float32(0.5) else "0" for p in prob)
-    wid = WatermarkID.custom(bits) if len(bits) == 16 else None           # an id has 16 bits; a net of another width leaves prob to read
-    return Segment(int(lo) * hop / sample_rate, end / sample_rate, wid, confidence(prob), float(count) / (end - int(lo) * hop), prob,
-                   (int(lo), int(hi)))
+def cut_rows(rows: list, unread: list, ring: int, period: int, hop: int):
+    """The rule that reads an event ring before it can overflow.  rows: a tick's tracker descriptors {stream, fsum_off, Fr_stride, f_lo, f_hi,
+    frame0, last_valid, final}; unread[stream]: frames tracked since the rings were last read, which bound the stream's waiting events by
+    frames // period + 1 (two closes lie at least `period` frames apart).  -> ([(read the rings first, rows)], unread after them): the rows
+    cut into pieces so that no stream's bound reaches `ring` between two reads.  A tick of ordinary pushes is one piece."""
+    step = max(1, ring * period - 1)                                       # frames // period + 1 <= ring
+    unread = list(unread)
+    out, left = [], rows
+    while left:
+        m = [min(step, r[4] - r[3]) for r in left]
+        drain = any(unread[r[0]] and (unread[r[0]] + k) // period + 1 >= ring for r, k in zip(left, m))
+        if drain:
+            unread = [0] * len(unread)
+        piece, nxt = [], []
+        for (s, off, Fr, lo, hi, f0, lv, fin), k in zip(left, m):
+            last = lo + k == hi
+            piece.append([s, off, Fr, lo, lo + k, f0, lv if last else hop, fin if last else 0])
+            unread[s] += k
+            if not last:
+                nxt.append([s, off, Fr, lo + k, hi, f0 + k, lv, fin])
+        out.append((drain, piece))
+        left = nxt
+    return out, unread
 
 
 def _open_run_of(hdr, acc, nb: int, eps: float):
@@ -268,7 +302,56 @@ def _open_run_of(hdr, acc, nb: int, eps: float):
     return int(hdr[1]), int(hdr[2]), float(cnt), prob
 
 
-class SegmentStreamSession(StreamSession):
+class _SegmentReader:
+    """What a segment session and a segment bank do with their tracker's events: hop, sample_rate, the event ring and the period of cut_rows,
+    per stream the Segments closed and not yet handed out, per ring-reading unit the frames tracked since its last read (a lockstep session
+    has ONE frame range, so one counter; a bank one per slot).  The class beside it says which streams exist:
+    _streams(read) -> [(stream, samples it has pushed, what read() holds for it)], read being the tracker's poll or open_runs."""
+
+    def _init_reader(self, hop: int, sample_rate: int, ring: int, min_gap_frames: int, min_len_frames: int) -> None:
+        self.hop, self.sample_rate, self.ring = hop, int(sample_rate), int(ring)
+        self._period = max(1, int(min_len_frames) + int(min_gap_frames))
+
+    def _clear_reader(self, streams: int, counters: int) -> None:
+        self._pending = [[] for _ in range(streams)]
+        self._unread = [0] * counters
+
+    def _confidence(self, prob: np.ndarray) -> float:
+        return float(np.asarray(prob, np.float32).mean())
+
+    def _segment_of(self, ev, t_in: int):
+        """A tracker event (lo, hi, count, prob) of a stream that has pushed t_in samples -> localize.Segment.  t_in is the true length once
+        the stream has ended and never short of a closed run before, so `end` is clipped only on the partial last frame."""
+        from .localize import Segment
+        from .watermark_id import WatermarkID
+        lo, hi, count, prob = ev
+        hop, fs = self.hop, self.sample_rate
+        end = min(int(hi) * hop, t_in)
+        prob = np.asarray(prob, np.float32)
+        bits = "".join("1" if p >= np.float32(0.5) else "0" for p in prob)
+        wid = WatermarkID.custom(bits) if len(bits) == 16 else None        # an id has 16 bits; a net of another width leaves prob to read
+        return Segment(int(lo) * hop / fs, end / fs, wid, self._confidence(prob), float(count) / (end - int(lo) * hop), prob, (int(lo), int(hi)))
+
+    def _drain(self) -> None:
+        """Read the rings (the one host synchronisation a push can make)."""
+        for s, t_in, evs in self._streams(self._tracker.poll):
+            if evs:
+                self._pending[s] += [self._segment_of(ev, t_in) for ev in evs]
+        self._unread = [0] * len(self._unread)
+
+    def _taken(self, s: int) -> list:
+        out, self._pending[s] = self._pending[s], []
+        return out
+
+    def _open_now(self) -> list:
+        """-> [(stream, the run that is open now as a provisional Segment (its frames so far), or None)]."""
+        return [(s, None if ev is None else self._segment_of(ev, t_in)) for s, t_in, ev in self._streams(self._tracker.open_runs)]
+
+    def _cut(self, rows: list):
+        return cut_rows(rows, self._unread, self.ring, self._period, self.hop)
+
+
+class SegmentStreamSession(_SegmentReader, StreamSession):
     """Localized detection of S live streams: push(x [S, n], gate=None) returns nothing; the watermarked stretches
     come out of poll() as localize.Segments once they have ended.  Backend independent: frame_sums(window [S,1,L], gate window [S,L] or
     None) -> the window's per-frame gated sums [S, nb + 1, ceil(L / hop)] (without a gate window it runs the locator itself), `tracker` has
@@ -277,70 +360,51 @@ class SegmentStreamSession(StreamSession):
     gate [S, n] (0 / 1) replaces the locator; its samples of an incomplete frame wait in a second history that goes through the same
     `advance`.  Whether a session is gated is settled by its first push and holds until reset().
 
-    capacity is the tracker's event ring.  The frames tracked since the last read bound the events waiting there by
-    frames // max(1, min_len_frames + min_gap_frames) + 1 (two closes lie at least that many frames apart); before a tick would let that
-    bound reach capacity the session reads the ring itself (the one host synchronisation a push can make), and a long push is tracked in
-    pieces that stay within it, so nothing is lost."""
+    capacity is the tracker's event ring.  Before a tick would let cut_rows' bound on the events waiting there reach capacity the session reads
+    the ring itself, and a long push is tracked in pieces that stay within it, so nothing is lost."""
 
-    def __init__(self, S: int, hop: int, H: int, frame_sums: Callable, tracker, advance: Callable = numpy_advance,
-                 new_history: Optional[Callable] = None, sample_rate: int = 16000, capacity: int = 64, min_gap_frames: int = 2,
-                 min_len_frames: int = 5):
+    def __init__(self, S: int, hop: int, H: int, frame_sums: Callable, tracker, advance: Callable = numpy_advance, arrays=None,
+                 sample_rate: int = 16000, capacity: int = 64, min_gap_frames: int = 2, min_len_frames: int = 5):
         if capacity < 1:
             raise ValueError("capacity must be at least 1")
-        StreamSession.__init__(self, S, hop, H, None, advance, new_history)
         self._frame_sums, self._tracker = frame_sums, tracker
-        self.sample_rate, self.capacity = int(sample_rate), int(capacity)
-        self._period = max(1, int(min_len_frames) + int(min_gap_frames))
-        self._on_reset()
+        self._init_reader(hop, sample_rate, capacity, min_gap_frames, min_len_frames)
+        self.capacity = self.ring
+        StreamSession.__init__(self, S, hop, H, None, advance, arrays)
 
     def _on_reset(self) -> None:
         self._ghist = None
         self._gated: Optional[bool] = None
-        self._unread = 0                                                   # frames tracked since the ring was last read
-        self._pending = [[] for _ in range(self.S)]
+        self._clear_reader(self.S, 1)
         self._tracker.reset()
 
-    # ---- events -> Segments
-    def _confidence(self, prob: np.ndarray) -> float:
-        return float(np.asarray(prob, np.float32).mean())
-
-    def _segment(self, ev):
-        return _segment_of(ev, self._t.hop, self._t.t_in, self.sample_rate, self._confidence)
-
-    def _drain(self) -> None:
-        for s, evs in enumerate(self._tracker.poll()):
-            self._pending[s] += [self._segment(ev) for ev in evs]
-        self._unread = 0
+    def _streams(self, read: Callable) -> list:
+        t_in = self._t.t_in
+        return [(s, t_in, v) for s, v in enumerate(read())]
 
     def poll(self):
         """-> per stream the Segments closed since the last poll, in stream order."""
         self._drain()
-        out, self._pending = self._pending, [[] for _ in range(self.S)]
-        return out
+        return [self._taken(s) for s in range(self.S)]
 
     def open_segments(self):
         """-> per stream the run that is open now as a provisional Segment (its frames so far), or None."""
-        return [None if ev is None else self._segment(ev) for ev in self._tracker.open_runs()]
+        return [seg for _, seg in self._open_now()]
 
     # ---- ticks
     def _track(self, fsum, f_lo: int, f_hi: int, last_valid: int, final: bool) -> None:
-        step = self.capacity * self._period - 1                            # frames // period + 1 <= capacity
-        while True:
-            m = min(step, f_hi - f_lo)
-            last = f_lo + m == f_hi
-            if self._unread and (self._unread + m) // self._period + 1 >= self.capacity:
+        pieces, unread = self._cut([[0, 0, 0, f_lo, f_hi, 0, last_valid, int(final)]])
+        for drain, ((_, _, _, lo, hi, _, lv, fin),) in pieces:
+            if drain:
                 self._drain()
-            self._tracker.advance(fsum, f_lo, f_lo + m, last_valid if last else self._t.hop, final and last)
-            self._unread += m
-            f_lo += m
-            if last:
-                return
+            self._tracker.advance(fsum, lo, hi, lv, bool(fin))
+        self._unread = unread
 
     def _gate_window(self, gate, x, t: Tick):
         if self._gated is None:
             self._gated = gate is not None
             if self._gated:
-                self._ghist = self._new_history(self.S, self._t.cap)
+                self._ghist = self._arr.zeros(self.S, self._t.cap)
         if self._gated != (gate is not None):
             raise ValueError("a session is gated on every push or on none; reset() to change")
         if not self._gated:
@@ -353,16 +417,13 @@ class SegmentStreamSession(StreamSession):
     def _tick(self, x, gate, t: Tick, final: bool) -> None:
         gwin = self._gate_window(gate, x, t)
         win, self._hist = self._advance(self._hist, x, t)
-        hop = self._t.hop
+        hop = self.hop
         if t.wlen > 0:
             fsum = self._frame_sums(win, gwin)
             f_hi = -(-t.wlen // hop)
             self._track(fsum, t.keep // hop, f_hi, t.wlen - (f_hi - 1) * hop, final)
         elif final:
-            self._track(self._no_frames(), 0, 0, hop, True)
-
-    def _no_frames(self):
-        return np.zeros((self.S, self._tracker.nb + 1, 0), np.float32)
+            self._track(self._arr.zeros(self.S, self._tracker.nb + 1, 0), 0, 0, hop, True)
 
     def push(self, x, gate=None) -> None:
         if x.shape[0] != self.S or len(x.shape) != 2:
@@ -372,34 +433,65 @@ class SegmentStreamSession(StreamSession):
     def flush(self):
         """The partial last frame, if any, runs with its true length, every open run closes -> the Segments not yet polled."""
         t = self._t.flush()
-        if self._unread:
+        if self._unread[0]:
             self._drain()                                                  # a close at `final` may follow the last one closely
-        e = self._empty()
+        e = self._arr.zeros(self.S, 0)
         self._tick(e, e if self._gated else None, t, True)
         return self.poll()
 
 
-class HipSegmentTracker:
+class _HipTrackerState:
+    """The state and the event rings of n streams on the device, in wv_segment_track's per-stream layouts, with the host's read cursors:
+    what HipSegmentTracker and HipBankSegmentTracker hold, and their two read-backs (one device-to-host copy each)."""
+    _what = "stream"
+
+    def __init__(self, n: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int, ring: int, device, eps: float):
+        import torch
+        from . import ops
+        self.nb, self.hop, self.min_on = int(nb), int(hop), float(min_on)
+        self.G, self.min_len, self.eps, self.device = int(min_gap_frames), int(min_len_frames), float(eps), device
+        self._n, self._ring, self._torch, self._ops = int(n), int(ring), torch, ops
+        with torch.cuda.device(device):
+            self._bytes = ops.segment_track_bytes(self._n, self.nb, self.G, self._ring)          # refuses what the kernel would
+        self._strides = (self._bytes[0] // self._n, self._bytes[1] // self._n)
+
+    def _clear(self) -> None:
+        torch = self._torch
+        self.state = torch.zeros(self._bytes[0], dtype=torch.uint8, device=self.device)
+        self.events = torch.zeros(self._bytes[1], dtype=torch.uint8, device=self.device)
+        self._read = [0] * self._n
+
+    def _new_events(self, streams) -> list:
+        """-> [(stream, its events (lo, hi, count, prob) since the last read)]; refuses a ring that has been overrun."""
+        n, recs = self._ops.segment_events(self.events, self._n, self.nb, self._ring)
+        out = []
+        for s in streams:
+            new = int(n[s]) - self._read[s]
+            if new > self._ring:
+                raise RuntimeError(f"{self._what} {s}: {new} segments closed since the last read of a ring of {self._ring}: events were lost")
+            out.append((s, [(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy())
+                            for r in (recs[s, e % self._ring] for e in range(self._read[s], int(n[s])))]))
+            self._read[s] = int(n[s])
+        return out
+
+    def _open_runs_of(self, streams) -> list:
+        hdr, acc = self._ops.segment_state(self.state, self._n, self.nb)
+        return [(s, _open_run_of(hdr[s], acc[s], self.nb, self.eps)) for s in streams]
+
+
+class HipSegmentTracker(_HipTrackerState):
     """localize.SegmentTracker's interface on wv_segment_track: state and event ring stay on the device; advance() is one launch and no
     synchronisation, poll() and open_runs() are one device-to-host copy each."""
 
     def __init__(self, S: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int, capacity: int, device,
                  eps: float = 1e-8):
-        import torch
-        from . import ops
-        self.S, self.nb, self.hop, self.min_on = int(S), int(nb), int(hop), float(min_on)
-        self.G, self.min_len, self.capacity, self.eps, self.device = int(min_gap_frames), int(min_len_frames), int(capacity), float(eps), device
-        self._torch, self._ops = torch, ops
-        with torch.cuda.device(device):
-            self._bytes = ops.segment_track_bytes(self.S, self.nb, self.G, self.capacity)       # refuses what the kernel would
+        super().__init__(S, nb, hop, min_on, min_gap_frames, min_len_frames, capacity, device, eps)
+        self.S, self.capacity = self._n, self._ring
         self.reset()
 
     def reset(self) -> None:
-        torch = self._torch
-        self.state = torch.zeros(self._bytes[0], dtype=torch.uint8, device=self.device)
-        self.events = torch.zeros(self._bytes[1], dtype=torch.uint8, device=self.device)
+        self._clear()
         self.frames_seen, self.closed = 0, False
-        self._read = [0] * self.S
 
     def advance(self, fsum, f_lo: int = 0, f_hi: Optional[int] = None, last_valid: Optional[int] = None, final: bool = False) -> None:
         if self.closed:
@@ -412,56 +504,52 @@ class HipSegmentTracker:
         self.closed = bool(final)
 
     def poll(self):
-        n, recs = self._ops.segment_events(self.events, self.S, self.nb, self.capacity)
-        out = []
-        for s in range(self.S):
-            new = int(n[s]) - self._read[s]
-            if new > self.capacity:
-                raise RuntimeError(f"stream {s}: {new} segments closed since the last read of a ring of {self.capacity}: events were lost")
-            out.append([(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy())
-                        for r in (recs[s, e % self.capacity] for e in range(self._read[s], int(n[s])))])
-            self._read[s] = int(n[s])
-        return out
+        return [evs for _, evs in self._new_events(range(self.S))]
 
     def open_runs(self):
-        hdr, acc = self._ops.segment_state(self.state, self.S, self.nb)
-        return [_open_run_of(hdr[s], acc[s], self.nb, self.eps) for s in range(self.S)]
+        return [run for _, run in self._open_runs_of(range(self.S))]
 
 
-class SegmentSession(SegmentStreamSession, _HipSession):
+class _SegmentNets:
+    """A detector and a locator HipNet bound for localized detection, as SegmentSession and SegmentBank use them: frame_sums(window batch,
+    gate windows or None) is the detector's frames kernel gated by the caller's 0 / 1 gate or by the locator's logits on the same windows."""
+
+    def _bind(self, detector, locator, threshold: float, precision: str, locator_precision: Optional[str], ring: int, ring_name: str):
+        """Refuses what cannot work before anything is built on the device -> (hop, halo) of the one window the two nets share."""
+        from .localize import gate_threshold
+        locator_precision = precision if locator_precision is None else locator_precision
+        if precision not in _PRECISIONS or locator_precision not in _PRECISIONS:
+            raise ValueError("precision must be 'f32' or 'f16'")
+        if detector.cfg.kind != "detector" or locator.cfg.kind != "locator":
+            raise ValueError("need a detector and a locator")
+        if ring < 1:
+            raise ValueError(f"{ring_name} must be at least 1")
+        self._arr = TorchArrays(detector.device)
+        self.net, self.locator, self.precision, self.locator_precision, self._torch = detector, locator, precision, locator_precision, self._arr.torch
+        self._logit_thr = gate_threshold(threshold)
+        return detector.cfg.hop_length, segment_halo(detector.cfg, locator.cfg)
+
+    def frame_sums(self, win, gwin, out=None):
+        if gwin is not None:
+            return self.net.detector_frame_sums(win, gwin, 0.5, self.precision, out=out)
+        return self.net.detector_frame_sums(win, self.locator.locator(win, precision=self.locator_precision), self._logit_thr, self.precision,
+                                            out=out)
+
+    def _confidence(self, prob: np.ndarray) -> float:
+        return float(self._torch.from_numpy(np.ascontiguousarray(prob, np.float32)).mean())      # as WaveVerify._segments takes it
+
+
+class SegmentSession(_SegmentNets, SegmentStreamSession, _HipSession):
     """SegmentStreamSession on a detector and a locator HipNet: one history and one window per tick for both nets, the locator's logits (or
     the caller's gate) gating the detector's frames kernel, one wv_segment_track per tick.  Nothing comes back to the host in push()."""
 
     def __init__(self, detector, locator, S: int, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2,
                  min_len_frames: int = 5, precision: str = "f32", locator_precision: Optional[str] = None, sample_rate: int = 16000,
                  capacity: int = 64):
-        import torch
-        from .localize import gate_threshold
-        locator_precision = precision if locator_precision is None else locator_precision
-        if precision not in ("f32", "f16") or locator_precision not in ("f32", "f16"):
-            raise ValueError("precision must be 'f32' or 'f16'")
-        if detector.cfg.kind != "detector" or locator.cfg.kind != "locator":
-            raise ValueError("need a detector and a locator")
-        if capacity < 1:
-            raise ValueError("capacity must be at least 1")
-        self.net, self.locator, self.precision, self.locator_precision, self._torch = detector, locator, precision, locator_precision, torch
-        self._logit_thr = gate_threshold(threshold)
-        hop, H = detector.cfg.hop_length, segment_halo(detector.cfg, locator.cfg)
+        hop, H = self._bind(detector, locator, threshold, precision, locator_precision, capacity, "capacity")
         tracker = HipSegmentTracker(S, detector.cfg.head_bits, hop, min_on, min_gap_frames, min_len_frames, capacity, detector.device)
-        SegmentStreamSession.__init__(self, S, hop, H, self._hip_frame_sums, tracker, self._hip_advance,
-                                      lambda S_, cap: torch.zeros((S_, cap), dtype=torch.float32, device=detector.device), sample_rate,
-                                      capacity, min_gap_frames, min_len_frames)
-
-    def _hip_frame_sums(self, win, gwin):
-        if gwin is not None:
-            return self.net.detector_frame_sums(win, gwin, 0.5, self.precision)
-        return self.net.detector_frame_sums(win, self.locator.locator(win, precision=self.locator_precision), self._logit_thr, self.precision)
-
-    def _no_frames(self):
-        return self._torch.zeros((self.S, self._tracker.nb + 1, 0), dtype=self._torch.float32, device=self.net.device)
-
-    def _confidence(self, prob: np.ndarray) -> float:
-        return float(self._torch.from_numpy(np.ascontiguousarray(prob, np.float32)).mean())      # as WaveVerify._segments takes it
+        SegmentStreamSession.__init__(self, S, hop, H, self.frame_sums, tracker, self._hip_advance, self._arr, sample_rate, capacity,
+                                      min_gap_frames, min_len_frames)
 
 
 # ---------------------------------------------------------------------------------------------------------------- session banks
@@ -556,13 +644,14 @@ def numpy_bank_advance(hist: np.ndarray, x: np.ndarray, desc: np.ndarray, A: int
 class StreamBank:
     """`capacity` independent live streams: each slot has its own _Ticker, is opened, pushed to and closed on its own,
     and the slots that complete frames on a tick share one launch per net (per pad_limit group).  forward(window batch [A, 1, Lmax], slots)
-    -> [A, C, Lmax]; advance(history, packed x, desc, A, Lmax) -> window batch, the history updated in place (numpy_bank_advance's contract).
+    -> [A, C, Lmax]; advance(history, packed x, desc, A, Lmax) -> window batch, the history updated in place (numpy_bank_advance's contract);
+    arrays: the backend of the histories (NumpyArrays() if None).
     A window batch is left-aligned: column 0 of row r is that stream's own h0, rows are zero beyond their wlen; the nets are causal and
     push-time wlen are hop multiples, so the padding changes no kept column.  close() runs its ragged window alone, at its true length.
     This base class runs on host arrays; push / close return per slot the kept columns [C, k], or None where nothing completed."""
 
     def __init__(self, capacity: int, hop: int, H: int, forward: Optional[Callable], advance: Optional[Callable] = numpy_bank_advance,
-                 new_history: Optional[Callable] = None, pad_limit: float = 1.5):
+                 arrays=None, pad_limit: float = 1.5):
         if capacity < 1:
             raise ValueError("a bank needs at least one slot")
         if not pad_limit >= 1.0:
@@ -572,7 +661,8 @@ class StreamBank:
         self._tickers = [_Ticker(hop, H) for _ in range(self.capacity)]
         self._is_open = [False] * self.capacity
         self._forward, self._advance = forward, advance
-        self._hist = (new_history or (lambda c, cap: np.zeros((c, cap), np.float32)))(self.capacity, self.hcap)
+        self._arr = arrays or NumpyArrays()
+        self._hist = self._arr.zeros(self.capacity, self.hcap)
         self.stats = {"ticks": 0, "launches": 0, "window_samples": 0, "padded_samples": 0}
 
     # ---- slots
@@ -613,23 +703,21 @@ class StreamBank:
     def close(self, slot: int):
         """The stream's partial last frame at its true length (what flush() is to a lockstep session) -> its last result; frees the slot."""
         self._check_slot(slot)
-        out = self._tick({slot: self._empty()}, {slot: self._tickers[slot].flush()})[slot]
+        out = self._tick({slot: self._arr.zeros(0)}, {slot: self._tickers[slot].flush()})[slot]
         self._is_open[slot] = False
         return out
 
-    def _empty(self):
-        return np.zeros(0, np.float32)
-
-    def _count(self, plan: BankPlan) -> None:
+    def _plan(self, xs: dict, ticks: dict) -> BankPlan:
+        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
         self.stats["ticks"] += 1
         self.stats["launches"] += sum(1 for ln in plan.launches if ln.A)
         self.stats["window_samples"] += sum(ln.A * ln.Lmax for ln in plan.launches)
         self.stats["padded_samples"] += plan.padded
+        return plan
 
     def _tick(self, xs: dict, ticks: dict) -> dict:
-        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
-        self._count(plan)
-        x = np.concatenate([np.asarray(xs[s]) for s in plan.slots]) if plan.slots else self._empty()
+        plan = self._plan(xs, ticks)
+        x = self._arr.cat([xs[s] for s in plan.slots])
         res = {s: None for s in xs}
         for ln in plan.launches:
             win = self._advance(self._hist, x, plan.desc[ln.p_lo:ln.p_hi], ln.A, ln.Lmax)
@@ -645,16 +733,12 @@ class _HipBank(StreamBank):
     """StreamBank on a HipNet: histories, windows and outputs stay on the device.  A tick uploads ONE table (the wv_bank_advance descriptors and
     whatever else its launches read), then runs per launch wv_bank_advance and the net on the window batch."""
 
-    def __init__(self, net, capacity: int, precision: str, pad_limit: float):
-        import torch
-        if precision not in ("f32", "f16"):
+    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5):
+        if precision not in _PRECISIONS:
             raise ValueError("precision must be 'f32' or 'f16'")
-        self.net, self.precision, self._torch = net, precision, torch
-        super().__init__(capacity, net.cfg.hop_length, _halo(net.cfg), None, None,
-                         lambda c, cap: torch.zeros((c, cap), dtype=torch.float32, device=net.device), pad_limit)
-
-    def _empty(self):
-        return self._torch.zeros(0, dtype=self._torch.float32, device=self.net.device)
+        arrays = TorchArrays(net.device)
+        self.net, self.precision, self._torch = net, precision, arrays.torch
+        super().__init__(capacity, net.cfg.hop_length, _halo(net.cfg), None, None, arrays, pad_limit)
 
     def _upload(self, sections: list) -> dict:
         """[(name, host array)] -> {name: device tensor}: one buffer, every section on an 8-byte boundary, one copy."""
@@ -670,6 +754,19 @@ class _HipBank(StreamBank):
         return {name: dev[o:o + a.nbytes].view(getattr(torch, a.dtype.name)).view(a.shape)
                 for o, (name, a) in zip(offs, sections)}
 
+    def _packed(self, xs: dict, slots: list):
+        """The tick's new samples (or gates) of `slots`, one after another in one device tensor; None where nobody brought any."""
+        dev, f32 = self.net.device, self._torch.float32
+        parts = [xs[s].to(dev, f32) for s in slots if xs[s].shape[0]]
+        return self._torch.cat(parts) if parts else None
+
+    def _bank_advance(self, hist, x, n_x: int, desc, ln: BankLaunch):
+        """wv_bank_advance for one launch: desc the tick's uploaded descriptor table -> the window batch [A, 1, Lmax], None where A = 0."""
+        win = self._torch.empty((ln.A, 1, ln.Lmax), dtype=self._torch.float32, device=self.net.device) if ln.A else None
+        _lib.check(self.net._lib.wv_bank_advance(hist.data_ptr(), self.capacity, self.hcap, _lib.ptr(x), n_x, desc[ln.p_lo:].data_ptr(),
+                                                 ln.p_hi - ln.p_lo, _lib.ptr(win), ln.A, ln.Lmax, _lib.stream()), "wv_bank_advance")
+        return win
+
     def _sections(self, plan: BankPlan) -> list:
         return []
 
@@ -677,36 +774,53 @@ class _HipBank(StreamBank):
         pass
 
     def _tick(self, xs: dict, ticks: dict) -> dict:
-        torch, dev = self._torch, self.net.device
-        from . import _lib
-        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
-        self._count(plan)
+        plan = self._plan(xs, ticks)
         if plan.launches:
-            with torch.cuda.device(dev):
-                parts = [xs[s].to(dev, torch.float32) for s in plan.slots if xs[s].shape[0]]
-                x = torch.cat(parts) if parts else None
+            with self._torch.cuda.device(self.net.device):
+                x = self._packed(xs, plan.slots)
                 tabs = self._upload([("desc", plan.desc)] + self._sections(plan))
                 self._begin(plan, tabs)
                 for ln in plan.launches:
-                    win = torch.empty((ln.A, 1, ln.Lmax), dtype=torch.float32, device=dev) if ln.A else None
-                    _lib.check(self.net._lib.wv_bank_advance(
-                        self._hist.data_ptr(), self.capacity, self.hcap, _lib.ptr(x), plan.n_x, tabs["desc"][ln.p_lo:].data_ptr(),
-                        ln.p_hi - ln.p_lo, _lib.ptr(win), ln.A, ln.Lmax, _lib.stream()), "wv_bank_advance")
+                    win = self._bank_advance(self._hist, x, plan.n_x, tabs["desc"], ln)
                     if ln.A:
                         self._launch(win, tabs, plan, ln)
                 return self._finish(plan, tabs)
         return self._finish(plan, None)
 
 
-class EmbedBank(_HipBank):
-    """Watermark up to `capacity` live 16 kHz mono streams, each on its own clock: open(message) -> slot, push({slot: x [n]}) -> {slot: the
-    watermarked samples of the frames that push completed [k]}, close(slot) -> the rest.  The values of a tick are views of one tensor.
-    messages: what turns open()'s argument into a [msg_dimension] bit tensor (WaveVerify passes its watermark-id table); without it open()
-    takes the bits themselves.  The messages live on the host and travel in the tick's table, so open() touches no device memory."""
+class _ColumnsBank(_HipBank):
+    """A _HipBank that returns per slot the kept columns [k] of _net(window batch, tabs, launch) -> [A, 1, Lmax]: wv_window_scatter packs
+    them into one tensor, and the values of a tick are views of it."""
 
-    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5, messages: Optional[Callable] = None):
+    def _sections(self, plan: BankPlan) -> list:
+        # wv_window_scatter's descriptor per window: {offset in `out` of the window's column 0, row stride (one row: unused), keep lo, keep hi}
+        return [("scatter", np.array([[plan.out[s][0] - t.keep, plan.n_out, t.keep, t.wlen] for s, t in plan.windows], np.int64).reshape(-1, 4))]
+
+    def _begin(self, plan: BankPlan, tabs: dict) -> None:
+        self._out = self._torch.empty(plan.n_out, dtype=self._torch.float32, device=self.net.device)
+
+    def _launch(self, win, tabs: dict, plan: BankPlan, ln: BankLaunch) -> None:
+        y = self._net(win, tabs, ln)
+        _lib.check(self.net._lib.wv_window_scatter(y.data_ptr(), tabs["scatter"][ln.a_lo:].data_ptr(), self._out.data_ptr(), plan.n_out, ln.A, 1,
+                                                   ln.Lmax, _lib.stream()), "wv_window_scatter")
+
+    def _finish(self, plan: BankPlan, tabs) -> dict:
+        out = self._out if tabs is not None else self._arr.zeros(0)
+        self._out = None
+        return {s: out[o:o + k] for s, (o, k) in plan.out.items()}
+
+
+class EmbedBank(_ColumnsBank):
+    """Watermark up to `capacity` live 16 kHz mono streams, each on its own clock: open(message) -> slot, push({slot: x [n]}) -> {slot: the
+    watermarked samples of the frames that push completed [k]}, close(slot) -> the rest.
+    messages: what turns open()'s argument into a [msg_dimension] bit tensor (WaveVerify passes its watermark-id table); without it open()
+    takes the bits themselves.  The messages live on the host and travel in the tick's table, so open() touches no device memory.
+    add_input=False: the generator's residual alone (what native_bank.py brings back to each slot's own rate)."""
+
+    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5, messages: Optional[Callable] = None,
+                 add_input: bool = True):
         super().__init__(net, capacity, precision, pad_limit)
-        self._messages = messages
+        self._messages, self.add_input = messages, bool(add_input)
         self._msg = np.zeros((self.capacity, net.cfg.msg_dimension), np.float32)
 
     def _on_open(self, slot: int, message) -> None:
@@ -716,45 +830,18 @@ class EmbedBank(_HipBank):
             raise ValueError(f"a message has {self._msg.shape[1]} bits, got {m.shape[0]}")
         self._msg[slot] = m
 
-    def _scatter_section(self, plan: BankPlan):
-        # wv_window_scatter's descriptor per window: {offset in `out` of the window's column 0, row stride (one row: unused), keep lo, keep hi}
-        return "scatter", np.array([[plan.out[s][0] - t.keep, plan.n_out, t.keep, t.wlen] for s, t in plan.windows], np.int64).reshape(-1, 4)
-
     def _sections(self, plan: BankPlan) -> list:
-        return [self._scatter_section(plan), ("msg", self._msg[[s for s, _ in plan.windows]])]
+        return super()._sections(plan) + [("msg", self._msg[[s for s, _ in plan.windows]])]
 
-    def _begin(self, plan: BankPlan, tabs: dict) -> None:
-        self._out = self._torch.empty(plan.n_out, dtype=self._torch.float32, device=self.net.device)
-
-    def _net_forward(self, win, tabs: dict, ln: BankLaunch):
-        return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=True, precision=self.precision)
-
-    def _launch(self, win, tabs: dict, plan: BankPlan, ln: BankLaunch) -> None:
-        from . import _lib
-        y = self._net_forward(win, tabs, ln)
-        _lib.check(self.net._lib.wv_window_scatter(y.data_ptr(), tabs["scatter"][ln.a_lo:].data_ptr(), self._out.data_ptr(), plan.n_out, ln.A, 1,
-                                                   ln.Lmax, _lib.stream()), "wv_window_scatter")
-
-    def _finish(self, plan: BankPlan, tabs) -> dict:
-        out = self._out if tabs is not None else self._empty()
-        self._out = None
-        return {s: out[o:o + k] for s, (o, k) in plan.out.items()}
+    def _net(self, win, tabs: dict, ln: BankLaunch):
+        return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=self.add_input, precision=self.precision)
 
 
-class LocateBank(EmbedBank):
+class LocateBank(_ColumnsBank):
     """Locate the watermark in up to `capacity` live streams: open() -> slot, push({slot: x [n]}) -> {slot: locator logits of the newly completed
     frames [k]}."""
 
-    def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5):
-        _HipBank.__init__(self, net, capacity, precision, pad_limit)
-
-    def _on_open(self, slot: int) -> None:
-        pass
-
-    def _sections(self, plan: BankPlan) -> list:
-        return [self._scatter_section(plan)]
-
-    def _net_forward(self, win, tabs: dict, ln: BankLaunch):
+    def _net(self, win, tabs: dict, ln: BankLaunch):
         return self.net.locator(win, precision=self.precision)
 
 
@@ -765,10 +852,10 @@ class DetectBank(_HipBank):
 
     def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5):
         super().__init__(net, capacity, precision, pad_limit)
-        torch, nb = self._torch, net.cfg.head_bits
-        self._acc = torch.zeros((self.capacity, nb), dtype=torch.float64, device=net.device)
-        self._seen = torch.zeros(self.capacity, dtype=torch.int64, device=net.device)
-        self._zero = (torch.zeros(nb, dtype=torch.float32, device=net.device), torch.zeros(nb, dtype=torch.int32, device=net.device))
+        zeros, nb = self._arr.zeros, net.cfg.head_bits
+        self._acc = zeros(self.capacity, nb, dtype="float64")
+        self._seen = zeros(self.capacity, dtype="int64")
+        self._zero = (zeros(nb), zeros(nb, dtype="int32"))
         self._last = [self._zero] * self.capacity
 
     def _on_open(self, slot: int) -> None:
@@ -791,7 +878,6 @@ class DetectBank(_HipBank):
     def _finish(self, plan: BankPlan, tabs) -> dict:
         torch, A, nb = self._torch, len(plan.windows), self.net.cfg.head_bits
         if A:
-            from . import _lib
             mp = torch.empty((A, nb), dtype=torch.float32, device=self.net.device)
             bits = torch.empty((A, nb), dtype=torch.int32, device=self.net.device)
             with torch.cuda.device(self.net.device):
@@ -805,7 +891,7 @@ class DetectBank(_HipBank):
 
 
 # ---------------------------------------------------------------------------------------------------------------- segment banks
-class SegmentStreamBank(StreamBank):
+class SegmentStreamBank(_SegmentReader, StreamBank):
     """Localized detection of up to `capacity` live streams, each on its own clock: open() -> slot, push({slot: x [n]})
     returns nothing (a gated bank takes {slot: (x [n], gate [n])}, the 0 / 1 gate replacing the locator), poll() -> {slot: the Segments that
     closed since the last poll}, open_segments() -> {slot: the run still open, or None}, close(slot) -> the slot's Segments not yet polled.
@@ -817,24 +903,20 @@ class SegmentStreamBank(StreamBank):
     where that stream's rows are and which of their frames are its own: [keep / hop, ceil(wlen / hop)).  The frames of a row beyond its wlen
     are computed on the batch's zero padding and belong to nobody; no descriptor reaches them.
 
-    ring is the tracker's event ring per slot.  The frames tracked since a slot was last read bound its waiting events by
-    frames // max(1, min_len_frames + min_gap_frames) + 1; before a tick would let any slot's bound reach `ring` the bank reads the rings
-    itself (the one host synchronisation a push can make), and a long push is tracked in pieces that stay within the bound, so nothing is lost."""
+    ring is the tracker's event ring per slot.  Before a tick would let cut_rows' bound on any slot's waiting events reach `ring` the bank reads
+    the rings itself, and a long push is tracked in pieces that stay within the bound, so nothing is lost."""
 
     def __init__(self, capacity: int, hop: int, H: int, frame_sums: Callable, tracker, advance: Optional[Callable] = numpy_bank_advance,
-                 new_history: Optional[Callable] = None, pad_limit: float = 1.5, gated: bool = False, sample_rate: int = 16000, ring: int = 64,
+                 arrays=None, pad_limit: float = 1.5, gated: bool = False, sample_rate: int = 16000, ring: int = 64,
                  min_gap_frames: int = 2, min_len_frames: int = 5):
         if ring < 1:
             raise ValueError("ring must be at least 1")
-        new_history = new_history or (lambda c, cap: np.zeros((c, cap), np.float32))
-        StreamBank.__init__(self, capacity, hop, H, None, advance, new_history, pad_limit)
+        StreamBank.__init__(self, capacity, hop, H, None, advance, arrays, pad_limit)
         self._frame_sums, self._tracker, self.gated = frame_sums, tracker, bool(gated)
-        self.sample_rate, self.ring = int(sample_rate), int(ring)
-        self._period = max(1, int(min_len_frames) + int(min_gap_frames))
-        self._ghist = new_history(self.capacity, self.hcap) if self.gated else None
+        self._init_reader(hop, sample_rate, ring, min_gap_frames, min_len_frames)
+        self._clear_reader(self.capacity, self.capacity)
+        self._ghist = self._arr.zeros(self.capacity, self.hcap) if self.gated else None
         self._frames = [0] * self.capacity                                 # frames tracked so far: the next tick's frame0
-        self._unread = [0] * self.capacity                                 # frames tracked since the slot's ring was last read
-        self._pending = [[] for _ in range(self.capacity)]
 
     # ---- slots
     def _on_open(self, slot: int) -> None:
@@ -842,31 +924,18 @@ class SegmentStreamBank(StreamBank):
         self._frames[slot] = self._unread[slot] = 0
         self._pending[slot] = []
 
-    # ---- events -> Segments
-    def _confidence(self, prob: np.ndarray) -> float:
-        return float(np.asarray(prob, np.float32).mean())
-
-    def _segment(self, slot: int, ev):
-        return _segment_of(ev, self.hop, self._tickers[slot].t_in, self.sample_rate, self._confidence)
-
-    def _drain(self) -> None:
-        slots = self.open_slots()
-        for s, evs in self._tracker.poll(slots).items():
-            self._pending[s] += [self._segment(s, ev) for ev in evs]
-        for s in slots:
-            self._unread[s] = 0
+    def _streams(self, read: Callable) -> list:
+        tk = self._tickers
+        return [(s, tk[s].t_in, v) for s, v in read(self.open_slots()).items()]
 
     def poll(self) -> dict:
         """-> {slot: the Segments closed since the last poll, in stream order} for every open slot."""
         self._drain()
-        out = {s: self._pending[s] for s in self.open_slots()}
-        for s in out:
-            self._pending[s] = []
-        return out
+        return {s: self._taken(s) for s in self.open_slots()}
 
     def open_segments(self) -> dict:
         """-> {slot: the run that is open now as a provisional Segment (its frames so far), or None} for every open slot."""
-        return {s: None if ev is None else self._segment(s, ev) for s, ev in self._tracker.open_runs(self.open_slots()).items()}
+        return dict(self._open_now())
 
     # ---- ticks
     def push(self, items: dict) -> None:
@@ -893,63 +962,40 @@ class SegmentStreamBank(StreamBank):
         self._check_slot(slot)
         if self._unread[slot]:
             self._drain()                                                  # a close at `final` may follow the last one closely
-        e = self._empty()
+        e = self._arr.zeros(0)
         self._tick({slot: e}, {slot: e if self.gated else None}, {slot: self._tickers[slot].flush()}, True)
         self._drain()
-        out, self._pending[slot] = self._pending[slot], []
         self._is_open[slot] = False
-        return out
+        return self._taken(slot)
 
     def _track_rows(self, plan: BankPlan, ticks: dict, final: bool):
-        """-> (offset of every launch's frame sums in the tick's arena, the arena's length, the tracker's descriptor rows)."""
+        """-> (offset of every launch's frame sums in the tick's arena, the arena's length, the tracker's descriptor rows); the slots' frame
+        counters move on to the tick's end."""
         hop, nb1 = self.hop, self._tracker.nb + 1
         offs, rows, n_fsum = [], [], 0
         for ln in plan.launches:
             Fr = -(-ln.Lmax // hop)
             offs.append(n_fsum)
             for r, (s, t) in enumerate(plan.windows[ln.a_lo:ln.a_lo + ln.A]):
-                f_hi = -(-t.wlen // hop)                                   # the frames from f_hi on are the batch's padding
-                rows.append([s, n_fsum + r * nb1 * Fr, Fr, t.keep // hop, f_hi, self._frames[s], t.wlen - (f_hi - 1) * hop, int(final)])
+                f_lo, f_hi = t.keep // hop, -(-t.wlen // hop)              # the frames from f_hi on are the batch's padding
+                rows.append([s, n_fsum + r * nb1 * Fr, Fr, f_lo, f_hi, self._frames[s], t.wlen - (f_hi - 1) * hop, int(final)])
+                self._frames[s] += f_hi - f_lo
             n_fsum += -(-ln.A * nb1 * Fr // 4) * 4                         # every launch's block starts on a 16-byte boundary
         if final:
             named = {r[0] for r in rows}
             rows += [[s, 0, 0, 0, 0, self._frames[s], hop, 1] for s in ticks if s not in named]     # no frame left: the open run still closes
         return offs, n_fsum, rows
 
-    def _pieces(self, rows: list):
-        """The tick's descriptor rows cut so that no slot's bound reaches `ring` between two reads -> ([(read the rings first, rows [P, 8])],
-        the slots' unread frames after them); the slots' frame counters move on to the tick's end.  A tick of ordinary pushes is one piece."""
-        step = max(1, self.ring * self._period - 1)                        # frames // period + 1 <= ring
-        unread, hop = list(self._unread), self.hop
-        out, left = [], [list(r) for r in rows]
-        while left:
-            m = [min(step, r[4] - r[3]) for r in left]
-            drain = any(unread[r[0]] and (unread[r[0]] + k) // self._period + 1 >= self.ring for r, k in zip(left, m))
-            if drain:
-                unread = [0] * self.capacity
-            piece, nxt = [], []
-            for (s, off, Fr, lo, hi, f0, lv, fin), k in zip(left, m):
-                last = lo + k == hi
-                piece.append([s, off, Fr, lo, lo + k, f0, lv if last else hop, fin if last else 0])
-                unread[s] += k
-                self._frames[s] = f0 + k
-                if not last:
-                    nxt.append([s, off, Fr, lo + k, hi, f0 + k, lv, fin])
-            out.append((drain, np.array(piece, np.int64).reshape(-1, 8)))
-            left = nxt
-        return out, unread
-
     def _tick(self, xs: dict, gs: dict, ticks: dict, final: bool) -> None:
-        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
-        self._count(plan)
+        plan = self._plan(xs, ticks)
         offs, n_fsum, rows = self._track_rows(plan, ticks, final)
-        pieces, unread = self._pieces(rows)
-        self._run(plan, xs, gs, offs, n_fsum, pieces)
+        pieces, unread = self._cut(rows)
+        self._run(plan, xs, gs, offs, n_fsum, [(drain, np.array(piece, np.int64).reshape(-1, 8)) for drain, piece in pieces])
         self._unread = unread
 
     def _run(self, plan: BankPlan, xs: dict, gs: dict, offs: list, n_fsum: int, pieces: list) -> None:
-        x = np.concatenate([np.asarray(xs[s]) for s in plan.slots]) if plan.slots else self._empty()
-        g = np.concatenate([np.asarray(gs[s]) for s in plan.slots]) if plan.slots and self.gated else None
+        x = self._arr.cat([xs[s] for s in plan.slots])
+        g = self._arr.cat([gs[s] for s in plan.slots]) if self.gated else None
         arena = np.zeros(n_fsum, self._tracker.dtype)
         for ln, off in zip(plan.launches, offs):
             desc = plan.desc[ln.p_lo:ln.p_hi]
@@ -964,24 +1010,17 @@ class SegmentStreamBank(StreamBank):
             self._tracker.advance(arena, rows)
 
 
-class HipBankSegmentTracker:
+class HipBankSegmentTracker(_HipTrackerState):
     """localize.BankSegmentTracker's interface on wv_bank_segment_track: the slots' state and event rings stay on the device in
     wv_segment_track's per-stream layouts; advance() is one launch and no synchronisation, reset() two fills on the stream, poll() and
     open_runs() one device-to-host copy each."""
+    _what = "slot"
 
     def __init__(self, capacity: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int, ring: int, device,
                  eps: float = 1e-8):
-        import torch
-        from . import ops
-        self.capacity, self.nb, self.hop, self.min_on = int(capacity), int(nb), int(hop), float(min_on)
-        self.G, self.min_len, self.ring, self.eps, self.device = int(min_gap_frames), int(min_len_frames), int(ring), float(eps), device
-        self._torch, self._ops = torch, ops
-        with torch.cuda.device(device):
-            sb, eb = ops.segment_track_bytes(self.capacity, self.nb, self.G, self.ring)          # refuses what the kernel would
-        self._strides = (sb // self.capacity, eb // self.capacity)
-        self.state = torch.zeros(sb, dtype=torch.uint8, device=device)
-        self.events = torch.zeros(eb, dtype=torch.uint8, device=device)
-        self._read = [0] * self.capacity
+        super().__init__(capacity, nb, hop, min_on, min_gap_frames, min_len_frames, ring, device, eps)
+        self.capacity, self.ring = self._n, self._ring
+        self._clear()
 
     def reset(self, slot: int) -> None:
         ss, es = self._strides
@@ -1000,23 +1039,13 @@ class HipBankSegmentTracker:
                                          self.min_on, self.G, self.min_len, self.state, self.events, self.ring, self.eps)
 
     def poll(self, slots) -> dict:
-        n, recs = self._ops.segment_events(self.events, self.capacity, self.nb, self.ring)
-        out = {}
-        for s in slots:
-            new = int(n[s]) - self._read[s]
-            if new > self.ring:
-                raise RuntimeError(f"slot {s}: {new} segments closed since the last read of a ring of {self.ring}: events were lost")
-            out[s] = [(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy())
-                      for r in (recs[s, e % self.ring] for e in range(self._read[s], int(n[s])))]
-            self._read[s] = int(n[s])
-        return out
+        return dict(self._new_events(slots))
 
     def open_runs(self, slots) -> dict:
-        hdr, acc = self._ops.segment_state(self.state, self.capacity, self.nb)
-        return {s: _open_run_of(hdr[s], acc[s], self.nb, self.eps) for s in slots}
+        return dict(self._open_runs_of(slots))
 
 
-class SegmentBank(SegmentStreamBank, _HipBank):
+class SegmentBank(_SegmentNets, SegmentStreamBank, _HipBank):
     """SegmentStreamBank on a detector and a locator HipNet: one history per slot for both nets (a gated bank has a second one for the gate,
     advanced by a second wv_bank_advance with the same rows), per launch the locator's logits (or the gate windows) gating the detector's
     frames kernel into that launch's block of the tick's arena, then ONE wv_bank_segment_track.  A tick uploads one table: the
@@ -1025,55 +1054,27 @@ class SegmentBank(SegmentStreamBank, _HipBank):
     def __init__(self, detector, locator, capacity: int = 64, pad_limit: float = 1.5, threshold: float = 0.5, min_on: float = 0.5,
                  min_gap_frames: int = 2, min_len_frames: int = 5, ring: int = 64, gated: bool = False, precision: str = "f32",
                  locator_precision: Optional[str] = None, sample_rate: int = 16000):
-        import torch
-        from .localize import gate_threshold
-        locator_precision = precision if locator_precision is None else locator_precision
-        if precision not in ("f32", "f16") or locator_precision not in ("f32", "f16"):
-            raise ValueError("precision must be 'f32' or 'f16'")
-        if detector.cfg.kind != "detector" or locator.cfg.kind != "locator":
-            raise ValueError("need a detector and a locator")
-        if ring < 1:
-            raise ValueError("ring must be at least 1")
-        self.net, self.locator, self.precision, self.locator_precision, self._torch = detector, locator, precision, locator_precision, torch
-        self._logit_thr = gate_threshold(threshold)
-        hop, H = detector.cfg.hop_length, segment_halo(detector.cfg, locator.cfg)
+        hop, H = self._bind(detector, locator, threshold, precision, locator_precision, ring, "ring")
         tracker = HipBankSegmentTracker(capacity, detector.cfg.head_bits, hop, min_on, min_gap_frames, min_len_frames, ring, detector.device)
-        SegmentStreamBank.__init__(self, capacity, hop, H, None, tracker, None,
-                                   lambda c, cap: torch.zeros((c, cap), dtype=torch.float32, device=detector.device), pad_limit, gated,
-                                   sample_rate, ring, min_gap_frames, min_len_frames)
-
-    def _confidence(self, prob: np.ndarray) -> float:
-        return float(self._torch.from_numpy(np.ascontiguousarray(prob, np.float32)).mean())      # as WaveVerify._segments takes it
-
-    def _bank_advance(self, hist, x, desc, ln: BankLaunch, n_x: int):
-        from . import _lib
-        win = self._torch.empty((ln.A, 1, ln.Lmax), dtype=self._torch.float32, device=self.net.device) if ln.A else None
-        _lib.check(self.net._lib.wv_bank_advance(hist.data_ptr(), self.capacity, self.hcap, _lib.ptr(x), n_x, desc[ln.p_lo:].data_ptr(),
-                                                 ln.p_hi - ln.p_lo, _lib.ptr(win), ln.A, ln.Lmax, _lib.stream()), "wv_bank_advance")
-        return win
+        SegmentStreamBank.__init__(self, capacity, hop, H, None, tracker, None, self._arr, pad_limit, gated, sample_rate, ring, min_gap_frames,
+                                   min_len_frames)
 
     def _run(self, plan: BankPlan, xs: dict, gs: dict, offs: list, n_fsum: int, pieces: list) -> None:
         torch, dev, nb1 = self._torch, self.net.device, self._tracker.nb + 1
         if not plan.launches and not pieces:
             return
         with torch.cuda.device(dev):
-            pushed = [s for s in plan.slots if xs[s].shape[0]]
-            x = torch.cat([xs[s].to(dev, torch.float32) for s in pushed]) if pushed else None
-            g = torch.cat([gs[s].to(dev, torch.float32) for s in pushed]) if pushed and self.gated else None
+            x = self._packed(xs, plan.slots)
+            g = self._packed(gs, plan.slots) if self.gated else None
             track = np.concatenate([rows for _, rows in pieces]) if pieces else np.zeros((0, 8), np.int64)
             tabs = self._upload([(name, a) for name, a in (("desc", plan.desc), ("track", track)) if a.size])
             arena = torch.empty(n_fsum, dtype=torch.float32, device=dev) if n_fsum else None
             for ln, off in zip(plan.launches, offs):
-                win = self._bank_advance(self._hist, x, tabs["desc"], ln, plan.n_x)
-                gwin = self._bank_advance(self._ghist, g, tabs["desc"], ln, plan.n_x) if self.gated else None
+                win = self._bank_advance(self._hist, x, plan.n_x, tabs["desc"], ln)
+                gwin = self._bank_advance(self._ghist, g, plan.n_x, tabs["desc"], ln) if self.gated else None
                 if ln.A:
                     Fr = -(-ln.Lmax // self.hop)
-                    out = arena[off:off + ln.A * nb1 * Fr].view(ln.A, nb1, Fr)
-                    if self.gated:
-                        self.net.detector_frame_sums(win, gwin, 0.5, self.precision, out=out)
-                    else:
-                        self.net.detector_frame_sums(win, self.locator.locator(win, precision=self.locator_precision), self._logit_thr,
-                                                     self.precision, out=out)
+                    self.frame_sums(win, gwin, out=arena[off:off + ln.A * nb1 * Fr].view(ln.A, nb1, Fr))
             p = 0
             for drain, rows in pieces:
                 if drain:
