@@ -267,7 +267,27 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          Refused with WV_EINVAL and nothing written: null desc, state or events, n_fsum < 0 or n_fsum > 0 without fsum;
  *                          capacity outside [1, WV_BANK_MAX_SLOTS], P outside [0, 65535], nb outside [1, WV_SEGMENT_MAX_BITS], hop < 1,
  *                          min_gap_frames outside [1, WV_SEGMENT_MAX_GAP], min_len_frames < 0, ring < 1, min_on not a number; state or
- *                          events shorter than `capacity` streams need, or not 8-byte aligned.  P == 0 is success without a launch. */
+ *                          events shorter than `capacity` streams need, or not 8-byte aligned.  P == 0 is success without a launch.
+ *   wv_span_gather         span embedding (window.py plan_spans / span_generator): dst [A,1,Lmax] from the packed clips
+ *                          src (n_src samples); desc [A][2] int64 device = {src offset, wlen}.  Row r = src[off .. off + wlen), then zeros in
+ *                          [wlen, Lmax): a left-aligned, right-zero-padded window batch of rows of their own lengths.  16-byte moves where
+ *                          source and destination are aligned, scalar at the edges.
+ *                          A descriptor row is SKIPPED whole (its dst row untouched) unless 0 <= off, off + wlen <= n_src and
+ *                          0 <= wlen <= Lmax; the other rows are served.
+ *                          Refused with WV_EINVAL and nothing written: null desc or dst, n_src < 0 or n_src > 0 without src, A outside
+ *                          [0, 65535], Lmax < 1.  A == 0 is success without a launch.
+ *   wv_span_scatter_add    y [A,1,Lmax] (the generator's residual on wv_span_gather's batch); desc [A][5] int64 device = {offset in out of the
+ *                          window's column 0, keep lo, keep hi, span start, span end}, the last four relative to the window's column 0 (the span
+ *                          start may be negative and the span end beyond Lmax: a span spread over several windows).  For j in [lo, hi):
+ *                            w = gain * ramp[m] where m = min(j - span start, span end - 1 - j) < F, else w = gain;
+ *                            v = w * y[r][j];   out[o + j] = x[o + j] + v   (v alone where x is null)
+ *                          all in f32, every rounding kept, no contraction to an fma.  ramp [F] f32 device, null when F == 0.  x may be out
+ *                          (each element is read and then written by the same thread); x and out are n_out floats.  Nothing outside the
+ *                          rows' keep ranges is written.  THE CALLER'S DUTY: the keep ranges of one call are disjoint in out.
+ *                          A descriptor row is SKIPPED whole unless 0 <= lo < hi <= Lmax, span start <= lo, hi <= span end, 0 <= o + lo and
+ *                          o + hi <= n_out; the other rows are served.
+ *                          Refused with WV_EINVAL and nothing written: null y, desc or out, n_out < 1, F < 0, F > 0 without ramp, gain not a
+ *                          number, A outside [0, 65535], Lmax < 1.  A == 0 is success without a launch. */
 #define WV_SEGMENT_MAX_GAP 64
 #define WV_SEGMENT_MAX_BITS 255
 #define WV_BANK_MAX_SLOTS 1048576
@@ -294,6 +314,9 @@ int wv_bank_detect_update(double* acc, int64_t* seen, int capacity, int nb, cons
 int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
                           int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes, void* events, size_t event_bytes,
                           int ring, void* stream);
+int wv_span_gather(const float* src, int64_t n_src, const int64_t* desc, float* dst, int A, int Lmax, void* stream);
+int wv_span_scatter_add(const float* y, const float* x, const int64_t* desc, const float* ramp, int F, float gain, float* out, int64_t n_out,
+                        int A, int Lmax, void* stream);
 
 /* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------

@@ -221,6 +221,75 @@ class WaveVerify:
         return window.windowed_generator(self._need("generator"), clips, self._messages(watermark_ids),
                                          self._window_samples(window_seconds), self.generator_precision)
 
+    # ------------------------------------------------------------------ span embedding (NOT in the reference)
+    def _span_messages(self, spans):
+        """Per clip a list of (start, end, watermark id) -> (messages [M,16] of the distinct ids, the spans with each id replaced by its
+        row, the validated ids in the spans' order)."""
+        rows, ids, out = {}, [], []
+        for lst in spans:
+            mine = []
+            for s, e, w in lst:
+                w = self._validate_watermark_id(w)
+                ids.append(w)
+                mine.append((s, e, rows.setdefault(w.to_bits(), len(rows))))
+            out.append(mine)
+        if not rows:
+            return torch.zeros((1, self.watermark_bits)), out, ids
+        return torch.cat([message_to_tensor(bits, self.watermark_bits) for bits in rows]), out, ids
+
+    @torch.no_grad()
+    def embed_spans_clips(self, clips, spans, window_seconds: float = 30.0, fade_samples: int = 0, strength: float = 1.0,
+                          pad_limit: float = 1.5):
+        """Watermark chosen stretches, each with its own id.  clips: a list of 1-D tensors of any lengths (or [B,1,T]); spans: per clip a
+        list of (start, end, watermark_id) in samples, disjoint (abutting is allowed) -> the clips, same kind: inside a span
+        x + w * G(x, id)'s residual of the whole clip, w = strength times a raised-cosine ramp of fade_samples at both span edges
+        (0: a hard cut); outside every span the input bit for bit.  Only halo + span samples go through the generator."""
+        msgs, rows, _ = self._span_messages(spans)
+        return window.span_generator(self._need("generator"), clips, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
+                                     pad_limit, fade_samples=fade_samples, gain=strength)
+
+    @torch.no_grad()
+    def embed_spans_native_batch(self, audio: torch.Tensor, sample_rate: int, spans, strength: float = 1.0, fade_samples: int = 0,
+                                 window_seconds: float = 30.0) -> torch.Tensor:
+        """embed_native_batch for chosen stretches: audio [B,C,Tn] (or [C,Tn]) at `sample_rate`; spans per clip (start, end, watermark_id) in
+        16 kHz samples of to_model_rate(audio), fade_samples too.  The masked residual is built dense at 16 kHz (zeros outside the spans),
+        then brought up to `sample_rate` and added to every channel by the one full-length native.upsample_add pass."""
+        gen = self._need("generator")
+        audio = audio.to(self.device)
+        msgs, rows, _ = self._span_messages(spans)
+        x16 = self.to_model_rate(audio, sample_rate)
+        d16 = window.span_generator(gen, x16, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
+                                    fade_samples=fade_samples, gain=1.0, add_input=False)
+        return native.upsample_add(audio, d16, sample_rate, strength)
+
+    def embed_spans(self, audio_path: Union[str, Path], spans, output_path: Optional[Union[str, Path]] = None, *, native: bool = False,
+                    strength: float = 1.0, fade_ms: float = 0.0, window_seconds: float = 30.0) -> Tuple[np.ndarray, int, List[WatermarkID]]:
+        """embed for chosen stretches of a file: spans (start_s, end_s, watermark_id) in seconds, rounded to 16 kHz samples; an end past the
+        file's end is clamped -> (array, sample rate, the validated ids) shaped as embed's.  native, strength: as in embed."""
+        if not native and strength != 1.0:
+            raise ValueError("strength other than 1.0 needs native=True (the reference's route adds the residual as it is)")
+        try:
+            fs = self.sample_rate
+            fade = int(round(float(fade_ms) * fs / 1000.0))
+            in_samples = lambda T: [[(int(round(float(s) * fs)), min(int(round(float(e) * fs)), T), w) for s, e, w in spans]]   # noqa: E731
+            ids = [self._validate_watermark_id(w) for _, _, w in spans]
+            if native:
+                audio, sr = load_audio_native(audio_path)                           # [C, Tn] at the file's rate
+                T16 = int(self.to_model_rate(audio.unsqueeze(0), sr).shape[-1])
+                wm = self.embed_spans_native_batch(audio.unsqueeze(0), sr, in_samples(T16), strength, fade, window_seconds).squeeze(0)
+                if output_path:
+                    save_audio(wm, output_path, sr)
+                out = wm.cpu().numpy()
+                return (out[0] if out.shape[0] == 1 else out), sr, ids
+            audio, _ = load_audio(audio_path, fs)
+            wm = self.embed_spans_clips(audio.unsqueeze(0), in_samples(int(audio.shape[-1])), window_seconds, fade).squeeze(0)
+            if output_path:
+                save_audio(wm, output_path, fs)
+            return wm.cpu().numpy().squeeze(), fs, ids
+        except Exception as e:
+            logger.error(f"Span embedding failed: {str(e)}")
+            raise RuntimeError(f"Failed to embed watermark spans: {str(e)}") from e
+
     def _clip_frame_sums(self, clips, window_seconds: float, threshold: float):
         """-> (per-clip frame sums, lengths): the locator windowed, its logits the gate of the windowed frames kernel."""
         W = self._window_samples(window_seconds)
@@ -289,6 +358,8 @@ class WaveVerify:
         """session.EmbedBank: up to `capacity` live 16 kHz mono streams that open, push and close on their own.
         bank.open(watermark_id) -> slot; bank.push({slot: x [n], ...}) -> {slot: the watermarked samples of the frames that push completed};
         bank.close(slot) -> the rest.  The streams that complete frames on a tick share one generator launch per pad_limit group.
+        bank.set_message(slot, watermark_id or None) -> the sample from which the stream carries that id, or (None) no watermark at all:
+        the input comes back bit for bit and costs no generator time; bank.open(None) starts that way.
         rates=(48000, 8000, ...): native_bank.NativeEmbedBank, every slot at its own rate and channel count:
         bank.open(watermark_id, sample_rate, channels, strength) with sample_rate one of up to 8 `rates` and channels <= max_channels,
         bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it."""

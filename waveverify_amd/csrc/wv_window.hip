@@ -12,6 +12,8 @@
 //   bank_detect_update_kernel  a detect bank's tick: the windows' sigmoid sums into the per-slot f64 accumulators, mean probabilities and bits out
 //   segment_track_kernel   a live segment session's tick: the new frames' sums -> the per-stream open run, gap ring and ring of closed segments
 //   bank_segment_track_kernel  a segment bank's tick: the same per-stream body, a descriptor per slot with its own frame range and row block
+//   span_gather_kernel     span embedding: packed clips -> a left-aligned, right-zero-padded window batch, a {offset, length} descriptor per row
+//   span_scatter_add_kernel  span embedding: out = x + w * residual over each row's keep range, w the span's gain and edge ramp
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
 #include <hip/hip_runtime.h>
 
@@ -383,6 +385,84 @@ __global__ __launch_bounds__(256) void bank_segment_track_kernel(const float* __
                          rec, ring);
 }
 
+// ---- span embedding: windows of chosen stretches, the residual added inside the stretch only -------------------
+// grid (ceil(Lmax / WIN_TILE), A).  desc[r] = {src offset, wlen}: row r = src[off .. off + wlen), then zeros in [wlen, Lmax).  A row that
+// reaches outside src or beyond Lmax is skipped whole (not even zero-filled).
+__global__ __launch_bounds__(WIN_NT) void span_gather_kernel(const float* __restrict__ src, int64_t n_src, const int64_t* __restrict__ desc,
+                                                             float* __restrict__ dst, int Lmax) {
+    const int r = blockIdx.y;
+    const int64_t off = desc[2 * r], wl = desc[2 * r + 1];
+    if (off < 0 || wl < 0 || wl > Lmax || off > n_src - wl) return;
+    const int wlen = (int)wl;
+    const float* s = src + off;                                 // never dereferenced where wlen == 0
+    float* d = dst + (size_t)r * Lmax;
+    const int j = blockIdx.x * WIN_TILE + threadIdx.x * WIN_PER_THREAD;
+    if (j >= Lmax) return;
+    const int count = Lmax - j < 4 ? Lmax - j : 4;
+    if (j >= wlen) {
+        bank_store4(d + j, count, make_float4(0.f, 0.f, 0.f, 0.f));
+    } else if (j + 4 <= wlen) {
+        bank_store4(d + j, 4, bank_load4(s, 0, s, j, 4));       // hv = 0: every sample is the second source's
+    } else {
+        for (int i = 0; i < count; ++i) d[j + i] = j + i < wlen ? s[j + i] : 0.f;   // a group that straddles wlen
+    }
+}
+
+// One descriptor row of wv_span_scatter_add = {offset in out of the window's column 0, keep lo, keep hi, span start, span end}, the last four
+// relative to the window's column 0; a row that breaks the contract is skipped whole (window.span_row_ok restates the predicate).
+struct SpanRow {
+    int64_t o, lo, hi, ss, se;
+    bool ok;
+};
+
+__device__ __forceinline__ SpanRow span_row(const int64_t* __restrict__ desc, int r, int64_t n_out, int Lmax) {
+    const int64_t* d = desc + 5 * (size_t)r;
+    SpanRow s = {d[0], d[1], d[2], d[3], d[4], false};
+    s.ok = s.lo >= 0 && s.lo < s.hi && s.hi <= Lmax && s.ss <= s.lo && s.hi <= s.se && s.o >= -s.lo && s.o <= n_out - s.hi;
+    return s;
+}
+
+// w(j) = gain * ramp[m] for m = min(j - span start, span end - 1 - j) < F, else gain.  An edge farther than F from j counts as F, so a span
+// edge anywhere in int64 never overflows the difference.
+__device__ __forceinline__ float span_weight(const SpanRow& s, int64_t j, const float* __restrict__ ramp, int F, float gain) {
+    const int64_t a = s.ss < j - F ? F : j - s.ss, b = s.se > j + F ? F : s.se - 1 - j;
+    const int64_t m = a < b ? a : b;
+    return m < F ? gain * ramp[m] : gain;
+}
+
+// grid (ceil(Lmax / WIN_TILE), A): for j in [lo, hi) out[o + j] = x[o + j] + w(j) * y[r][j] (w * y alone where x is null), three roundings.
+// x may be out: a thread reads x[o + j] before it writes out[o + j], and nobody else touches that element.  x and out carry no __restrict__.
+__global__ __launch_bounds__(WIN_NT) void span_scatter_add_kernel(const float* __restrict__ y, const float* x, const int64_t* __restrict__ desc,
+                                                                  const float* __restrict__ ramp, int F, float gain, float* out, int64_t n_out,
+                                                                  int Lmax) {
+    const int r = blockIdx.y;
+    const SpanRow s = span_row(desc, r, n_out, Lmax);
+    if (!s.ok) return;
+    const int lo = (int)s.lo, hi = (int)s.hi;
+    const int j = blockIdx.x * WIN_TILE + threadIdx.x * WIN_PER_THREAD;
+    if (j + WIN_PER_THREAD <= lo || j >= hi) return;
+    const float* yr = y + (size_t)r * Lmax;
+    const float* xr = x ? x + s.o : nullptr;
+    float* d = out + s.o;
+    if (j >= lo && j + WIN_PER_THREAD <= hi && aligned16(yr + j) && aligned16(d + j) && (!xr || aligned16(xr + j))) {
+        const float4 v = *reinterpret_cast<const float4*>(yr + j);
+        float4 u = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (xr) u = *reinterpret_cast<const float4*>(xr + j);
+        const float p0 = span_weight(s, j, ramp, F, gain) * v.x, p1 = span_weight(s, j + 1, ramp, F, gain) * v.y;
+        const float p2 = span_weight(s, j + 2, ramp, F, gain) * v.z, p3 = span_weight(s, j + 3, ramp, F, gain) * v.w;
+        *reinterpret_cast<float4*>(d + j) = xr ? make_float4(u.x + p0, u.y + p1, u.z + p2, u.w + p3) : make_float4(p0, p1, p2, p3);
+        return;
+    }
+#pragma unroll
+    for (int i = 0; i < WIN_PER_THREAD; ++i) {
+        const int q = j + i;
+        if (q >= lo && q < hi) {
+            const float p = span_weight(s, q, ramp, F, gain) * yr[q];
+            d[q] = xr ? xr[q] + p : p;
+        }
+    }
+}
+
 }  // namespace wv
 
 using wv::fail;
@@ -520,5 +600,26 @@ extern "C" int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const in
     const int nt = (nb + 1 + 63) / 64 * 64;
     hipLaunchKernelGGL(wv::bank_segment_track_kernel, dim3(P), dim3(nt), 0, (hipStream_t)stream, fsum, n_fsum, desc, capacity, nb, hop, min_on,
                        min_gap_frames, min_len_frames, eps, (char*)state, l.state_stride, (char*)events, l.event_stride, l.rec, ring);
+    return launched();
+}
+
+extern "C" int wv_span_gather(const float* src, int64_t n_src, const int64_t* desc, float* dst, int A, int Lmax, void* stream) {
+    if (!desc || !dst || n_src < 0 || (n_src > 0 && !src))
+        return fail(WV_EINVAL, "wv_span_gather: null desc or dst, n_src < 0, or samples without src");
+    if (A < 0 || A > 65535 || Lmax < 1) return fail(WV_EINVAL, "wv_span_gather: A outside [0, 65535] or Lmax < 1");
+    if (A == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::span_gather_kernel, dim3((Lmax + wv::WIN_TILE - 1) / wv::WIN_TILE, A), dim3(wv::WIN_NT), 0, (hipStream_t)stream, src, n_src,
+                       desc, dst, Lmax);
+    return launched();
+}
+
+extern "C" int wv_span_scatter_add(const float* y, const float* x, const int64_t* desc, const float* ramp, int F, float gain, float* out,
+                                   int64_t n_out, int A, int Lmax, void* stream) {
+    if (!y || !desc || !out || n_out < 1) return fail(WV_EINVAL, "wv_span_scatter_add: null y, desc or out, or n_out < 1");
+    if (F < 0 || (F > 0 && !ramp) || !(gain == gain) || A < 0 || A > 65535 || Lmax < 1)
+        return fail(WV_EINVAL, "wv_span_scatter_add: F < 0, a fade without ramp, gain not a number, A outside [0, 65535] or Lmax < 1");
+    if (A == 0) return WV_OK;
+    hipLaunchKernelGGL(wv::span_scatter_add_kernel, dim3((Lmax + wv::WIN_TILE - 1) / wv::WIN_TILE, A), dim3(wv::WIN_NT), 0, (hipStream_t)stream, y, x,
+                       desc, ramp, F, gain, out, n_out, Lmax);
     return launched();
 }

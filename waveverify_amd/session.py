@@ -12,7 +12,9 @@ turn the frame sums into closed localize.Segments on the device (wv_segment_trac
 Session banks (StreamBank, section 7d-6) drop the lockstep: `capacity` slots, each an independent stream with its own _Ticker that is opened,
 pushed to (any number of samples, or not at all on a tick) and closed on its own.  The slots that complete frames on a tick become the rows of
 one left-aligned, right-zero-padded window batch per pad_limit group (wv_bank_advance, the histories updated in place); per stream the
-concatenated outputs are still the whole-clip forward on what it pushed.
+concatenated outputs are still the whole-clip forward on what it pushed.  A slot can be put into pass-through (section 7d-9): its history
+still advances, it gets its input back bit for bit and joins no net launch; EmbedBank.set_message switches a stream's id, or its watermark
+off, that way.
 
 Segment banks (SegmentBank, section 7d-7) are the two together: per slot the segment session's tracker, fed by the bank's launches.  The frame
 sums of a tick's launches lie in one arena, and one wv_bank_segment_track call takes a descriptor per slot with that slot's own frame range,
@@ -556,12 +558,14 @@ class SegmentSession(_SegmentNets, SegmentStreamSession, _HipSession):
 @dataclass
 class BankLaunch:
     """One wv_bank_advance call and, where A > 0, one net forward on its [A, 1, Lmax] window batch: rows [p_lo, p_hi) of the tick's descriptor
-    table, the first A of them the windows (row r of the batch is descriptor p_lo + r and window a_lo + r of the tick)."""
+    table, the first A of them the windows (row r of the batch is descriptor p_lo + r and window a_lo + r of the tick).  passthrough: the
+    rows are slots in pass-through, and the launch's "forward" is the window batch itself."""
     p_lo: int
     p_hi: int
     a_lo: int
     A: int
     Lmax: int
+    passthrough: bool = False
 
 
 @dataclass
@@ -579,25 +583,32 @@ class BankPlan:
     padded: int
 
 
-def plan_tick(ticks: dict, sizes: dict, pad_limit: float = 1.5) -> BankPlan:
+def plan_tick(ticks: dict, sizes: dict, pad_limit: float = 1.5, passthrough=frozenset()) -> BankPlan:
     """ticks {slot: Tick}, sizes {slot: samples pushed} -> the tick's launches.  The windows are sorted by (wlen, slot) and cut greedily
     wherever the next would be longer than pad_limit times the shortest of the launch, so a launch pads no row by more than that factor.
     Slots that complete no frame ride in the first launch (a launch of their own without windows if there is none); a slot with nothing to
-    do at all has no descriptor."""
+    do at all has no descriptor.
+    passthrough: slots whose windows go through no net.  Those that complete frames form ONE launch of their own after the others, whatever
+    their lengths (its forward is the window batch itself, so padding costs a copy and no arithmetic); it counts nothing towards `padded`."""
     slots = sorted(ticks)
     x_off, n_x = {}, 0
     for s in slots:
         x_off[s] = n_x
         n_x += sizes[s]
     groups: list = []
-    for s in sorted((s for s in slots if ticks[s].wlen > 0), key=lambda s: (ticks[s].wlen, s)):
+    for s in sorted((s for s in slots if ticks[s].wlen > 0 and s not in passthrough), key=lambda s: (ticks[s].wlen, s)):
         if groups and ticks[s].wlen <= pad_limit * ticks[groups[-1][0]].wlen:
             groups[-1].append(s)
         else:
             groups.append([s])
+    through = sorted((s for s in slots if ticks[s].wlen > 0 and s in passthrough), key=lambda s: (ticks[s].wlen, s))
+    n_net = len(groups)                                                # the groups from here on are pass-through
+    if through:
+        groups.append(through)
     idle = [s for s in slots if ticks[s].wlen == 0 and sizes[s] > 0]
     if idle and not groups:
         groups.append([])
+        n_net = 1
     rows, launches, windows, out, n_out, padded = [], [], [], {}, 0, 0
     for g, members in enumerate(groups):
         p_lo, a_lo = len(rows), len(windows)
@@ -608,11 +619,11 @@ def plan_tick(ticks: dict, sizes: dict, pad_limit: float = 1.5) -> BankPlan:
             windows.append((s, t))
             out[s] = (n_out, t.wlen - t.keep)
             n_out += t.wlen - t.keep
-            padded += Lmax - t.wlen
+            padded += Lmax - t.wlen if g < n_net else 0
         for s in (idle if g == 0 else ()):
             t = ticks[s]
             rows.append([s, t.hv, x_off[s], sizes[s], 0, 0, t.drop, t.hv2])
-        launches.append(BankLaunch(p_lo, len(rows), a_lo, len(members), Lmax))
+        launches.append(BankLaunch(p_lo, len(rows), a_lo, len(members), Lmax, g >= n_net))
     for s in slots:
         out.setdefault(s, (n_out, 0))
     return BankPlan(np.array(rows, np.int64).reshape(-1, 8), launches, slots, n_x, windows, out, n_out, padded)
@@ -648,7 +659,9 @@ class StreamBank:
     arrays: the backend of the histories (NumpyArrays() if None).
     A window batch is left-aligned: column 0 of row r is that stream's own h0, rows are zero beyond their wlen; the nets are causal and
     push-time wlen are hop multiples, so the padding changes no kept column.  close() runs its ragged window alone, at its true length.
-    This base class runs on host arrays; push / close return per slot the kept columns [C, k], or None where nothing completed."""
+    This base class runs on host arrays; push / close return per slot the kept columns [C, k], or None where nothing completed.
+    A slot in PASS-THROUGH (set_passthrough; section 7d-9) still advances its history with every push, so that the net finds real context
+    when it is switched back in, but takes part in no forward: it gets back the window's own columns [keep, wlen), its input bit for bit."""
 
     def __init__(self, capacity: int, hop: int, H: int, forward: Optional[Callable], advance: Optional[Callable] = numpy_bank_advance,
                  arrays=None, pad_limit: float = 1.5):
@@ -660,6 +673,7 @@ class StreamBank:
         self.hop, self.H, self.hcap = hop, H, H + hop
         self._tickers = [_Ticker(hop, H) for _ in range(self.capacity)]
         self._is_open = [False] * self.capacity
+        self._through: set = set()                                         # the slots in pass-through
         self._forward, self._advance = forward, advance
         self._arr = arrays or NumpyArrays()
         self._hist = self._arr.zeros(self.capacity, self.hcap)
@@ -670,6 +684,7 @@ class StreamBank:
         """-> the lowest free slot, starting from nothing: its ticker is reset, so the history the slot's last stream left is never read."""
         for slot, taken in enumerate(self._is_open):
             if not taken:
+                self._through.discard(slot)
                 self._on_open(slot, *args)
                 self._tickers[slot].reset()
                 self._is_open[slot] = True
@@ -685,6 +700,13 @@ class StreamBank:
     def samples_seen(self, slot: int) -> int:
         """Samples of the slot's stream whose outputs have been produced."""
         self._check_slot(slot)
+        return self._tickers[slot].t_out
+
+    def set_passthrough(self, slot: int, on: bool) -> int:
+        """Puts the slot into pass-through, or back under the net, from its next frame on -> that frame's first sample (samples_seen(slot), a
+        hop multiple).  Samples already pushed towards that frame are emitted under the new setting."""
+        self._check_slot(slot)
+        (self._through.add if on else self._through.discard)(slot)
         return self._tickers[slot].t_out
 
     def _check_slot(self, slot) -> None:
@@ -708,10 +730,10 @@ class StreamBank:
         return out
 
     def _plan(self, xs: dict, ticks: dict) -> BankPlan:
-        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit)
+        plan = plan_tick(ticks, {s: int(x.shape[0]) for s, x in xs.items()}, self.pad_limit, self._through)
         self.stats["ticks"] += 1
-        self.stats["launches"] += sum(1 for ln in plan.launches if ln.A)
-        self.stats["window_samples"] += sum(ln.A * ln.Lmax for ln in plan.launches)
+        self.stats["launches"] += sum(1 for ln in plan.launches if ln.A and not ln.passthrough)
+        self.stats["window_samples"] += sum(ln.A * ln.Lmax for ln in plan.launches if not ln.passthrough)
         self.stats["padded_samples"] += plan.padded
         return plan
 
@@ -723,7 +745,7 @@ class StreamBank:
             win = self._advance(self._hist, x, plan.desc[ln.p_lo:ln.p_hi], ln.A, ln.Lmax)
             if ln.A:
                 rows = plan.windows[ln.a_lo:ln.a_lo + ln.A]
-                y = self._forward(win, [s for s, _ in rows])
+                y = win if ln.passthrough else self._forward(win, [s for s, _ in rows])
                 for r, (s, t) in enumerate(rows):
                     res[s] = y[r][..., t.keep:t.wlen]
         return res
@@ -739,6 +761,9 @@ class _HipBank(StreamBank):
         arrays = TorchArrays(net.device)
         self.net, self.precision, self._torch = net, precision, arrays.torch
         super().__init__(capacity, net.cfg.hop_length, _halo(net.cfg), None, None, arrays, pad_limit)
+
+    def set_passthrough(self, slot: int, on: bool) -> int:
+        raise ValueError(f"{type(self).__name__}: on the device pass-through is switched by set_message, on the banks that have it")
 
     def _upload(self, sections: list) -> dict:
         """[(name, host array)] -> {name: device tensor}: one buffer, every section on an 8-byte boundary, one copy."""
@@ -800,7 +825,7 @@ class _ColumnsBank(_HipBank):
         self._out = self._torch.empty(plan.n_out, dtype=self._torch.float32, device=self.net.device)
 
     def _launch(self, win, tabs: dict, plan: BankPlan, ln: BankLaunch) -> None:
-        y = self._net(win, tabs, ln)
+        y = win if ln.passthrough else self._net(win, tabs, ln)                # pass-through: the kept columns are the input's own
         _lib.check(self.net._lib.wv_window_scatter(y.data_ptr(), tabs["scatter"][ln.a_lo:].data_ptr(), self._out.data_ptr(), plan.n_out, ln.A, 1,
                                                    ln.Lmax, _lib.stream()), "wv_window_scatter")
 
@@ -815,7 +840,11 @@ class EmbedBank(_ColumnsBank):
     watermarked samples of the frames that push completed [k]}, close(slot) -> the rest.
     messages: what turns open()'s argument into a [msg_dimension] bit tensor (WaveVerify passes its watermark-id table); without it open()
     takes the bits themselves.  The messages live on the host and travel in the tick's table, so open() touches no device memory.
-    add_input=False: the generator's residual alone (what native_bank.py brings back to each slot's own rate)."""
+    add_input=False: the generator's residual alone (what native_bank.py brings back to each slot's own rate).
+    set_message(slot, message) changes a stream's id mid-stream and set_message(slot, None) switches its watermark off (pass-through: the
+    input comes back bit for bit and the slot takes part in no generator launch), both from the slot's next frame on; open(None) opens in
+    pass-through.  Per stream the concatenated output is span embedding (window.span_generator, hard cuts) of what it pushed, the span
+    edges at the indices set_message returned."""
 
     def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5, messages: Optional[Callable] = None,
                  add_input: bool = True):
@@ -823,12 +852,31 @@ class EmbedBank(_ColumnsBank):
         self._messages, self.add_input = messages, bool(add_input)
         self._msg = np.zeros((self.capacity, net.cfg.msg_dimension), np.float32)
 
-    def _on_open(self, slot: int, message) -> None:
+    def _message_row(self, message) -> np.ndarray:
         m = self._messages(message) if self._messages is not None else message
         m = np.asarray(m.detach().cpu() if hasattr(m, "detach") else m, np.float32).reshape(-1)
         if m.shape[0] != self._msg.shape[1]:
             raise ValueError(f"a message has {self._msg.shape[1]} bits, got {m.shape[0]}")
-        self._msg[slot] = m
+        return m
+
+    def _set(self, slot: int, message) -> None:
+        """Everything is checked before the slot changes."""
+        if message is None:
+            if not self.add_input:
+                raise ValueError("pass-through returns the input; a bank that returns the residual alone (add_input=False) has none")
+            self._through.add(slot)
+        else:
+            self._msg[slot] = self._message_row(message)
+            self._through.discard(slot)
+
+    def _on_open(self, slot: int, message) -> None:
+        self._set(slot, message)
+
+    def set_message(self, slot: int, message) -> int:
+        """The slot's id from its next frame on (None: no watermark) -> that frame's first sample, samples_seen(slot)."""
+        self._check_slot(slot)
+        self._set(slot, message)
+        return self._tickers[slot].t_out
 
     def _sections(self, plan: BankPlan) -> list:
         return super()._sections(plan) + [("msg", self._msg[[s for s, _ in plan.windows]])]

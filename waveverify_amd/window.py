@@ -284,3 +284,217 @@ def windowed_detector_frame_sums(net, clips, gates=None, gate_thr: float = 0.0, 
         if as_batch:
             return out.view(len(lengths), nb1, frames[0])
         return [out[nb1 * f0: nb1 * (f0 + n)].view(nb1, n) for f0, n in zip(fbases, frames)]
+
+
+# --------------------------------------------------------------------------- span embedding
+# Watermark chosen stretches of a clip, each with its own id: out = x + w * G(x, msg(id)) inside a span, x bit for bit outside.  The
+# generator is causal and halo(cfg) bounds how far back an output looks, so the residual over [s, e) needs the input from
+# floor_hop(s) - H only: a span becomes one or more windows of its clip, the windows of all clips and spans share launches as a bank's
+# rows do (left-aligned, right-zero-padded), and two data-movement kernels stand around each generator launch (wv_span_gather,
+# wv_span_scatter_add).  plan_spans and the two numpy twins are integers and host arrays only.
+@dataclass(frozen=True)
+class SpanWindow:
+    clip: int        # index of the clip
+    start: int       # first input sample, in the clip's coordinates: a hop multiple
+    length: int      # input samples; start + length is a hop multiple or the clip's true end
+    keep_lo: int     # columns the window adds its residual to, [keep_lo, keep_hi) in the clip's coordinates: a piece of its span
+    keep_hi: int
+    span_lo: int     # the whole span [span_lo, span_hi) (the ramps count from its edges, not from the piece's)
+    span_hi: int
+    msg: object      # the span's third element: the window's message row
+
+
+def span_ramp(fade_samples: int):
+    """ramp[j] = float32(0.5 - 0.5 cos(pi (j + 0.5) / fade_samples)), formed in float64 and rounded once; None for a hard cut."""
+    import numpy as np
+    F = int(fade_samples)
+    if F < 0 or F != fade_samples:
+        raise ValueError("fade_samples must be a non-negative integer")
+    if F == 0:
+        return None
+    return (0.5 - 0.5 * np.cos(np.pi * (np.arange(F, dtype=np.float64) + 0.5) / F)).astype(np.float32)
+
+
+def check_spans(lengths: Sequence[int], spans) -> List[list]:
+    """-> per clip its spans [(start, end, msg)] sorted by start, refusing what span embedding does not define: a span that is empty,
+    inverted or outside its clip, and spans of one clip that overlap (abutting is allowed)."""
+    if len(spans) != len(lengths):
+        raise ValueError(f"{len(lengths)} clips but {len(spans)} span lists")
+    out = []
+    for b, (T, lst) in enumerate(zip(lengths, spans)):
+        T = int(T)
+        if T < 1:
+            raise ValueError(f"clip {b} is empty")
+        mine = sorted(((int(s), int(e), m) for s, e, m in lst), key=lambda v: v[:2])
+        for s, e, _ in mine:
+            if s >= e:
+                raise ValueError(f"clip {b}: span [{s}, {e}) is empty or inverted")
+            if s < 0 or e > T:
+                raise ValueError(f"clip {b}: span [{s}, {e}) lies outside the clip's {T} samples")
+        for (_, e0, _), (s1, _, _) in zip(mine, mine[1:]):
+            if s1 < e0:
+                raise ValueError(f"clip {b}: spans overlap at sample {s1}")
+        out.append(mine)
+    return out
+
+
+def plan_spans(lengths: Sequence[int], spans, window: int, cfg: NetConfig, pad_limit: float = 1.5, max_windows: int = 64) -> List[List[SpanWindow]]:
+    """Windows for the spans [(start, end, msg)] of clips of the given lengths, grouped into launches.
+    A span [s, e) of a clip of T samples: its first window starts at max(0, floor_hop(s) - H) and, where that fits `window` (rounded up
+    to the hop, at least H + hop), ends at min(ceil_hop(e), T) and keeps [s, e).  A longer one is cut as plan() cuts clips: the first
+    piece is `window` long, each further piece starts H before the first column it keeps, the last ends at min(ceil_hop(e), T).  Keep
+    ranges are the span's own samples (no hop multiples) and tile every span once.
+    Launches: the windows of all clips and spans sorted by length, left-aligned, to be right-zero-padded to the launch's longest; a new
+    launch starts where the next window would be longer than pad_limit times the launch's shortest or after max_windows rows.  A window
+    that ends at a clip's ragged true end shares a launch only with windows of its own length (what StreamBank.close() does for it)."""
+    hop, H = cfg.hop_length, halo(cfg)
+    if max_windows < 1:
+        raise ValueError("max_windows must be >= 1")
+    if not pad_limit >= 1.0:
+        raise ValueError("pad_limit must be at least 1 (float('inf'): as few launches as the ragged ends allow)")
+    L = max(-(-int(window) // hop) * hop, H + hop)
+    wins = []
+    for b, mine in enumerate(check_spans(lengths, spans)):
+        T = int(lengths[b])
+        for s, e, m in mine:
+            start = max(0, s // hop * hop - H)
+            end = min(-(-e // hop) * hop, T)
+            if end - start <= L:
+                wins.append(SpanWindow(b, start, end - start, s, e, s, e, m))
+                continue
+            wins.append(SpanWindow(b, start, L, s, start + L, s, e, m))
+            k = start + L
+            while k + (L - H) < e:
+                wins.append(SpanWindow(b, k - H, L, k, k + L - H, s, e, m))
+                k += L - H
+            wins.append(SpanWindow(b, k - H, end - (k - H), k, e, s, e, m))
+    wins.sort(key=lambda w: (w.length, w.clip, w.start))
+    ragged = lambda w: (w.start + w.length) % hop != 0                  # only a clip's true end is off the hop grid
+    out: List[List[SpanWindow]] = []
+    lone = False                                                        # the open launch holds a ragged window
+    for w in wins:
+        g = out[-1] if out else None
+        fits = g is not None and len(g) < max_windows and w.length <= pad_limit * g[0].length
+        if fits and (lone or ragged(w)) and w.length != g[0].length:
+            fits = False
+        if fits:
+            g.append(w)
+            lone = lone or ragged(w)
+        else:
+            out.append([w])
+            lone = ragged(w)
+    return out
+
+
+def span_gather_desc(wins: Sequence[SpanWindow], bases: Sequence[int]) -> List[List[int]]:
+    """wv_span_gather's rows {offset in the packed clips, wlen}."""
+    return [[bases[w.clip] + w.start, w.length] for w in wins]
+
+
+def span_scatter_desc(wins: Sequence[SpanWindow], bases: Sequence[int]) -> List[List[int]]:
+    """wv_span_scatter_add's rows {offset in the packed output of the window's column 0, keep lo, keep hi, span start, span end}, the last
+    four relative to the window's column 0."""
+    return [[bases[w.clip] + w.start, w.keep_lo - w.start, w.keep_hi - w.start, w.span_lo - w.start, w.span_hi - w.start] for w in wins]
+
+
+def span_gather_row_ok(row, n_src: int, Lmax: int) -> bool:
+    """Whether wv_span_gather serves a descriptor row (it skips any other whole)."""
+    off, wlen = (int(v) for v in row)
+    return 0 <= off and 0 <= wlen <= Lmax and off + wlen <= n_src
+
+
+def span_row_ok(row, n_out: int, Lmax: int) -> bool:
+    """Whether wv_span_scatter_add serves a descriptor row (it skips any other whole)."""
+    o, lo, hi, ss, se = (int(v) for v in row)
+    return 0 <= lo < hi <= Lmax and ss <= lo and hi <= se and 0 <= o + lo and o + hi <= n_out
+
+
+def numpy_span_gather(src, desc, A: int, Lmax: int, dst=None):
+    """Reference of wv_span_gather on host arrays -> dst [A, 1, Lmax] (a fresh array of zeros if none is given: the kernel leaves a skipped
+    row as it was)."""
+    import numpy as np
+    dst = np.zeros((A, 1, Lmax), src.dtype) if dst is None else dst
+    for r, row in enumerate(np.asarray(desc, np.int64).reshape(-1, 2)[:A]):
+        if span_gather_row_ok(row, int(src.shape[0]), Lmax):
+            off, wlen = int(row[0]), int(row[1])
+            dst[r, 0, :wlen] = src[off:off + wlen]
+            dst[r, 0, wlen:] = 0
+    return dst
+
+
+def numpy_span_scatter_add(y, x, desc, ramp, gain, out):
+    """Reference of wv_span_scatter_add on host arrays, in out's dtype with every rounding kept: w = gain * ramp[m] (gain alone beyond the
+    ramp), v = w * y, out = x + v (v alone where x is None).  x may be out.  Only the served rows' keep ranges are written."""
+    import numpy as np
+    dt = out.dtype.type
+    A, _, Lmax = y.shape
+    F = 0 if ramp is None else int(len(ramp))
+    g = dt(gain)
+    for r, row in enumerate(np.asarray(desc, np.int64).reshape(-1, 5)[:A]):
+        if not span_row_ok(row, int(out.shape[0]), Lmax):
+            continue
+        o, lo, hi, ss, se = (int(v) for v in row)
+        j = np.arange(lo, hi, dtype=np.int64)
+        m = np.minimum(j - ss, se - 1 - j)
+        w = np.full(hi - lo, g, out.dtype)
+        if F:
+            inside = m < F
+            w[inside] = g * np.asarray(ramp)[m[inside]].astype(out.dtype)
+        v = w * y[r, 0, lo:hi].astype(out.dtype)
+        out[o + lo:o + hi] = v if x is None else x[o + lo:o + hi].astype(out.dtype) + v
+    return out
+
+
+def _clip_lengths(clips) -> List[int]:
+    if hasattr(clips, "dim"):
+        if clips.dim() not in (2, 3) or (clips.dim() == 3 and clips.shape[1] != 1):
+            raise ValueError(f"expected audio of shape [B,1,T] or a list of 1-D clips, got {tuple(clips.shape)}")
+        return [int(clips.shape[-1])] * int(clips.shape[0])
+    if not len(clips):
+        raise ValueError("no clips")
+    return [int(c.numel()) for c in clips]
+
+
+def span_generator(net, clips, msgs, spans, window: int = 480000, precision: str = "f32", pad_limit: float = 1.5, max_windows: int = 64,
+                   fade_samples: int = 0, gain: float = 1.0, add_input: bool = True):
+    """Span embedding of every clip: out = x + w * G(x, msgs[m]) over each span (start, end, m) of spans[clip], x bit for bit elsewhere;
+    w = gain * ramp(distance to the span's nearer edge), ramp = span_ramp(fade_samples).  clips as windowed_generator takes them, the
+    result the same kind; msgs [M, msg_dimension]; spans: per clip a list of (start, end, row of msgs) in samples.
+    add_input=False: the masked residual alone, zeros outside the spans (what the native-rate route brings up to the file's rate).
+    Everything is planned and checked before anything touches the device; per launch wv_span_gather -> net.generator on the window batch
+    with each row's own message -> wv_span_scatter_add."""
+    import numpy as np
+    torch = _torch()
+    lengths = _clip_lengths(clips)
+    ramp = span_ramp(fade_samples)
+    if not gain == gain:
+        raise ValueError("gain is not a number")
+    n_msg = int(msgs.shape[0]) if msgs.dim() > 1 else 1
+    launches = plan_spans(lengths, spans, window, net.cfg, pad_limit, max_windows)
+    for w in (w for g in launches for w in g):
+        if isinstance(w.msg, bool) or not isinstance(w.msg, (int, np.integer)) or not 0 <= w.msg < n_msg:
+            raise ValueError(f"clip {w.clip}: span message row {w.msg!r} is not a row of the {n_msg} messages")
+    with torch.cuda.device(net.device):
+        packed, lengths, bases, as_batch = _pack(clips, net.device)
+        out = packed.clone() if add_input else torch.zeros_like(packed)
+        if launches:
+            msgs = msgs.to(net.device).float().reshape(n_msg, -1)
+            flat = [w for g in launches for w in g]
+            table = np.concatenate([np.array(span_gather_desc(flat, bases), np.int64).reshape(-1), np.array(span_scatter_desc(flat, bases), np.int64).reshape(-1),
+                                    np.array([w.msg for w in flat], np.int64)])
+            table = torch.from_numpy(table).to(net.device)                 # one copy for every launch's descriptors
+            N = len(flat)
+            gdesc, sdesc, rows = table[:2 * N].view(N, 2), table[2 * N:7 * N].view(N, 5), table[7 * N:]
+            ramp_t = None if ramp is None else torch.from_numpy(ramp).to(net.device)
+            F = 0 if ramp is None else int(ramp.shape[0])
+            a = 0
+            for wins in launches:
+                A, Lmax = len(wins), wins[-1].length
+                xw = torch.empty((A, 1, Lmax), dtype=torch.float32, device=net.device)
+                _lib.check(net._lib.wv_span_gather(packed.data_ptr(), packed.numel(), gdesc[a:].data_ptr(), xw.data_ptr(), A, Lmax, _lib.stream()),
+                           "wv_span_gather")
+                y = net.generator(xw, msgs.index_select(0, rows[a:a + A]).contiguous(), add_input=False, precision=precision).contiguous()
+                _lib.check(net._lib.wv_span_scatter_add(y.data_ptr(), out.data_ptr() if add_input else None, sdesc[a:].data_ptr(), _lib.ptr(ramp_t), F,
+                                                        float(gain), out.data_ptr(), out.numel(), A, Lmax, _lib.stream()), "wv_span_scatter_add")
+                a += A
+        return _unpack(out, lengths, bases, as_batch)
