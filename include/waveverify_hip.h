@@ -268,6 +268,41 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          capacity outside [1, WV_BANK_MAX_SLOTS], P outside [0, 65535], nb outside [1, WV_SEGMENT_MAX_BITS], hop < 1,
  *                          min_gap_frames outside [1, WV_SEGMENT_MAX_GAP], min_len_frames < 0, ring < 1, min_on not a number; state or
  *                          events shorter than `capacity` streams need, or not 8-byte aligned.  P == 0 is success without a launch.
+ *   wv_segment_track_split / wv_bank_segment_track_split
+ *                          wv_segment_track and wv_bank_segment_track under a SPLIT RULE (localize.SplitRule is the definition, DESIGN.md
+ *                          section 7d-10): runs [lo, hi) are found exactly as there (same ON rule, gap merge, close and min_len_frames drop of
+ *                          the whole run), and a run is also cut where the decoded id changes.  With W = window_frames and plo the start of
+ *                          the run's current piece (lo at first), a frame boundary g is a CANDIDATE once plo + W <= g and g + W <= hi.  L_k
+ *                          and R_k (k = 0 .. nb, row nb the count row) are the sums of row k over frames [g - W, g) and [g, g + W), each f32
+ *                          widened to f64 and added one by one in ascending order.  Where L_nb > 0 and R_nb > 0, S(g) = the sum over
+ *                          k = 0 .. nb - 1 in ascending k of |L_k / L_nb - R_k / R_nb| and d(g) = the number of k with
+ *                          (L_k / L_nb >= 0.5) != (R_k / R_nb >= 0.5); g QUALIFIES when S(g) >= threshold and d(g) >= min_bits.  Candidates
+ *                          are evaluated in ascending g as soon as `hi` allows, with at most one pending (cg, cS): first, if one is pending
+ *                          and g - cg >= W, cg is committed; then a qualifying g becomes pending if none is or S(g) > cS strictly.  A commit
+ *                          emits the piece [plo, cg) and sets plo = cg.  When the run closes, a pending cut is committed without waiting and
+ *                          [plo, hi) is emitted.  So every piece has at least W frames, a cut at g is known once frame g + 2 W - 1 has
+ *                          arrived, and a run in which no candidate qualifies gives the event wv_segment_track gives, bit for bit.  A piece's
+ *                          sums are one ascending f64 pass over its own frames, prob = S / (float(N) + eps) as above.  No value depends on
+ *                          an fma contraction.  One workgroup per stream or descriptor row, thread k <= nb owns row k; the bit terms and
+ *                          votes go through LDS and are added in ascending k alike by every thread; no atomics; state is read before the
+ *                          last barrier and written after it; fsum (and desc) are only read.
+ *                          Buffers as for wv_segment_track, sized by wv_segment_split_bytes(S or capacity, nb, min_gap_frames,
+ *                          window_frames, capacity or ring), all zeros for a fresh stream:
+ *                            state,  per stream (stride 64 + 8 (nb + 1) + roundup8(4 (2 W + min_gap_frames)(nb + 1)) bytes):
+ *                                    int64 {open 0/1, lo, hi, frames seen, plo, pending 0/1, cg}; f64 cS; f64 sum[nb + 1] of the current piece
+ *                                    over [plo, sb), sb = max(plo, hi - 2 W + 1); f32 ring[2 W + min_gap_frames][nb + 1], the raw columns of
+ *                                    the frames from sb on (the off frames after hi among them), split frame j in slot j % (2 W + min_gap_frames)
+ *                            events, per stream (stride 8 + capacity * rec bytes, rec = 32 + roundup8(4 nb)):
+ *                                    int64 n = events so far; record c: int64 lo, int64 hi, f64 count, int64 flags (bit 0: the piece's start is
+ *                                    an id change, bit 1: its end is one; neither: a locator edge), f32 prob[nb]; event e is record e % capacity.
+ *                          A state that cannot follow from zeros and gapless ticks is taken as closed with no events and never becomes an
+ *                          address.  As for wv_segment_track, gapless ticks are THE CALLER'S DUTY: frame0 is not compared with the stored
+ *                          "frames seen", so a tick that skips or repeats frames while a run is open (possible only within the
+ *                          min_gap_frames of slack the check leaves) reads ring columns of other frames: values, never addresses, and
+ *                          sums that are then undefined.  The bank form skips bad descriptor rows whole by wv_bank_segment_track's predicate and serves the others.
+ *                          Refused with WV_EINVAL and nothing written: everything wv_segment_track / wv_bank_segment_track refuse, and
+ *                          window_frames outside [max(2, min_gap_frames, min_len_frames), WV_SPLIT_MAX_WINDOW], threshold not above 0,
+ *                          min_bits outside [1, nb].  P == 0 (and a tick without frames that is not final) is success without a launch.
  *   wv_span_gather         span embedding (window.py plan_spans / span_generator): dst [A,1,Lmax] from the packed clips
  *                          src (n_src samples); desc [A][2] int64 device = {src offset, wlen}.  Row r = src[off .. off + wlen), then zeros in
  *                          [wlen, Lmax): a left-aligned, right-zero-padded window batch of rows of their own lengths.  16-byte moves where
@@ -291,6 +326,7 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
 #define WV_SEGMENT_MAX_GAP 64
 #define WV_SEGMENT_MAX_BITS 255
 #define WV_BANK_MAX_SLOTS 1048576
+#define WV_SPLIT_MAX_WINDOW 256
 int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream);
 int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream);
 int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
@@ -314,6 +350,13 @@ int wv_bank_detect_update(double* acc, int64_t* seen, int capacity, int nb, cons
 int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
                           int min_gap_frames, int min_len_frames, float eps, void* state, size_t state_bytes, void* events, size_t event_bytes,
                           int ring, void* stream);
+int wv_segment_split_bytes(int S, int nb, int min_gap_frames, int window_frames, int capacity, size_t* state_bytes, size_t* event_bytes);
+int wv_segment_track_split(const float* fsum, int S, int nb, int Fr_stride, int f_lo, int f_hi, int64_t frame0, int hop, int last_valid,
+                           int final, double min_on, int min_gap_frames, int min_len_frames, float eps, int window_frames, double threshold,
+                           int min_bits, void* state, size_t state_bytes, void* events, size_t event_bytes, int capacity, void* stream);
+int wv_bank_segment_track_split(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
+                                int min_gap_frames, int min_len_frames, float eps, int window_frames, double threshold, int min_bits,
+                                void* state, size_t state_bytes, void* events, size_t event_bytes, int ring, void* stream);
 int wv_span_gather(const float* src, int64_t n_src, const int64_t* desc, float* dst, int A, int Lmax, void* stream);
 int wv_span_scatter_add(const float* y, const float* x, const int64_t* desc, const float* ramp, int F, float gain, float* out, int64_t n_out,
                         int A, int Lmax, void* stream);

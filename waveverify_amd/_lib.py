@@ -84,6 +84,11 @@ SIGNATURES = {
     "wv_bank_detect_update": (C.c_int, [_VP, _VP, C.c_int, C.c_int, _VP, _VP, C.c_int, _VP, _VP, _VP]),
     "wv_bank_segment_track": (C.c_int, [_VP, C.c_int64, _VP] + [C.c_int] * 4 + [C.c_double, C.c_int, C.c_int, C.c_float, _VP, C.c_size_t, _VP,
                                         C.c_size_t, C.c_int, _VP]),
+    "wv_segment_split_bytes": (C.c_int, [C.c_int] * 5 + [C.POINTER(C.c_size_t)] * 2),
+    "wv_segment_track_split": (C.c_int, [_VP] + [C.c_int] * 5 + [C.c_int64] + [C.c_int] * 3 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_int,
+                                         C.c_double, C.c_int, _VP, C.c_size_t, _VP, C.c_size_t, C.c_int, _VP]),
+    "wv_bank_segment_track_split": (C.c_int, [_VP, C.c_int64, _VP] + [C.c_int] * 4 + [C.c_double, C.c_int, C.c_int, C.c_float, C.c_int, C.c_double,
+                                              C.c_int, _VP, C.c_size_t, _VP, C.c_size_t, C.c_int, _VP]),
     "wv_span_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int, C.c_int, _VP]),
     "wv_span_scatter_add": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_float, _VP, C.c_int64, C.c_int, C.c_int, _VP]),
     "wv_op_pw_dw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,

@@ -175,6 +175,44 @@ class WaveVerify:
                                   prob[i].numpy(), (lo, hi)))
         return out
 
+    def _segments_split(self, fsum, lengths, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int, split) -> List[List[Segment]]:
+        """_segments under a localize.SplitRule: the clips' frame sums stay on the device and go through ONE wv_bank_segment_track_split
+        launch, a descriptor per clip {clip, offset of its rows, row length, 0, its frames, 0, the last frame's samples, final}; only the
+        event records in use come back (the counters are read first)."""
+        per_clip = list(fsum) if not isinstance(fsum, torch.Tensor) else None
+        B = len(per_clip) if per_clip is not None else fsum.shape[0]
+        nb = (per_clip[0] if per_clip is not None else fsum).shape[-2] - 1
+        split.check(nb, min_gap_frames, min_len_frames)
+        Frs = [int(f.shape[1]) for f in per_clip] if per_clip is not None else [int(fsum.shape[2])] * B
+        arena = torch.cat([f.float().reshape(-1) for f in per_clip]) if per_clip is not None else fsum.float().contiguous().reshape(-1)
+        desc, off = [], 0
+        for b, (Fr, T) in enumerate(zip(Frs, lengths)):
+            desc.append([b, off, Fr, 0, Fr, 0, int(T) - (Fr - 1) * hop, 1])
+            off += (nb + 1) * Fr
+        # events are disjoint stretches of frames: a piece of a cut run has at least window_frames, an uncut run at least
+        # max(1, min_len_frames) and min_gap_frames off frames behind it (but for a clip's last)
+        ring = max(Frs) // min(split.window_frames, max(1, min_len_frames) + min_gap_frames) + 1
+        dev = arena.device
+        with torch.cuda.device(dev):
+            sb, eb = ops.segment_split_bytes(B, nb, min_gap_frames, split.window_frames, ring)
+            state = torch.zeros(sb, dtype=torch.uint8, device=dev)
+            events = torch.zeros(eb, dtype=torch.uint8, device=dev)
+            ops.bank_segment_track_split(arena, torch.tensor(desc, dtype=torch.int64).to(dev), B, B, nb, hop, min_on, min_gap_frames,
+                                         min_len_frames, split, state, events, ring)
+            rows = events.view(B, -1)
+            n = rows[:, :8].contiguous().cpu().numpy().view("<i8").reshape(B)      # the counters first, then only the records in use
+            used = ops.split_event_dtype(nb).itemsize * int(n.max()) if B else 0
+            recs = rows[:, 8:8 + used].contiguous().cpu().numpy().view(ops.split_event_dtype(nb)).reshape(B, -1)
+        out: List[List[Segment]] = [[] for _ in lengths]
+        for b, T in enumerate(lengths):
+            for r in recs[b, :int(n[b])]:
+                lo, hi, prob = int(r["lo"]), int(r["hi"]), torch.from_numpy(r["prob"].copy())
+                end = min(hi * hop, int(T))
+                wid = WatermarkID.custom(tensor_to_message(prob)) if nb == 16 else None     # an id has 16 bits; another width leaves prob to read
+                out[b].append(Segment(lo * hop / self.sample_rate, end / self.sample_rate, wid, float(prob.mean()),
+                                      float(r["count"]) / (end - lo * hop), prob.numpy(), (lo, hi), (bool(r["flags"] & 1), bool(r["flags"] & 2))))
+        return out
+
     @torch.no_grad()
     def detect_localized_batch(self, audio: torch.Tensor, threshold: float = 0.5,
                                gate: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -191,13 +229,18 @@ class WaveVerify:
 
     @torch.no_grad()
     def detect_segments_batch(self, audio: torch.Tensor, threshold: float = 0.5, gate: Optional[torch.Tensor] = None, min_on: float = 0.5,
-                              min_gap_frames: int = 2, min_len_frames: int = 5) -> List[List[Segment]]:
+                              min_gap_frames: int = 2, min_len_frames: int = 5, split=None) -> List[List[Segment]]:
         """Per clip the list of watermarked Segments (localize.segments_from_counts on the gated sample counts per detector frame), each
-        decoded over its own gated samples: a clip spliced from differently marked sources gives one Segment per source."""
+        decoded over its own gated samples: a clip spliced from differently marked sources gives one Segment per source.
+        split: a localize.SplitRule; a run is then also cut where the decoded id changes inside it (abutting stretches marked with
+        different ids), each Segment's `change` saying which of its ends is such a cut."""
         det = self._need("detector")
         g, thr = self._gate(audio, threshold, gate)
         fsum = det.detector_frame_sums(audio, g, thr, self.detector_precision)
-        return self._segments(fsum, [int(audio.shape[-1])] * fsum.shape[0], det.hop_length, min_on, min_gap_frames, min_len_frames)
+        lengths = [int(audio.shape[-1])] * fsum.shape[0]
+        if split is not None:
+            return self._segments_split(fsum, lengths, det.hop_length, min_on, min_gap_frames, min_len_frames, split)
+        return self._segments(fsum, lengths, det.hop_length, min_on, min_gap_frames, min_len_frames)
 
     # ------------------------------------------------------------------ windowed: variable-length clips, live sessions (NOT in the reference)
     def _window_samples(self, window_seconds: float) -> int:
@@ -319,10 +362,13 @@ class WaveVerify:
 
     @torch.no_grad()
     def detect_segments_clips(self, clips, window_seconds: float = 30.0, threshold: float = 0.5, min_on: float = 0.5, min_gap_frames: int = 2,
-                              min_len_frames: int = 5) -> List[List[Segment]]:
+                              min_len_frames: int = 5, split=None) -> List[List[Segment]]:
         """detect_segments_batch for clips of any lengths, windowed."""
         fsum, lengths = self._clip_frame_sums(clips, window_seconds, threshold)
-        return self._segments(fsum, lengths, self._need("detector").hop_length, min_on, min_gap_frames, min_len_frames)
+        hop = self._need("detector").hop_length
+        if split is not None:
+            return self._segments_split(fsum, lengths, hop, min_on, min_gap_frames, min_len_frames, split)
+        return self._segments(fsum, lengths, hop, min_on, min_gap_frames, min_len_frames)
 
     @torch.no_grad()
     def locate_clips(self, clips, window_seconds: float = 30.0):
@@ -472,14 +518,14 @@ class WaveVerify:
             logger.error(f"Detection failed: {str(e)}")
             raise RuntimeError(f"Failed to detect watermark: {str(e)}") from e
 
-    def segments(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None) -> List[Segment]:
+    def segments(self, audio_path: Union[str, Path], *, window_seconds: Optional[float] = None, split=None) -> List[Segment]:
         """NOT in the reference: the file's watermarked Segments (start_s, end_s, watermark, confidence, coverage), each decoded over its
-        own marked samples; an empty list where the locator marks nothing."""
+        own marked samples; an empty list where the locator marks nothing.  split: a localize.SplitRule, as detect_segments_batch takes."""
         try:
             audio, _ = load_audio(audio_path, self.sample_rate)
             if window_seconds is None:
-                return self.detect_segments_batch(audio.unsqueeze(0))[0]
-            return self.detect_segments_clips(audio.unsqueeze(0), window_seconds)[0]
+                return self.detect_segments_batch(audio.unsqueeze(0), split=split)[0]
+            return self.detect_segments_clips(audio.unsqueeze(0), window_seconds, split=split)[0]
         except Exception as e:
             logger.error(f"Segment detection failed: {str(e)}")
             raise RuntimeError(f"Failed to detect watermark segments: {str(e)}") from e

@@ -12,6 +12,7 @@
 //   bank_detect_update_kernel  a detect bank's tick: the windows' sigmoid sums into the per-slot f64 accumulators, mean probabilities and bits out
 //   segment_track_kernel   a live segment session's tick: the new frames' sums -> the per-stream open run, gap ring and ring of closed segments
 //   bank_segment_track_kernel  a segment bank's tick: the same per-stream body, a descriptor per slot with its own frame range and row block
+//   segment_split_kernel / bank_segment_split_kernel  the two trackers under a split rule: a run is also cut where the decoded id changes
 //   span_gather_kernel     span embedding: packed clips -> a left-aligned, right-zero-padded window batch, a {offset, length} descriptor per row
 //   span_scatter_add_kernel  span embedding: out = x + w * residual over each row's keep range, w the span's gain and edge ramp
 // Every kernel checks its indices against the buffer sizes it is given, so a bad table skips work instead of writing out of bounds.
@@ -385,6 +386,208 @@ __global__ __launch_bounds__(256) void bank_segment_track_kernel(const float* __
                          rec, ring);
 }
 
+// ---- splitting a run where the decoded id changes (localize.SplitRule is the definition) -------------------------
+// Byte layout (the header states it for callers): per stream `state` holds int64 {open, lo, hi, frames seen, plo, pending 0/1, cg}, f64 cS,
+// f64 sums [nb + 1] of the current piece over [plo, sb) and the ring [2 W + G][nb + 1] f32 of raw frame columns, frame j in slot
+// j % (2 W + G); `events` holds an int64 event counter and `capacity` records {int64 lo, int64 hi, f64 count, int64 flags, f32 prob[nb]}.
+// The next boundary to evaluate, gn = max(plo + W, hi - W + 1), and the first frame still in the ring, sb = max(plo, gn - W), follow from
+// the header: every boundary with W frames of the run on its right is evaluated as soon as `hi` allows it.
+static inline SegLayout split_layout(int nb, int G, int W, int capacity) {
+    SegLayout l;
+    l.state_stride = 64 + 8 * (size_t)(nb + 1) + up8(4 * (size_t)(2 * W + G) * (nb + 1));
+    l.rec = 32 + up8(4 * (size_t)nb);
+    l.event_stride = 8 + (size_t)capacity * l.rec;
+    return l;
+}
+
+struct SplitShared {
+    double L[256], R[256], D[256], cnt;
+    int V[256];
+};
+
+// One stream's tick under a split rule, run by one workgroup of nb + 1 threads rounded up to a wave, every thread together (the barriers
+// inside are reached by all: every decision below is taken alike by every thread, from the count row of fsum, which all read, and from values
+// that went through LDS).  Thread k <= nb owns row k: its window sums, its row of the ring and its piece sum.  A frame column stays in the
+// ring while a cut may still fall before it (from sb on); it joins the piece's f64 sum, in ascending order, when sb passes it or when its
+// piece is emitted, so the sum is one ascending pass over the piece whatever the ticks.  Frames of this tick are read from fsum, older ones
+// from the ring; at the end of the tick the columns from max(sb, frame0) on go into the ring (fewer than 2 W + G, so slots never collide).
+// Reads of the state come before the last barrier, writes after it; event records are write-only.
+__device__ __forceinline__ void segment_split_stream(const float* __restrict__ fs, size_t Fr, int nb, int n, long long frame0, int hop, int last_valid,
+                                                     int final_, double min_on, int G, int min_len, float eps, int W, double thr, int min_bits,
+                                                     char* st, char* ev, size_t rec, int capacity, SplitShared& sh) {
+    const int k = threadIdx.x;
+    const bool owns = k <= nb;
+    const int r = owns ? k : nb;
+    const float* crow = fs + (size_t)nb * Fr;
+    const float* krow = fs + (size_t)r * Fr;
+    long long* hdr = reinterpret_cast<long long*>(st);
+    double* cSp = reinterpret_cast<double*>(hdr + 7);
+    double* accp = cSp + 1;
+    float* ring = reinterpret_cast<float*>(accp + nb + 1);
+    long long* nevp = reinterpret_cast<long long*>(ev);
+    char* recs = reinterpret_cast<char*>(nevp + 1);
+    const int RC = 2 * W + G;
+
+    bool open = hdr[0] != 0, pend = hdr[5] != 0;
+    long long lo = hdr[1], hi = hdr[2], plo = hdr[4], cg = hdr[6], nev = *nevp;
+    double cS = *cSp, acc = accp[r];
+    // a state that cannot follow from zeros and gapless ticks is taken as closed; ring slots are addressed by j % RC with j >= 0 only
+    if (open && !(frame0 <= (1LL << 62) && lo >= 0 && lo <= plo && plo < hi && hi <= frame0 && frame0 - hi < G && (hdr[5] == 0 || hdr[5] == 1)))
+        open = false;
+    if (open && pend) {
+        const long long gn0 = plo + W > hi - W + 1 ? plo + W : hi - W + 1;
+        if (!(cg >= plo + W && cg <= hi - W && gn0 - cg <= W)) open = false;
+    }
+    if (!open) pend = false;
+    if (nev < 0 || nev > (1LL << 62)) nev = 0;
+    long long gn = 0, sb = 0;
+    if (open) {
+        gn = plo + W > hi - W + 1 ? plo + W : hi - W + 1;
+        sb = plo > gn - W ? plo : gn - W;
+    }
+
+    auto col = [&](long long j) -> double {
+        return (double)(j >= frame0 ? krow[j - frame0] : ring[(size_t)(j % RC) * (nb + 1) + r]);
+    };
+    auto add_to = [&](long long e) {
+        for (; sb < e; ++sb) acc += col(sb);
+    };
+    // the piece [plo, e) becomes the next event; flags bit 0: its start is a cut, bit 1: its end is one
+    auto emit = [&](long long e, long long flags) {
+        add_to(e);
+        if (k == nb) sh.cnt = acc;
+        __syncthreads();
+        const double cnt = sh.cnt;
+        char* rp = recs + (size_t)(nev % capacity) * rec;
+        if (k == 0) {
+            reinterpret_cast<long long*>(rp)[0] = plo;
+            reinterpret_cast<long long*>(rp)[1] = e;
+            reinterpret_cast<double*>(rp)[2] = cnt;
+            reinterpret_cast<long long*>(rp)[3] = flags | (plo > lo ? 1 : 0);
+        }
+        if (k < nb) {
+            const float d = (float)cnt + eps;
+            reinterpret_cast<float*>(rp + 32)[k] = cnt > 0.0 ? (float)(acc / (double)d) : 0.f;
+        }
+        ++nev;
+        __syncthreads();
+    };
+    auto commit = [&]() {
+        emit(cg, 2);
+        plo = cg;
+        pend = false;
+        acc = 0.0;
+    };
+    auto evaluate = [&](long long g) {
+        if (pend && g - cg >= W) commit();
+        double L = 0.0, Rs = 0.0;
+        for (long long j = g - W; j < g; ++j) L += col(j);
+        for (long long j = g; j < g + W; ++j) Rs += col(j);
+        if (owns) {
+            sh.L[k] = L;
+            sh.R[k] = Rs;
+        }
+        __syncthreads();
+        const double Ln = sh.L[nb], Rn = sh.R[nb];
+        const bool ok = Ln > 0.0 && Rn > 0.0;
+        if (ok && k < nb) {
+            const double pL = L / Ln, pR = Rs / Rn;
+            sh.D[k] = fabs(pL - pR);
+            sh.V[k] = (pL >= 0.5) != (pR >= 0.5) ? 1 : 0;
+        }
+        __syncthreads();
+        if (ok) {
+            double S = 0.0;
+            int d = 0;
+            for (int q = 0; q < nb; ++q) {
+                S += sh.D[q];
+                d += sh.V[q];
+            }
+            if (S >= thr && d >= min_bits && (!pend || S > cS)) {
+                pend = true;
+                cg = g;
+                cS = S;
+            }
+        }
+        __syncthreads();
+    };
+    auto close = [&]() {
+        if (hi - lo >= min_len) {
+            if (pend) commit();
+            emit(hi, 0);
+        }
+        open = pend = false;
+    };
+
+    for (int i = 0; i < n; ++i) {
+        const long long g = frame0 + i;
+        const float c = crow[i];
+        const int valid = (final_ && i == n - 1) ? last_valid : hop;
+        const bool on = valid > 0 && (double)c >= min_on * (double)valid;
+        if (on) {
+            if (!open) {
+                open = true;
+                pend = false;
+                lo = plo = sb = g;
+                gn = g + W;
+                acc = 0.0;
+            }
+            hi = g + 1;
+            while (gn + W <= hi) {
+                evaluate(gn);
+                ++gn;
+                add_to(plo > gn - W ? plo : gn - W);
+            }
+        } else if (open && g + 1 - hi >= G) {
+            close();
+        }
+    }
+    if (final_ && open) close();
+    __syncthreads();
+
+    const long long fend = frame0 + n;
+    if (owns) {
+        if (open)
+            for (long long j = sb > frame0 ? sb : frame0; j < fend; ++j) ring[(size_t)(j % RC) * (nb + 1) + k] = krow[j - frame0];
+        accp[k] = acc;
+    }
+    if (k == 0) {
+        hdr[0] = open ? 1 : 0;
+        hdr[1] = lo;
+        hdr[2] = hi;
+        hdr[3] = fend;
+        hdr[4] = plo;
+        hdr[5] = pend ? 1 : 0;
+        hdr[6] = cg;
+        *cSp = cS;
+        *nevp = nev;
+    }
+}
+
+// grid (S), block = nb + 1 rounded up to a wave: wv_segment_track's launch shape with the split body.
+__global__ __launch_bounds__(256) void segment_split_kernel(const float* __restrict__ fsum, int nb, int Fr, int f_lo, int n, long long frame0, int hop,
+                                                            int last_valid, int final_, double min_on, int G, int min_len, float eps, int W,
+                                                            double thr, int min_bits, char* state, size_t state_stride, char* events,
+                                                            size_t event_stride, size_t rec, int capacity) {
+    __shared__ SplitShared sh;
+    const int s = blockIdx.x;
+    segment_split_stream(fsum + (size_t)s * (nb + 1) * Fr + f_lo, (size_t)Fr, nb, n, frame0, hop, last_valid, final_, min_on, G, min_len, eps, W, thr,
+                         min_bits, state + (size_t)s * state_stride, events + (size_t)s * event_stride, rec, capacity, sh);
+}
+
+// grid (P), block = nb + 1 rounded up to a wave: wv_bank_segment_track's descriptors and row predicate with the split body.
+__global__ __launch_bounds__(256) void bank_segment_split_kernel(const float* __restrict__ fsum, int64_t n_fsum, const int64_t* __restrict__ desc,
+                                                                 int capacity, int nb, int hop, double min_on, int G, int min_len, float eps, int W,
+                                                                 double thr, int min_bits, char* state, size_t state_stride, char* events,
+                                                                 size_t event_stride, size_t rec, int ring) {
+    __shared__ SplitShared sh;
+    const TrackRow r = track_row(desc, blockIdx.x, capacity, nb, hop, n_fsum);
+    if (!r.ok || (r.f_hi == r.f_lo && !r.final_)) return;
+    segment_split_stream(fsum + r.off + r.f_lo, (size_t)r.Fr, nb, (int)(r.f_hi - r.f_lo), (long long)r.frame0, hop, (int)r.last_valid,
+                         r.final_ != 0, min_on, G, min_len, eps, W, thr, min_bits, state + (size_t)r.slot * state_stride,
+                         events + (size_t)r.slot * event_stride, rec, ring, sh);
+}
+
 // ---- span embedding: windows of chosen stretches, the residual added inside the stretch only -------------------
 // grid (ceil(Lmax / WIN_TILE), A).  desc[r] = {src offset, wlen}: row r = src[off .. off + wlen), then zeros in [wlen, Lmax).  A row that
 // reaches outside src or beyond Lmax is skipped whole (not even zero-filled).
@@ -600,6 +803,78 @@ extern "C" int wv_bank_segment_track(const float* fsum, int64_t n_fsum, const in
     const int nt = (nb + 1 + 63) / 64 * 64;
     hipLaunchKernelGGL(wv::bank_segment_track_kernel, dim3(P), dim3(nt), 0, (hipStream_t)stream, fsum, n_fsum, desc, capacity, nb, hop, min_on,
                        min_gap_frames, min_len_frames, eps, (char*)state, l.state_stride, (char*)events, l.event_stride, l.rec, ring);
+    return launched();
+}
+
+static const char* split_rule_bad(int nb, int G, int min_len, int W, double thr, int min_bits) {
+    const int need = G > min_len ? (G > 2 ? G : 2) : (min_len > 2 ? min_len : 2);
+    if (W < need || W > WV_SPLIT_MAX_WINDOW) return "window_frames outside [max(2, min_gap_frames, min_len_frames), " WV_STR(WV_SPLIT_MAX_WINDOW) "]";
+    if (!(thr > 0.0)) return "threshold not above 0";
+    if (min_bits < 1 || min_bits > nb) return "min_bits outside [1, nb]";
+    return nullptr;
+}
+
+extern "C" int wv_segment_split_bytes(int S, int nb, int min_gap_frames, int window_frames, int capacity, size_t* state_bytes,
+                                      size_t* event_bytes) {
+    if (!state_bytes || !event_bytes || S < 1 || S > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS || min_gap_frames < 1 ||
+        min_gap_frames > WV_SEGMENT_MAX_GAP || window_frames < 2 || window_frames > WV_SPLIT_MAX_WINDOW || capacity < 1)
+        return fail(WV_EINVAL, "wv_segment_split_bytes: null output, S outside [1, 65535], nb outside [1, "
+                               WV_STR(WV_SEGMENT_MAX_BITS) "], min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP)
+                               "], window_frames outside [2, " WV_STR(WV_SPLIT_MAX_WINDOW) "] or capacity < 1");
+    const wv::SegLayout l = wv::split_layout(nb, min_gap_frames, window_frames, capacity);
+    *state_bytes = (size_t)S * l.state_stride;
+    *event_bytes = (size_t)S * l.event_stride;
+    return WV_OK;
+}
+
+extern "C" int wv_segment_track_split(const float* fsum, int S, int nb, int Fr_stride, int f_lo, int f_hi, int64_t frame0, int hop, int last_valid,
+                                      int final, double min_on, int min_gap_frames, int min_len_frames, float eps, int window_frames,
+                                      double threshold, int min_bits, void* state, size_t state_bytes, void* events, size_t event_bytes,
+                                      int capacity, void* stream) {
+    if (!state || !events || S < 1 || S > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS)
+        return fail(WV_EINVAL, "wv_segment_track_split: null state / events, S outside [1, 65535] or nb outside [1, " WV_STR(WV_SEGMENT_MAX_BITS) "]");
+    if (min_gap_frames < 1 || min_gap_frames > WV_SEGMENT_MAX_GAP || min_len_frames < 0 || capacity < 1 || !(min_on == min_on))
+        return fail(WV_EINVAL, "wv_segment_track_split: min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP) "], min_len_frames < 0, capacity < 1 "
+                               "or min_on not a number");
+    if (const char* bad = split_rule_bad(nb, min_gap_frames, min_len_frames, window_frames, threshold, min_bits))
+        return fail(WV_EINVAL, std::string("wv_segment_track_split: ") + bad);
+    if (f_lo < 0 || f_hi < f_lo || f_hi > Fr_stride || (f_hi > f_lo && !fsum) || frame0 < 0 || hop < 1 || last_valid < 0 || last_valid > hop)
+        return fail(WV_EINVAL, "wv_segment_track_split: frames [f_lo, f_hi) outside [0, Fr_stride] (or frames without fsum), frame0 < 0, hop < 1 or "
+                               "last_valid outside [0, hop]");
+    const wv::SegLayout l = wv::split_layout(nb, min_gap_frames, window_frames, capacity);
+    if (state_bytes < (size_t)S * l.state_stride || event_bytes < (size_t)S * l.event_stride || ((uintptr_t)state & 7) || ((uintptr_t)events & 7))
+        return fail(WV_EINVAL, "wv_segment_track_split: state or events shorter than wv_segment_split_bytes gives, or not 8-byte aligned");
+    if (f_hi == f_lo && !final) return WV_OK;
+    const int nt = (nb + 1 + 63) / 64 * 64;
+    hipLaunchKernelGGL(wv::segment_split_kernel, dim3(S), dim3(nt), 0, (hipStream_t)stream, fsum, nb, Fr_stride, f_lo, f_hi - f_lo, (long long)frame0,
+                       hop, last_valid, final, min_on, min_gap_frames, min_len_frames, eps, window_frames, threshold, min_bits, (char*)state,
+                       l.state_stride, (char*)events, l.event_stride, l.rec, capacity);
+    return launched();
+}
+
+extern "C" int wv_bank_segment_track_split(const float* fsum, int64_t n_fsum, const int64_t* desc, int P, int capacity, int nb, int hop, double min_on,
+                                           int min_gap_frames, int min_len_frames, float eps, int window_frames, double threshold, int min_bits,
+                                           void* state, size_t state_bytes, void* events, size_t event_bytes, int ring, void* stream) {
+    if (!desc || !state || !events || n_fsum < 0 || (n_fsum > 0 && !fsum))
+        return fail(WV_EINVAL, "wv_bank_segment_track_split: null desc, state or events, n_fsum < 0, or frame sums without fsum");
+    if (capacity < 1 || capacity > WV_BANK_MAX_SLOTS || P < 0 || P > 65535 || nb < 1 || nb > WV_SEGMENT_MAX_BITS || hop < 1)
+        return fail(WV_EINVAL, "wv_bank_segment_track_split: capacity outside [1, " WV_STR(WV_BANK_MAX_SLOTS) "], P outside [0, 65535], nb outside [1, "
+                               WV_STR(WV_SEGMENT_MAX_BITS) "] or hop < 1");
+    if (min_gap_frames < 1 || min_gap_frames > WV_SEGMENT_MAX_GAP || min_len_frames < 0 || ring < 1 || !(min_on == min_on))
+        return fail(WV_EINVAL, "wv_bank_segment_track_split: min_gap_frames outside [1, " WV_STR(WV_SEGMENT_MAX_GAP) "], min_len_frames < 0, ring < 1 "
+                               "or min_on not a number");
+    if (const char* bad = split_rule_bad(nb, min_gap_frames, min_len_frames, window_frames, threshold, min_bits))
+        return fail(WV_EINVAL, std::string("wv_bank_segment_track_split: ") + bad);
+    const wv::SegLayout l = wv::split_layout(nb, min_gap_frames, window_frames, ring);
+    if (state_bytes / l.state_stride < (size_t)capacity || event_bytes / l.event_stride < (size_t)capacity || ((uintptr_t)state & 7) ||
+        ((uintptr_t)events & 7))
+        return fail(WV_EINVAL, "wv_bank_segment_track_split: state or events shorter than wv_segment_split_bytes gives for `capacity` streams, or "
+                               "not 8-byte aligned");
+    if (P == 0) return WV_OK;
+    const int nt = (nb + 1 + 63) / 64 * 64;
+    hipLaunchKernelGGL(wv::bank_segment_split_kernel, dim3(P), dim3(nt), 0, (hipStream_t)stream, fsum, n_fsum, desc, capacity, nb, hop, min_on,
+                       min_gap_frames, min_len_frames, eps, window_frames, threshold, min_bits, (char*)state, l.state_stride, (char*)events,
+                       l.event_stride, l.rec, ring);
     return launched();
 }
 

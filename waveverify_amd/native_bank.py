@@ -444,3 +444,7 @@ class NativeSegmentBank(_HipBankStages, HostFrontBank):
 
     def open_segments(self) -> dict:
         return self.inner.open_segments()
+
+    def set_split(self, rule) -> None:
+        """session.SegmentBank.set_split on the 16 kHz frames: only before the first open()."""
+        self.inner.set_split(rule)

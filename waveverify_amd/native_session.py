@@ -397,3 +397,7 @@ class NativeSegmentSession(_HipStages, HostFrontSession):
 
     def open_segments(self):
         return self.inner.open_segments()
+
+    def set_split(self, rule) -> None:
+        """session.SegmentSession.set_split on the 16 kHz frames: only before the first push."""
+        self.inner.set_split(rule)

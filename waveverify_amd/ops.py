@@ -280,6 +280,80 @@ def segment_state(state, S: int, nb: int):
     return hdr, acc
 
 
+# ---- the same two trackers under a split rule (localize.SplitRule) ------------------------------------
+def segment_split_bytes(S: int, nb: int, min_gap_frames: int, window_frames: int, capacity: int):
+    """wv_segment_split_bytes -> (state bytes, event bytes) of S split trackers."""
+    import ctypes as C
+    sb, eb = C.c_size_t(), C.c_size_t()
+    _lib.check(_lib.load().wv_segment_split_bytes(int(S), int(nb), int(min_gap_frames), int(window_frames), int(capacity), C.byref(sb),
+                                                  C.byref(eb)), "wv_segment_split_bytes")
+    return sb.value, eb.value
+
+
+def _byte_buffers(state, events) -> None:
+    if not (state.is_cuda and events.is_cuda and state.dtype == torch.uint8 and events.dtype == torch.uint8 and state.is_contiguous()
+            and events.is_contiguous()):
+        raise ValueError("state and events must be contiguous uint8 tensors on the GPU")
+
+
+def segment_track_split(fsum, f_lo: int, f_hi: int, frame0: int, hop: int, last_valid: int, final: bool, min_on: float, min_gap_frames: int,
+                        min_len_frames: int, rule, state, events, capacity: int, eps: float = 1e-8) -> None:
+    """wv_segment_track_split: segment_track's tick under `rule` (a localize.SplitRule); state / events of segment_split_bytes."""
+    lib = _lib.load()
+    fsum = _lib.dev(fsum, _ON_GPU)
+    S, nb1, Fr = fsum.shape
+    _byte_buffers(state, events)
+    _lib.check(lib.wv_segment_track_split(fsum.data_ptr() if Fr else None, S, nb1 - 1, max(Fr, 1), int(f_lo), int(f_hi), int(frame0), int(hop),
+                                          int(last_valid), int(bool(final)), float(min_on), int(min_gap_frames), int(min_len_frames),
+                                          float(eps), int(rule.window_frames), float(rule.threshold), int(rule.min_bits), state.data_ptr(),
+                                          state.numel(), events.data_ptr(), events.numel(), int(capacity), _lib.stream()),
+               "wv_segment_track_split")
+
+
+def bank_segment_track_split(fsum, desc, P: int, capacity: int, nb: int, hop: int, min_on: float, min_gap_frames: int, min_len_frames: int,
+                             rule, state, events, ring: int, eps: float = 1e-8) -> None:
+    """wv_bank_segment_track_split: bank_segment_track's tick under `rule`; state / events of segment_split_bytes(capacity, ..., ring)."""
+    lib = _lib.load()
+    if fsum is not None and not (fsum.is_cuda and fsum.dtype == torch.float32 and fsum.is_contiguous()):
+        raise ValueError("fsum must be a contiguous float32 tensor on the GPU")
+    if not (desc.is_cuda and desc.dtype == torch.int64 and desc.is_contiguous() and desc.numel() >= 8 * int(P)):
+        raise ValueError("desc must be a contiguous int64 tensor on the GPU with 8 values per row")
+    _byte_buffers(state, events)
+    n_fsum = 0 if fsum is None else fsum.numel()
+    _lib.check(lib.wv_bank_segment_track_split(fsum.data_ptr() if n_fsum else None, n_fsum, desc.data_ptr(), int(P), int(capacity), int(nb),
+                                               int(hop), float(min_on), int(min_gap_frames), int(min_len_frames), float(eps),
+                                               int(rule.window_frames), float(rule.threshold), int(rule.min_bits), state.data_ptr(),
+                                               state.numel(), events.data_ptr(), events.numel(), int(ring), _lib.stream()),
+               "wv_bank_segment_track_split")
+
+
+def split_event_dtype(nb: int) -> np.dtype:
+    """One event record of the split trackers' `events` buffer; flags bit 0: the start is an id change, bit 1: the end is one."""
+    return np.dtype({"names": ["lo", "hi", "count", "flags", "prob"], "formats": ["<i8", "<i8", "<f8", "<i8", ("<f4", (int(nb),))],
+                     "offsets": [0, 8, 16, 24, 32], "itemsize": 32 + (4 * int(nb) + 7) // 8 * 8})
+
+
+def split_events(events, S: int, nb: int, capacity: int):
+    """segment_events for the split trackers -> (n [S] int64 events so far, records [S, capacity] of split_event_dtype)."""
+    raw = events.cpu().numpy().reshape(S, -1)
+    rec = split_event_dtype(nb)
+    n = raw[:, :8].copy().view("<i8").reshape(S)
+    recs = raw[:, 8:8 + capacity * rec.itemsize].copy().view(rec).reshape(S, capacity)
+    return n, recs
+
+
+def split_state(state, S: int, nb: int, min_gap_frames: int, window_frames: int):
+    """The split trackers' `state` read back -> (header [S, 7] int64 {open, lo, hi, frames seen, plo, pending, cg}, cS [S] float64, sums
+    [S, nb + 1] float64 of the current pieces over [plo, sb), ring [S, 2 W + G, nb + 1] float32)."""
+    raw = state.cpu().numpy().reshape(S, -1)
+    RC, a = 2 * int(window_frames) + int(min_gap_frames), 64 + 8 * (nb + 1)
+    hdr = raw[:, :56].copy().view("<i8").reshape(S, 7)
+    cS = raw[:, 56:64].copy().view("<f8").reshape(S)
+    acc = raw[:, 64:a].copy().view("<f8").reshape(S, nb + 1)
+    ring = raw[:, a:a + 4 * RC * (nb + 1)].copy().view("<f4").reshape(S, RC, nb + 1)
+    return hdr, cS, acc, ring
+
+
 # ---- the f16 mode's units (csrc/wv_h16.hip).  A "c8" tensor is torch.float16 [B, roundup(C,16)/8, T, 8] --------------------------
 def _c8(t: torch.Tensor) -> torch.Tensor:
     if not (t.is_cuda and t.dtype == torch.float16 and t.dim() == 4 and t.shape[-1] == 8 and t.is_contiguous()):

@@ -304,6 +304,20 @@ def _open_run_of(hdr, acc, nb: int, eps: float):
     return int(hdr[1]), int(hdr[2]), float(cnt), prob
 
 
+def _open_piece_of(hdr, acc, ring, nb: int, W: int, eps: float):
+    """One stream's header, sums and ring as ops.split_state reads them -> its current piece (plo, hi, count, prob, (start is a change,
+    False)), or None: the ring's columns [sb, hi) join the sums in ascending order, as the kernel will add them."""
+    if not hdr[0]:
+        return None
+    lo, hi, plo = int(hdr[1]), int(hdr[2]), int(hdr[4])
+    acc = acc.copy()
+    for j in range(max(plo, hi - 2 * W + 1), hi):
+        acc += ring[j % ring.shape[0]].astype(np.float64)
+    cnt = acc[nb]
+    prob = (acc[:nb] / np.float64(np.float32(cnt) + np.float32(eps))).astype(np.float32) if cnt > 0.0 else np.zeros(nb, np.float32)
+    return plo, hi, float(cnt), prob, (plo > lo, False)
+
+
 class _SegmentReader:
     """What a segment session and a segment bank do with their tracker's events: hop, sample_rate, the event ring and the period of cut_rows,
     per stream the Segments closed and not yet handed out, per ring-reading unit the frames tracked since its last read (a lockstep session
@@ -313,6 +327,17 @@ class _SegmentReader:
     def _init_reader(self, hop: int, sample_rate: int, ring: int, min_gap_frames: int, min_len_frames: int) -> None:
         self.hop, self.sample_rate, self.ring = hop, int(sample_rate), int(ring)
         self._period = max(1, int(min_len_frames) + int(min_gap_frames))
+        self._cut_ring = self.ring
+        self.split = None
+
+    def _set_split(self, rule) -> None:
+        """The tracker takes the rule (and checks it against its own parameters).  Under a rule a stream can close more events over the same
+        frames: cuts inside a run lie at least window_frames >= period / 2 frames apart and a close can emit two pieces at once, fewer than
+        6 (frames // period + 1) events in all, so cut_rows works with a sixth of the ring."""
+        if rule is not None and self.ring < 6:
+            raise ValueError(f"a split rule needs an event ring of at least 6, got {self.ring}")
+        self._tracker.set_split(rule)
+        self.split, self._cut_ring = rule, self.ring if rule is None else self.ring // 6
 
     def _clear_reader(self, streams: int, counters: int) -> None:
         self._pending = [[] for _ in range(streams)]
@@ -326,13 +351,15 @@ class _SegmentReader:
         the stream has ended and never short of a closed run before, so `end` is clipped only on the partial last frame."""
         from .localize import Segment
         from .watermark_id import WatermarkID
-        lo, hi, count, prob = ev
+        lo, hi, count, prob = ev[:4]
+        change = tuple(bool(c) for c in ev[4]) if len(ev) > 4 else (False, False)
         hop, fs = self.hop, self.sample_rate
         end = min(int(hi) * hop, t_in)
         prob = np.asarray(prob, np.float32)
         bits = "".join("1" if p >= np.float32(0.5) else "0" for p in prob)
         wid = WatermarkID.custom(bits) if len(bits) == 16 else None        # an id has 16 bits; a net of another width leaves prob to read
-        return Segment(int(lo) * hop / fs, end / fs, wid, self._confidence(prob), float(count) / (end - int(lo) * hop), prob, (int(lo), int(hi)))
+        return Segment(int(lo) * hop / fs, end / fs, wid, self._confidence(prob), float(count) / (end - int(lo) * hop), prob, (int(lo), int(hi)),
+                       change)
 
     def _drain(self) -> None:
         """Read the rings (the one host synchronisation a push can make)."""
@@ -350,7 +377,7 @@ class _SegmentReader:
         return [(s, None if ev is None else self._segment_of(ev, t_in)) for s, t_in, ev in self._streams(self._tracker.open_runs)]
 
     def _cut(self, rows: list):
-        return cut_rows(rows, self._unread, self.ring, self._period, self.hop)
+        return cut_rows(rows, self._unread, self._cut_ring, self._period, self.hop)
 
 
 class SegmentStreamSession(_SegmentReader, StreamSession):
@@ -390,8 +417,16 @@ class SegmentStreamSession(_SegmentReader, StreamSession):
         return [self._taken(s) for s in range(self.S)]
 
     def open_segments(self):
-        """-> per stream the run that is open now as a provisional Segment (its frames so far), or None."""
+        """-> per stream the run that is open now as a provisional Segment (its frames so far), or None.  Under a split rule: the run's
+        current piece."""
         return [seg for _, seg in self._open_now()]
+
+    def set_split(self, rule) -> None:
+        """Cut runs where the decoded id changes (localize.SplitRule; None: off).  Only before the first push (or
+        after reset()); poll(), flush() and open_segments() then deal in pieces, known 2 * window_frames frames after a change."""
+        if self._gated is not None:
+            raise RuntimeError("set_split is legal only before the first push; reset() first")
+        self._set_split(rule)
 
     # ---- ticks
     def _track(self, fsum, f_lo: int, f_hi: int, last_valid: int, final: bool) -> None:
@@ -453,9 +488,23 @@ class _HipTrackerState:
         self.nb, self.hop, self.min_on = int(nb), int(hop), float(min_on)
         self.G, self.min_len, self.eps, self.device = int(min_gap_frames), int(min_len_frames), float(eps), device
         self._n, self._ring, self._torch, self._ops = int(n), int(ring), torch, ops
-        with torch.cuda.device(device):
-            self._bytes = ops.segment_track_bytes(self._n, self.nb, self.G, self._ring)          # refuses what the kernel would
+        self._size(None)
+
+    def _size(self, rule) -> None:
+        """The buffers' sizes without or with a split rule (the two kernels have layouts of their own)."""
+        ops = self._ops
+        with self._torch.cuda.device(self.device):                                                # refuses what the kernel would
+            self._bytes = (ops.segment_track_bytes(self._n, self.nb, self.G, self._ring) if rule is None else
+                           ops.segment_split_bytes(self._n, self.nb, self.G, rule.window_frames, self._ring))
         self._strides = (self._bytes[0] // self._n, self._bytes[1] // self._n)
+        self.split = rule
+
+    def set_split(self, rule) -> None:
+        """Track under `rule` (None: plainly) from zeroed buffers: the split kernels replace the plain ones."""
+        if rule is not None:
+            rule.check(self.nb, self.G, self.min_len)
+        self._size(rule)
+        self._clear()
 
     def _clear(self) -> None:
         torch = self._torch
@@ -465,20 +514,33 @@ class _HipTrackerState:
 
     def _new_events(self, streams) -> list:
         """-> [(stream, its events (lo, hi, count, prob) since the last read)]; refuses a ring that has been overrun."""
-        n, recs = self._ops.segment_events(self.events, self._n, self.nb, self._ring)
+        rule = self.split
+        n, recs = (self._ops.segment_events if rule is None else self._ops.split_events)(self.events, self._n, self.nb, self._ring)
         out = []
         for s in streams:
             new = int(n[s]) - self._read[s]
             if new > self._ring:
                 raise RuntimeError(f"{self._what} {s}: {new} segments closed since the last read of a ring of {self._ring}: events were lost")
-            out.append((s, [(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy())
-                            for r in (recs[s, e % self._ring] for e in range(self._read[s], int(n[s])))]))
+            new = [(int(r["lo"]), int(r["hi"]), float(r["count"]), r["prob"].copy()) +
+                   (() if rule is None else ((bool(r["flags"] & 1), bool(r["flags"] & 2)),))
+                   for r in (recs[s, e % self._ring] for e in range(self._read[s], int(n[s])))]
+            out.append((s, new))
             self._read[s] = int(n[s])
         return out
 
     def _open_runs_of(self, streams) -> list:
+        if self.split is not None:
+            W = self.split.window_frames
+            hdr, _, acc, ring = self._ops.split_state(self.state, self._n, self.nb, self.G, W)
+            return [(s, _open_piece_of(hdr[s], acc[s], ring[s], self.nb, W, self.eps)) for s in streams]
         hdr, acc = self._ops.segment_state(self.state, self._n, self.nb)
         return [(s, _open_run_of(hdr[s], acc[s], self.nb, self.eps)) for s in streams]
+
+    def split_state(self, streams) -> list:
+        """-> [(stream, localize.SegmentTracker.split_state's tuple or None)], read from the device."""
+        hdr, cS, acc, _ = self._ops.split_state(self.state, self._n, self.nb, self.G, self.split.window_frames)
+        return [(s, (int(hdr[s][1]), int(hdr[s][2]), int(hdr[s][4]), int(hdr[s][6]) if hdr[s][5] else -1, float(cS[s]) if hdr[s][5] else 0.0,
+                     acc[s].copy()) if hdr[s][0] else None) for s in streams]
 
 
 class HipSegmentTracker(_HipTrackerState):
@@ -495,13 +557,22 @@ class HipSegmentTracker(_HipTrackerState):
         self._clear()
         self.frames_seen, self.closed = 0, False
 
+    def set_split(self, rule) -> None:
+        super().set_split(rule)
+        self.frames_seen, self.closed = 0, False
+
     def advance(self, fsum, f_lo: int = 0, f_hi: Optional[int] = None, last_valid: Optional[int] = None, final: bool = False) -> None:
         if self.closed:
             raise RuntimeError("tracker saw its final frame; call reset() to start over")
         f_hi = int(fsum.shape[2]) if f_hi is None else int(f_hi)
+        lv = self.hop if last_valid is None else last_valid
         with self._torch.cuda.device(self.device):
-            self._ops.segment_track(fsum, f_lo, f_hi, self.frames_seen, self.hop, self.hop if last_valid is None else last_valid, final,
-                                    self.min_on, self.G, self.min_len, self.state, self.events, self.capacity, self.eps)
+            if self.split is None:
+                self._ops.segment_track(fsum, f_lo, f_hi, self.frames_seen, self.hop, lv, final, self.min_on, self.G, self.min_len, self.state,
+                                        self.events, self.capacity, self.eps)
+            else:
+                self._ops.segment_track_split(fsum, f_lo, f_hi, self.frames_seen, self.hop, lv, final, self.min_on, self.G, self.min_len,
+                                              self.split, self.state, self.events, self.capacity, self.eps)
         self.frames_seen += f_hi - int(f_lo)
         self.closed = bool(final)
 
@@ -965,9 +1036,18 @@ class SegmentStreamBank(_SegmentReader, StreamBank):
         self._clear_reader(self.capacity, self.capacity)
         self._ghist = self._arr.zeros(self.capacity, self.hcap) if self.gated else None
         self._frames = [0] * self.capacity                                 # frames tracked so far: the next tick's frame0
+        self._opened = False
 
     # ---- slots
+    def set_split(self, rule) -> None:
+        """Cut runs where the decoded id changes (localize.SplitRule; None: off), for every slot.  Only before the
+        first open(); poll(), close() and open_segments() then deal in pieces, known 2 * window_frames frames after a change."""
+        if self._opened:
+            raise RuntimeError("set_split is legal only before the bank's first open()")
+        self._set_split(rule)
+
     def _on_open(self, slot: int) -> None:
+        self._opened = True
         self._tracker.reset(slot)                                          # whatever the slot's last stream left is never seen
         self._frames[slot] = self._unread[slot] = 0
         self._pending[slot] = []
@@ -1082,9 +1162,14 @@ class HipBankSegmentTracker(_HipTrackerState):
         if not hasattr(desc, "data_ptr"):
             desc = torch.from_numpy(np.ascontiguousarray(desc, np.int64)).to(self.device)
         P = int(desc.numel() // 8) if P is None else int(P)
+        fsum = fsum if fsum is not None and fsum.numel() else None
         with torch.cuda.device(self.device):
-            self._ops.bank_segment_track(fsum if fsum is not None and fsum.numel() else None, desc, P, self.capacity, self.nb, self.hop,
-                                         self.min_on, self.G, self.min_len, self.state, self.events, self.ring, self.eps)
+            if self.split is None:
+                self._ops.bank_segment_track(fsum, desc, P, self.capacity, self.nb, self.hop, self.min_on, self.G, self.min_len, self.state,
+                                             self.events, self.ring, self.eps)
+            else:
+                self._ops.bank_segment_track_split(fsum, desc, P, self.capacity, self.nb, self.hop, self.min_on, self.G, self.min_len,
+                                                   self.split, self.state, self.events, self.ring, self.eps)
 
     def poll(self, slots) -> dict:
         return dict(self._new_events(slots))
