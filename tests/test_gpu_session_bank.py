@@ -287,11 +287,21 @@ def _play(bank, kind, steps, data):
     return BK.run(bank, steps, {n: cu(x) for n, (x, _) in data.items()}, (lambda n: (data[n][1],)) if kind == "generator" else (lambda n: ()))[0]
 
 
-@functools.lru_cache(maxsize=None)
-def _references(cid, sched):
-    """-> (steps, data, {stream: whole-input reference [C, T] float64}) of a schedule, computed once for all pad_limits."""
+_REFERENCES = {}
+
+
+def _references(cid, sched, steps=None):
+    """-> (steps, data, {stream: whole-input reference [C, T] float64}) of a schedule, computed once for all pad_limits.  sched names one of
+    bank_cases.schedules(cfg), or the `steps` themselves, which are then remembered under that name."""
+    if (cid, sched) not in _REFERENCES:
+        _REFERENCES[cid, sched] = _compute_references(cid, sched, steps)
+    assert steps is None or steps == _REFERENCES[cid, sched][0], (cid, sched)
+    return _REFERENCES[cid, sched]
+
+
+def _compute_references(cid, sched, steps):
     case, cfg, net, onet = _net(cid)
-    steps = dict(BK.schedules(cfg))[sched]
+    steps = dict(BK.schedules(cfg))[sched] if steps is None else steps
     data = BK.stream_data(case, steps)
     refs = {}
     for n, (x, m) in data.items():
@@ -314,7 +324,7 @@ def _mean16(cid, sched, name, upto):
     return O16.detect_mean_prob(onet, x[None, None, :upto]).double().numpy()[0]
 
 
-def _check_stream(cid, sched, name, events, x, ref, hop, kind, f16, what):
+def _check_stream(cid, sched, name, events, x, ref, hop, kind, f16, what, tag=""):
     """One stream's results over a schedule: column counts, then the concatenation (or every DetectState) against its whole-input reference."""
     seen = [(pos // hop * hop if k == "push" else pos) for k, pos, _ in events]
     assert seen[-1] == x.size, what
@@ -335,9 +345,9 @@ def _check_stream(cid, sched, name, events, x, ref, hop, kind, f16, what):
             checks = [c for j, c in enumerate(checks) if j in (0, len(checks) - 1) or c is big]
         for _, upto, st in checks:
             if f16:
-                measure("f16 DetectBank mean probability / det_mean_bar(T)", rel_err(st.mean_prob, _mean16(cid, sched, name, upto), 1.0) / det_mean_bar(upto), 1.0)
+                measure(tag + "f16 DetectBank mean probability / det_mean_bar(T)", rel_err(st.mean_prob, _mean16(cid, sched, name, upto), 1.0) / det_mean_bar(upto), 1.0)
             else:
-                measure("exact DetectBank mean probability", rel_err(st.mean_prob, sigmoid64(ref[:, :upto]).mean(axis=1), 1.0), MEAN_BAR)
+                measure(tag + "exact DetectBank mean probability", rel_err(st.mean_prob, sigmoid64(ref[:, :upto]).mean(axis=1), 1.0), MEAN_BAR)
         return None
     done = 0
     for (k, pos, r), upto in zip(events, seen):
@@ -346,24 +356,25 @@ def _check_stream(cid, sched, name, events, x, ref, hop, kind, f16, what):
     return torch.cat([r for _, _, r in events]) if x.size else None
 
 
-def _check_bank(cid, sched, pad, precision):
+def _check_bank(cid, sched, pad, precision, steps=None, capacity=BK.CAPACITY, tag=""):
+    """A schedule by name, or the steps themselves under the name `sched` (tag: what their MEASURE lines start with)."""
     case, cfg, net, _ = _net(cid)
     kind, hop, f16 = cfg.kind, cfg.hop_length, precision == "f16"
-    steps, data, refs = _references(cid, sched)
-    bank = _bank(net, kind, precision, pad)
+    steps, data, refs = _references(cid, sched, steps)
+    bank = _bank(net, kind, precision, pad, capacity)
     out = _play(bank, kind, steps, data)
     assert bank.open_slots() == []
     mag = max(float(np.abs(r).max()) for r in refs.values())      # the reference's largest magnitude over the schedule's streams
     for n, (x, _) in data.items():
         what = f"{cid} {sched} pad_limit {pad} stream {n}"
-        got = _check_stream(cid, sched, n, out[n], x, refs.get(n), hop, kind, f16, what)
+        got = _check_stream(cid, sched, n, out[n], x, refs.get(n), hop, kind, f16, what, tag)
         if got is None:
             continue
         ref = refs[n][0]
         if kind == "generator":
-            measure("f16 EmbedBank (absolute)" if f16 else "exact EmbedBank", rel_err(got, ref, 1.0 if f16 else mag), WM_BAR if f16 else GEN_BAR)
+            measure(tag + ("f16 EmbedBank (absolute)" if f16 else "exact EmbedBank"), rel_err(got, ref, 1.0 if f16 else mag), WM_BAR if f16 else GEN_BAR)
         else:
-            measure("f16 LocateBank logits" if f16 else "exact LocateBank logits", rel_err(got, ref, max(1.0, mag) if f16 else mag),
+            measure(tag + ("f16 LocateBank logits" if f16 else "exact LocateBank logits"), rel_err(got, ref, max(1.0, mag) if f16 else mag),
                     LOGIT_BAR16 if f16 else LOGIT_BAR32)
     return bank
 
