@@ -322,11 +322,35 @@ int wv_profile_collect(int index, char* name_out, int name_cap, int64_t* launche
  *                          A descriptor row is SKIPPED whole unless 0 <= lo < hi <= Lmax, span start <= lo, hi <= span end, 0 <= o + lo and
  *                          o + hi <= n_out; the other rows are served.
  *                          Refused with WV_EINVAL and nothing written: null y, desc or out, n_out < 1, F < 0, F > 0 without ramp, gain not a
- *                          number, A outside [0, 65535], Lmax < 1.  A == 0 is success without a launch. */
+ *                          number, A outside [0, 65535], Lmax < 1.  A == 0 is success without a launch.
+ *   wv_snr_floor           the SNR floor of embedding (snr_floor.py; csrc/wv_snr_floor.hip): x (n_x floats) holds 16 kHz
+ *                          model input, r (n_r floats) the generator's residual for it, out (n_out floats) takes the result.  desc [A][8] int64
+ *                          device = {offset of the row in x, in r, in out, n, the strength s as its f32 bits (0 .. 2^32 - 1), index into gstate
+ *                          or -1, fresh flag, offset in gains or -1}.  ramp [L] f32 device = float32((k + 1) / L); rho = 10^(-min_snr_db / 10).
+ *                          Per row, frames of L samples counted from the row's sample 0 (a short last frame only at a stream's true end):
+ *                            Ex = sum x^2, Er = sum r^2 in float64, in THE fixed order: sample k of the frame goes to partial (k >> 2) & 15,
+ *                              each partial adds in ascending k from +0.0, then p[j] += p[j ^ 8], ^ 4, ^ 2, ^ 1;
+ *                            g[f] = s where Er == 0, else q < (double)s ? (float)q : s with q = sqrt((rho * Ex) / Er), divide and square
+ *                              root correctly rounded;  g_prev = g[f - 1], for frame 0 gstate[index] or, with index -1 or the fresh flag
+ *                              set (the stored value is then not read), g[0];
+ *                            w[k] = g_prev < g[f] ? min(g[f], g_prev + (g[f] - g_prev) * ramp[k]) : g[f]     f32, every rounding kept;
+ *                            v = w * r;  add == 0: out = v;  add == 1: out = x + v, but x's own bits where v is +0 or -0.
+ *                          gstate[index] = the row's last g (a row of n == 0 leaves it alone); gains[offset + f] = g[f].  n_max bounds every
+ *                          row's n and sizes the grid.  One launch; the result does not depend on the tile size, the geometry or the row's
+ *                          place in the call.  THE CALLER'S DUTY: two rows of one call never name the same state, rows' ranges in out and
+ *                          gains are disjoint, and gstate / gains overlap no other argument.
+ *                          A descriptor row is SKIPPED whole unless 0 <= n <= n_max, its three ranges lie inside n_x, n_r and n_out, s is
+ *                          finite and >= 0, -1 <= index < n_state, and the gains offset is -1 or offset + ceil(n / L) <= n_gains; the other
+ *                          rows are served.
+ *                          Refused with WV_EINVAL and nothing written: null x, r, out, desc or ramp; a negative size; n_state > 0 without
+ *                          gstate or n_gains > 0 without gains; L outside [1, WV_SNR_FLOOR_MAX_FRAME]; rho not finite or <= 0; A outside
+ *                          [0, 65535]; n_max outside [0, 2^31 - 1]; add not 0 or 1; out overlapping x or r (a tile reads the frame before
+ *                          it again).  A == 0 or n_max == 0 is success without a launch. */
 #define WV_SEGMENT_MAX_GAP 64
 #define WV_SEGMENT_MAX_BITS 255
 #define WV_BANK_MAX_SLOTS 1048576
 #define WV_SPLIT_MAX_WINDOW 256
+#define WV_SNR_FLOOR_MAX_FRAME 1048576
 int wv_window_gather(const float* src, int64_t n_src, const int64_t* offs, float* dst, int W, int L, void* stream);
 int wv_window_scatter(const float* y, const int64_t* desc, float* out, int64_t n_out, int W, int C, int L, void* stream);
 int wv_detector_forward_windowed(wv_model* m, const float* x, const int* keep_lo, const int* keep_hi, float* psum,
@@ -360,6 +384,8 @@ int wv_bank_segment_track_split(const float* fsum, int64_t n_fsum, const int64_t
 int wv_span_gather(const float* src, int64_t n_src, const int64_t* desc, float* dst, int A, int Lmax, void* stream);
 int wv_span_scatter_add(const float* y, const float* x, const int64_t* desc, const float* ramp, int F, float gain, float* out, int64_t n_out,
                         int A, int Lmax, void* stream);
+int wv_snr_floor(const float* x, int64_t n_x, const float* r, int64_t n_r, float* out, int64_t n_out, const int64_t* desc, int A, int64_t n_max,
+                 float* gstate, int n_state, float* gains, int64_t n_gains, const float* ramp, int L, double rho, int add, void* stream);
 
 /* ==== csrc/wv_ops.hip ===================================================================== */
 /* ---- single fused units ----------------------------------------------------------------

@@ -91,6 +91,8 @@ SIGNATURES = {
                                               C.c_int, _VP, C.c_size_t, _VP, C.c_size_t, C.c_int, _VP]),
     "wv_span_gather": (C.c_int, [_VP, C.c_int64, _VP, _VP, C.c_int, C.c_int, _VP]),
     "wv_span_scatter_add": (C.c_int, [_VP, _VP, _VP, _VP, C.c_int, C.c_float, _VP, C.c_int64, C.c_int, C.c_int, _VP]),
+    "wv_snr_floor": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int64, _VP, C.c_int, C.c_int64, _VP, C.c_int, _VP, C.c_int64, _VP, C.c_int,
+                               C.c_double, C.c_int, _VP]),
     "wv_op_pw_dw": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
                               C.c_int, _VP, C.c_float, _VP]),

@@ -17,7 +17,7 @@ from typing import Dict, List, Mapping, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import localize, native, native_bank, native_session, ops, session, window
+from . import localize, native, native_bank, native_session, ops, session, snr_floor, window
 from .checkpoint import load_checkpoint
 from .config import NetConfig, default_config
 from .init import random_state_dict
@@ -32,6 +32,8 @@ logger = logging.getLogger(__name__)
 class WaveVerify:
     DEFAULT_SAMPLE_RATE: int = 16000
     DEFAULT_WATERMARK_BITS: int = 16
+    # NOT in the reference: the SNR floor of embedding in dB (set_snr_floor).  None runs nothing new.
+    snr_floor_db: Optional[float] = None
 
     def __init__(self, checkpoint: Union[str, Path, Mapping] = "base", device: str = "auto") -> None:
         """checkpoint: "base" (the reference's download URL is empty upstream, utils.py:45-52, so
@@ -94,6 +96,17 @@ class WaveVerify:
             raise ValueError("precision must be 'f32' or 'f16'")
         self.generator_precision = self.detector_precision = self.locator_precision = precision
 
+    def set_snr_floor(self, min_snr_db: Optional[float]) -> None:
+        """NOT in the reference: with a number, every embed route scales the generator's residual frame by frame (frames of the generator's
+        hop at 16 kHz) so that in no frame the watermark is louder than min_snr_db below the programme, and silence stays silent
+        (snr_floor.py).  None (the default) switches it off.  The floor is defined on the 16 kHz mono time
+        line; at a native rate the per-channel SNR is not bounded by it."""
+        self.snr_floor_db = snr_floor.check_db(min_snr_db)
+
+    def _floor(self, x, residual, strength=1.0, add: bool = True):
+        """The floor on a 16 kHz input and its residual, frames of the generator's hop."""
+        return snr_floor.apply(x, residual, self.snr_floor_db, strength, frame=self._need("generator").hop_length, add=add)
+
     def _need(self, name: str) -> HipNet:
         net = getattr(self.model, name)
         if net is None:
@@ -104,7 +117,11 @@ class WaveVerify:
     @torch.no_grad()
     def embed_batch(self, audio: torch.Tensor, message: torch.Tensor) -> torch.Tensor:
         """audio [B,1,T] (or [B,T]); message [B,16] or [1,16] (0/1) -> watermarked [B,1,T]."""
-        return self._need("generator").generator(audio, message, add_input=True, precision=self.generator_precision)
+        gen = self._need("generator")
+        if self.snr_floor_db is None:
+            return gen.generator(audio, message, add_input=True, precision=self.generator_precision)
+        x = gen._prep(audio)
+        return self._floor(x, gen.generator(x, message, add_input=False, precision=self.generator_precision))
 
     @torch.no_grad()
     def detect_batch(self, audio: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -138,6 +155,8 @@ class WaveVerify:
             delta = gen.generator(x16, message, add_input=False, precision=self.generator_precision)
         else:
             delta = window.windowed_generator(gen, x16, message, self._window_samples(window_seconds), self.generator_precision, add_input=False)
+        if self.snr_floor_db is not None:                                  # the strength moves into the floor
+            return native.upsample_add(audio, self._floor(x16, delta, strength, add=False), sample_rate, 1.0)
         return native.upsample_add(audio, delta, sample_rate, strength)
 
     # ------------------------------------------------------------------ localized detection (NOT in the reference's package API)
@@ -261,8 +280,18 @@ class WaveVerify:
     def embed_clips(self, clips, watermark_ids, window_seconds: float = 30.0):
         """clips: a list of 1-D tensors of any lengths (or [B,1,T]); watermark_ids: one per clip, or one for all
         -> the watermarked clips, same kind as `clips`.  Long clips run as windows (window.py)."""
+        if self.snr_floor_db is not None:
+            clips = self._on_device(clips)
+            return self._floor(clips, window.windowed_generator(self._need("generator"), clips, self._messages(watermark_ids),
+                                                                self._window_samples(window_seconds), self.generator_precision, add_input=False))
         return window.windowed_generator(self._need("generator"), clips, self._messages(watermark_ids),
                                          self._window_samples(window_seconds), self.generator_precision)
+
+    def _on_device(self, clips):
+        """clips ([B,1,T] or a list of 1-D tensors) as float32 on the device, the same kind."""
+        if isinstance(clips, torch.Tensor):
+            return clips.to(self.device, torch.float32)
+        return [c.to(self.device, torch.float32) for c in clips]
 
     # ------------------------------------------------------------------ span embedding (NOT in the reference; DESIGN.md section 7d-9)
     def _span_messages(self, spans):
@@ -288,6 +317,11 @@ class WaveVerify:
         x + w * G(x, id)'s residual of the whole clip, w = strength times a raised-cosine ramp of fade_samples at both span edges
         (0: a hard cut); outside every span the input bit for bit.  Only halo + span samples go through the generator."""
         msgs, rows, _ = self._span_messages(spans)
+        if self.snr_floor_db is not None:                                  # the masked residual (span weights and strength inside), then the floor
+            clips = self._on_device(clips)
+            return self._floor(clips, window.span_generator(self._need("generator"), clips, msgs, rows, self._window_samples(window_seconds),
+                                                            self.generator_precision, pad_limit, fade_samples=fade_samples, gain=strength,
+                                                            add_input=False))
         return window.span_generator(self._need("generator"), clips, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
                                      pad_limit, fade_samples=fade_samples, gain=strength)
 
@@ -301,6 +335,10 @@ class WaveVerify:
         audio = audio.to(self.device)
         msgs, rows, _ = self._span_messages(spans)
         x16 = self.to_model_rate(audio, sample_rate)
+        if self.snr_floor_db is not None:                                  # the strength moves into the masked residual, under the floor
+            d16 = window.span_generator(gen, x16, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
+                                        fade_samples=fade_samples, gain=strength, add_input=False)
+            return native.upsample_add(audio, self._floor(x16, d16, add=False), sample_rate, 1.0)
         d16 = window.span_generator(gen, x16, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
                                     fade_samples=fade_samples, gain=1.0, add_input=False)
         return native.upsample_add(audio, d16, sample_rate, strength)
@@ -382,6 +420,8 @@ class WaveVerify:
         """Live watermarking of len(watermark_ids) streams in lockstep.  With the defaults: session.EmbedSession, 16 kHz mono, push(x [S, n]).
         Any other sample_rate, channels or strength: native_session.NativeEmbedSession, push(x [S, C, n]) -> [S, C, k] at the stream's own rate
         and channel count, the arithmetic of embed_native_batch; a rate is refused as embed(native=True) refuses it."""
+        if self.snr_floor_db is not None:
+            raise ValueError("the lockstep embed sessions have no SNR floor: use open_embed_bank, or set_snr_floor(None)")
         gen, msg = self._need("generator"), self._messages(watermark_ids)
         if (int(sample_rate), int(channels), float(strength)) == (self.sample_rate, 1, 1.0):
             return session.EmbedSession(gen, msg, self.generator_precision)
@@ -408,12 +448,17 @@ class WaveVerify:
         the input comes back bit for bit and costs no generator time; bank.open(None) starts that way.
         rates=(48000, 8000, ...): native_bank.NativeEmbedBank, every slot at its own rate and channel count:
         bank.open(watermark_id, sample_rate, channels, strength) with sample_rate one of up to 8 `rates` and channels <= max_channels,
-        bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it."""
+        bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it.
+        With set_snr_floor(db) in force the bank is built under that floor; a later set_snr_floor does not reach it."""
         messages = lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0]        # noqa: E731
         if rates is None:
-            return session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit, messages=messages)
-        rates = native_bank.check_rates(rates)                             # before anything is built on the device
-        return native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
+            bank = session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit, messages=messages)
+        else:
+            rates = native_bank.check_rates(rates)                         # before anything is built on the device
+            bank = native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
+        if self.snr_floor_db is not None:
+            bank.set_snr_floor(self.snr_floor_db)                          # the bank takes the value at construction
+        return bank
 
     def open_detect_bank(self, capacity: int = 64, pad_limit: float = 1.5, rates=None, max_channels: int = 2):
         """session.DetectBank: bank.open() -> slot; bank.push({slot: x [n]}) -> {slot: DetectState over that stream's completed frames}.

@@ -317,10 +317,24 @@ class HostEmbedBank(HostFrontBank):
         self._pend = zeros(self.capacity, 2, self.max_channels, max(EmbedPlan(r, self.inner.hop, self.inner.H).pcap for r in self.rates))
         self._strength = [1.0] * self.capacity
 
+    def _floored(self) -> bool:
+        """Whether the inner bank shapes its residual under an SNR floor (session.EmbedBank.set_snr_floor): it then applies each slot's own
+        strength itself, and the back stage's gains are 1."""
+        return getattr(self.inner, "snr_floor_db", None) is not None
+
+    def set_snr_floor(self, min_snr_db) -> None:
+        """session.EmbedBank.set_snr_floor on the 16 kHz frames: only before the first open().  The floor is defined on the 16 kHz mono time
+        line; the per-channel SNR at a slot's own rate is not bounded by it."""
+        self.inner.set_snr_floor(min_snr_db)
+
     def open(self, message, sample_rate: int = MODEL_RATE, channels: int = 1, strength: float = 1.0) -> int:
         strength = float(strength)
+        if self._floored() and not (np.isfinite(strength) and strength >= 0):
+            raise ValueError(f"under an SNR floor strength must be finite and >= 0, got {strength}")
         slot = super().open(message, sample_rate=sample_rate, channels=channels)
         self._strength[slot] = strength
+        if self._floored():
+            self.inner._strength[slot] = strength
         return slot
 
     def latency_samples(self, slot: int) -> int:
@@ -344,7 +358,7 @@ class HostEmbedBank(HostFrontBank):
         back = [up_row(s, self._rate[s], self._chan[s], t, r_off[s], x_off[s], t.front.n, out_off[s], self._half[s]) for s, t in ticks.items()]
         x, ys, tabs = self._front_tick(xs, {s: t.front for s, t in ticks.items()},
                                        [("back", np.array(back, np.int64).reshape(-1, 15)),
-                                        ("gain", np.array([self._strength[s] for s in ticks], self._arr.dtype))])
+                                        ("gain", np.array([1.0 if self._floored() else self._strength[s] for s in ticks], self._arr.dtype))])
         r = self._residuals(ys, ticks, r_off, final)
         out = self._up_add(r, x, tabs, n_out, up_blocks(back))
         self.stats["back_launches"] += 1

@@ -32,7 +32,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, snr_floor
 from .localize import bank_track_row_ok  # noqa: F401  (wv_bank_segment_track's row predicate, restated beside bank_row_ok)
 from .window import halo as _halo
 
@@ -915,13 +915,35 @@ class EmbedBank(_ColumnsBank):
     set_message(slot, message) changes a stream's id mid-stream and set_message(slot, None) switches its watermark off (pass-through: the
     input comes back bit for bit and the slot takes part in no generator launch), both from the slot's next frame on; open(None) opens in
     pass-through.  Per stream the concatenated output is span embedding (window.span_generator, hard cuts) of what it pushed, the span
-    edges at the indices set_message returned."""
+    edges at the indices set_message returned.
+    set_snr_floor(min_snr_db), before the first open(): the SNR floor of snr_floor.py.  The generator launches then
+    return the residual alone and ONE wv_snr_floor call per launch turns (window batch, residual) into the rows wv_window_scatter packs; each
+    row starts at its window's keep column, a frame boundary of its stream, and carries its slot's gain of the frame before in a [capacity]
+    device array.  A slot's state is fresh at open() and on leaving pass-through; pass-through launches stay as they are.  Per stream the
+    concatenated output is the file route's floor on the whole stream."""
 
     def __init__(self, net, capacity: int = 64, precision: str = "f32", pad_limit: float = 1.5, messages: Optional[Callable] = None,
                  add_input: bool = True):
         super().__init__(net, capacity, precision, pad_limit)
         self._messages, self.add_input = messages, bool(add_input)
         self._msg = np.zeros((self.capacity, net.cfg.msg_dimension), np.float32)
+        self.snr_floor_db: Optional[float] = None
+        self._opened = False
+        self._strength = np.ones(self.capacity, np.float32)                # per slot, under a floor (native_bank sets each slot's own)
+        self._fresh: set = set()                                           # slots whose next floor row ignores the stored gain
+
+    def set_snr_floor(self, min_snr_db: Optional[float]) -> None:
+        """The floor in dB for every slot (None: off).  Only before the bank's first open()."""
+        if self._opened:
+            raise RuntimeError("set_snr_floor is legal only before the bank's first open()")
+        db = snr_floor.check_db(min_snr_db)
+        if db is None:
+            self.snr_floor_db = self._rho = self._ramp = self._gstate = None
+            return
+        rho, ramp = snr_floor.rho_of(db), snr_floor.floor_ramp(self.hop)
+        self.snr_floor_db, self._rho = db, rho
+        self._ramp = self._torch.from_numpy(ramp).to(self.net.device)
+        self._gstate = self._arr.zeros(self.capacity)
 
     def _message_row(self, message) -> np.ndarray:
         m = self._messages(message) if self._messages is not None else message
@@ -938,10 +960,15 @@ class EmbedBank(_ColumnsBank):
             self._through.add(slot)
         else:
             self._msg[slot] = self._message_row(message)
+            if slot in self._through:
+                self._fresh.add(slot)                                      # leaving pass-through: no gain of a frame before
             self._through.discard(slot)
 
     def _on_open(self, slot: int, message) -> None:
         self._set(slot, message)
+        self._opened = True
+        self._fresh.add(slot)                                              # whatever gain the slot's last stream left is never read
+        self._strength[slot] = 1.0
 
     def set_message(self, slot: int, message) -> int:
         """The slot's id from its next frame on (None: no watermark) -> that frame's first sample, samples_seen(slot)."""
@@ -949,11 +976,37 @@ class EmbedBank(_ColumnsBank):
         self._set(slot, message)
         return self._tickers[slot].t_out
 
+    def _floor_rows(self, plan: BankPlan) -> np.ndarray:
+        """wv_snr_floor's descriptor per window, launch by launch: the row's kept columns [keep, wlen) of its launch's window batch, in x, r
+        and out alike; the slot's strength; its state, fresh where the slot has no frame before.  Pass-through rows are never read."""
+        rows = np.zeros((len(plan.windows), snr_floor.DESC), np.int64)
+        for ln in plan.launches:
+            if ln.passthrough:
+                continue
+            for r in range(ln.A):
+                s, t = plan.windows[ln.a_lo + r]
+                at = r * ln.Lmax + t.keep
+                rows[ln.a_lo + r] = [at, at, at, t.wlen - t.keep, snr_floor.strength_bits(self._strength[s]), s, int(s in self._fresh), -1]
+                self._fresh.discard(s)
+        return rows
+
     def _sections(self, plan: BankPlan) -> list:
-        return super()._sections(plan) + [("msg", self._msg[[s for s, _ in plan.windows]])]
+        sec = super()._sections(plan) + [("msg", self._msg[[s for s, _ in plan.windows]])]
+        if self.snr_floor_db is not None:
+            sec.append(("floor", self._floor_rows(plan)))
+        return sec
 
     def _net(self, win, tabs: dict, ln: BankLaunch):
-        return self.net.generator(win, tabs["msg"][ln.a_lo:ln.a_lo + ln.A], add_input=self.add_input, precision=self.precision)
+        msg = tabs["msg"][ln.a_lo:ln.a_lo + ln.A]
+        if self.snr_floor_db is None:
+            return self.net.generator(win, msg, add_input=self.add_input, precision=self.precision)
+        y = self.net.generator(win, msg, add_input=False, precision=self.precision)
+        out = self._torch.empty_like(y)                                    # only the kept columns are written, and only they are read
+        n = ln.A * ln.Lmax
+        _lib.check(self.net._lib.wv_snr_floor(win.data_ptr(), n, y.data_ptr(), n, out.data_ptr(), n, tabs["floor"][ln.a_lo:].data_ptr(), ln.A, ln.Lmax,
+                                              self._gstate.data_ptr(), self.capacity, None, 0, self._ramp.data_ptr(), self.hop, self._rho,
+                                              int(self.add_input), _lib.stream()), "wv_snr_floor")
+        return out
 
 
 class LocateBank(_ColumnsBank):
