@@ -898,6 +898,32 @@ int wv_native_downmix_resample(const float* x, const float* kernels_t, float* y,
 int wv_native_upsample_add(const float* x, const float* delta, const float* kernels_t, float* out, int B, int C, int T16, int Tn, int orig, int nw, int L,
                            int width, float gain, void* stream);
 
+/* ---- csrc/wv_channel_floor.hip: the back end under a PER-CHANNEL SNR floor at the file's own rate (DESIGN.md section 7d-12;
+ * waveverify_amd/channel_floor.py is the definition, bit for bit).  x, delta, kernels_t, out, B .. width: wv_native_upsample_add's, and u[b][m] is
+ * that call's fmaf chain through the same device function.  hop: the generator's hop at 16 kHz; rho = 10^(-min_snr_db / 10); strengths [B] f32
+ * DEVICE, the cap s of each row; add 0 / 1; gains: null, or [B][C][F] f32 DEVICE that takes every g; F = ((Tn - 1) * orig) / (nw * hop) + 1.
+ *   native sample m belongs to frame (m * orig) / (nw * hop) in int64: frame f is [start(f), start(f + 1)) cut at Tn, start(f) = ceil(f * nw *
+ *     hop / orig), its nominal length L_f = start(f + 1) - start(f) (lengths differ by at most one; a frame may be empty where nw * hop < orig);
+ *   Ex[c][f] = sum x[b][c]^2, Eu[f] = sum u[b]^2 over the frame in float64, in wv_snr_floor's fixed order with k counted inside the frame;
+ *   g[c][f] = s where Eu == 0, else q < (double)s ? (float)q : s with q = sqrt((rho * Ex) / Eu), divide and square root correctly rounded;
+ *   w = g_prev < g[c][f] ? min(g[c][f], g_prev + (g[c][f] - g_prev) * ramp) : g[c][f] in f32, every rounding kept, g_prev = g[c][f - 1] (frame 0:
+ *     g[c][0]), ramp = float32((k + 1) / L_f) formed in float64 and rounded once;
+ *   v = w * u;  add == 0: out = v;  add == 1: out = x + v, but x's own bits where v is +0 or -0.
+ * Two launches: the first reads x and delta and fills the workspace (u [B][Tn], then g [B][C][F], each on a 256-byte boundary), the second reads
+ * the workspace and x and writes out.  out may be x: each element is read for its last time, then written, by the same thread of the second
+ * launch.  The workspace is the caller's, on a 256-byte boundary, at least wv_native_floor_up_add_bytes(...) bytes, contents undefined before
+ * and after.  A row whose strength is negative, infinite or not a number is SKIPPED whole; the other rows are served.
+ * Refused with WV_EINVAL, nothing launched and nothing written: everything wv_native_upsample_add refuses; null strengths or workspace; hop < 1;
+ * nw * hop or F beyond 2^31 - 1; rho not finite or <= 0; add not 0 or 1; a workspace that is misaligned or too small; a frame of
+ * ceil(nw * hop / orig) > WV_CHANNEL_FLOOR_MAX_FRAME native samples, or one that together with the 256-output input window
+ * (((nw + 254) / nw) * orig + L floats) passes WV_CHANNEL_FLOOR_LDS_FLOATS: the first launch holds both in LDS. */
+#define WV_CHANNEL_FLOOR_MAX_FRAME 4096
+#define WV_CHANNEL_FLOOR_LDS_FLOATS 15360
+int wv_native_floor_up_add_bytes(int B, int C, int T16, int Tn, int orig, int nw, int L, int width, int hop, size_t* workspace_bytes);
+int wv_native_floor_up_add(const float* x, const float* delta, const float* kernels_t, float* out, int B, int C, int T16, int Tn, int orig, int nw, int L,
+                           int width, int hop, double rho, const float* strengths, int add, float* gains, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
 /* ---- the same two ends for live sessions: S streams in lockstep, one launch per end and push, the state on the device.
  * A stage's sequence is cat(history[s][0 .. hv), new[s][0 .. n)), never materialised.  Output 0 of a call is phase 0 of the first phase group the
  * stream has not emitted yet, and its first tap is sequence sample -pad (0 <= pad <= width; pad > 0 only while the stream's start lies inside the

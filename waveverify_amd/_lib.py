@@ -216,6 +216,8 @@ SIGNATURES = {
     "wv_fx_resample": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_native_downmix_resample": (C.c_int, [_VP, _VP, _VP] + [C.c_int] * 8 + [_VP]),
     "wv_native_upsample_add": (C.c_int, [_VP, _VP, _VP, _VP] + [C.c_int] * 8 + [C.c_float, _VP]),
+    "wv_native_floor_up_add_bytes": (C.c_int, [C.c_int] * 9 + [C.POINTER(C.c_size_t)]),
+    "wv_native_floor_up_add": (C.c_int, [_VP, _VP, _VP, _VP] + [C.c_int] * 9 + [C.c_double, _VP, C.c_int, _VP, _VP, C.c_size_t, _VP]),
     "wv_native_session_down": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP] + [C.c_int] * 8 + [_VP]),
     "wv_native_session_up_add": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int, _VP, _VP, C.c_int, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int,
                                            C.c_float, _VP, _VP] + [C.c_int] * 8 + [_VP]),

@@ -28,12 +28,18 @@ from .watermark_id import WatermarkID
 
 logger = logging.getLogger(__name__)
 
+# a native push is not aligned to the floor's frames: a live channel floor would have to hold output until each native frame completes
+_NO_LIVE_CHANNEL_FLOOR = ("the live native-rate embed routes have no per-channel SNR floor (DESIGN.md section 7d-12): embed files with "
+                          "embed(native=True) / embed_native_batch, or call set_channel_snr_floor(None) first")
+
 
 class WaveVerify:
     DEFAULT_SAMPLE_RATE: int = 16000
     DEFAULT_WATERMARK_BITS: int = 16
     # NOT in the reference: the SNR floor of embedding in dB (set_snr_floor).  None runs nothing new.
     snr_floor_db: Optional[float] = None
+    # NOT in the reference: the per-channel floor of the native-rate file routes (set_channel_snr_floor).
+    channel_snr_floor_db: Optional[float] = None
 
     def __init__(self, checkpoint: Union[str, Path, Mapping] = "base", device: str = "auto") -> None:
         """checkpoint: "base" (the reference's download URL is empty upstream, utils.py:45-52, so
@@ -100,8 +106,25 @@ class WaveVerify:
         """NOT in the reference: with a number, every embed route scales the generator's residual frame by frame (frames of the generator's
         hop at 16 kHz) so that in no frame the watermark is louder than min_snr_db below the programme, and silence stays silent
         (snr_floor.py).  None (the default) switches it off.  The floor is defined on the 16 kHz mono time
-        line; at a native rate the per-channel SNR is not bounded by it."""
+        line; at a native rate it does not bound the SNR of a channel: set_channel_snr_floor does."""
         self.snr_floor_db = snr_floor.check_db(min_snr_db)
+
+    def set_channel_snr_floor(self, min_snr_db: Optional[float]) -> None:
+        """NOT in the reference: with a number, the native-rate file routes (embed_native_batch, embed_spans_native_batch, embed and
+        embed_spans with native=True) hold the floor on every ORIGINAL channel at the file's own rate: in no native frame of any channel
+        is the watermark louder than min_snr_db below that channel, and a silent channel comes back bit for bit (channel_floor.py,
+        native.upsample_add_floor).  None (the default) switches it off.  The 16 kHz routes are not touched:
+        their one mono channel is set_snr_floor's.  With both floors set the 16 kHz floor shapes the residual first, `strength` inside
+        it, and the channel floor runs on that residual with cap 1.0; alone, `strength` is the channel floor's cap.  The live native
+        routes (open_embed_session with a rate, open_embed_bank(rates=...)) have no channel floor and refuse to open under one."""
+        self.channel_snr_floor_db = snr_floor.check_db(min_snr_db)
+
+    def _native_back_end(self, audio, delta, sample_rate: int, strength):
+        """The last step of the native-rate file routes: delta onto every channel, under the channel floor where one is set."""
+        if self.channel_snr_floor_db is None:
+            return native.upsample_add(audio, delta, sample_rate, strength)
+        return native.upsample_add_floor(audio, delta, sample_rate, self.channel_snr_floor_db, strength,
+                                         hop=self._need("generator").hop_length)
 
     def _floor(self, x, residual, strength=1.0, add: bool = True):
         """The floor on a 16 kHz input and its residual, frames of the generator's hop."""
@@ -156,8 +179,8 @@ class WaveVerify:
         else:
             delta = window.windowed_generator(gen, x16, message, self._window_samples(window_seconds), self.generator_precision, add_input=False)
         if self.snr_floor_db is not None:                                  # the strength moves into the floor
-            return native.upsample_add(audio, self._floor(x16, delta, strength, add=False), sample_rate, 1.0)
-        return native.upsample_add(audio, delta, sample_rate, strength)
+            return self._native_back_end(audio, self._floor(x16, delta, strength, add=False), sample_rate, 1.0)
+        return self._native_back_end(audio, delta, sample_rate, strength)
 
     # ------------------------------------------------------------------ localized detection (NOT in the reference's package API)
     def _gate(self, audio, threshold: float, gate):
@@ -338,10 +361,10 @@ class WaveVerify:
         if self.snr_floor_db is not None:                                  # the strength moves into the masked residual, under the floor
             d16 = window.span_generator(gen, x16, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
                                         fade_samples=fade_samples, gain=strength, add_input=False)
-            return native.upsample_add(audio, self._floor(x16, d16, add=False), sample_rate, 1.0)
+            return self._native_back_end(audio, self._floor(x16, d16, add=False), sample_rate, 1.0)
         d16 = window.span_generator(gen, x16, msgs, rows, self._window_samples(window_seconds), self.generator_precision,
                                     fade_samples=fade_samples, gain=1.0, add_input=False)
-        return native.upsample_add(audio, d16, sample_rate, strength)
+        return self._native_back_end(audio, d16, sample_rate, strength)
 
     def embed_spans(self, audio_path: Union[str, Path], spans, output_path: Optional[Union[str, Path]] = None, *, native: bool = False,
                     strength: float = 1.0, fade_ms: float = 0.0, window_seconds: float = 30.0) -> Tuple[np.ndarray, int, List[WatermarkID]]:
@@ -422,8 +445,11 @@ class WaveVerify:
         and channel count, the arithmetic of embed_native_batch; a rate is refused as embed(native=True) refuses it."""
         if self.snr_floor_db is not None:
             raise ValueError("the lockstep embed sessions have no SNR floor: use open_embed_bank, or set_snr_floor(None)")
+        plain = (int(sample_rate), int(channels), float(strength)) == (self.sample_rate, 1, 1.0)
+        if not plain and self.channel_snr_floor_db is not None:
+            raise ValueError(_NO_LIVE_CHANNEL_FLOOR)
         gen, msg = self._need("generator"), self._messages(watermark_ids)
-        if (int(sample_rate), int(channels), float(strength)) == (self.sample_rate, 1, 1.0):
+        if plain:
             return session.EmbedSession(gen, msg, self.generator_precision)
         return native_session.NativeEmbedSession(gen, msg, sample_rate, channels, strength, self.generator_precision)
 
@@ -449,11 +475,14 @@ class WaveVerify:
         rates=(48000, 8000, ...): native_bank.NativeEmbedBank, every slot at its own rate and channel count:
         bank.open(watermark_id, sample_rate, channels, strength) with sample_rate one of up to 8 `rates` and channels <= max_channels,
         bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it.
-        With set_snr_floor(db) in force the bank is built under that floor; a later set_snr_floor does not reach it."""
+        With set_snr_floor(db) in force the bank is built under that floor; a later set_snr_floor does not reach it.
+        With set_channel_snr_floor(db) in force a bank with `rates` is refused: the live native routes have no channel floor (section 7d-12)."""
         messages = lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0]        # noqa: E731
         if rates is None:
             bank = session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit, messages=messages)
         else:
+            if self.channel_snr_floor_db is not None:
+                raise ValueError(_NO_LIVE_CHANNEL_FLOOR)
             rates = native_bank.check_rates(rates)                         # before anything is built on the device
             bank = native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
         if self.snr_floor_db is not None:

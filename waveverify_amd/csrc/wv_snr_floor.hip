@@ -20,6 +20,7 @@
 #include <cmath>
 #include <cstdint>
 
+#include "wv_floor_math.h"
 #include "wv_host.h"
 
 namespace wv {
@@ -53,43 +54,8 @@ __device__ __forceinline__ FloorRow floor_row(const int64_t* __restrict__ desc, 
     return w;
 }
 
-// The 16 lanes of a group: sum of squares of p[0 .. len) in the order above; every lane returns the folded sum.
-__device__ __forceinline__ double frame_energy(const float* __restrict__ p, int len, int lane) {
-    double e = 0.0;
-    const bool vec = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
-    for (int k = lane * 4; k < len; k += 64) {
-        if (vec && k + 4 <= len) {
-            const float4 v = *reinterpret_cast<const float4*>(p + k);
-            e += (double)v.x * (double)v.x;
-            e += (double)v.y * (double)v.y;
-            e += (double)v.z * (double)v.z;
-            e += (double)v.w * (double)v.w;
-        } else {
-            for (int i = k; i < k + 4 && i < len; ++i) e += (double)p[i] * (double)p[i];
-        }
-    }
-    e += __shfl_xor(e, 8, 16);
-    e += __shfl_xor(e, 4, 16);
-    e += __shfl_xor(e, 2, 16);
-    e += __shfl_xor(e, 1, 16);
-    return e;
-}
-
-__device__ __forceinline__ float floor_gain(double Ex, double Er, float s, double rho) {
-    if (Er == 0.0) return s;
-    const double q = __dsqrt_rn(__ddiv_rn(rho * Ex, Er));
-    return q < (double)s ? (float)q : s;
-}
-
-__device__ __forceinline__ float floor_weight(float gp, float g, float ramp) {
-    if (gp < g) {
-        const float w = gp + (g - gp) * ramp;
-        return w < g ? w : g;
-    }
-    return g;
-}
-
-__device__ __forceinline__ float floor_out(float x, float v, int add) { return add ? (v == 0.f ? x : x + v) : v; }
+// frame_energy (the 16 lanes of a group, the order above), floor_gain, floor_weight and floor_out: wv_floor_math.h, shared with the
+// per-channel floor (csrc/wv_channel_floor.hip).
 
 // out, x and r carry no __restrict__ towards each other beyond what the entry point has checked (no overlap).
 __global__ __launch_bounds__(SF_NT) void snr_floor_kernel(const float* __restrict__ x, int64_t n_x, const float* __restrict__ r, int64_t n_r,

@@ -6,6 +6,7 @@ torchaudio's polyphase table as `effects.resample_kernels` restates it (width 6,
 handed to the kernels transposed; a 16 kHz file takes the same two kernels with the one-tap identity table.  There is no CPU fallback."""
 from __future__ import annotations
 
+import ctypes
 import math
 from typing import Dict, Optional, Tuple
 
@@ -129,3 +130,54 @@ def upsample_add(audio: torch.Tensor, delta: torch.Tensor, sample_rate: int, gai
         _lib.check(_lib.load().wv_native_upsample_add(x.data_ptr(), d.data_ptr(), kt.data_ptr(), out.data_ptr(), B, C, T16, Tn, orig, nw, L, width,
                                                      float(gain), _lib.stream()), "wv_native_upsample_add")
     return out
+
+
+def floor_frames(Tn: int, sample_rate: int, hop: int = 320) -> int:
+    """The frames of the per-channel floor in Tn native samples: frame(Tn - 1) + 1, frame(m) = (m * orig) // (nw * hop)."""
+    orig, nw, _, _ = table_geometry(MODEL_RATE, sample_rate)
+    return ((int(Tn) - 1) * orig) // (nw * int(hop)) + 1
+
+
+def upsample_add_floor(audio: torch.Tensor, delta: torch.Tensor, sample_rate: int, min_snr_db: float, strength=1.0, hop: int = 320,
+                       add: bool = True, return_gains: bool = False, out: Optional[torch.Tensor] = None):
+    """upsample_add under the per-channel SNR floor (channel_floor.py): audio [B,C,Tn] at `sample_rate`, delta
+    [B,1,T16] (or [B,T16]) at 16 kHz -> audio + w * up(delta), [B,C,Tn], w chosen per channel and native frame so that in no frame of any
+    channel the watermark is louder than min_snr_db below that channel, and a silent channel comes back bit for bit.  strength: the cap of w,
+    one number or one per row, finite and >= 0.  hop: the generator's hop_length (the frames are the 16 kHz floor's, seen from the native
+    time line).  add=False: w * up(delta) alone.  return_gains: also the gains [B, C, F].  out: as in upsample_add; `audio` itself works."""
+    from . import snr_floor
+    rho = snr_floor.rho_of(min_snr_db)
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f"hop must be >= 1, got {hop}")
+    rows = int(audio.shape[0]) if audio.dim() == 3 else 1
+    s = np.broadcast_to(np.asarray(strength, np.float64), (rows,)) if np.ndim(strength) == 0 else np.asarray(strength, np.float64).reshape(-1)
+    if s.shape[0] != rows or not (np.isfinite(s).all() and (s >= 0).all()):
+        raise ValueError("strength must be finite and >= 0, one number or one per row")
+    x = _planar(audio)
+    B, C, Tn = x.shape
+    d = _lib.dev(delta, _ON_GPU)
+    if d.dim() == 3 and d.shape[1] == 1:
+        d = d.squeeze(1)
+    if d.dim() != 2 or d.shape[0] != B or d.shape[1] < 1:
+        raise ValueError(f"expected delta of shape [{B},1,T16] or [{B},T16], got {tuple(delta.shape)}")
+    T16 = int(d.shape[1])
+    if upsampled_length(T16, sample_rate) < Tn:
+        raise ValueError(f"delta of {T16} samples at 16 kHz gives {upsampled_length(T16, sample_rate)} samples at {sample_rate} Hz, fewer than the "
+                         f"audio's {Tn}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (B, C, Tn)):
+        raise ValueError(f"out must be a contiguous float32 tensor of shape {(B, C, Tn)} on {x.device}")
+    with torch.cuda.device(x.device):
+        _, (kt, orig, nw, L, width) = tables(sample_rate, x.device)
+        lib = _lib.load()
+        need = ctypes.c_size_t(0)
+        _lib.check(lib.wv_native_floor_up_add_bytes(B, C, T16, Tn, orig, nw, L, width, hop, ctypes.byref(need)), "wv_native_floor_up_add_bytes")
+        ws = _lib.scratch(need.value, x.device)
+        st = torch.from_numpy(s.astype(np.float32)).to(x.device)
+        gains = torch.empty((B, C, floor_frames(Tn, sample_rate, hop)), dtype=torch.float32, device=x.device) if return_gains else None
+        _lib.check(lib.wv_native_floor_up_add(x.data_ptr(), d.data_ptr(), kt.data_ptr(), out.data_ptr(), B, C, T16, Tn, orig, nw, L, width, hop, rho,
+                                              st.data_ptr(), 1 if add else 0, _lib.ptr(gains), ws.data_ptr(), need.value, _lib.stream()),
+                   "wv_native_floor_up_add")
+    return (out, gains) if return_gains else out
