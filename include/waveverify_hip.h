@@ -988,6 +988,37 @@ int wv_native_bank_up_add(float* rhist, int rcap, float* pend, int pcap, int Cma
                           const wv_native_rate* rates, int n_rates, const int64_t* desc, const float* gain, int P, int blocks, float* out, int64_t n_out,
                           void* stream);
 
+/* ---- csrc/wv_live_floor.hip: wv_native_bank_up_add under the PER-CHANNEL SNR floor (native_bank.numpy_bank_floor_up_add
+ * restates it, row rule included): per stream the concatenated output is wv_native_floor_up_add's arithmetic (channel_floor.numpy_channel_floor) on
+ * everything the stream pushed, bit for bit.  A sample leaves only when its whole native frame has its u, so besides rhist and pend a slot keeps
+ *   uhold [capacity][2][ucap]  the u already formed for samples not yet emitted (fewer than one frame), and
+ *   gprev [capacity][2][Cmax]  the gains of the last frame emitted, per channel,
+ * ping-pong like the others.  With seq_u = cat(uhold[0 .. uv), new u) and seq_x[c] = cat(pend[c][0 .. pv), x[c][0 .. n)), both beginning at the
+ * stream's first sample not yet emitted, start(f0), start(f) = ceil(f * nw * hop / orig):
+ *   desc [P][21] = {slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half, f0, nf, uv, uv2, g_off, final}: the first fifteen
+ *     are wv_native_bank_up_add's, except that k counts the samples that LEAVE; the chain forms k + uv2 - uv new u.  Frames f0 .. f0 + nf - 1 complete:
+ *     their Eu and Ex[c] come from seq_u and seq_x in wv_snr_floor's fixed order, the gains follow wv_native_floor_up_add's rule with cap[p] (f32,
+ *     DEVICE) as the cap s and rho, the gain before frame f0 is gprev (the stream's frame 0 takes its own gain and reads no state), and
+ *     out[c][i] = seq_x[c][i] + w * seq_u[i], i < k, with seq_x's own bits where w * seq_u[i] is +0 or -0: C planar channels of k floats at
+ *     out + out_off.  The other half takes rhist's next samples, seq_x[c][k .. k + pv2), seq_u[k .. k + uv2) and the gains of frame f0 + nf - 1
+ *     (nf == 0: gprev as it was).  g_off >= 0: the gains go to gains + g_off as [C][nf] as well; -1: nowhere.  final: the stream's last call, whose
+ *     last frame is cut at k with its nominal length in the ramp.
+ * One launch.  `blocks` is at least the largest per-row need, ceil(nf / NF) + ceil(rv2 / 256) + ceil(pv2 / 256) + ceil(uv2 / 256) + (nf == 0), NF the
+ * rate's frames per workgroup (native_bank.floor_tile_frames).
+ * ROW RULE: wv_native_bank_up_add's with k + uv2 - uv as the outputs of the chain, and 0 <= uv, uv2 <= ucap; final in {0, 1} and uv2 == 0 where it is
+ * set; k + uv2 - uv >= 0; f0 >= 0, 0 <= nf <= 2^31 - 257, f0 + nf <= 2^62 / (nw * hop); k == start(f0 + nf) - start(f0), at final instead
+ * start(f0 + nf - 1) - start(f0) < k <= start(f0 + nf) - start(f0) (nf == 0: k == 0); g_off == -1, or g_off >= 0 and g_off + C * nf <= n_gains;
+ * cap[p] finite and >= 0.  Any other row is skipped WHOLE: no output, no gains, both halves of all four states untouched.
+ * Refused with WV_EINVAL, nothing launched or written: everything wv_native_bank_up_add refuses; null uhold or gprev, gains null with n_gains > 0;
+ * ucap < 1, n_gains < 0, hop < 1, rho not finite or <= 0; a rate with nw * hop beyond 2^31 - 1, a frame of ceil(nw * hop / orig) >
+ * WV_CHANNEL_FLOOR_MAX_FRAME native samples, or TWO such frames (a workgroup also holds the frame before its own) that with the 256-output input
+ * window and 1088 floats of gains pass WV_CHANNEL_FLOOR_LDS_FLOATS; states or arenas that overlap (r and x may).  P == 0 or blocks == 0 is success
+ * without a launch. */
+int wv_native_bank_floor_up_add(float* rhist, int rcap, float* pend, int pcap, float* uhold, int ucap, float* gprev, int Cmax, int capacity,
+                                const float* r, int64_t n_r, const float* x, int64_t n_x, const wv_native_rate* rates, int n_rates, const int64_t* desc,
+                                const float* cap, int P, int blocks, int hop, double rho, float* out, int64_t n_out, float* gains, int64_t n_gains,
+                                void* stream);
+
 /* ==== csrc/wv_fx_time.hip: plain-arithmetic time-domain effects ----------------------------------------------------------------
  * The reference's remaining AudioEffects that are arithmetic of its own (utils/effect_augmentation.py:1081-1332,1504-1681,1873-2132,
  * 2338-2404): PINNED to the reference by tests/golden/effects_time.npz, bit for bit where the result is a selection or one rounding

@@ -224,6 +224,9 @@ SIGNATURES = {
     "wv_native_bank_down": (C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_int64, C.POINTER(WvNativeRate), C.c_int, _VP, C.c_int, C.c_int, _VP, C.c_int64, _VP]),
     "wv_native_bank_up_add": (C.c_int, [_VP, C.c_int, _VP, C.c_int, C.c_int, C.c_int, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(WvNativeRate), C.c_int, _VP,
                                         _VP, C.c_int, C.c_int, _VP, C.c_int64, _VP]),
+    "wv_native_bank_floor_up_add": (C.c_int, [_VP, C.c_int, _VP, C.c_int, _VP, C.c_int, _VP, C.c_int, C.c_int, _VP, C.c_int64, _VP, C.c_int64,
+                                              C.POINTER(WvNativeRate), C.c_int, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_double, _VP, C.c_int64, _VP,
+                                              C.c_int64, _VP]),
     "wv_fx_pointwise": (C.c_int, [_VP, _VP, _VP, C.c_int, C.c_int, C.c_int, C.c_float, _VP]),
     "wv_fx_median": (C.c_int, [_VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),
     "wv_fx_shush": (C.c_int, [_VP, _VP, _VP, _VP, _VP, C.c_int, C.c_int, C.c_int, _VP]),

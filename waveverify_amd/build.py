@@ -11,9 +11,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "lib", "libwaveverify_hip.so")
-SOURCES = ["wv_kernels.hip", "wv_k1.hip", "wv_rb.hip", "wv_h16.hip", "wv_model.hip", "wv_ops.hip", "wv_train.hip", "wv_aug.hip", "wv_fx.hip", "wv_fx_time.hip", "wv_window.hip", "wv_specloss.hip", "wv_metrics.hip", "wv_stoi.hip", "wv_loudness.hip", "wv_native.hip", "wv_snr_floor.hip", "wv_channel_floor.hip"]
+SOURCES = ["wv_kernels.hip", "wv_k1.hip", "wv_rb.hip", "wv_h16.hip", "wv_model.hip", "wv_ops.hip", "wv_train.hip", "wv_aug.hip", "wv_fx.hip", "wv_fx_time.hip", "wv_window.hip", "wv_specloss.hip", "wv_metrics.hip", "wv_stoi.hip", "wv_loudness.hip", "wv_native.hip", "wv_snr_floor.hip", "wv_channel_floor.hip", "wv_live_floor.hip"]
 HEADERS = [os.path.join(CSRC, "wv_kernels.h"), os.path.join(CSRC, "wv_dev.h"), os.path.join(CSRC, "wv_host.h"),
-           os.path.join(CSRC, "wv_native_chain.h"), os.path.join(CSRC, "wv_floor_math.h"),
+           os.path.join(CSRC, "wv_native_chain.h"), os.path.join(CSRC, "wv_native_bank.h"), os.path.join(CSRC, "wv_floor_math.h"),
            os.path.join(os.path.dirname(HERE), "include", "waveverify_hip.h")]
 ARCH = "gfx950"
 

@@ -98,6 +98,37 @@ def numpy_channel_floor(x: np.ndarray, u: np.ndarray, orig: int, nw: int, hop: i
     return out, g
 
 
+def numpy_floor_frames(x: np.ndarray, u: np.ndarray, starts: np.ndarray, s, rho: float, gprev=None) -> Tuple[np.ndarray, np.ndarray]:
+    """numpy_channel_floor on a STRETCH of a stream that begins at a frame's start (the live route): x [C, n], u [n],
+    starts [F + 1] the nominal starts of the stretch's frames counted from its sample 0 (the last frame is cut at n), gprev [C] the gains of the
+    frame before the stretch, None where the stretch begins the stream (frame 0 takes its own) -> (out [C, n], g [C, F]).  Every sample and
+    gain has the bits numpy_channel_floor gives it on the whole stream."""
+    x = np.asarray(x, np.float32)
+    u = np.asarray(u, np.float32)
+    st = np.asarray(starts, np.int64)
+    C, n = x.shape
+    F = len(st) - 1
+    if F <= 0:
+        return np.empty((C, 0), np.float32), np.empty((C, 0), np.float32)
+    Eu = frame_energy_var(u, st)
+    g = np.stack([gains_of(frame_energy_var(x[c], st), Eu, s, rho) for c in range(C)])
+    before = np.concatenate([g[:, :1] if gprev is None else np.asarray(gprev, np.float32).reshape(C, 1), g[:, :-1]], axis=1)
+    m = np.arange(n, dtype=np.int64)
+    f = np.searchsorted(st, m, side="right") - 1                           # the frame that holds m: empty frames hold nothing
+    k = m - st[f]
+    Lf = (st[1:] - st[:-1])[f]
+    ramp = ((k + 1).astype(np.float64) / Lf.astype(np.float64)).astype(np.float32)
+    out = np.empty_like(x)
+    for c in range(C):
+        G, P = g[c][f], before[c][f]
+        with np.errstate(invalid="ignore", over="ignore"):
+            up = P + (G - P) * ramp
+            w = np.where(P < G, np.where(up < G, up, G), G).astype(np.float32)
+            v = (w * u).astype(np.float32)
+            out[c] = np.where(v == 0, x[c], x[c] + v).astype(np.float32)
+    return out, g
+
+
 def native_frame_snr_db(x: np.ndarray, v: np.ndarray, orig: int, nw: int, hop: int) -> np.ndarray:
     """10 log10(Ex / sum v^2) per native frame of ONE channel in float64 (plain sums); +inf where the frame carries no watermark."""
     Tn = len(x)

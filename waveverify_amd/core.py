@@ -28,9 +28,11 @@ from .watermark_id import WatermarkID
 
 logger = logging.getLogger(__name__)
 
-# a native push is not aligned to the floor's frames: a live channel floor would have to hold output until each native frame completes
-_NO_LIVE_CHANNEL_FLOOR = ("the live native-rate embed routes have no per-channel SNR floor (DESIGN.md section 7d-12): embed files with "
-                          "embed(native=True) / embed_native_batch, or call set_channel_snr_floor(None) first")
+# the live per-channel floor holds output until each native frame completes: a bank of its own opener has it, the
+# lockstep sessions, which have no 16 kHz floor either, do not
+_NO_LIVE_CHANNEL_FLOOR = ("open_embed_bank(rates=...) and the lockstep native-rate embed sessions have no per-channel SNR floor: open the bank "
+                          "with open_native_embed_bank (DESIGN.md section 7d-13), embed files with embed(native=True) / embed_native_batch, or "
+                          "call set_channel_snr_floor(None) first")
 
 
 class WaveVerify:
@@ -38,7 +40,8 @@ class WaveVerify:
     DEFAULT_WATERMARK_BITS: int = 16
     # NOT in the reference: the SNR floor of embedding in dB (set_snr_floor).  None runs nothing new.
     snr_floor_db: Optional[float] = None
-    # NOT in the reference: the per-channel floor of the native-rate file routes (set_channel_snr_floor).
+    # NOT in the reference: the per-channel floor of the native-rate file routes (set_channel_snr_floor) and of
+    # open_native_embed_bank (section 7d-13).
     channel_snr_floor_db: Optional[float] = None
 
     def __init__(self, checkpoint: Union[str, Path, Mapping] = "base", device: str = "auto") -> None:
@@ -476,7 +479,7 @@ class WaveVerify:
         bank.open(watermark_id, sample_rate, channels, strength) with sample_rate one of up to 8 `rates` and channels <= max_channels,
         bank.push({slot: x [C, n]}) -> {slot: [C, k]} at the slot's rate.  A rate is refused as embed(native=True) refuses it.
         With set_snr_floor(db) in force the bank is built under that floor; a later set_snr_floor does not reach it.
-        With set_channel_snr_floor(db) in force a bank with `rates` is refused: the live native routes have no channel floor (section 7d-12)."""
+        With set_channel_snr_floor(db) in force a bank with `rates` is refused here: open_native_embed_bank builds it under that floor."""
         messages = lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0]        # noqa: E731
         if rates is None:
             bank = session.EmbedBank(self._need("generator"), capacity, self.generator_precision, pad_limit, messages=messages)
@@ -487,6 +490,25 @@ class WaveVerify:
             bank = native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
         if self.snr_floor_db is not None:
             bank.set_snr_floor(self.snr_floor_db)                          # the bank takes the value at construction
+        return bank
+
+    def open_native_embed_bank(self, rates, capacity: int = 64, pad_limit: float = 1.5, max_channels: int = 2, channel_snr_floor_db="instance"):
+        """native_bank.NativeEmbedBank as open_embed_bank(rates=...) builds it, under the PER-CHANNEL SNR floor:
+        channel_snr_floor_db defaults to the instance's set_channel_snr_floor value ("instance"); a number sets it for this bank, None builds
+        the bank without it.  Under the floor a sample leaves only when its whole native frame has its residual (bank.latency_samples(slot) says
+        how late), per stream the concatenated output is embed_native_batch's channel floor on the whole recording, a silent channel comes
+        back bit for bit, and bank.gains(slot) returns the gains [C, nf] of the frames the slot's last push or close emitted.
+        set_snr_floor's value is handed over as open_embed_bank hands it over; with both floors the inner 16 kHz floor carries each slot's
+        strength and the channel floor's cap is 1, as for files."""
+        db = self.channel_snr_floor_db if isinstance(channel_snr_floor_db, str) and channel_snr_floor_db == "instance" else channel_snr_floor_db
+        db = snr_floor.check_db(db)
+        rates = native_bank.check_rates(rates)                             # before anything is built on the device
+        messages = lambda w: message_to_tensor(self._validate_watermark_id(w).to_bits(), self.watermark_bits)[0]        # noqa: E731
+        bank = native_bank.NativeEmbedBank(self._need("generator"), rates, capacity, max_channels, self.generator_precision, pad_limit, messages)
+        if self.snr_floor_db is not None:
+            bank.set_snr_floor(self.snr_floor_db)
+        if db is not None:
+            bank.set_channel_snr_floor(db)
         return bank
 
     def open_detect_bank(self, capacity: int = 64, pad_limit: float = 1.5, rates=None, max_channels: int = 2):

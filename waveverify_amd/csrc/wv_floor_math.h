@@ -1,5 +1,6 @@
-// The arithmetic of the SNR floors (DESIGN sections 7d-11 and 7d-12), shared by csrc/wv_snr_floor.hip and csrc/wv_channel_floor.hip: the
-// fixed-order frame energy, the gain rule, the weight rule and the output rule exist once.  Device only; compile with -ffp-contract=off.
+// The arithmetic of the SNR floors (DESIGN sections 7d-11 to 7d-13), shared by csrc/wv_snr_floor.hip, csrc/wv_channel_floor.hip and
+// csrc/wv_live_floor.hip: the fixed-order frame energy, the gain rule, the weight rule and the output rule exist once.  Device only; compile
+// with -ffp-contract=off.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -24,6 +25,23 @@ __device__ __forceinline__ double frame_energy(const float* __restrict__ p, int 
             for (int i = k; i < k + 4 && i < len; ++i) e += (double)p[i] * (double)p[i];
         }
     }
+    e += __shfl_xor(e, 8, 16);
+    e += __shfl_xor(e, 4, 16);
+    e += __shfl_xor(e, 2, 16);
+    e += __shfl_xor(e, 1, 16);
+    return e;
+}
+
+// frame_energy for a frame that is not one array (the live delay line followed by the new samples): get(k) is sample k.  The same partials, the
+// same order within each and the same folds, so the sum has frame_energy's bits.  All 16 lanes of the group must call it.
+template <class Get>
+__device__ __forceinline__ double frame_energy_by(const Get& get, int len, int lane) {
+    double e = 0.0;
+    for (int k = lane * 4; k < len; k += 64)
+        for (int i = k; i < k + 4 && i < len; ++i) {
+            const double v = (double)get(i);
+            e += v * v;
+        }
     e += __shfl_xor(e, 8, 16);
     e += __shfl_xor(e, 4, 16);
     e += __shfl_xor(e, 2, 16);

@@ -1,5 +1,5 @@
 // The resampler arithmetic of the native-rate route, shared by every kernel that forms the up-sampled residual
-// (csrc/wv_native.hip, csrc/wv_channel_floor.hip): ONE device function makes the fmaf chain, so the bits of u[m] cannot differ between them.
+// (csrc/wv_native.hip, csrc/wv_channel_floor.hip, csrc/wv_live_floor.hip): ONE device function makes the fmaf chain, so the bits of u[m] cannot differ between them.
 #pragma once
 
 #include <hip/hip_runtime.h>

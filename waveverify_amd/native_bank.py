@@ -7,7 +7,8 @@ channels.  Here every slot of a bank has its OWN rate (one of the bank's `rates`
     inner bank    the 16 kHz bank of session.py (the generator returning its residual alone)
     back stage    every slot's residual -> its own rate, strength times it added to its delayed originals, ONE launch (wv_native_bank_up_add)
 
-whatever the mix of rates on the tick.  The integer plans are native_session's StagePlan / EmbedPlan, one per slot; a tick turns them into
+whatever the mix of rates on the tick.  Under set_channel_snr_floor the back stage is wv_native_bank_floor_up_add instead: whole native frames
+leave per tick, with the held residual and the last frame's gains as two more ping-pong states.  The integer plans are native_session's StagePlan / EmbedPlan, one per slot; a tick turns them into
 descriptor rows.  The stages' state is ping-pong per slot: a row's `half` names the half holding the slot's state, the launch writes the next
 state into the other, and the bank flips the bit of every slot the tick named.  The Host* classes run the state machine on numpy arrays (any
 float dtype) through numpy_bank_down / numpy_bank_up_add, which restate the kernels row rule included; the Native* classes bind it to the HIP
@@ -17,14 +18,16 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import _lib, native
+from . import _lib, channel_floor, native, snr_floor
 from .native import MODEL_RATE
-from .native_session import EmbedPlan, EmbedTick, StagePlan, StageTick, numpy_down, numpy_up_add
+from .native_session import EmbedPlan, EmbedTick, StagePlan, StageTick, numpy_down, numpy_resample, numpy_up_add
 from .session import DetectBank, EmbedBank, LocateBank, NumpyArrays, SegmentBank, plan_tick
 
 MAX_RATES = 8                                        # WV_NATIVE_BANK_MAX_RATES
 MAX_COUNT = 2 ** 31 - 257                            # the largest sample count of a descriptor row
 TILE = 256
+FLOOR_DESC = 21                                      # fields of a wv_native_bank_floor_up_add descriptor row
+FLOOR_MAX_NF, FLOOR_U_FLOATS, FLOOR_G_FLOATS = 16, 8192, 17 * 64      # csrc/wv_live_floor.hip's LF_MAX_NF, LF_U_FLOATS, LF_G_FLOATS
 
 
 def _tiles(v: int) -> int:
@@ -77,6 +80,44 @@ def native_bank_up_row_ok(row, capacity: int, rcap: int, pcap: int, Cmax: int, n
             and _range_ok(out_off, C, k, n_out))
 
 
+def floor_tile_frames(orig: int, nw: int, L: int, hop: int) -> int:
+    """The frames one workgroup of wv_native_bank_floor_up_add serves at a rate (lf_geom of csrc/wv_live_floor.hip); 0: the entry point refuses the
+    rate, because a frame passes channel_floor.MAX_FRAME or two frames, the input window and the gains pass channel_floor.LDS_FLOATS."""
+    maxlen = -(-nw * hop // orig)
+    room = min(channel_floor.LDS_FLOATS - FLOOR_G_FLOATS - (((nw + TILE - 2) // nw) * orig + L), FLOOR_U_FLOATS)
+    if maxlen > channel_floor.MAX_FRAME or room < 2 * maxlen:
+        return 0
+    return min(room // maxlen - 1, FLOOR_MAX_NF)
+
+
+def _start(f: int, M: int, orig: int) -> int:
+    return -(-f * M // orig)
+
+
+def native_bank_floor_up_row_ok(row, cap, capacity: int, rcap: int, pcap: int, ucap: int, Cmax: int, n_r: int, n_x: int, n_out: int, n_gains: int,
+                                rates, hop: int) -> bool:
+    """Whether wv_native_bank_floor_up_add serves a descriptor row with the cap `cap` (it skips any other whole)."""
+    slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half, f0, nf, uv, uv2, g_off, final = (int(v) for v in row)
+    cap = np.float32(cap)
+    if not (np.isfinite(cap) and cap >= 0):
+        return False
+    if not (0 <= slot < capacity and 0 <= rate < len(rates) and 1 <= C <= min(64, Cmax) and half in (0, 1) and final in (0, 1)):
+        return False
+    orig, nw, _, width = rates[rate]
+    M, nu = nw * hop, k + uv2 - uv
+    if not (_roll_ok(rcap, rv, nr, rdrop, rv2) and 0 <= pv <= pcap and 0 <= n <= MAX_COUNT and k >= 0 and 0 <= pv + n - k <= pcap
+            and 0 <= uv <= ucap and 0 <= uv2 <= ucap and not (final and uv2) and 0 <= pad <= width and _count_ok(nu, rv + nr, pad, orig, nw)
+            and f0 >= 0 and 0 <= nf <= MAX_COUNT and f0 + nf <= 2 ** 62 // M):
+        return False
+    whole = _start(f0 + nf, M, orig) - _start(f0, M, orig)
+    if final:
+        frames = k == 0 if nf == 0 else _start(f0 + nf - 1, M, orig) - _start(f0, M, orig) < k <= whole
+    else:
+        frames = k == whole
+    return (frames and _range_ok(r_off, 1, nr, n_r) and _range_ok(x_off, C, n, n_x) and _range_ok(out_off, C, k, n_out)
+            and (g_off == -1 or _range_ok(g_off, C, nf, n_gains)))
+
+
 def down_row(slot: int, rate: int, C: int, t: StageTick, x_off: int, y_off: int, half: int) -> list:
     return [slot, rate, C, t.hv, x_off, t.n, y_off, t.n_out, t.pad, t.drop, t.hv2, half]
 
@@ -86,6 +127,11 @@ def up_row(slot: int, rate: int, C: int, t: EmbedTick, r_off: int, x_off: int, n
     return [slot, rate, C, b.hv, r_off, b.n, x_off, n, out_off, b.n_out, b.pad, b.drop, b.hv2, t.pv, half]
 
 
+def floor_up_row(slot: int, rate: int, C: int, t: EmbedTick, r_off: int, x_off: int, n: int, out_off: int, half: int, g_off: int = -1) -> list:
+    b, fl = t.back, t.floor
+    return [slot, rate, C, b.hv, r_off, b.n, x_off, n, out_off, fl.k, b.pad, b.drop, b.hv2, t.pv, half, fl.f0, fl.nf, fl.uv, fl.uv2, g_off, int(t.final)]
+
+
 def down_blocks(desc) -> int:
     """The x-extent wv_native_bank_down needs for these rows: the largest tile-plus-history-block count."""
     return max((_tiles(r[7]) + _tiles(r[10]) for r in np.asarray(desc).reshape(-1, 12)), default=0)
@@ -93,6 +139,16 @@ def down_blocks(desc) -> int:
 
 def up_blocks(desc) -> int:
     return max((_tiles(r[9]) + _tiles(r[12]) + _tiles(r[13] + r[7] - r[9]) for r in np.asarray(desc).reshape(-1, 15)), default=0)
+
+
+def floor_up_blocks(desc, rates, hop: int) -> int:
+    """The x-extent wv_native_bank_floor_up_add needs for these rows; rates: [(orig, nw, L, width)] of the call's table."""
+    need = 0
+    for r in np.asarray(desc).reshape(-1, FLOOR_DESC):
+        nf = int(r[16])
+        tiles = -(-nf // max(floor_tile_frames(*rates[int(r[1])][:3], hop), 1))
+        need = max(need, tiles + _tiles(r[12]) + _tiles(r[13] + r[7] - r[9]) + _tiles(r[18]) + (nf == 0))
+    return need
 
 
 def _geometry(tables) -> list:
@@ -140,6 +196,36 @@ def numpy_bank_up_add(rhist: np.ndarray, pend: np.ndarray, r: np.ndarray, x: np.
     return out
 
 
+def numpy_bank_floor_up_add(rhist: np.ndarray, pend: np.ndarray, uhold: np.ndarray, gprev: np.ndarray, r: np.ndarray, x: np.ndarray,
+                            desc: np.ndarray, cap: np.ndarray, tables, hop: int, rho: float, n_out: int, n_gains: int = 0):
+    """Reference of wv_native_bank_floor_up_add: rhist [capacity, 2, rcap], pend [capacity, 2, Cmax, pcap], uhold
+    [capacity, 2, ucap], gprev [capacity, 2, Cmax], r and x the packed residuals and new originals, desc [P, 21], cap [P] -> (out [n_out] float32,
+    gains [n_gains] float32).  The resampler runs in the states' dtype, the floor in float32 (channel_floor.numpy_floor_frames)."""
+    capacity, _, rcap = rhist.shape
+    Cmax, pcap = pend.shape[2:]
+    ucap = uhold.shape[2]
+    out, gains = np.zeros(n_out, np.float32), np.zeros(n_gains, np.float32)
+    geo = _geometry(tables)
+    for p, row in enumerate(np.asarray(desc).reshape(-1, FLOOR_DESC)):
+        if not native_bank_floor_up_row_ok(row, cap[p], capacity, rcap, pcap, ucap, Cmax, int(r.shape[0]), int(x.shape[0]), n_out, n_gains, geo, hop):
+            continue
+        slot, rate, C, rv, r_off, nr, x_off, n, out_off, k, pad, rdrop, rv2, pv, half, f0, nf, uv, uv2, g_off, final = (int(v) for v in row)
+        orig, nw = geo[rate][:2]
+        seq = np.concatenate([rhist[slot, half, :rv], np.asarray(r[r_off:r_off + nr], rhist.dtype)])
+        seq_u = np.concatenate([uhold[slot, half, :uv], numpy_resample(seq[None], pad, k + uv2 - uv, tables[rate])[0].astype(uhold.dtype)])
+        seq_x = np.concatenate([pend[slot, half, :C, :pv], np.asarray(x[x_off:x_off + C * n], pend.dtype).reshape(C, n)], axis=1)
+        starts = np.array([_start(f0 + i, nw * hop, orig) - _start(f0, nw * hop, orig) for i in range(nf + 1)], np.int64)
+        o, g = channel_floor.numpy_floor_frames(seq_x[:, :k], seq_u[:k], starts, cap[p], rho, None if f0 == 0 else gprev[slot, half, :C])
+        out[out_off:out_off + C * k] = o.reshape(-1)
+        if g_off >= 0:
+            gains[g_off:g_off + C * nf] = g.reshape(-1)
+        rhist[slot, 1 - half, :rv2] = seq[rdrop:rdrop + rv2]
+        pend[slot, 1 - half, :C, :pv + n - k] = seq_x[:, k:]
+        uhold[slot, 1 - half, :uv2] = seq_u[k:k + uv2]
+        gprev[slot, 1 - half, :C] = g[:, -1] if nf else gprev[slot, half, :C]
+    return out, gains
+
+
 # ---------------------------------------------------------------------------------------------------------------- the banks
 class _BankStages:
     """The two stages and their state on host arrays of the backend's dtype; _HipBankStages states the same on the device."""
@@ -155,6 +241,11 @@ class _BankStages:
 
     def _up_add(self, r, x, tabs: dict, n_out: int, blocks: int):
         return numpy_bank_up_add(self._rhist, self._pend, r, x, tabs["back"], tabs["gain"], self._btabs, n_out)
+
+    def _floor_up_add(self, r, x, tabs: dict, n_out: int, n_gains: int, blocks: int):
+        out, gains = numpy_bank_floor_up_add(self._rhist, self._pend, self._uhold, self._gprev, np.asarray(r), x, tabs["back"], tabs["gain"],
+                                             self._btabs, self.inner.hop, self._crho, n_out, n_gains)
+        return out.astype(self._pend.dtype), gains
 
 
 class _HipBankStages(_BankStages):
@@ -191,6 +282,20 @@ class _HipBankStages(_BankStages):
                 desc.data_ptr(), tabs["gain"].data_ptr(), desc.shape[0], blocks, out.data_ptr() if n_out else None, n_out, _lib.stream()),
                 "wv_native_bank_up_add")
         return out
+
+    def _floor_up_add(self, r, x, tabs: dict, n_out: int, n_gains: int, blocks: int):
+        torch, dev = self._arr.torch, self._arr.device
+        out = torch.empty(n_out, dtype=torch.float32, device=dev)
+        gains = torch.empty(n_gains, dtype=torch.float32, device=dev)
+        desc = tabs["back"]
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().wv_native_bank_floor_up_add(
+                self._rhist.data_ptr(), self._rhist.shape[2], self._pend.data_ptr(), self._pend.shape[3], self._uhold.data_ptr(), self._uhold.shape[2],
+                self._gprev.data_ptr(), self._pend.shape[2], self.capacity, r.data_ptr() if r.numel() else None, r.numel(),
+                x.data_ptr() if x.numel() else None, x.numel(), self._brates, len(self.rates), desc.data_ptr(), tabs["gain"].data_ptr(), desc.shape[0],
+                blocks, self.inner.hop, self._crho, out.data_ptr() if n_out else None, n_out, gains.data_ptr() if n_gains else None, n_gains,
+                _lib.stream()), "wv_native_bank_floor_up_add")
+        return out, gains
 
 
 class HostFrontBank(_BankStages):
@@ -305,17 +410,51 @@ class HostEmbedBank(HostFrontBank):
     """Watermark up to `capacity` live streams, each at its own rate and channel count: open(message, sample_rate, channels, strength) -> slot;
     push({slot: x [C, n]}) -> {slot: [C, k]}, the watermarked samples that no later input can change, each x + strength * (the generator's
     residual brought to the slot's rate) on every channel; close(slot) -> the rest, after which as many samples have come out as went in and their
-    concatenation is that of a NativeEmbedSession given the same pushes.  `inner` returns the RESIDUAL of its new frames per slot."""
+    concatenation is that of a NativeEmbedSession given the same pushes.  `inner` returns the RESIDUAL of its new frames per slot.
+    set_channel_snr_floor(min_snr_db), before the first open(): the per-channel SNR floor of channel_floor.py on every slot (DESIGN.md section
+    7d-13).  A sample then leaves only when its whole native frame has its residual, latency_samples(slot) grows by one nominal frame, and per
+    stream the concatenated output is channel_floor.numpy_channel_floor on everything the stream pushed; gains(slot) is the trace."""
+
+    channel_snr_floor_db = None
+    _ever_opened = False
 
     def _new_plan(self, sample_rate: int):
-        return EmbedPlan(sample_rate, self.inner.hop, self.inner.H)
+        return EmbedPlan(sample_rate, self.inner.hop, self.inner.H, self.channel_snr_floor_db is not None)
 
     def _new_state(self) -> None:
         super()._new_state()
         zeros = self._arr.zeros
+        plans = [self._new_plan(r) for r in self.rates]
         self._rhist = zeros(self.capacity, 2, max(t[3] for t in self._btabs))
-        self._pend = zeros(self.capacity, 2, self.max_channels, max(EmbedPlan(r, self.inner.hop, self.inner.H).pcap for r in self.rates))
+        self._pend = zeros(self.capacity, 2, self.max_channels, max(p.pcap for p in plans))
         self._strength = [1.0] * self.capacity
+        if self.channel_snr_floor_db is not None:
+            self._uhold = zeros(self.capacity, 2, max(p.ucap for p in plans))
+            self._gprev = zeros(self.capacity, 2, self.max_channels)
+            self._gains = [None] * self.capacity
+
+    def set_channel_snr_floor(self, min_snr_db) -> None:
+        """The per-channel floor in dB for every slot (None: off).  Only before the bank's first open().  With set_snr_floor also in force the
+        inner bank carries each slot's strength and this floor's cap is 1, as the file route composes the two."""
+        if self._ever_opened:
+            raise RuntimeError("set_channel_snr_floor is legal only before the bank's first open()")
+        db = snr_floor.check_db(min_snr_db)
+        if db is not None:
+            for r, t in zip(self.rates, self._btabs):
+                if floor_tile_frames(*(int(v) for v in t[1:4]), self.inner.hop) < 1:
+                    raise ValueError(f"the channel floor's frame at {r} Hz under hop {self.inner.hop} does not fit the kernel's LDS")
+        self.channel_snr_floor_db = db
+        self._crho = None if db is None else snr_floor.rho_of(db)
+        self._new_state()
+
+    def gains(self, slot: int):
+        """The channel floor's gains [C, nf] of the native frames the slot's last push or close emitted ([C, 0] where it emitted none): the live
+        form of the file route's return_gains."""
+        if self.channel_snr_floor_db is None:
+            raise RuntimeError("gains() is the channel floor's trace: call set_channel_snr_floor first")
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.capacity or self._gains[slot] is None:
+            raise ValueError(f"slot {slot!r} has not been opened")
+        return self._gains[slot]
 
     def _floored(self) -> bool:
         """Whether the inner bank shapes its residual under an SNR floor (session.EmbedBank.set_snr_floor): it then applies each slot's own
@@ -329,10 +468,13 @@ class HostEmbedBank(HostFrontBank):
 
     def open(self, message, sample_rate: int = MODEL_RATE, channels: int = 1, strength: float = 1.0) -> int:
         strength = float(strength)
-        if self._floored() and not (np.isfinite(strength) and strength >= 0):
+        if (self._floored() or self.channel_snr_floor_db is not None) and not (np.isfinite(strength) and strength >= 0):
             raise ValueError(f"under an SNR floor strength must be finite and >= 0, got {strength}")
         slot = super().open(message, sample_rate=sample_rate, channels=channels)
+        self._ever_opened = True
         self._strength[slot] = strength
+        if self.channel_snr_floor_db is not None:
+            self._gains[slot] = self._arr.zeros(int(channels), 0)
         if self._floored():
             self.inner._strength[slot] = strength
         return slot
@@ -351,7 +493,27 @@ class HostEmbedBank(HostFrontBank):
         plan = plan_tick({s: t.inner[0] for s, t in ticks.items()}, {s: t.front.n_out for s, t in ticks.items()}, self.inner.pad_limit)
         return {s: plan.out[s][0] for s in ticks}
 
+    def _floor_embed_tick(self, xs: dict, ticks: dict, final: bool) -> dict:
+        """_embed_tick under the channel floor: the same single upload and front launch, the back launch wv_native_bank_floor_up_add."""
+        r_off = {s: 0 for s in ticks} if final else self._residual_offsets(ticks)
+        x_off, _ = self._packed(ticks, lambda s, t: self._chan[s] * t.front.n)
+        out_off, n_out = self._packed(ticks, lambda s, t: self._chan[s] * t.floor.k)
+        g_off, n_gains = self._packed(ticks, lambda s, t: self._chan[s] * t.floor.nf)
+        back = [floor_up_row(s, self._rate[s], self._chan[s], t, r_off[s], x_off[s], t.front.n, out_off[s], self._half[s], g_off[s])
+                for s, t in ticks.items()]
+        x, ys, tabs = self._front_tick(xs, {s: t.front for s, t in ticks.items()},
+                                       [("back", np.array(back, np.int64).reshape(-1, FLOOR_DESC)),
+                                        ("gain", np.array([1.0 if self._floored() else self._strength[s] for s in ticks], np.float32))])
+        r = self._residuals(ys, ticks, r_off, final)
+        out, gains = self._floor_up_add(r, x, tabs, n_out, n_gains, floor_up_blocks(back, [t[1:] for t in self._btabs], self.inner.hop))
+        self.stats["back_launches"] += 1
+        for s, t in ticks.items():
+            self._gains[s] = gains[g_off[s]:g_off[s] + self._chan[s] * t.floor.nf].reshape(self._chan[s], t.floor.nf)
+        return {s: out[out_off[s]:out_off[s] + self._chan[s] * t.floor.k].reshape(self._chan[s], t.floor.k) for s, t in ticks.items()}
+
     def _embed_tick(self, xs: dict, ticks: dict, final: bool) -> dict:
+        if self.channel_snr_floor_db is not None:
+            return self._floor_embed_tick(xs, ticks, final)
         r_off = {s: 0 for s in ticks} if final else self._residual_offsets(ticks)
         x_off, _ = self._packed(ticks, lambda s, t: self._chan[s] * t.front.n)
         out_off, n_out = self._packed(ticks, lambda s, t: self._chan[s] * t.back.n_out)

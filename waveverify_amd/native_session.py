@@ -89,9 +89,21 @@ class StagePlan:
 
 
 @dataclass
+class FloorTick:
+    """The channel floor's part of one push: native frames f0 .. f0 + nf - 1 complete and their k samples leave; uv samples
+    of u were held before the push, uv2 are held after it, so uv + back.n_out == k + uv2."""
+    f0: int
+    nf: int
+    uv: int
+    uv2: int
+    k: int
+
+
+@dataclass
 class EmbedTick:
     """One push of a native embed session: the front stage's tick, the inner 16 kHz session's ticks (one; at flush its push and its flush) and the
-    residual samples they return, the back stage's tick (back.n_out native samples come out) and the delay line's lengths before and after."""
+    residual samples they return, the back stage's tick (back.n_out native samples come out) and the delay line's lengths before and after.
+    Under a channel floor back.n_out counts the u formed, floor.k the samples that come out."""
     front: StageTick
     inner: tuple
     n_res: int
@@ -99,12 +111,19 @@ class EmbedTick:
     pv: int
     pv2: int
     final: bool = False
+    floor: Optional[FloorTick] = None
 
 
 class EmbedPlan:
-    """front StagePlan -> 16 kHz ticker of hop `hop` (halo H) -> back StagePlan, and the delay line of originals."""
+    """front StagePlan -> 16 kHz ticker of hop `hop` (halo H) -> back StagePlan, and the delay line of originals.
+    channel_floor: the emission rule of the live per-channel SNR floor (DESIGN.md section 7d-13).  The back stage yields u up to t_u = back.t_out;
+    a sample leaves only when its whole native frame has its u, so after a tick start(Fd) samples have left, Fd the largest f with
+    start(f) <= t_u, start(f) = ceil(f * nw * hop / orig) (channel_floor.frame_starts), and the last t_u - start(Fd) < one frame of u are held.
+    The frames counted as complete are those up to the one that holds sample start(Fd) - 1: an EMPTY frame (nw * hop < orig) behind it is counted
+    with the next sample that leaves, so that a stream that ends there has the frames of its whole recording and no more.  flush() emits
+    everything up to t_in, the last frame cut."""
 
-    def __init__(self, sample_rate: int, hop: int, H: int = 0):
+    def __init__(self, sample_rate: int, hop: int, H: int = 0, channel_floor: bool = False):
         native.check_rate(sample_rate)
         self.sample_rate, self.hop = int(sample_rate), int(hop)
         self.front = StagePlan(*native.table_geometry(sample_rate, MODEL_RATE))
@@ -113,14 +132,18 @@ class EmbedPlan:
         # the output lags the input by FEWER than this many native samples: fewer than L_front not yet through the front stage, fewer than hop
         # waiting for their frame, fewer than L_back residual samples not yet through the back stage
         self.latency_samples = self.front.L + -(-(self.hop + self.back.L) * self.sample_rate // MODEL_RATE)
+        self.channel_floor = bool(channel_floor)
+        if self.channel_floor:
+            self.ucap = -(-self.back.nw * self.hop // self.back.orig)      # a nominal frame, ceil(nw * hop / orig): more than is ever held
+            self.latency_samples += self.ucap
         self.pcap = self.latency_samples
-        self.t_in = self.t_out = 0
+        self.t_in = self.t_out = self.frames = 0
 
     def reset(self) -> None:
         self.front.reset()
         self.back.reset()
         self.ticker.reset()
-        self.t_in = self.t_out = 0
+        self.t_in = self.t_out = self.frames = 0
 
     @staticmethod
     def _res(t: Tick) -> int:
@@ -130,9 +153,17 @@ class EmbedPlan:
         n_res = sum(self._res(t) for t in inner)
         pv = self.t_in - self.t_out
         self.t_in += n
+        held = self.back.t_out - self.t_out                                 # u formed for samples not yet emitted: 0 without the floor
         b = self.back.flush(n_res, limit=self.t_in) if final else self.back.push(n_res)
-        self.t_out += b.n_out
-        return EmbedTick(f, inner, n_res, b, pv, self.t_in - self.t_out, final)
+        if not self.channel_floor:
+            self.t_out += b.n_out
+            return EmbedTick(f, inner, n_res, b, pv, self.t_in - self.t_out, final)
+        M, orig, t_u, uv = self.back.nw * self.hop, self.back.orig, self.back.t_out, held
+        end = t_u if final else -(-(t_u * orig // M) * M // orig)            # start(Fd)
+        frames = ((end - 1) * orig) // M + 1 if end else 0                  # the frames of a recording of `end` samples
+        fl = FloorTick(self.frames, frames - self.frames, uv, t_u - end, end - self.t_out)
+        self.t_out, self.frames = end, frames
+        return EmbedTick(f, inner, n_res, b, pv, self.t_in - self.t_out, final, fl)
 
     def push(self, n: int) -> EmbedTick:
         f = self.front.push(n)
